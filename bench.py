@@ -7,7 +7,13 @@ PackedSeq, with the achieved HBM GB/s against the MI355X roofline.
 A "step" is one pass of the hot path (one fused-kernel launch: packed-seq decode -> ntHash ->
 sliding min -> strand vote -> dedup/collect) over synthetic input that is already resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W [--workload headline|contigs|strong]
+    python bench.py --gpus N --steps K --warmup W [--workload headline|contigs|strong] [--full] [--dump-outputs DIR]
+
+A plain run measures the headline figure and nothing else.  `--full` adds everything measured beside it: the
+secondary configurations and component rows in `extra`, the live shader-clock probe behind `roofline.valu`,
+`median_of_5`, the 1/8 shard row, `end_to_end` (the host-to-host call), `cpu_baseline`, and at N > 1 the weak and
+contig figures.  `--dump-outputs DIR` writes what the last timed step computed as float64 .npy files (see
+dump_outputs); the inputs are seeded, so two builds can be compared output for output.
 
   strong    ONE 3.1 Gbp sequence, canonical k=21 w=11 (BASELINE config 3), cut into N window ranges (absolute
             positions, exact seam, no data-path collective): `value` = 3.1e9 x steps / max-over-ranks time.
@@ -25,7 +31,7 @@ With N > 1 and no launcher in the environment the script starts its N ranks itse
 before anything in this process touches a GPU); under torchrun it uses the ranks it is given.  The
 timed region follows the driver contract: W untimed steps, barrier + synchronize, exactly K steps,
 synchronize + barrier, max over ranks.  Rank 0 prints ONE JSON line.  `vs_baseline` stays null: BASELINE.md
-holds no published number for this metric on this hardware (the CPU figure measured beside it is
+holds no published number for this metric on this hardware (the CPU figure measured beside it with `--full` is
 `cpu_baseline`, a reported baseline and not a target).
 """
 import argparse
@@ -182,6 +188,38 @@ def cpu_baseline():
                   f"reference's own published figure (unstated x86 AVX2, 1 thread, not measured here) "
                   f"is 0.455 Gbases/s",
     }
+
+
+# --------------------------------------------------------------------------- --dump-outputs
+DUMP_SAMPLE = 4_000_000  # positions in the seeded sample (32 MB as float64)
+DUMP_BLOCK = 1 << 16     # positions per block sum: 65 536 x (2^32 - 1) stays below 2^53, exact in float64
+
+
+def dump_outputs(out_dir, out, count, offsets=None):
+    """What the last timed step handed its caller, as float64 .npy files in `out_dir` (rank 0's share at N > 1):
+    count.npy          the number of positions
+    positions.npy      the positions at DUMP_SAMPLE indices drawn with a fixed seed (all of them when there are fewer)
+    block_sums.npy     the sum of every DUMP_BLOCK consecutive positions: every position counts towards one entry
+    offsets.npy        contigs workload: the per-contig offsets into the positions
+    Positions are u32 (the int32 device buffer read as unsigned) and exact in float64."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    pos = out[:count].to(torch.int64) & 0xFFFFFFFF
+    if count > DUMP_SAMPLE:
+        idx = np.unique(np.random.default_rng(SEED).integers(0, count, DUMP_SAMPLE))
+        sample = pos[torch.from_numpy(idx).to(pos.device)]
+    else:
+        sample = pos
+    pad = (-count) % DUMP_BLOCK
+    sums = torch.nn.functional.pad(pos, (0, pad)).view(-1, DUMP_BLOCK).sum(dim=1)
+    np.save(os.path.join(out_dir, "count.npy"), np.array([count], dtype=np.float64))
+    np.save(os.path.join(out_dir, "positions.npy"), sample.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(out_dir, "block_sums.npy"), sums.cpu().numpy().astype(np.float64))
+    if offsets is not None:
+        np.save(os.path.join(out_dir, "offsets.npy"), np.asarray(offsets, dtype=np.float64))
+    del pos, sample, sums
 
 
 # --------------------------------------------------------------------------- recorded counters
@@ -378,14 +416,23 @@ def main():
     ap.add_argument("--workload", choices=["headline", "contigs", "strong"], default=None,
                     help="default: the strong split of ONE 3.1 Gbp sequence (at --gpus 1: the headline configuration)")
     ap.add_argument("--bases", type=int, default=N_BASES, help="bases per GPU (headline) / in total (strong)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure (secondary configurations, component rows, "
+                         "clock probe, median-of-5, shard row, end-to-end call, CPU baseline, N > 1 extras)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the untimed secondary configurations, the median-of-5 and the end-to-end figure")
+                    help="with --full: skip the untimed secondary configurations, the median-of-5 and the end-to-end figure")
     ap.add_argument("--single-process", action="store_true",
                     help="N devices driven from THIS process through the C ABI's device group (mm_run_sharded_host: "
                          "host buffers in, one dense host result out, one host thread per device, no torch.distributed). "
                          "PCIe-inclusive by construction: a separate line, never the headline `value`")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.single_process and args.dump_outputs:
+        ap.error("--dump-outputs is not available with --single-process")
     args.workload = resolve_workload(args.workload, args.gpus)
     if args.single_process:
         sys.exit(single_process(args))
@@ -471,7 +518,7 @@ def main():
 
     link_trace("start")
     extras = []
-    if rank == 0 and world == 1 and not args.no_extra and args.workload == "headline" and args.bases == N_BASES and not os.environ.get("MM_BENCH_SKIP_SECONDARY"):
+    if args.full and rank == 0 and world == 1 and not args.no_extra and args.workload == "headline" and args.bases == N_BASES and not os.environ.get("MM_BENCH_SKIP_SECONDARY"):
         # Secondary configurations of BASELINE.json (untimed region, before the headline so that they
         # also bring the clocks up): kernel time by HIP events, median of 5 after 12 warm-up steps.
         def secondary(name, builder, n, seed, density, contigs=None, super_kmers=False):
@@ -641,13 +688,15 @@ def main():
     dt = time.perf_counter() - t0
     kern_ms, launches = ws.kernel_time(True)
     ws.enable_timing(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, outputs(), offs if args.workload == "contigs" else None)
     # Shader clock under this kernel, sampled OUTSIDE the timed region over a few more identical steps: 16 sleeping
     # waves on a stream of their own read the shader cycle counter against the 100 MHz real-time counter
     # (mm_clock_probe_*).  Not inside the timed loop: a second active queue alone slows the steps by ~7 %
     # (measured: 1.96 against 1.82 ms), whatever runs on it.
     link_trace("after the timed loop")
     live_clock = None
-    if rank == 0 and world == 1 and hasattr(ws, "clock_probe_begin"):
+    if args.full and rank == 0 and world == 1 and hasattr(ws, "clock_probe_begin"):
         try:
             probe_steps = max(4, args.steps // 2)
             ws.clock_probe_begin(int(probe_steps * kern_ms / max(1, launches) * 1000 * 0.9))
@@ -729,7 +778,7 @@ def main():
                     line["end_to_end"] = end_to_end
                 if extras or multi_extra:
                     line["extra"] = extras + multi_extra
-                if not args.no_cpu_baseline and world == 1:
+                if args.full and not args.no_cpu_baseline and world == 1:
                     line["cpu_baseline"] = cpu_baseline()
                 sys.stdout.flush()
                 os.dup2(saved_stdout, 1)
@@ -739,7 +788,7 @@ def main():
 
     # ---------------------------------------------------------------- N > 1, default workload: the other two figures
     # (untimed region; the same barrier + max-over-ranks protocol, a handful of steps each)
-    if distributed and args.workload == "strong" and not args.no_extra:
+    if args.full and distributed and args.workload == "strong" and not args.no_extra:
         # The two extra figures run collectives that the default line does not need (barriers around a second and a
         # third workload, point-to-point sends of the gather).  A rank that fails or hangs inside them must not take the
         # headline down: after MM_BENCH_EXTRA_TIMEOUT seconds (default 240) rank 0 prints the line with what it has and
@@ -830,7 +879,7 @@ def main():
         total_out = int(sum(counts))
 
     # ---------------------------------------------------------------- untimed extras (rank 0, N = 1)
-    if rank == 0 and world == 1 and not args.no_extra:
+    if args.full and rank == 0 and world == 1 and not args.no_extra:
         med, allms = timed_kernel_ms(step)
         median5 = {"kernel_ms": round(med, 4), "Gbases_per_s": round(my_bases / med / 1e6, 1),
                    "all_ms": [round(x, 4) for x in allms],

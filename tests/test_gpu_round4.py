@@ -296,7 +296,7 @@ def test_bench_world2_line_is_strong(sm, gpu):
     env["MM_BENCH_BACKEND"] = "gloo"
     n = 200_000_000
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2",
-                        "--bases", str(n), "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--bases", str(n), "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["scaling"] == "strong"
@@ -320,7 +320,7 @@ def test_bench_extras_cannot_take_the_line_down(sm, gpu):
     env["MM_BENCH_EXTRA_TIMEOUT"] = "0"
     n = 200_000_000
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2",
-                        "--bases", str(n), "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--bases", str(n), "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and line["value"] > 0
