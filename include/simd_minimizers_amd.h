@@ -210,6 +210,69 @@ int mm_run_host_ascii(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *
                       uint64_t n_bases, uint32_t *out_pos, uint32_t *out_sk, uint64_t capacity,
                       uint64_t *out_count);
 
+/* ------------------------------------------------------------------- text */
+
+/* General byte text, the reference's `&[u8]` input (src/lib.rs:59, :71-72): one character per byte, all 256
+ * values legal.  The hasher is mm_hasher_t's rolling rot-xor form with 256-entry tables indexed by the byte:
+ *   h_fw(i) = fw_xor ^ XOR_j rotl(fw[s[i+j]], rot*(k-1-j));  h_rc(i) = rc_xor ^ XOR_j rotl(rc[s[i+j]], rot*j)
+ *   h = canonical ? h_fw + h_rc (wrapping) : h_fw
+ * Canonical windows vote on the bytes themselves: a window is canonical when more than half of its l = k+w-1
+ * bytes have bit 1 set (c & 2; src/canonical.rs:26-28 on the characters as a `&[u8]` yields them). */
+typedef struct mm_text_hasher {
+    uint32_t fw[256];
+    uint32_t rc[256];
+    uint32_t rot;
+    uint32_t canonical;
+    uint32_t fw_xor;
+    uint32_t rc_xor;
+    uint32_t kind; /* mm_hasher_kind_t */
+} mm_text_hasher_t;
+
+/* MulHasher::<CANONICAL>::new(k) over bytes (src/lib.rs:71-72: "for `&[u8]`, mulHash is used").
+ * PARITY UNPINNED: its arithmetic is not in the reference tree and the reference holds no known-answer vector
+ * for it, so this fills the tables with this engine's restatement of the published idea - the character value
+ * times a pseudo-random constant, fw[c] = c * 0x9E3779B1, in NtHasher's rolling form - and a caller who has the
+ * real crate puts ITS per-byte values into mm_text_hasher_t instead.  rc[c] = comp(c) * 0x9E3779B1 where comp
+ * swaps A<->T and C<->G (either case) and keeps every other byte: a complement stated as data, replaceable
+ * like the rest of the table. */
+int mm_text_mul_hasher(mm_text_hasher_t *out, int canonical);
+/* NtHasher (or any 4-symbol hasher) over ASCII DNA (packed-seq AsciiSeq, src/lib.rs:92-98):
+ * fw[c] = h->fw[(c >> 1) & 3], rc[c] = h->rc[(c >> 1) & 3]; rot, canonical, fw_xor, rc_xor, kind copied. */
+int mm_text_hasher_from_dna(mm_text_hasher_t *out, const mm_hasher_t *h);
+
+/* minimizers / canonical_minimizers / closed_syncmers / open_syncmers ... over `&[u8]` (src/lib.rs:240-321)
+ * + .hasher() (:327).  `hasher == NULL` means mm_text_mul_hasher with the matching canonical.  The same
+ * precondition checks and error codes as mm_plan_create.  A text plan is accepted by the mm_run_text_*
+ * entry points only; every other run entry point returns MM_ERR_BAD_MODE for it, and the text entry points
+ * return MM_ERR_BAD_MODE for a plan of mm_plan_create. */
+int mm_plan_create_text(mm_plan_t **out, uint32_t k, uint32_t w, int canonical_windows, mm_mode_t mode,
+                        const mm_text_hasher_t *hasher);
+
+/* Builder::run on device-resident text (src/lib.rs:378-448).  The contract of mm_run_device_async:
+ *  d_text        device pointer to n bytes of text, any alignment
+ *  text_bytes    readable bytes at d_text (>= n, else MM_ERR_CAPACITY)
+ *  win_begin/end half-open window range (win_end = UINT64_MAX: to the last window), output in window order,
+ *                the dedup seam against window win_begin - 1
+ *  d_out_pos / d_out_sk / capacity / d_count   as for mm_run_device_async (d_out_pos == NULL counts only)
+ * n >= 2^32 returns MM_ERR_LEN_TOO_LARGE before anything is touched.  Kernels: the fused text kernel for
+ * w <= 128 and k <= 1024 (one launch; MM_PATH_FUSED), the generic family's text kernels otherwise and under
+ * mm_workspace_force_generic (MM_PATH_GENERIC).  The hasher tables travel through a ring of eight page-locked
+ * staging slots: a call waits only to reuse a slot whose upload, eight distinct table sets back, is still queued. */
+int mm_run_text_device_async(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_text, uint64_t text_bytes,
+                             uint64_t n, uint64_t win_begin, uint64_t win_end, uint32_t *d_out_pos,
+                             uint32_t *d_out_sk, uint64_t capacity, uint64_t *d_count);
+/* Same, then waits and returns the count; MM_ERR_CAPACITY if it exceeded `capacity`. */
+int mm_run_text_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_text, uint64_t text_bytes,
+                       uint64_t n, uint64_t win_begin, uint64_t win_end, uint32_t *d_out_pos, uint32_t *d_out_sk,
+                       uint64_t capacity, uint64_t *out_count);
+/* Window sizes with a PREBUILT fused text instance (every other w <= 128 runs in the fused kernel's run-time-w
+ * instance, larger w in the generic family); the same sizes for canonical_windows 0 and 1.  Writes up to
+ * `capacity` sizes in ascending order to `out` (may be null) and returns how many there are.  No GPU needed. */
+int mm_text_prebuilt_window_sizes(int canonical_windows, uint32_t *out, int capacity);
+/* Builder::run on host text: H2D copy, kernels, D2H copy.  `out_pos == NULL` only counts. */
+int mm_run_text_host(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *text, uint64_t n,
+                     uint32_t *out_pos, uint32_t *out_sk, uint64_t capacity, uint64_t *out_count);
+
 /* ----------------------------------------------------------------- values */
 
 /* Output::values_u64 (src/lib.rs:584-612): k-mer (minimizers) or l-mer (syncmers) at each

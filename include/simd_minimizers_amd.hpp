@@ -50,6 +50,12 @@ struct AsciiSeq {
     uint64_t len;
 };
 
+// general byte text, the reference's &[u8] (src/lib.rs:59): one character per byte, all 256 values legal
+struct TextSeq {
+    const uint8_t *data;
+    uint64_t len;
+};
+
 // seq-hash NtHasher<CANONICAL>::new(k)
 template <bool CANONICAL = true>
 struct NtHasher {
@@ -73,6 +79,17 @@ struct AntiLexHasher {
     mm_hasher_t tables;
     uint32_t k;
     explicit AntiLexHasher(uint32_t k_) : k(k_) { check(mm_antilex_hasher(&tables, k_, CANONICAL)); }
+    bool is_canonical() const { return CANONICAL; }
+};
+
+// MulHasher<CANONICAL>::new(k) over bytes, the default of &[u8] text (src/lib.rs:71-72; PARITY UNPINNED, see
+// mm_text_mul_hasher).  Any mm_text_hasher_t - mm_text_hasher_from_dna of an NtHasher, tables of the caller's own -
+// goes to Builder::hasher as well.
+template <bool CANONICAL = true>
+struct TextMulHasher {
+    mm_text_hasher_t tables;
+    uint32_t k;
+    explicit TextMulHasher(uint32_t k_) : k(k_) { check(mm_text_mul_hasher(&tables, CANONICAL)); }
     bool is_canonical() const { return CANONICAL; }
 };
 
@@ -144,6 +161,17 @@ class Builder {  // src/lib.rs:225-230
         b.hasher_ = h.tables;
         b.has_hasher_ = true;
         return b;
+    }
+    // the hasher of byte text (TextSeq runs); the hasher of 2-bit sequences is kept
+    Builder hasher(const mm_text_hasher_t &h) const {
+        Builder b = *this;
+        b.text_hasher_ = h;
+        b.has_text_hasher_ = true;
+        return b;
+    }
+    template <bool C>
+    Builder hasher(const TextMulHasher<C> &h) const {
+        return hasher(h.tables);
     }
     Builder super_kmers(std::vector<uint32_t> *sk) const {  // src/lib.rs:341 (minimizers only)
         static_assert(SYNCMER == 0, "super_kmers() is only defined for minimizers");
@@ -219,6 +247,32 @@ class Builder {  // src/lib.rs:225-230
         return v;
     }
     std::vector<uint32_t> run_once(PackedSeq seq) const {  // src/lib.rs:364
+        std::vector<uint32_t> v;
+        run(seq, v);
+        return v;
+    }
+    // src/lib.rs:378 on &[u8] text (mm_run_text_host): positions are APPENDED to min_pos with the last() rule.
+    // (No Output: k-mer values of byte text are not defined by this engine.)
+    std::vector<uint32_t> &run(TextSeq seq, std::vector<uint32_t> &min_pos) const {
+        Workspace &ws = ws_ ? *ws_ : Workspace::thread_default();
+        mm_plan_t *plan = nullptr;
+        check(mm_plan_create_text(&plan, k_, w_, CANONICAL, (mm_mode_t)SYNCMER,
+                                  has_text_hasher_ ? &text_hasher_ : nullptr));
+        const uint64_t l = (uint64_t)k_ + w_ - 1;
+        const uint64_t cap = seq.len >= l ? seq.len - l + 1 : 0;
+        std::vector<uint32_t> pos(cap ? cap : 1), sk(sk_ && cap ? cap : 1);
+        uint64_t n = 0;
+        int r = mm_run_text_host(plan, ws.get(), seq.data, seq.len, pos.data(), sk_ ? sk.data() : nullptr, cap, &n);
+        mm_plan_destroy(plan);
+        check(r);
+        size_t first = 0;
+        if (SYNCMER == 0)
+            while (first < n && !min_pos.empty() && pos[first] == min_pos.back()) ++first;
+        min_pos.insert(min_pos.end(), pos.begin() + first, pos.begin() + n);
+        if (sk_) sk_->insert(sk_->end(), sk.begin() + first, sk.begin() + n);
+        return min_pos;
+    }
+    std::vector<uint32_t> run_once(TextSeq seq) const {
         std::vector<uint32_t> v;
         run(seq, v);
         return v;
@@ -302,6 +356,8 @@ class Builder {  // src/lib.rs:225-230
     uint32_t k_, w_;
     mm_hasher_t hasher_{};
     bool has_hasher_ = false;
+    mm_text_hasher_t text_hasher_{};
+    bool has_text_hasher_ = false;
     std::vector<uint32_t> *sk_ = nullptr;
     Workspace *ws_ = nullptr;
 };

@@ -55,6 +55,49 @@ class Hasher(C.Structure):
         return bool(self.canonical)
 
 
+class TextHasher(C.Structure):
+    """The hasher of general byte text: ``Hasher``'s rolling form with 256-entry tables indexed by the byte
+    (see include/simd_minimizers_amd.h: mm_text_hasher_t)."""
+    _fields_ = [("fw", C.c_uint32 * 256), ("rc", C.c_uint32 * 256), ("rot", C.c_uint32),
+                ("canonical", C.c_uint32), ("fw_xor", C.c_uint32), ("rc_xor", C.c_uint32), ("kind", C.c_uint32)]
+
+    @staticmethod
+    def from_tables(fw, rc, rot=7, canonical=True, fw_xor=0, rc_xor=0) -> "TextHasher":
+        h = TextHasher()
+        for i in range(256):
+            h.fw[i] = int(fw[i]) & 0xFFFFFFFF
+            h.rc[i] = int(rc[i]) & 0xFFFFFFFF
+        h.rot = rot
+        h.canonical = 1 if canonical else 0
+        h.fw_xor, h.rc_xor = int(fw_xor) & 0xFFFFFFFF, int(rc_xor) & 0xFFFFFFFF
+        h.kind = 0
+        return h
+
+    @staticmethod
+    def from_dna(hasher: "Hasher") -> "TextHasher":
+        """A 4-symbol hasher over ASCII DNA: fw[c] = hasher.fw[(c >> 1) & 3] (mm_text_hasher_from_dna)."""
+        h = TextHasher()
+        _check(lib().mm_text_hasher_from_dna(C.byref(h), C.byref(hasher)))
+        return h
+
+    def is_canonical(self) -> bool:
+        return bool(self.canonical)
+
+
+_TEXT_TYPES = (bytes, bytearray, memoryview)
+
+
+def _is_text(seq) -> bool:
+    """``&[u8]`` input: bytes, bytearray or a uint8 numpy array (one character per byte, all 256 values legal)."""
+    return isinstance(seq, _TEXT_TYPES) or (isinstance(seq, np.ndarray) and seq.dtype == np.uint8)
+
+
+def _text_array(seq) -> np.ndarray:
+    if isinstance(seq, np.ndarray):
+        return np.ascontiguousarray(seq.reshape(-1))
+    return np.frombuffer(bytes(seq), dtype=np.uint8)
+
+
 _lib = None
 
 
@@ -140,6 +183,16 @@ def lib():
                                     C.c_uint64, vp, vp, C.c_uint64, u64p]
         L.mm_run_host.argtypes = [vp, vp, u8p, C.c_uint64, C.c_uint64, u32p, u32p, C.c_uint64, u64p]
         L.mm_run_host_ascii.argtypes = [vp, vp, u8p, C.c_uint64, u32p, u32p, C.c_uint64, u64p]
+        if hasattr(L, "mm_plan_create_text"):
+            L.mm_text_mul_hasher.argtypes = [C.POINTER(TextHasher), C.c_int]
+            L.mm_text_hasher_from_dna.argtypes = [C.POINTER(TextHasher), C.POINTER(Hasher)]
+            L.mm_plan_create_text.argtypes = [C.POINTER(vp), C.c_uint32, C.c_uint32, C.c_int, C.c_int,
+                                              C.POINTER(TextHasher)]
+            text_args = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, vp, vp, C.c_uint64]
+            L.mm_run_text_device_async.argtypes = text_args + [vp]
+            L.mm_run_text_device.argtypes = text_args + [u64p]
+            L.mm_run_text_host.argtypes = [vp, vp, u8p, C.c_uint64, u32p, u32p, C.c_uint64, u64p]
+            L.mm_text_prebuilt_window_sizes.argtypes = [C.c_int, u32p, C.c_int]
         L.mm_values_u64_device_async.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64,
                                                  C.c_uint32, C.c_int, vp, C.c_uint64, vp]
         L.mm_values_u64_host.argtypes = [vp, u8p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, u32p,
@@ -208,6 +261,8 @@ EXPORTED_SYMBOLS = [
     "mm_device_group_gather_batch", "mm_debug_launch_plan", "mm_debug_launch_lds", "mm_debug_lane_plan",
     "mm_debug_last_lane_table",
     "mm_run_packed_reads_device_async", "mm_run_packed_reads_device", "mm_run_packed_reads_host",
+    "mm_text_mul_hasher", "mm_text_hasher_from_dna", "mm_plan_create_text", "mm_run_text_device_async",
+    "mm_run_text_device", "mm_run_text_host", "mm_text_prebuilt_window_sizes",
 ]
 
 
@@ -217,6 +272,15 @@ def prebuilt_window_sizes(canonical: bool, reads: bool = False) -> list:
     n = L.mm_prebuilt_window_sizes(int(canonical), int(reads), None, 0)
     buf = (C.c_uint32 * max(1, n))()
     L.mm_prebuilt_window_sizes(int(canonical), int(reads), buf, n)
+    return [int(x) for x in buf[:n]]
+
+
+def text_prebuilt_window_sizes(canonical: bool) -> list:
+    """Window sizes with a prebuilt fused text instance (mm_text_prebuilt_window_sizes): what the text tests sweep."""
+    L = lib()
+    n = L.mm_text_prebuilt_window_sizes(int(canonical), None, 0)
+    buf = (C.c_uint32 * max(1, n))()
+    L.mm_text_prebuilt_window_sizes(int(canonical), buf, n)
     return [int(x) for x in buf[:n]]
 
 
@@ -600,6 +664,14 @@ def MulHasher(k: int | None = None, canonical: bool = True) -> Hasher:
     return h
 
 
+def TextMulHasher(k: int | None = None, canonical: bool = True) -> TextHasher:
+    """seq-hash ``MulHasher::<CANONICAL>::new(k)`` over bytes, the default hasher of ``&[u8]`` text
+    (src/lib.rs:71-72).  PARITY UNPINNED: this engine's restatement (mm_text_mul_hasher in the C header)."""
+    h = TextHasher()
+    _check(lib().mm_text_mul_hasher(C.byref(h), int(canonical)))
+    return h
+
+
 def AntiLexHasher(k: int, canonical: bool = True) -> Hasher:
     """seq-hash ``AntiLexHasher::<CANONICAL>::new(k)`` (src/test.rs:83,109).  PARITY UNPINNED."""
     h = Hasher()
@@ -608,10 +680,11 @@ def AntiLexHasher(k: int, canonical: bool = True) -> Hasher:
 
 
 class Plan:
-    def __init__(self, k, w, canonical, mode, hasher):
+    def __init__(self, k, w, canonical, mode, hasher, text=False):
         h = C.c_void_p()
         hp = C.byref(hasher) if hasher is not None else None
-        _check(lib().mm_plan_create(C.byref(h), k, w, int(canonical), mode, hp))
+        create = lib().mm_plan_create_text if text else lib().mm_plan_create
+        _check(create(C.byref(h), k, w, int(canonical), mode, hp))
         self.h = h
 
     def __del__(self):
@@ -624,6 +697,11 @@ class Plan:
 
     def value_len(self) -> int:
         return lib().mm_plan_value_len(self.h)
+
+
+def _no_text_values(seq):
+    if _is_text(seq):
+        raise MinimizerError(ERR["BAD_MODE"], "k-mer values of byte text are not supported (2-bit sequences only)")
 
 
 class Output:
@@ -648,6 +726,7 @@ class Output:
         pos = np.ascontiguousarray(self.min_pos, dtype=np.uint32)
         vals = np.zeros(2 * len(pos), dtype=np.uint64)
         seq = self.seq
+        _no_text_values(seq)
         if isinstance(seq, AsciiSeq):
             seq = PackedSeqVec.from_ascii(seq.seq)
         if len(pos):
@@ -661,6 +740,7 @@ class Output:
         pos = np.ascontiguousarray(self.min_pos, dtype=np.uint32)
         vals = np.zeros(len(pos), dtype=np.uint64)
         seq = self.seq
+        _no_text_values(seq)
         if isinstance(seq, AsciiSeq):
             seq = PackedSeqVec.from_ascii(seq.seq)
         if len(pos):
@@ -673,21 +753,27 @@ class Output:
 class Builder:
     """``Builder<CANONICAL, H, SkPos, SYNCMER>`` (src/lib.rs:225-230)."""
 
-    def __init__(self, k, w, canonical, mode, hasher=None, sk_pos=None, workspace=None):
+    def __init__(self, k, w, canonical, mode, hasher=None, sk_pos=None, workspace=None, text_hasher=None):
         self.k, self.w, self.canonical, self.mode = k, w, canonical, mode
         self._hasher, self._sk, self._workspace = hasher, sk_pos, workspace
+        self._text_hasher = text_hasher  # hasher of byte text (None: TextMulHasher, the default of ``&[u8]``)
         self._plan = None
+        self._text_plan = None
 
-    def hasher(self, hasher: Hasher) -> "Builder":  # src/lib.rs:327
-        return Builder(self.k, self.w, self.canonical, self.mode, hasher, self._sk, self._workspace)
+    def hasher(self, hasher) -> "Builder":  # src/lib.rs:327
+        """A ``Hasher`` for 2-bit sequences, or a ``TextHasher`` for byte text; the other kind is kept."""
+        if isinstance(hasher, TextHasher):
+            return Builder(self.k, self.w, self.canonical, self.mode, self._hasher, self._sk, self._workspace, hasher)
+        return Builder(self.k, self.w, self.canonical, self.mode, hasher, self._sk, self._workspace, self._text_hasher)
 
     def super_kmers(self, sk_pos: list) -> "Builder":  # src/lib.rs:341 (minimizers only)
         if self.mode != MM_MINIMIZERS:
             raise MinimizerError(ERR["BAD_MODE"], "super_kmers() is only defined for minimizers")
-        return Builder(self.k, self.w, self.canonical, self.mode, self._hasher, sk_pos, self._workspace)
+        return Builder(self.k, self.w, self.canonical, self.mode, self._hasher, sk_pos, self._workspace,
+                       self._text_hasher)
 
     def workspace(self, ws: Workspace) -> "Builder":
-        return Builder(self.k, self.w, self.canonical, self.mode, self._hasher, self._sk, ws)
+        return Builder(self.k, self.w, self.canonical, self.mode, self._hasher, self._sk, ws, self._text_hasher)
 
     def _ws(self) -> Workspace:
         return self._workspace or default_workspace()
@@ -696,6 +782,12 @@ class Builder:
         if self._plan is None:
             self._plan = Plan(self.k, self.w, self.canonical, self.mode, self._hasher)
         return self._plan
+
+    def text_plan(self) -> Plan:
+        """The plan of byte-text runs (mm_plan_create_text)."""
+        if self._text_plan is None:
+            self._text_plan = Plan(self.k, self.w, self.canonical, self.mode, self._text_hasher, text=True)
+        return self._text_plan
 
     # -- host sequences -------------------------------------------------
     def run(self, seq, min_pos: list) -> Output:
@@ -744,8 +836,8 @@ class Builder:
     def _run_arrays(self, seq):
         L = lib()
         ws = self._ws()
-        plan = self.plan()
         n = len(seq)
+        plan = self.text_plan() if _is_text(seq) else self.plan()
         lwin = self.k + self.w - 1
         cap = max(1, n - lwin + 1) if n >= lwin else 1
         pos = np.zeros(cap, dtype=np.uint32)
@@ -753,7 +845,11 @@ class Builder:
         sk = np.zeros(cap, dtype=np.uint32) if want_sk else None
         cnt = C.c_uint64()
         skp = _p(sk, C.c_uint32) if want_sk else None
-        if isinstance(seq, AsciiSeq):
+        if _is_text(seq):  # ``&[u8]`` (src/lib.rs:59): the text path
+            a = _text_array(seq)
+            _check(L.mm_run_text_host(self.text_plan().h, ws.h, _p(a, C.c_uint8) if n else None, n,
+                                      _p(pos, C.c_uint32), skp, cap, C.byref(cnt)))
+        elif isinstance(seq, AsciiSeq):
             a = np.frombuffer(seq.seq, dtype=np.uint8)
             _check(L.mm_run_host_ascii(plan.h, ws.h, _p(a, C.c_uint8) if n else None, n,
                                        _p(pos, C.c_uint32), skp, cap, C.byref(cnt)))
@@ -840,6 +936,26 @@ class Builder:
             _check(code)
             return cnt.value
         _check(L.mm_run_device_async(*args, C.c_void_p(d_count.data_ptr()) if d_count is not None else None))
+        return None
+
+    def run_text_device(self, d_text, n: int, out_pos, out_sk=None, win_begin: int = 0, win_end: int = U64_MAX,
+                        sync: bool = True, d_count=None):
+        """Run on device-resident byte text (``&[u8]``; a torch uint8 CUDA tensor of at least ``n`` bytes).
+        ``out_pos``/``out_sk``/``d_count`` as for ``run_device``.  Returns the count if ``sync``."""
+        L = lib()
+        cap = out_pos.numel() if out_pos is not None else 0
+        args = [self.text_plan().h, self._ws().h, C.c_void_p(d_text.data_ptr()) if d_text is not None else None,
+                d_text.numel() if d_text is not None else 0, n, win_begin, win_end,
+                C.c_void_p(out_pos.data_ptr()) if out_pos is not None else None,
+                C.c_void_p(out_sk.data_ptr()) if out_sk is not None else None, cap]
+        if sync:
+            cnt = C.c_uint64()
+            code = L.mm_run_text_device(*args, C.byref(cnt))
+            if code == ERR["CAPACITY"]:
+                raise MinimizerError(code, f"output capacity {cap} < {cnt.value}")
+            _check(code)
+            return cnt.value
+        _check(L.mm_run_text_device_async(*args, C.c_void_p(d_count.data_ptr()) if d_count is not None else None))
         return None
 
 

@@ -126,6 +126,25 @@ mm::HashTables make_tables(const mm_hasher_t &h, uint32_t k) {
     return t;
 }
 
+// The rolling tables of a text hasher for one k (TextTables, mm_launch.h): make_tables' algebra with the (out, in) pair
+// split into two look-ups, the constant XOR terms folded into t_in.
+mm::TextTables make_text_tables(const mm_text_hasher_t &h, uint32_t k) {
+    mm::TextTables t;
+    const uint32_t R = h.rot & 31u;
+    const uint32_t df = rotl32(h.fw_xor, R) ^ h.fw_xor, dr = rotr32(h.rc_xor, R) ^ h.rc_xor;
+    for (int c = 0; c < 256; ++c) {
+        t.t_in[c].x = h.fw[c] ^ df;
+        t.t_in[c].y = rotl32(h.rc[c], (uint32_t)(((uint64_t)R * (k - 1)) & 31u)) ^ dr;
+        t.t_out[c].x = rotl32(h.fw[c], (uint32_t)(((uint64_t)R * k) & 31u));
+        t.t_out[c].y = rotr32(h.rc[c], R);
+    }
+    t.fw0 = h.fw_xor;
+    t.rc0 = h.rc_xor;
+    t.rot = R;
+    t.canonical = h.canonical ? 1u : 0u;
+    return t;
+}
+
 }  // namespace
 
 struct mm_plan {
@@ -134,6 +153,9 @@ struct mm_plan {
     uint32_t mode;
     mm_hasher_t hasher;
     mm::HashTables ht;
+    // text plans (mm_plan_create_text): byte input, 256-entry tables; hasher / ht above are unused
+    bool text = false;
+    mm::TextTables tt;
 };
 
 struct mm_workspace {
@@ -214,6 +236,14 @@ struct mm_workspace {
     uint64_t d_amb_bytes = 0;
     unsigned long long *d_vals = nullptr;
     uint64_t d_vals_elems = 0;
+    // text runs: a ring of device copies of text plans' tables, staged through page-locked slots; a slot is rewritten only
+    // after the event of its last upload (kTextTableSlots - 1 other uploads later), so no text call waits for the stream
+    static const int kTextTableSlots = 8;
+    mm::TextTables *d_text_tables = nullptr;  // [kTextTableSlots]
+    mm::TextTables *h_text_tables = nullptr;  // [kTextTableSlots] page-locked: what each device slot holds
+    hipEvent_t ev_text_tables[kTextTableSlots] = {};
+    bool text_slot_used[kTextTableSlots] = {};
+    int text_slot_next = 0;
     // knobs / diagnostics
     bool force_generic = false;
     uint32_t nblk = 0;
@@ -501,6 +531,82 @@ int mm_plan_create(mm_plan_t **out, uint32_t k, uint32_t w, int canonical_window
     return MM_OK;
 }
 
+// PARITY UNPINNED, like mm_mul_hasher: "multiplies each character value by a pseudo-random constant"
+// (src/lib.rs:71-72) over bytes, in NtHasher's rolling form; the constant and the complement are this engine's.
+int mm_text_mul_hasher(mm_text_hasher_t *out, int canonical) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (!out) return MM_ERR_NULL;
+    for (uint32_t c = 0; c < 256; ++c) {
+        uint32_t comp = c;
+        switch (c) {
+            case 'A': comp = 'T'; break;
+            case 'T': comp = 'A'; break;
+            case 'C': comp = 'G'; break;
+            case 'G': comp = 'C'; break;
+            case 'a': comp = 't'; break;
+            case 't': comp = 'a'; break;
+            case 'c': comp = 'g'; break;
+            case 'g': comp = 'c'; break;
+            default: break;
+        }
+        out->fw[c] = c * 0x9E3779B1u;
+        out->rc[c] = comp * 0x9E3779B1u;
+    }
+    out->rot = 7;
+    out->canonical = canonical ? 1u : 0u;
+    out->fw_xor = out->rc_xor = 0;
+    out->kind = MM_HASHER_MUL;
+    return MM_OK;
+}
+
+// packed-seq AsciiSeq's code of a byte, (c >> 1) & 3 (src/lib.rs:92-98), as a table over all 256 bytes
+int mm_text_hasher_from_dna(mm_text_hasher_t *out, const mm_hasher_t *h) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (!out || !h) return MM_ERR_NULL;
+    for (uint32_t c = 0; c < 256; ++c) {
+        out->fw[c] = h->fw[(c >> 1) & 3u];
+        out->rc[c] = h->rc[(c >> 1) & 3u];
+    }
+    out->rot = h->rot;
+    out->canonical = h->canonical;
+    out->fw_xor = h->fw_xor;
+    out->rc_xor = h->rc_xor;
+    out->kind = h->kind;
+    return MM_OK;
+}
+
+int mm_plan_create_text(mm_plan_t **out, uint32_t k, uint32_t w, int canonical_windows, mm_mode_t mode,
+                        const mm_text_hasher_t *hasher) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (!out) return MM_ERR_NULL;
+    *out = nullptr;
+    // (the checks of mm_plan_create, in its order)
+    if (k == 0) return MM_ERR_K_ZERO;
+    if (w == 0) return MM_ERR_W_ZERO;
+    if (w >= (1u << 15)) return MM_ERR_W_TOO_LARGE;
+    if ((int)mode < 0 || (int)mode > 2) return MM_ERR_BAD_MODE;
+    if (mode == MM_OPEN_SYNCMERS && w % 2 == 0) return MM_ERR_OPEN_EVEN_W;
+    mm_text_hasher_t h;
+    if (hasher) h = *hasher;
+    else mm_text_mul_hasher(&h, canonical_windows);
+    if (canonical_windows) {
+        if (!h.canonical) return MM_ERR_HASHER_NOT_CANONICAL;
+        if (((uint64_t)k + w - 1) % 2 == 0) return MM_ERR_EVEN_L;
+    }
+    mm_plan *p = new (std::nothrow) mm_plan;
+    if (!p) return MM_ERR_ALLOC;
+    p->k = k;
+    p->w = w;
+    p->canonical_windows = canonical_windows ? 1 : 0;
+    p->mode = (uint32_t)mode;
+    memset(&p->hasher, 0, sizeof(p->hasher));
+    memset(&p->ht, 0, sizeof(p->ht));
+    p->text = true;
+    p->tt = make_text_tables(h, k);
+    *out = p;
+    return MM_OK;
+}
+
 void mm_plan_destroy(mm_plan_t *plan) { delete plan; }
 
 uint32_t mm_plan_value_len(const mm_plan_t *plan) {
@@ -621,6 +727,10 @@ void mm_workspace_destroy(mm_workspace_t *ws) {
     if (ws->h_small) hipHostFree(ws->h_small);
     if (ws->d_amb) hipFree(ws->d_amb);
     if (ws->d_vals) hipFree(ws->d_vals);
+    if (ws->d_text_tables) hipFree(ws->d_text_tables);
+    if (ws->h_text_tables) hipHostFree(ws->h_text_tables);
+    for (int i = 0; i < mm_workspace::kTextTableSlots; ++i)
+        if (ws->ev_text_tables[i]) hipEventDestroy(ws->ev_text_tables[i]);
     if (ws->own_stream && ws->stream) hipStreamDestroy(ws->stream);
     delete ws;
 }
@@ -832,6 +942,12 @@ int mm_debug_last_lane_table(mm_workspace_t *ws, uint32_t *out4, uint64_t capaci
 
 uint64_t mm_fused_overread_bytes(void) { return mm::fused_overread_bytes(); }
 
+int mm_text_prebuilt_window_sizes(int canonical_windows, uint32_t *out, int capacity) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    (void)canonical_windows;  // (the same sizes for both strands)
+    return mm::text_prebuilt_windows(out, capacity < 0 ? 0 : capacity);
+}
+
 int mm_prebuilt_window_sizes(int canonical_windows, int reads_mode, uint32_t *out, int capacity) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
     return mm::fused_prebuilt_windows(canonical_windows != 0, reads_mode != 0, out, capacity < 0 ? 0 : capacity);
@@ -1033,6 +1149,7 @@ int mm_run_device_async(const mm_plan_t *plan, mm_workspace_t *ws, const void *d
                         uint64_t win_begin, uint64_t win_end, uint32_t *d_out_pos,
                         uint32_t *d_out_sk, uint64_t capacity, uint64_t *d_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
     if (ws) ws->async_unchecked = true;
     return run_device_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_bases, win_begin,
                                  win_end, d_out_pos, d_out_sk, capacity, d_count, false);
@@ -1400,6 +1517,7 @@ int mm_run_batch_device(const mm_plan_t *plan, mm_workspace_t *ws, uint64_t n_se
                         uint32_t *d_out_pos, uint32_t *d_out_sk, uint64_t capacity,
                         uint64_t *out_offsets) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
     if (!plan || !ws || !out_offsets) return MM_ERR_NULL;
     if (n_seqs && (!d_packed || !packed_bytes || !n_bases)) return MM_ERR_NULL;
     MM_HIP(set_device(ws->device));
@@ -1619,6 +1737,7 @@ int mm_run_packed_reads_device_async(const mm_plan_t *plan, mm_workspace_t *ws, 
                                      uint32_t *d_out_pos, uint32_t *d_out_sk, uint64_t capacity, uint64_t *d_out_offsets,
                                      uint64_t *d_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
     if (!d_read_starts && n_reads) return MM_ERR_NULL;
     if (ws) ws->async_unchecked = true;
     return run_reads_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_reads, 0, max_read_len, nullptr, d_out_pos,
@@ -1630,6 +1749,7 @@ int mm_run_packed_reads_device(const mm_plan_t *plan, mm_workspace_t *ws, const 
                                uint32_t max_read_len, uint32_t *d_out_pos, uint32_t *d_out_sk, uint64_t capacity,
                                uint64_t *d_out_offsets, uint64_t *out_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
     if (!ws || (!d_read_starts && n_reads)) return MM_ERR_NULL;
     for (int attempt = 0; attempt < 2; ++attempt) {
         int r = run_reads_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_reads, 0, max_read_len, nullptr,
@@ -1652,6 +1772,7 @@ int mm_run_reads_device_async(const mm_plan_t *plan, mm_workspace_t *ws, const v
                               uint32_t *d_out_pos, uint64_t capacity, uint64_t *d_out_offsets,
                               uint64_t *d_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
     if (ws) ws->async_unchecked = true;
     return run_reads_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_reads, read_stride,
                                 read_len, d_read_lens, d_out_pos, capacity, d_out_offsets, d_count);
@@ -1686,6 +1807,7 @@ int mm_run_reads_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d
                         uint32_t *d_out_pos, uint64_t capacity, uint64_t *d_out_offsets,
                         uint64_t *out_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
     return run_reads_sync(plan, ws, d_packed, packed_bytes, base_offset, n_reads, read_stride, read_len,
                           d_read_lens, d_out_pos, capacity, d_out_offsets, out_count, nullptr);
 }
@@ -1696,6 +1818,7 @@ int mm_run_reads_superkmers_device_async(const mm_plan_t *plan, mm_workspace_t *
                                          uint32_t *d_out_pos, uint32_t *d_out_sk, uint64_t capacity,
                                          uint64_t *d_out_offsets, uint64_t *d_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
     if (ws) ws->async_unchecked = true;
     if (!d_out_sk) return MM_ERR_NULL;
     return run_reads_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_reads, read_stride,
@@ -1709,6 +1832,7 @@ int mm_run_reads_superkmers_device(const mm_plan_t *plan, mm_workspace_t *ws, co
                                    uint32_t *d_out_pos, uint32_t *d_out_sk, uint64_t capacity,
                                    uint64_t *d_out_offsets, uint64_t *out_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
     if (!d_out_sk) return MM_ERR_NULL;
     return run_reads_sync(plan, ws, d_packed, packed_bytes, base_offset, n_reads, read_stride, read_len,
                           d_read_lens, d_out_pos, capacity, d_out_offsets, out_count, nullptr, d_out_sk);
@@ -1722,6 +1846,7 @@ int mm_run_reads_skip_ambiguous_device_async(const mm_plan_t *plan, mm_workspace
                                              uint32_t *d_out_pos, uint64_t capacity,
                                              uint64_t *d_out_offsets, uint64_t *d_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
     if (ws) ws->async_unchecked = true;
     const AmbArgs amb{d_amb, amb_bytes, amb_offset};
     return run_reads_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_reads, read_stride,
@@ -1735,6 +1860,7 @@ int mm_run_reads_skip_ambiguous_device(const mm_plan_t *plan, mm_workspace_t *ws
                                        const uint32_t *d_read_lens, uint32_t *d_out_pos,
                                        uint64_t capacity, uint64_t *d_out_offsets, uint64_t *out_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
     const AmbArgs amb{d_amb, amb_bytes, amb_offset};
     return run_reads_sync(plan, ws, d_packed, packed_bytes, base_offset, n_reads, read_stride, read_len,
                           d_read_lens, d_out_pos, capacity, d_out_offsets, out_count, &amb);
@@ -1747,6 +1873,7 @@ int mm_run_skip_ambiguous_device_async(const mm_plan_t *plan, mm_workspace_t *ws
                                        uint64_t win_begin, uint64_t win_end, uint32_t *d_out_pos,
                                        uint64_t capacity, uint64_t *d_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
     if (ws) ws->async_unchecked = true;
     const AmbArgs amb{d_amb, amb_bytes, amb_offset};
     return run_device_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_bases, win_begin,
@@ -1797,6 +1924,7 @@ int mm_run_skip_ambiguous_device(const mm_plan_t *plan, mm_workspace_t *ws, cons
                                  uint64_t win_begin, uint64_t win_end, uint32_t *d_out_pos,
                                  uint64_t capacity, uint64_t *out_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
     const AmbArgs amb{d_amb, amb_bytes, amb_offset};
     return run_device_sync(plan, ws, d_packed, packed_bytes, base_offset, n_bases, win_begin, win_end,
                            d_out_pos, nullptr, capacity, out_count, &amb);
@@ -1807,6 +1935,7 @@ int mm_run_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packe
                   uint64_t win_begin, uint64_t win_end, uint32_t *d_out_pos, uint32_t *d_out_sk,
                   uint64_t capacity, uint64_t *out_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
     return run_device_sync(plan, ws, d_packed, packed_bytes, base_offset, n_bases, win_begin, win_end,
                            d_out_pos, d_out_sk, capacity, out_count, nullptr);
 }
@@ -2192,6 +2321,7 @@ int mm_run_host(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *packed
                 uint64_t base_offset, uint64_t n_bases, uint32_t *out_pos, uint32_t *out_sk,
                 uint64_t capacity, uint64_t *out_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
     if (!plan || !ws) return MM_ERR_NULL;
     if (n_bases >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
     if (out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;
@@ -2223,6 +2353,7 @@ int mm_run_packed_reads_host(const mm_plan_t *plan, mm_workspace_t *ws, const ui
                              const uint64_t *read_starts, uint32_t max_read_len, uint32_t *out_pos, uint32_t *out_sk,
                              uint64_t capacity, uint64_t *out_offsets, uint64_t *out_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
     if (!plan || !ws || !out_offsets) return MM_ERR_NULL;
     if (n_reads && (!read_starts || !packed)) return MM_ERR_NULL;
     if (out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;
@@ -2266,6 +2397,7 @@ int mm_run_host_ascii(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *
                       uint64_t n_bases, uint32_t *out_pos, uint32_t *out_sk, uint64_t capacity,
                       uint64_t *out_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
     if (!plan || !ws) return MM_ERR_NULL;
     if (n_bases >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
     if (out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;
@@ -2288,11 +2420,189 @@ int mm_run_host_ascii(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *
                            out_count);
 }
 
+// ------------------------------------------------------------------- text
+// General byte text (&[u8]): the generic family's text kernels (mm_generic.hip).  The contracts of the packed twins.
+// The device copy of a text plan's tables on this workspace: a slot that holds them already, else the next slot of the ring,
+// uploaded on the workspace stream (ordered behind every earlier launch that reads the slot's old tables).
+static int text_tables_on_device(mm_workspace_t *ws, const mm::TextTables &tt, const mm::TextTables **out) {
+    const int S = mm_workspace::kTextTableSlots;
+    if (!ws->d_text_tables) {
+        MM_HIP(hipMalloc(&ws->d_text_tables, S * sizeof(mm::TextTables)));
+        MM_HIP(hipHostMalloc(&ws->h_text_tables, S * sizeof(mm::TextTables), hipHostMallocDefault));
+        for (int i = 0; i < S; ++i) MM_HIP(hipEventCreateWithFlags(&ws->ev_text_tables[i], hipEventDisableTiming));
+    }
+    for (int i = 0; i < S; ++i)
+        if (ws->text_slot_used[i] && memcmp(&ws->h_text_tables[i], &tt, sizeof(tt)) == 0) {
+            *out = ws->d_text_tables + i;
+            return MM_OK;
+        }
+    const int i = ws->text_slot_next;
+    ws->text_slot_next = (i + 1) % S;
+    // (the page-locked slot is rewritten only after its previous upload has left it)
+    if (ws->text_slot_used[i]) MM_HIP(hipEventSynchronize(ws->ev_text_tables[i]));
+    ws->h_text_tables[i] = tt;
+    ws->text_slot_used[i] = true;
+    MM_HIP(hipMemcpyAsync(ws->d_text_tables + i, ws->h_text_tables + i, sizeof(tt), hipMemcpyHostToDevice, ws->stream));
+    MM_HIP(hipEventRecord(ws->ev_text_tables[i], ws->stream));
+    *out = ws->d_text_tables + i;
+    return MM_OK;
+}
+
+static int run_text_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_text, uint64_t text_bytes,
+                               uint64_t n, uint64_t win_begin, uint64_t win_end, uint32_t *d_out_pos,
+                               uint32_t *d_out_sk, uint64_t capacity, uint64_t *d_count) {
+    if (!plan || !ws) return MM_ERR_NULL;
+    if (!plan->text) return MM_ERR_BAD_MODE;  // (a plan of mm_plan_create: packed entry points only)
+    if (n >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
+    if (d_out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;  // src/lib.rs:339
+    if (!d_out_pos) capacity = 0;
+    const uint64_t l = (uint64_t)plan->k + plan->w - 1;
+    const uint64_t n_w = n >= l ? n - l + 1 : 0;
+    if (win_end > n_w) win_end = n_w;
+    if (win_begin < win_end) {  // (every check before the first stream operation)
+        if (!d_text) return MM_ERR_NULL;
+        if (text_bytes < n) return MM_ERR_CAPACITY;
+    }
+    MM_HIP(set_device(ws->device));
+    MM_HIP(hipMemsetAsync(ws->total, 0, 2 * sizeof(unsigned long long), ws->stream));
+    if (win_begin < win_end) {
+        mm::TextRunArgs a;
+        int r = text_tables_on_device(ws, plan->tt, &a.tables);
+        if (r) return r;
+        a.text = static_cast<const uint8_t *>(d_text);
+        a.n = n;
+        a.k = plan->k;
+        a.w = plan->w;
+        a.canonical_windows = plan->canonical_windows;
+        a.mode = plan->mode;
+        a.win_begin = win_begin;
+        a.win_end = win_end;
+        a.out.pos = d_out_pos;
+        a.out.sk = d_out_sk;
+        a.out.cap = capacity;
+        a.out.total = ws->total;
+        a.out.ticket = ws->ticket;
+        a.out.error = reinterpret_cast<uint32_t *>(ws->total + 1);
+        a.timing_start = a.timing_stop = nullptr;
+        a.hash_rc = plan->tt.canonical != 0;
+        a.fw0 = plan->tt.fw0;
+        a.rc0 = plan->tt.rc0;
+        a.rot = plan->tt.rot;
+        a.scratch = nullptr;
+        a.generic_round_windows = 0;
+        const uint64_t nwin = win_end - win_begin;
+        const bool fused = !ws->force_generic && mm::text_walk_supported(plan->k, plan->w);
+        if (fused) {
+            r = grow_status(ws, mm::text_walk_tiles(nwin) + 1);
+            if (r) return r;
+        } else {
+            a.generic_round_windows = nwin < (1ull << 24) ? nwin : (1ull << 24);
+            uint8_t *sp = reinterpret_cast<uint8_t *>(ws->scratch);
+            r = grow(sp, ws->scratch_bytes, mm::generic_scratch_bytes(a.generic_round_windows, plan->w), 1);
+            ws->scratch = sp;
+            if (r) return r;
+            a.scratch = ws->scratch;
+            r = grow_status(ws, mm::generic_status_words(a.generic_round_windows));
+            if (r) return r;
+        }
+        a.out.status = ws->status;
+        ws->status_dirty = true;  // (both text families clear and write untagged words)
+        if (ws->timing) {
+            hipEvent_t e0, e1;
+            MM_HIP(hipEventCreate(&e0));
+            MM_HIP(hipEventCreate(&e1));
+            ws->events.emplace_back(e0, e1);
+            a.timing_start = e0;
+            a.timing_stop = e1;
+        }
+        if ((fused ? mm::launch_text_walk(a, ws->stream) : mm::launch_generic_text(a, ws->stream)) != 0) {
+            g_last_error = std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError());
+            return MM_ERR_HIP;
+        }
+        ws->last_path = fused ? MM_PATH_FUSED : MM_PATH_GENERIC;
+    }
+    if (d_count)
+        MM_HIP(hipMemcpyAsync(d_count, ws->total, sizeof(unsigned long long), hipMemcpyDeviceToDevice, ws->stream));
+    return MM_OK;
+}
+
+int mm_run_text_device_async(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_text, uint64_t text_bytes,
+                             uint64_t n, uint64_t win_begin, uint64_t win_end, uint32_t *d_out_pos,
+                             uint32_t *d_out_sk, uint64_t capacity, uint64_t *d_count) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (ws) ws->async_unchecked = true;
+    return run_text_async_impl(plan, ws, d_text, text_bytes, n, win_begin, win_end, d_out_pos, d_out_sk, capacity,
+                               d_count);
+}
+
+static int run_text_sync(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_text, uint64_t text_bytes,
+                         uint64_t n, uint64_t win_begin, uint64_t win_end, uint32_t *d_out_pos, uint32_t *d_out_sk,
+                         uint64_t capacity, uint64_t *out_count) {
+    if (!ws) return MM_ERR_NULL;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        // (as run_device_sync: an unchecked asynchronous run finishes before the words are reused)
+        if (ws->async_unchecked) MM_HIP(hipStreamSynchronize(ws->stream));
+        int r = run_text_async_impl(plan, ws, d_text, text_bytes, n, win_begin, win_end, d_out_pos, d_out_sk,
+                                    capacity, nullptr);
+        if (r) return r;
+        MM_HIP(hipMemcpyAsync(ws->h_total, ws->total, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                              ws->stream));
+        MM_HIP(hipStreamSynchronize(ws->stream));
+        const int je = judge_run_error(ws);
+        if (je < 0) return je;
+        if (je == 0) break;
+    }
+    if (out_count) *out_count = ws->h_total[0];
+    if (d_out_pos && ws->h_total[0] > capacity) return MM_ERR_CAPACITY;
+    return MM_OK;
+}
+
+int mm_run_text_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_text, uint64_t text_bytes,
+                       uint64_t n, uint64_t win_begin, uint64_t win_end, uint32_t *d_out_pos, uint32_t *d_out_sk,
+                       uint64_t capacity, uint64_t *out_count) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    return run_text_sync(plan, ws, d_text, text_bytes, n, win_begin, win_end, d_out_pos, d_out_sk, capacity,
+                         out_count);
+}
+
+int mm_run_text_host(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *text, uint64_t n,
+                     uint32_t *out_pos, uint32_t *out_sk, uint64_t capacity, uint64_t *out_count) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (!plan || !ws) return MM_ERR_NULL;
+    if (!plan->text) return MM_ERR_BAD_MODE;
+    if (n >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
+    if (out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;
+    if (n && !text) return MM_ERR_NULL;
+    MM_HIP(set_device(ws->device));
+    const uint64_t l = (uint64_t)plan->k + plan->w - 1;
+    const uint64_t n_w = n >= l ? n - l + 1 : 0;
+    const uint64_t cap = out_pos ? (capacity < n_w ? capacity : n_w) : 0;
+    uint8_t *dtext = reinterpret_cast<uint8_t *>(ws->d_ascii);
+    int r = grow(dtext, ws->d_ascii_bytes, n + 16, 1);
+    ws->d_ascii = dtext;
+    if (r == MM_OK) r = grow(ws->d_out, ws->d_out_elems, cap ? cap : 1, sizeof(uint32_t));
+    if (r == MM_OK && out_sk) r = grow(ws->d_sk, ws->d_sk_elems, cap ? cap : 1, sizeof(uint32_t));
+    if (r) return r;
+    if (n) MM_HIP(hipMemcpyAsync(dtext, text, n, hipMemcpyHostToDevice, ws->stream));
+    uint64_t count = 0;
+    r = run_text_sync(plan, ws, dtext, n, n, 0, UINT64_MAX, cap ? ws->d_out : nullptr, (out_sk && cap) ? ws->d_sk : nullptr,
+                      cap, &count);
+    if (out_count) *out_count = count;
+    if (r) return r;
+    if (out_pos && count) {
+        MM_HIP(hipMemcpyAsync(out_pos, ws->d_out, count * sizeof(uint32_t), hipMemcpyDeviceToHost, ws->stream));
+        if (out_sk) MM_HIP(hipMemcpyAsync(out_sk, ws->d_sk, count * sizeof(uint32_t), hipMemcpyDeviceToHost, ws->stream));
+        MM_HIP(hipStreamSynchronize(ws->stream));
+    }
+    return MM_OK;
+}
+
 int mm_run_skip_ambiguous_host(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *packed,
                                uint64_t base_offset, const uint8_t *amb, uint64_t amb_offset,
                                uint64_t n_bases, uint32_t *out_pos, uint64_t capacity,
                                uint64_t *out_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
     if (!plan || !ws) return MM_ERR_NULL;
     if (n_bases >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
     if (!plan->canonical_windows) return MM_ERR_HASHER_NOT_CANONICAL;
@@ -2321,6 +2631,7 @@ int mm_run_skip_ambiguous_host_ascii(const mm_plan_t *plan, mm_workspace_t *ws, 
                                      uint64_t n_bases, uint32_t *out_pos, uint64_t capacity,
                                      uint64_t *out_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
     if (!plan || !ws) return MM_ERR_NULL;
     if (n_bases >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
     if (!plan->canonical_windows) return MM_ERR_HASHER_NOT_CANONICAL;
@@ -2999,6 +3310,7 @@ int mm_run_sharded_host(const mm_plan_t *plan, mm_device_group_t *g, const uint8
                         uint64_t n_bases, uint32_t *out_pos, uint32_t *out_sk, uint64_t capacity,
                         uint64_t *out_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
     if (!plan || !g || g->ws.empty()) return MM_ERR_NULL;
     if (n_bases >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
     if (out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;
@@ -3098,6 +3410,7 @@ int mm_run_sharded_host(const mm_plan_t *plan, mm_device_group_t *g, const uint8
 int mm_run_sharded_device(const mm_plan_t *plan, mm_device_group_t *g, uint64_t base_offset, uint64_t n_bases,
                           int want_superkmers, uint64_t *counts, uint64_t *total) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
     if (!plan || !g || g->ws.empty()) return MM_ERR_NULL;
     if (g->seq_bytes == 0) {
         g_last_error = "mm_run_sharded_device: no resident sequence (mm_device_group_upload / _adopt first)";
@@ -3311,6 +3624,7 @@ int mm_device_group_upload_batch(mm_device_group_t *g, uint64_t n_seqs, const ui
 int mm_run_batch_sharded_device(const mm_plan_t *plan, mm_device_group_t *g, const uint64_t *base_offsets,
                                 const uint64_t *n_bases, int want_superkmers, uint64_t *out_counts, uint64_t *total) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
     if (!plan || !g || g->ws.empty() || g->batch.size() != g->ws.size() || !n_bases) return MM_ERR_NULL;
     if (want_superkmers && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;
     const uint64_t N = g->ws.size(), n_seqs = g->seq_entry.size();
@@ -3492,6 +3806,7 @@ int mm_run_batch_sharded_host(const mm_plan_t *plan, mm_device_group_t *g, uint6
                               const uint8_t *const *packed, const uint64_t *base_offsets, const uint64_t *n_bases,
                               uint32_t *out_pos, uint32_t *out_sk, uint64_t capacity, uint64_t *out_offsets) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
     if (!plan || !g || g->ws.empty() || !out_offsets) return MM_ERR_NULL;
     if (n_seqs && (!packed || !n_bases)) return MM_ERR_NULL;
     if (out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;

@@ -163,35 +163,128 @@ __global__ __launch_bounds__(kBlockThreads) void generic_compact_kernel(
     if (tid == 0 && bid == gridDim.x - 1) *out.total = s_excl + block_total;
 }
 
-// --------------------------------------------------------------- launcher
-int launch_generic(const RunArgs &a, hipStream_t stream) {
-    // a.scratch holds: hash (u32 per k-mer of a round) then winpos (u32 per window of a round)
-    const uint64_t round = a.generic_round_windows;
-    uint32_t *hash = reinterpret_cast<uint32_t *>(a.scratch);
-    uint32_t *winpos = hash + (round + a.w + 1);
-    if (a.timing_start) hipEventRecord(a.timing_start, stream);
-    for (uint64_t wb = a.win_begin; wb < a.win_end; wb += round) {
-        uint64_t we = wb + round < a.win_end ? wb + round : a.win_end;
-        uint64_t win_first = wb > 0 ? wb - 1 : 0;  // one extra window in front for the dedup seam
-        uint64_t km_begin = win_first, km_end = we + a.w - 1;
-        uint64_t n_km = km_end - km_begin;
-        uint32_t g1 = (uint32_t)((n_km + (uint64_t)kBlockThreads * kKmersPerLane - 1) /
-                                 ((uint64_t)kBlockThreads * kKmersPerLane));
-        hipLaunchKernelGGL(generic_hash_kernel, dim3(g1), dim3(kBlockThreads), 0, stream, a.seq,
-                           a.ht, a.k, km_begin, km_end, hash);
-        uint64_t n_w = we - win_first;
-        uint32_t g2 = (uint32_t)((n_w + kBlockThreads - 1) / kBlockThreads);
-        hipLaunchKernelGGL(generic_window_kernel, dim3(g2), dim3(kBlockThreads), 0, stream, a.seq,
-                           a.k, a.w, a.canonical_windows, km_begin, hash, win_first, we, winpos, a.wamb);
-        uint32_t g3 = (uint32_t)((we - wb + kWinPerBlockC - 1) / kWinPerBlockC);
-        if (hipMemsetAsync(a.out.status, 0, sizeof(unsigned long long) * g3, stream) != hipSuccess)
-            return -1;
-        if (hipMemsetAsync(a.out.ticket, 0, sizeof(uint32_t), stream) != hipSuccess) return -1;
-        hipLaunchKernelGGL(generic_compact_kernel, dim3(g3), dim3(kBlockThreads), 0, stream, a.w,
-                           a.mode, win_first, wb, we, winpos, a.out, a.wamb ? 1 : 0);
+// ------------------------------------------------------------------ text
+// General byte text (mm_text_hasher_t): the same three stages, with byte loads and the 256-entry rolling tables of
+// TextTables staged in LDS (4 KB).  The forward window stage is generic_window_kernel itself; canonical windows vote
+// on the bytes (c & 2, src/canonical.rs:26-28) in generic_text_window_kernel.  Every load lies inside the text: the
+// last k-mer of a round ends at the last byte of its last window.
+static_assert(kBlockThreads == 256, "one table entry per thread");
+
+__global__ __launch_bounds__(kBlockThreads) void generic_text_hash_kernel(
+    const uint8_t *__restrict__ text, const TextTables *__restrict__ tt, uint32_t k, uint64_t km_begin,
+    uint64_t km_end, uint32_t *__restrict__ hash /* [km_end - km_begin] */) {
+    __shared__ uint2 s_in[256], s_out[256];
+    s_in[threadIdx.x] = tt->t_in[threadIdx.x];
+    s_out[threadIdx.x] = tt->t_out[threadIdx.x];
+    __syncthreads();
+    const uint64_t first = km_begin + ((uint64_t)blockIdx.x * kBlockThreads + threadIdx.x) * kKmersPerLane;
+    if (first >= km_end) return;
+    const uint64_t last = first + kKmersPerLane < km_end ? first + kKmersPerLane : km_end;
+    const uint32_t R = tt->rot;
+    const bool canonical = tt->canonical != 0;
+    const uint8_t *p = text + first;  // first byte of k-mer `first`
+    uint32_t fw = tt->fw0, rc = tt->rc0;
+    for (uint32_t j = 0; j < k; ++j) {
+        const uint2 t = s_in[p[j]];
+        fw = rotl32(fw, R) ^ t.x;
+        rc = rotr32(rc, R) ^ t.y;
     }
-    if (a.timing_stop) hipEventRecord(a.timing_stop, stream);
+    for (uint64_t e = first;; ++e) {
+        hash[e - km_begin] = canonical ? fw + rc : fw;
+        if (e + 1 >= last) break;
+        const uint2 ti = s_in[p[k]], to = s_out[p[0]];
+        fw = rotl32(fw, R) ^ ti.x ^ to.x;
+        rc = rotr32(rc, R) ^ ti.y ^ to.y;
+        ++p;
+    }
+}
+
+// One canonical window per lane: leftmost / rightmost argmin as generic_window_kernel, the strand vote over the
+// window's l bytes.
+__global__ __launch_bounds__(kBlockThreads) void generic_text_window_kernel(
+    const uint8_t *__restrict__ text, uint32_t k, uint32_t w, uint64_t km_begin, const uint32_t *__restrict__ hash,
+    uint64_t win_first, uint64_t win_end, uint32_t *__restrict__ winpos /* [win_end - win_first] */) {
+    const uint64_t i = win_first + (uint64_t)blockIdx.x * kBlockThreads + threadIdx.x;
+    if (i >= win_end) return;
+    const uint32_t *h = hash + (i - km_begin);
+    uint32_t best = h[0] & 0xffff0000u;
+    uint32_t left = 0, right = 0;
+    for (uint32_t j = 1; j < w; ++j) {
+        const uint32_t v = h[j] & 0xffff0000u;
+        if (v < best) {
+            best = v;
+            left = right = j;
+        } else if (v == best) {
+            right = j;
+        }
+    }
+    const uint32_t l = k + w - 1;
+    const uint8_t *s = text + i;
+    uint32_t odd = 0;
+    for (uint32_t q = 0; q < l; ++q) odd += (s[q] >> 1) & 1u;
+    winpos[i - win_first] = (uint32_t)(i + ((2ull * odd > l) ? left : right));
+}
+
+// --------------------------------------------------------------- launcher
+// The rounds of a run (up to round_windows windows each, one window in front of every round for the dedup seam): the hash
+// and window stages of the input (`stages(win_first, we, km_begin, km_end, hash, winpos)`), then the ordered compaction.
+template <class Stages>
+static int generic_rounds(uint32_t w, uint32_t mode, uint64_t win_begin, uint64_t win_end, uint64_t round, void *scratch,
+                          const OutParams &out, int skip, hipEvent_t timing_start, hipEvent_t timing_stop,
+                          hipStream_t stream, Stages stages) {
+    // scratch holds: hash (u32 per k-mer of a round) then winpos (u32 per window of a round)
+    uint32_t *hash = reinterpret_cast<uint32_t *>(scratch);
+    uint32_t *winpos = hash + (round + w + 1);
+    if (timing_start) hipEventRecord(timing_start, stream);
+    for (uint64_t wb = win_begin; wb < win_end; wb += round) {
+        const uint64_t we = wb + round < win_end ? wb + round : win_end;
+        const uint64_t win_first = wb > 0 ? wb - 1 : 0;  // one extra window in front for the dedup seam
+        const uint64_t km_begin = win_first, km_end = we + w - 1;
+        stages(win_first, we, km_begin, km_end, hash, winpos);
+        const uint32_t g3 = (uint32_t)((we - wb + kWinPerBlockC - 1) / kWinPerBlockC);
+        if (hipMemsetAsync(out.status, 0, sizeof(unsigned long long) * g3, stream) != hipSuccess) return -1;
+        if (hipMemsetAsync(out.ticket, 0, sizeof(uint32_t), stream) != hipSuccess) return -1;
+        hipLaunchKernelGGL(generic_compact_kernel, dim3(g3), dim3(kBlockThreads), 0, stream, w, mode, win_first, wb, we,
+                           winpos, out, skip);
+    }
+    if (timing_stop) hipEventRecord(timing_stop, stream);
     return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+static uint32_t hash_blocks(uint64_t n_km) {
+    return (uint32_t)((n_km + (uint64_t)kBlockThreads * kKmersPerLane - 1) / ((uint64_t)kBlockThreads * kKmersPerLane));
+}
+
+int launch_generic(const RunArgs &a, hipStream_t stream) {
+    return generic_rounds(a.w, a.mode, a.win_begin, a.win_end, a.generic_round_windows, a.scratch, a.out,
+                          a.wamb ? 1 : 0, a.timing_start, a.timing_stop, stream,
+                          [&](uint64_t win_first, uint64_t we, uint64_t km_begin, uint64_t km_end, uint32_t *hash,
+                              uint32_t *winpos) {
+        hipLaunchKernelGGL(generic_hash_kernel, dim3(hash_blocks(km_end - km_begin)), dim3(kBlockThreads), 0, stream,
+                           a.seq, a.ht, a.k, km_begin, km_end, hash);
+        const uint32_t g2 = (uint32_t)((we - win_first + kBlockThreads - 1) / kBlockThreads);
+        hipLaunchKernelGGL(generic_window_kernel, dim3(g2), dim3(kBlockThreads), 0, stream, a.seq, a.k, a.w,
+                           a.canonical_windows, km_begin, hash, win_first, we, winpos, a.wamb);
+    });
+}
+
+int launch_generic_text(const TextRunArgs &a, hipStream_t stream) {
+    return generic_rounds(a.w, a.mode, a.win_begin, a.win_end, a.generic_round_windows, a.scratch, a.out, 0,
+                          a.timing_start, a.timing_stop, stream,
+                          [&](uint64_t win_first, uint64_t we, uint64_t km_begin, uint64_t km_end, uint32_t *hash,
+                              uint32_t *winpos) {
+        hipLaunchKernelGGL(generic_text_hash_kernel, dim3(hash_blocks(km_end - km_begin)), dim3(kBlockThreads), 0,
+                           stream, a.text, a.tables, a.k, km_begin, km_end, hash);
+        const uint32_t g2 = (uint32_t)((we - win_first + kBlockThreads - 1) / kBlockThreads);
+        if (a.canonical_windows) {
+            hipLaunchKernelGGL(generic_text_window_kernel, dim3(g2), dim3(kBlockThreads), 0, stream, a.text, a.k, a.w,
+                               km_begin, hash, win_first, we, winpos);
+        } else {
+            const SeqView none{nullptr, 0u, 0u, 0u};  // (forward windows read no sequence)
+            hipLaunchKernelGGL(generic_window_kernel, dim3(g2), dim3(kBlockThreads), 0, stream, none, a.k, a.w, 0,
+                               km_begin, hash, win_first, we, winpos, (const uint32_t *)nullptr);
+        }
+    });
 }
 
 uint64_t generic_scratch_bytes(uint64_t round_windows, uint32_t w) {

@@ -164,6 +164,38 @@ uint64_t generic_scratch_bytes(uint64_t round_windows, uint32_t w);
 uint64_t generic_status_words(uint64_t round_windows);
 int launch_generic(const RunArgs &a, hipStream_t stream);
 
+// ---- text (general bytes, mm_text_hasher_t; mm_generic.hip): the generic family with byte loads and 256-entry tables
+// Rolling tables prepared on the host for one (text hasher, k), the hasher's XOR constants folded in as in HashTables:
+//   fw' = rotl(fw, rot) ^ t_in[in].x ^ t_out[out].x ;  rc' = rotr(rc, rot) ^ t_in[in].y ^ t_out[out].y
+//   warm-up (no byte leaves yet): t_in alone.  The tables live in device memory (4 KB: too large for kernel arguments).
+struct TextTables {
+    uint2 t_in[256];   // (fw[c] ^ df, rotl(rc[c], rot*(k-1)) ^ dr)
+    uint2 t_out[256];  // (rotl(fw[c], rot*k), rotr(rc[c], rot))
+    uint32_t fw0, rc0, rot, canonical;
+};
+struct TextRunArgs {
+    const uint8_t *text;
+    uint64_t n;
+    const TextTables *tables;  // device
+    uint32_t k, w;
+    int canonical_windows;
+    uint32_t mode;
+    uint64_t win_begin, win_end;
+    OutParams out;
+    void *scratch;  // generic_scratch_bytes(generic_round_windows, w)
+    uint64_t generic_round_windows;
+    hipEvent_t timing_start, timing_stop;
+    // (host copies of the scalars of *tables, for the fused kernel's arguments)
+    bool hash_rc;
+    uint32_t fw0, rc0, rot;
+};
+int launch_generic_text(const TextRunArgs &a, hipStream_t stream);
+// ---- the fused text kernel (mm_text_walk.hip): one launch, w <= 128 and k <= 1024 (prebuilt W: 5, 11, 19)
+bool text_walk_supported(uint32_t k, uint32_t w);
+int text_prebuilt_windows(uint32_t *out, int capacity);
+uint64_t text_walk_tiles(uint64_t windows);  // = look-back words of a launch
+int launch_text_walk(const TextRunArgs &a, hipStream_t stream);  // 0, -1 (HIP failure), -2 (not supported)
+
 // ---- auxiliary kernels (mm_aux.hip)
 int launch_values_u64(SeqView seq, uint32_t len, int canonical, const uint32_t *d_pos,
                       uint64_t n_pos, unsigned long long *d_values, hipStream_t stream);

@@ -1,0 +1,76 @@
+// mm_text_walk.hip - instances and launcher of the fused text kernel (mm_text_walk_impl.h).
+//
+// Prebuilt with a fixed W (unrolled minimum) for the paper's windows w = 5, 11, 19 (bench/src/bin/paper.rs:343-361), forward
+// and canonical windows, with and without the reverse-strand hash, for minimizers and both syncmer modes; every other
+// w <= kTextMaxW runs in the W = 0 instances of the same kernel (w read at run time), larger w and k > kTextMaxK take the
+// generic family's text kernels.
+#include "mm_launch.h"
+#include "mm_text_walk_impl.h"
+
+namespace mm {
+
+namespace {
+
+typedef void (*TextWalkFn)(TextWalkParams);
+
+template <int W, bool CANON, bool HASH_RC>
+TextWalkFn pick_mode(uint32_t mode) {
+    if (mode == 0) return text_walk_kernel<W, CANON, HASH_RC, 0>;
+    if (mode == 1) return text_walk_kernel<W, CANON, HASH_RC, 1>;
+    return text_walk_kernel<W, CANON, HASH_RC, 2>;
+}
+template <int W>
+TextWalkFn pick(bool canon, bool hash_rc, uint32_t mode) {
+    if (canon) return pick_mode<W, true, true>(mode);  // (canonical windows need a canonical hasher: mm_plan_create_text)
+    return hash_rc ? pick_mode<W, false, true>(mode) : pick_mode<W, false, false>(mode);
+}
+
+const uint32_t kTextPrebuiltW[] = {5, 11, 19};
+
+}  // namespace
+
+bool text_walk_supported(uint32_t k, uint32_t w) { return w <= kTextMaxW && k <= kTextMaxK; }
+
+int text_prebuilt_windows(uint32_t *out, int capacity) {
+    const int n = (int)(sizeof(kTextPrebuiltW) / sizeof(kTextPrebuiltW[0]));
+    for (int i = 0; i < n && i < capacity; ++i)
+        if (out) out[i] = kTextPrebuiltW[i];
+    return n;
+}
+
+uint64_t text_walk_tiles(uint64_t windows) { return (windows + kTextTile - 1) / kTextTile; }
+
+int launch_text_walk(const TextRunArgs &a, hipStream_t stream) {
+    if (!text_walk_supported(a.k, a.w)) return -2;
+    const bool canon = a.canonical_windows != 0;
+    const bool hash_rc = a.hash_rc;
+    TextWalkFn fn;
+    switch (a.w) {
+        case 5: fn = pick<5>(canon, hash_rc, a.mode); break;
+        case 11: fn = pick<11>(canon, hash_rc, a.mode); break;
+        case 19: fn = pick<19>(canon, hash_rc, a.mode); break;
+        default: fn = pick<0>(canon, hash_rc, a.mode); break;
+    }
+    TextWalkParams p;
+    p.text = a.text;
+    p.n = a.n;
+    p.tables = reinterpret_cast<const uint2 *>(a.tables);
+    p.fw0 = a.fw0;
+    p.rc0 = a.rc0;
+    p.rot = a.rot;
+    p.k = a.k;
+    p.w = a.w;
+    p.win_begin = a.win_begin;
+    p.win_end = a.win_end;
+    p.out = a.out;
+    const uint64_t tiles = text_walk_tiles(a.win_end - a.win_begin);
+    // (untagged look-back words and the ticket, cleared per launch as the generic family does)
+    if (hipMemsetAsync(a.out.status, 0, sizeof(unsigned long long) * tiles, stream) != hipSuccess) return -1;
+    if (hipMemsetAsync(a.out.ticket, 0, sizeof(uint32_t), stream) != hipSuccess) return -1;
+    if (a.timing_start) hipEventRecord(a.timing_start, stream);
+    hipLaunchKernelGGL(fn, dim3((uint32_t)tiles), dim3(kTextThreads), 0, stream, p);
+    if (a.timing_stop) hipEventRecord(a.timing_stop, stream);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+}  // namespace mm

@@ -1,0 +1,222 @@
+// mm_text_walk_impl.h - the fused kernel of general byte text (mm_text_hasher_t).
+//
+// One workgroup = one tile of kTextTile consecutive windows (tiles taken from an atomic ticket, so the decoupled look-back
+// only ever waits for tiles that have started), in ONE kernel:
+//   1. stage: the tile's text (kTextTile + w + k - 1 bytes, from the byte before its first window) into LDS with 16-byte
+//      raw-buffer loads (past the end of the text: zeros through the descriptor), the two rolling tables beside it;
+//   2. hash: every thread rolls an odd-length run of k-mers (warm-up of k characters, then one t_in and one t_out look-up per
+//      character) and stores key = (hash & 0xffff0000) | tile-local position - the reference's key (src/sliding_min.rs:
+//      104-127); positions stay below 2^16 inside a tile, so min(key) IS the leftmost argmin and max(key ^ 0xffff0000) the
+//      rightmost one (src/sliding_min.rs:196-197);
+//   3. window minima: window u of the tile takes the minimum over keys u .. u+w-1; threads take windows round robin, so a
+//      wave reads consecutive keys (no bank conflicts); the selected offsets (left | right << 8, w <= 128) go to LDS;
+//   4. collect: every thread walks kTextPerThread consecutive windows with the lazy strand vote (2 #{c & 2} > l counted
+//      over the window's bytes, one byte in and one out per window; src/canonical.rs:26-28), the dedup against the
+//      previous window / the syncmer predicate (src/collect.rs:15-76, src/syncmers.rs:19-48), a block scan, the look-back
+//      across tiles (lookback_exclusive) and the stores in window order.
+// The first window of a tile dedups against the window in front of it (the tile computes one extra window), which is also
+// the seam rule of a window range.
+#pragma once
+#include "mm_common.h"
+
+namespace mm {
+
+constexpr uint32_t kTextThreads = 256;
+constexpr uint32_t kTextPerThread = 32;                           // windows per thread in the collect stage
+constexpr uint32_t kTextTile = kTextThreads * kTextPerThread;     // 8192 windows per workgroup
+constexpr uint32_t kTextMaxW = 128;                               // (left | right << 8 offsets; key array size)
+constexpr uint32_t kTextMaxK = 1024;                              // (LDS text buffer)
+constexpr uint32_t kTextKeys = kTextTile + 1 + kTextMaxW;         // k-mers of a tile, with the window in front
+constexpr uint32_t kTextHashRun = (kTextKeys + kTextThreads - 1) / kTextThreads;  // 33: odd, conflict-free key stores
+// (the hash stage's runs read up to kTextHashRun * kTextThreads + k bytes: those past the tile's span feed k-mers that no
+// window uses)
+constexpr uint32_t kTextBytes = (kTextHashRun * kTextThreads + kTextMaxK + 32 + 15) & ~15u;
+constexpr uint32_t kTextSelStride = kTextPerThread / 2 + 1;       // dwords per thread's 32 offsets (+1: no conflicts)
+static_assert(kTextHashRun % 2 == 1, "odd runs keep the key stores of a wave on distinct banks");
+static_assert(kTextThreads == 256, "one table entry per thread");
+
+struct TextWalkParams {
+    const uint8_t *text;       // caller's pointer (any alignment)
+    uint64_t n;                // characters
+    const uint2 *tables;       // device: t_in[256] then t_out[256] (TextTables)
+    uint32_t fw0, rc0, rot;
+    uint32_t k, w;             // (w: runtime value, also for the instances with a fixed W)
+    uint64_t win_begin, win_end;
+    OutParams out;
+};
+
+typedef uint32_t u32x4t __attribute__((ext_vector_type(4)));
+
+template <int W, bool CANON, bool HASH_RC, int MODE>
+__global__ __launch_bounds__(kTextThreads) void text_walk_kernel(TextWalkParams p) {
+    __shared__ uint2 s_in[256], s_out[256];
+    __shared__ __attribute__((aligned(16))) uint8_t s_text[kTextBytes];
+    __shared__ uint32_t s_key[kTextHashRun * kTextThreads];
+    __shared__ uint32_t s_sel[kTextSelStride * kTextThreads];
+    __shared__ uint32_t s_bid;
+    __shared__ uint32_t s_wave_tot[kTextThreads / kWave];
+    __shared__ unsigned long long s_excl;
+
+    const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    const uint32_t w = W > 0 ? (uint32_t)W : p.w;
+    const uint32_t k = p.k;
+    if (tid == 0) s_bid = atomicAdd(p.out.ticket, 1u);
+    s_in[tid] = p.tables[tid];
+    s_out[tid] = p.tables[256 + tid];
+
+    // ---- 1. stage the tile's bytes: global byte g0 + q at s_text[off0 + q], g0 = first window - 1
+    __syncthreads();
+    const uint32_t bid = s_bid;
+    const uint64_t w0 = p.win_begin + (uint64_t)bid * kTextTile;
+    const long long g0 = (long long)w0 - 1;
+    const uintptr_t addr = reinterpret_cast<uintptr_t>(p.text);
+    const uint32_t sh = (uint32_t)(addr & 15u);
+    const long long a0 = g0 + (long long)sh;           // offset of byte g0 from the 16-byte boundary below the text
+    const long long a0a = a0 >= 0 ? (a0 & ~15ll) : -16;  // (-1 only in the first tile: its byte g0 does not exist)
+    const uint32_t off0 = (uint32_t)(a0 - a0a);
+    const uint64_t tbase = a0a >= 0 ? (uint64_t)a0a : 0u;
+    // the tile's own descriptor (offsets stay small for any n < 2^32), whole dwords up to the end of the text: the text's
+    // last dword may hold bytes behind it - same dword, same page - that only k-mers past the last window see
+    const uint64_t rem = ((p.n + sh + 3u) & ~3ull) - tbase;
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+        reinterpret_cast<void *>(addr - sh + tbase), 0, (int)(uint32_t)(rem < 0xfffffff0ull ? rem : 0xfffffff0ull), 0x00020000);
+    const uint32_t span = kTextTile + 1 + w + k;       // bytes the tile reads (+1 spare)
+    const uint32_t chunks = (off0 + span + 15) / 16;
+    for (uint32_t c = tid; c < chunks; c += kTextThreads) {
+        const long long o = a0a + 16ll * c - (long long)tbase;
+        u32x4t v = {0u, 0u, 0u, 0u};
+        if (o >= 0) v = __builtin_amdgcn_raw_buffer_load_b128(rs, (uint32_t)o, 0, 0);  // (past the end: zeros)
+        *reinterpret_cast<u32x4t *>(s_text + 16 * c) = v;
+    }
+    __syncthreads();
+
+    // ---- 2. keys of k-mers u = 0 .. kTextTile + w - 1 (k-mer u starts at byte g0 + u)
+    {
+        const uint32_t R = p.rot;
+        const uint32_t u0 = tid * kTextHashRun;
+        const uint32_t n_keys = kTextTile + w;
+        if (u0 < n_keys) {
+            const uint8_t *s = s_text + off0 + u0;
+            uint32_t fw = p.fw0, rc = p.rc0;
+            for (uint32_t j = 0; j < k; ++j) {
+                const uint2 t = s_in[s[j]];
+                fw = rotl32(fw, R) ^ t.x;
+                if (HASH_RC) rc = rotr32(rc, R) ^ t.y;
+            }
+#pragma unroll 4
+            for (uint32_t j = 0; j < kTextHashRun; ++j) {
+                const uint32_t h = HASH_RC ? fw + rc : fw;
+                s_key[u0 + j] = (h & 0xffff0000u) | (u0 + j);
+                const uint2 ti = s_in[s[j + k]], to = s_out[s[j]];
+                fw = rotl32(fw, R) ^ ti.x ^ to.x;
+                if (HASH_RC) rc = rotr32(rc, R) ^ ti.y ^ to.y;
+            }
+        }
+    }
+    __syncthreads();
+
+    // ---- 3. window minima, windows u = 0 .. kTextTile round robin; offsets to s_sel (thread t's windows 32t+1 .. 32t+32
+    // at dwords 17t .. : window u at half (u - 1) % 32 of thread (u - 1) / 32; window 0 at thread 255's spare dword)
+    for (uint32_t u = tid; u <= kTextTile; u += kTextThreads) {
+        uint32_t lo = s_key[u], hi = s_key[u] ^ 0xffff0000u;
+        if (W > 0) {
+#pragma unroll
+            for (int j = 1; j < (W > 0 ? W : 1); ++j) {
+                const uint32_t v = s_key[u + j];
+                lo = min(lo, v);
+                if (CANON) hi = max(hi, v ^ 0xffff0000u);
+            }
+        } else {
+            for (uint32_t j = 1; j < w; ++j) {
+                const uint32_t v = s_key[u + j];
+                lo = min(lo, v);
+                if (CANON) hi = max(hi, v ^ 0xffff0000u);
+            }
+        }
+        const uint32_t sel = ((lo & 0xffffu) - u) | (CANON ? (((hi & 0xffffu) - u) << 8) : 0u);
+        const uint32_t v = u == 0 ? kTextPerThread * kTextThreads : u - 1;
+        const uint32_t t = v / kTextPerThread, e = v % kTextPerThread;
+        uint16_t *q = reinterpret_cast<uint16_t *>(s_sel + (t < kTextThreads ? t * kTextSelStride : kTextThreads * kTextSelStride - 1));
+        q[t < kTextThreads ? e : 0] = (uint16_t)sel;
+    }
+    __syncthreads();
+
+    // ---- 4. collect: windows w0 + 32 tid + j, j < 32, with the window in front for the dedup
+    const uint32_t l = k + w - 1;
+    const uint16_t *mysel = reinterpret_cast<const uint16_t *>(s_sel + tid * kTextSelStride);
+    const uint32_t u_first = tid * kTextPerThread + 1;  // tile-local index of the first window (window w0 + 32 tid)
+    // strand vote of window u: bytes u .. u+l-1 of the tile (s_text[off0 + u ..])
+    uint32_t odd = 0;
+    const uint32_t u_prev = u_first - 1;
+    if (CANON) {
+        const uint8_t *s = s_text + off0 + u_prev;
+        for (uint32_t q = 0; q < l; ++q) odd += (s[q] >> 1) & 1u;
+    }
+    auto pos_of = [&](uint32_t u, uint32_t sel, uint32_t odd_u) -> uint32_t {
+        const uint32_t off = CANON ? ((2u * odd_u > l) ? (sel & 0xffu) : (sel >> 8)) : sel;
+        return (uint32_t)(w0 - 1 + u + off);
+    };
+    uint32_t prev = 0;
+    bool have_prev = false;
+    if (w0 + u_prev >= 1 && w0 + u_prev - 1 < p.win_end) {  // (window w0 + u_prev - 1 exists)
+        // (window u_prev: the spare slot for u_prev = 0, else the last offset of the previous thread)
+        const uint16_t *q = u_prev == 0 ? reinterpret_cast<const uint16_t *>(s_sel + kTextThreads * kTextSelStride - 1)
+                                        : reinterpret_cast<const uint16_t *>(s_sel + (tid - 1) * kTextSelStride) +
+                                              (kTextPerThread - 1);
+        prev = pos_of(u_prev, *q, odd);
+        have_prev = true;
+    }
+    uint32_t flags = 0;
+    uint32_t vals[kTextPerThread];
+#pragma unroll
+    for (uint32_t j = 0; j < kTextPerThread; ++j) {
+        const uint32_t u = u_first + j;
+        if (CANON) {
+            const uint8_t *s = s_text + off0;
+            odd += ((s[u + l - 1] >> 1) & 1u) - ((s[u - 1] >> 1) & 1u);
+        }
+        const uint64_t g = w0 + tid * kTextPerThread + j;
+        const uint32_t pp = pos_of(u, mysel[j], odd);
+        bool f = false;
+        if (g < p.win_end) {
+            if (MODE == 0) f = !have_prev || pp != prev;
+            else if (MODE == 1) f = (pp == (uint32_t)g) || (pp == (uint32_t)g + w - 1);
+            else f = (pp == (uint32_t)g + w / 2);
+        }
+        vals[j] = MODE == 0 ? pp : (uint32_t)g;
+        flags |= (uint32_t)f << j;
+        prev = pp;
+        have_prev = true;
+    }
+    const uint32_t cnt = __popc(flags);
+    const uint32_t incl = wave_inclusive_sum(cnt);
+    if (lane == kWave - 1) s_wave_tot[wave] = incl;
+    __syncthreads();
+    uint32_t wave_base = 0, block_total = 0;
+#pragma unroll
+    for (uint32_t v = 0; v < kTextThreads / kWave; ++v) {
+        const uint32_t t = s_wave_tot[v];
+        if (v < wave) wave_base += t;
+        block_total += t;
+    }
+    if (wave == 0) {
+        const unsigned long long carry = (bid == 0) ? *p.out.total : 0ull;
+        const unsigned long long e = lookback_exclusive(p.out.status, bid, block_total, carry, p.out.error);
+        if (lane == 0) s_excl = e;
+    }
+    __syncthreads();
+    unsigned long long dst = s_excl + wave_base + (incl - cnt);
+#pragma unroll
+    for (uint32_t j = 0; j < kTextPerThread; ++j) {
+        if (flags & (1u << j)) {
+            if (dst < p.out.cap) {
+                p.out.pos[dst] = vals[j];
+                if (p.out.sk) p.out.sk[dst] = (uint32_t)(w0 + tid * kTextPerThread + j);
+            }
+            ++dst;
+        }
+    }
+    if (tid == 0 && bid == gridDim.x - 1) *p.out.total = s_excl + block_total;
+}
+
+}  // namespace mm
