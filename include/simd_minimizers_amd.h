@@ -82,7 +82,8 @@ enum {
     MM_ERR_NO_DEVICE = -20,           /* no HIP device: the engine has no CPU fallback */
     MM_ERR_HIP = -21,                 /* a HIP call failed; see mm_last_error() */
     MM_ERR_ALLOC = -22,
-    MM_ERR_ORDER = -23                /* mm_workspace_check: a look-back of an asynchronous run timed out */
+    MM_ERR_ORDER = -23,               /* mm_workspace_check: a look-back of an asynchronous run timed out */
+    MM_ERR_UNSORTED = -24             /* mm_run_text_batch_host: record starts decrease */
 };
 
 const char *mm_strerror(int code);
@@ -272,6 +273,38 @@ int mm_text_prebuilt_window_sizes(int canonical_windows, uint32_t *out, int capa
 /* Builder::run on host text: H2D copy, kernels, D2H copy.  `out_pos == NULL` only counts. */
 int mm_run_text_host(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *text, uint64_t n,
                      uint32_t *out_pos, uint32_t *out_sk, uint64_t capacity, uint64_t *out_count);
+
+/* Builder::run per record (src/lib.rs:378) over MANY records of byte text in one call: protein databases,
+ * proteomes, ORF sets, lines of text.  Record r is the bytes [starts[r], starts[r + 1]) of the text, and its
+ * slice out_pos[out_offsets[r] .. out_offsets[r + 1]) is exactly what mm_run_text_host returns for that record
+ * alone (likewise out_sk): positions and super-k-mer indices are record-local, the dedup restarts at every record,
+ * no window spans two records.  starts is non-decreasing, starts[0] may be above 0; empty records and records
+ * shorter than l = k + w - 1 get empty slices.  n_records == 0 is legal (count 0, offsets[0] = 0).
+ *  d_text / text_bytes    the text, any alignment; n_chars = d_starts[n_records] (> text_bytes: MM_ERR_CAPACITY)
+ *  d_starts               device, [n_records + 1]; unordered starts are the caller's contract breach: the output
+ *                         is then undefined, but nothing outside the buffers named here is read or written
+ *  d_out_pos (or NULL: count only, offsets still written) / d_out_sk (or NULL) / capacity / d_count
+ *                         as for mm_run_text_device_async; d_out_offsets [n_records + 1] is always written
+ * n_chars >= 2^32 or n_records >= 2^31 returns MM_ERR_LEN_TOO_LARGE before anything is touched.  Kernels: ONE
+ * launch of the fused text kernel (w <= 128, k <= 1024; MM_PATH_FUSED) behind a small launch that finds each
+ * tile's records; other plans and mm_workspace_force_generic run one generic-family launch per record
+ * (MM_PATH_GENERIC) after copying the starts to the host: correct, but slow - meant for the odd plan, not for
+ * throughput. */
+int mm_run_text_batch_device_async(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_text,
+                                   uint64_t text_bytes, uint64_t n_records,
+                                   const uint64_t *d_starts /* [n_records + 1] */, uint64_t n_chars,
+                                   uint32_t *d_out_pos, uint32_t *d_out_sk /* or NULL */, uint64_t capacity,
+                                   uint64_t *d_out_offsets /* [n_records + 1] */, uint64_t *d_count);
+/* Same, then waits and returns the count; MM_ERR_CAPACITY if it exceeded `capacity` (*out_count: the need). */
+int mm_run_text_batch_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_text, uint64_t text_bytes,
+                             uint64_t n_records, const uint64_t *d_starts, uint64_t n_chars, uint32_t *d_out_pos,
+                             uint32_t *d_out_sk, uint64_t capacity, uint64_t *d_out_offsets, uint64_t *out_count);
+/* The same from HOST memory: one upload of the text (bytes 0 .. starts[n_records]) and the starts, one launch, one
+ * download.  Starts that decrease return MM_ERR_UNSORTED before anything is touched. */
+int mm_run_text_batch_host(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *text, uint64_t n_records,
+                           const uint64_t *starts /* host, [n_records + 1] */, uint32_t *out_pos,
+                           uint32_t *out_sk /* or NULL */, uint64_t capacity,
+                           uint64_t *out_offsets /* [n_records + 1] */, uint64_t *out_count);
 
 /* ----------------------------------------------------------------- values */
 

@@ -12,6 +12,7 @@
 // simd_minimizers::Error carrying the MM_ERR_* code.  All compute happens in the HIP library.
 #pragma once
 #include <cstdint>
+#include <cstring>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -321,6 +322,33 @@ class Builder {  // src/lib.rs:225-230
         uint64_t n = 0;
         const int r = mm_run_packed_reads_host(plan, ws.get(), packed.data(), reads.size(), starts.data(), longest, pos.data(),
                                                sk_ ? sk.data() : nullptr, cap, offsets.data(), &n);
+        mm_plan_destroy(plan);
+        check(r);
+        pos.resize(n);
+        if (sk_) sk_->assign(sk.begin(), sk.begin() + n);
+    }
+
+    // Builder::run per record over many records of byte text (src/lib.rs:378) in ONE call (mm_run_text_batch_host):
+    // pos and offsets are OVERWRITTEN, record r's record-local positions at pos[offsets[r] .. offsets[r + 1]); the
+    // super-k-mer indices (super_kmers()) likewise overwrite their vector.
+    void run_many(const std::vector<TextSeq> &records, std::vector<uint32_t> &pos, std::vector<uint64_t> &offsets) const {
+        Workspace &ws = ws_ ? *ws_ : Workspace::thread_default();
+        std::vector<uint64_t> starts(records.size() + 1, 0);
+        for (size_t r = 0; r < records.size(); ++r) starts[r + 1] = starts[r] + records[r].len;
+        const uint64_t total = starts.back();
+        std::vector<uint8_t> text(total ? total : 1);
+        for (size_t r = 0; r < records.size(); ++r)
+            if (records[r].len) memcpy(text.data() + starts[r], records[r].data, records[r].len);
+        mm_plan_t *plan = nullptr;
+        check(mm_plan_create_text(&plan, k_, w_, CANONICAL, (mm_mode_t)SYNCMER,
+                                  has_text_hasher_ ? &text_hasher_ : nullptr));
+        const uint64_t cap = total ? total : 1;
+        pos.assign(cap, 0);
+        std::vector<uint32_t> sk(sk_ ? cap : 0);
+        offsets.assign(records.size() + 1, 0);
+        uint64_t n = 0;
+        const int r = mm_run_text_batch_host(plan, ws.get(), text.data(), records.size(), starts.data(), pos.data(),
+                                             sk_ ? sk.data() : nullptr, cap, offsets.data(), &n);
         mm_plan_destroy(plan);
         check(r);
         pos.resize(n);

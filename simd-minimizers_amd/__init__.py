@@ -26,6 +26,7 @@ ERR = {
     "W_ZERO": -1, "W_TOO_LARGE": -2, "LEN_TOO_LARGE": -3, "EVEN_L": -4,
     "HASHER_NOT_CANONICAL": -5, "OPEN_EVEN_W": -6, "K_ZERO": -7, "CAPACITY": -8, "BAD_MODE": -9,
     "NULL": -10, "VALUE_LEN": -11, "FORMAT": -12, "NO_DEVICE": -20, "HIP": -21, "ALLOC": -22, "ORDER": -23,
+    "UNSORTED": -24,
 }
 
 
@@ -193,6 +194,10 @@ def lib():
             L.mm_run_text_device.argtypes = text_args + [u64p]
             L.mm_run_text_host.argtypes = [vp, vp, u8p, C.c_uint64, u32p, u32p, C.c_uint64, u64p]
             L.mm_text_prebuilt_window_sizes.argtypes = [C.c_int, u32p, C.c_int]
+            batch_args = [vp, vp, vp, C.c_uint64, C.c_uint64, vp, C.c_uint64, vp, vp, C.c_uint64, vp]
+            L.mm_run_text_batch_device_async.argtypes = batch_args + [vp]
+            L.mm_run_text_batch_device.argtypes = batch_args + [u64p]
+            L.mm_run_text_batch_host.argtypes = [vp, vp, u8p, C.c_uint64, u64p, u32p, u32p, C.c_uint64, u64p, u64p]
         L.mm_values_u64_device_async.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64,
                                                  C.c_uint32, C.c_int, vp, C.c_uint64, vp]
         L.mm_values_u64_host.argtypes = [vp, u8p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, u32p,
@@ -263,6 +268,7 @@ EXPORTED_SYMBOLS = [
     "mm_run_packed_reads_device_async", "mm_run_packed_reads_device", "mm_run_packed_reads_host",
     "mm_text_mul_hasher", "mm_text_hasher_from_dna", "mm_plan_create_text", "mm_run_text_device_async",
     "mm_run_text_device", "mm_run_text_host", "mm_text_prebuilt_window_sizes",
+    "mm_run_text_batch_device_async", "mm_run_text_batch_device", "mm_run_text_batch_host",
 ]
 
 
@@ -1174,6 +1180,63 @@ def run_reads_host(builder: "Builder", reads, super_kmers: bool = False):
                                           offs.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(cnt)))
     n = int(cnt.value)
     return pos[:n], [int(o) for o in offs], (sk[:n] if sk is not None else None)
+
+
+def _text_records(records):
+    """Records of byte text (``bytes`` / ``bytearray`` / ``memoryview`` / ``np.uint8``) -> (text, starts): the records back
+    to back and their [n + 1] starts."""
+    arrs = []
+    for s in records:
+        if not _is_text(s):
+            raise TypeError(f"byte-text records are bytes, bytearray or np.uint8 arrays, not {type(s).__name__}")
+        arrs.append(_text_array(s))
+    starts = np.zeros(len(arrs) + 1, dtype=np.uint64)
+    starts[1:] = np.cumsum([len(a) for a in arrs], dtype=np.uint64)
+    text = np.concatenate(arrs).astype(np.uint8, copy=False) if int(starts[-1]) else np.zeros(1, dtype=np.uint8)
+    return text, starts
+
+
+def run_text_batch_host(builder: "Builder", records, super_kmers: bool = False):
+    """Many records of byte text (``&[u8]``: protein, other alphabets, lines of text) in ONE call
+    (``mm_run_text_batch_host``); returns (positions, offsets, indices or None) - record r's record-local positions are
+    ``positions[offsets[r]:offsets[r + 1]]``, what ``Builder.run`` returns for it alone.  The text plan of ``builder``
+    (its ``TextHasher``, default ``TextMulHasher``) runs."""
+    text, starts = _text_records(records)
+    n_rec = len(starts) - 1
+    total = int(starts[-1])
+    cap = max(1, total)
+    pos = np.empty(cap, dtype=np.uint32)
+    sk = np.empty(cap, dtype=np.uint32) if super_kmers else None
+    offs = np.zeros(n_rec + 1, dtype=np.uint64)
+    cnt = C.c_uint64()
+    ws = builder._ws()
+    _check(lib().mm_run_text_batch_host(builder.text_plan().h, ws.h, _p(text, C.c_uint8), n_rec, _p(starts, C.c_uint64),
+                                        _p(pos, C.c_uint32), _p(sk, C.c_uint32) if sk is not None else None, cap,
+                                        _p(offs, C.c_uint64), C.byref(cnt)))
+    n = int(cnt.value)
+    return pos[:n], [int(o) for o in offs], (sk[:n] if sk is not None else None)
+
+
+def run_text_batch_device(builder: "Builder", d_text, d_starts, n_chars: int, out_pos, out_offsets, out_sk=None):
+    """Many records of device-resident byte text in one launch (``mm_run_text_batch_device``): ``d_text`` a uint8 CUDA
+    tensor, ``d_starts`` an int64 CUDA tensor of n + 1 non-decreasing record starts (``n_chars = d_starts[n]``),
+    ``out_offsets`` an int64 CUDA tensor of n + 1; ``out_pos`` (None: count only) / ``out_sk`` int32 tensors.  Returns the
+    number of positions."""
+    n_rec = d_starts.numel() - 1
+    if n_rec < 0:
+        raise ValueError("d_starts holds n + 1 starts")
+    cap = out_pos.numel() if out_pos is not None else 0
+    cnt = C.c_uint64()
+    code = lib().mm_run_text_batch_device(
+        builder.text_plan().h, builder._ws().h, C.c_void_p(d_text.data_ptr()) if d_text is not None else None,
+        d_text.numel() if d_text is not None else 0, n_rec, C.c_void_p(d_starts.data_ptr()), int(n_chars),
+        C.c_void_p(out_pos.data_ptr()) if out_pos is not None else None,
+        C.c_void_p(out_sk.data_ptr()) if out_sk is not None else None, cap, C.c_void_p(out_offsets.data_ptr()),
+        C.byref(cnt))
+    if code == ERR["CAPACITY"] and out_pos is not None and cnt.value > cap:
+        raise MinimizerError(code, f"output capacity {cap} < {cnt.value}")
+    _check(code)
+    return int(cnt.value)
 
 
 def run_packed_reads_device(builder: "Builder", records: FastaRecords, out_pos, out_offsets, out_sk=None, max_read_len=None):

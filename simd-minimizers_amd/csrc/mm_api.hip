@@ -244,6 +244,9 @@ struct mm_workspace {
     hipEvent_t ev_text_tables[kTextTableSlots] = {};
     bool text_slot_used[kTextTableSlots] = {};
     int text_slot_next = 0;
+    // text batches (mm_run_text_batch_*): per tile, the range of record starts its collect stage reads
+    unsigned long long *d_text_tiles = nullptr;
+    uint64_t d_text_tiles_elems = 0;
     // knobs / diagnostics
     bool force_generic = false;
     uint32_t nblk = 0;
@@ -440,6 +443,7 @@ const char *mm_strerror(int code) {
         case MM_ERR_HIP: return "HIP call failed";
         case MM_ERR_ALLOC: return "device allocation failed";
         case MM_ERR_ORDER: return "look-back timed out in an asynchronous run (repeat it; ticket mode is now on)";
+        case MM_ERR_UNSORTED: return "record starts must not decrease";
         default: return "unknown error";
     }
 }
@@ -728,6 +732,7 @@ void mm_workspace_destroy(mm_workspace_t *ws) {
     if (ws->d_amb) hipFree(ws->d_amb);
     if (ws->d_vals) hipFree(ws->d_vals);
     if (ws->d_text_tables) hipFree(ws->d_text_tables);
+    if (ws->d_text_tiles) hipFree(ws->d_text_tiles);
     if (ws->h_text_tables) hipHostFree(ws->h_text_tables);
     for (int i = 0; i < mm_workspace::kTextTableSlots; ++i)
         if (ws->ev_text_tables[i]) hipEventDestroy(ws->ev_text_tables[i]);
@@ -2594,6 +2599,218 @@ int mm_run_text_host(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *t
         if (out_sk) MM_HIP(hipMemcpyAsync(out_sk, ws->d_sk, count * sizeof(uint32_t), hipMemcpyDeviceToHost, ws->stream));
         MM_HIP(hipStreamSynchronize(ws->stream));
     }
+    return MM_OK;
+}
+
+// ------------------------------------------------------------- text batch
+// Many records of byte text in one call (Builder::run per record, src/lib.rs:378): record r = bytes [starts[r],
+// starts[r+1]) of the text, its record-local positions at out[offsets[r] .. offsets[r+1]).  The fused text kernel takes the
+// whole batch in ONE launch (BATCH instances, mm_text_walk_impl.h); plans it does not take run one generic-family launch
+// per record in stream order (slow: the starts come back to the host first), each appending to the same output and total.
+// The argument checks of the batch entry points, before anything is touched (no workspace needed).
+static int text_batch_check(const mm_plan_t *plan, const void *d_text, uint64_t text_bytes, uint64_t n_records,
+                            const uint64_t *d_starts, uint64_t n_chars, const uint32_t *d_out_sk,
+                            const uint64_t *d_out_offsets) {
+    if (!plan) return MM_ERR_NULL;
+    if (!plan->text) return MM_ERR_BAD_MODE;  // (a plan of mm_plan_create: packed entry points only)
+    if (n_chars >= (1ull << 32) || n_records >= (1ull << 31)) return MM_ERR_LEN_TOO_LARGE;
+    if (d_out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;  // src/lib.rs:339
+    if (!d_out_offsets || (n_records && !d_starts)) return MM_ERR_NULL;
+    if (n_chars > text_bytes) return MM_ERR_CAPACITY;
+    if (n_chars && !d_text) return MM_ERR_NULL;
+    return MM_OK;
+}
+
+static int run_text_batch_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_text, uint64_t text_bytes,
+                                     uint64_t n_records, const uint64_t *d_starts, uint64_t n_chars, uint32_t *d_out_pos,
+                                     uint32_t *d_out_sk, uint64_t capacity, uint64_t *d_out_offsets, uint64_t *d_count) {
+    int r = text_batch_check(plan, d_text, text_bytes, n_records, d_starts, n_chars, d_out_sk, d_out_offsets);
+    if (r) return r;
+    if (!ws) return MM_ERR_NULL;
+    if (!d_out_pos) capacity = 0;
+    MM_HIP(set_device(ws->device));
+    MM_HIP(hipMemsetAsync(ws->total, 0, 2 * sizeof(unsigned long long), ws->stream));
+    const uint64_t l = (uint64_t)plan->k + plan->w - 1;
+    if (n_records == 0 || n_chars < l) {  // (no window anywhere: every record's slice is empty)
+        MM_HIP(hipMemsetAsync(d_out_offsets, 0, (n_records + 1) * sizeof(uint64_t), ws->stream));
+    } else {
+        mm::TextRunArgs a;
+        r = text_tables_on_device(ws, plan->tt, &a.tables);
+        if (r) return r;
+        a.text = static_cast<const uint8_t *>(d_text);
+        a.k = plan->k;
+        a.w = plan->w;
+        a.canonical_windows = plan->canonical_windows;
+        a.mode = plan->mode;
+        a.out.pos = d_out_pos;
+        a.out.sk = d_out_sk;
+        a.out.cap = capacity;
+        a.out.total = ws->total;
+        a.out.ticket = ws->ticket;
+        a.out.error = reinterpret_cast<uint32_t *>(ws->total + 1);
+        a.timing_start = a.timing_stop = nullptr;
+        a.hash_rc = plan->tt.canonical != 0;
+        a.fw0 = plan->tt.fw0;
+        a.rc0 = plan->tt.rc0;
+        a.rot = plan->tt.rot;
+        a.scratch = nullptr;
+        a.generic_round_windows = 0;
+        const bool fused = !ws->force_generic && mm::text_walk_supported(plan->k, plan->w);
+        if (fused) {
+            const uint64_t tiles = mm::text_batch_tiles(n_chars);
+            r = grow_status(ws, tiles + 1);
+            if (r == MM_OK) r = grow(ws->d_text_tiles, ws->d_text_tiles_elems, 2 * tiles, sizeof(unsigned long long));
+            if (r) return r;
+            a.out.status = ws->status;
+            ws->status_dirty = true;  // (the text kernels clear and write untagged words)
+            a.n = n_chars;
+            a.win_begin = 0;
+            a.win_end = n_chars - l + 1;
+            a.batch = true;
+            a.starts = d_starts;
+            a.n_records = n_records;
+            a.tile_rec = ws->d_text_tiles;
+            a.offsets = reinterpret_cast<unsigned long long *>(d_out_offsets);
+            if (ws->timing) {
+                hipEvent_t e0, e1;
+                MM_HIP(hipEventCreate(&e0));
+                MM_HIP(hipEventCreate(&e1));
+                ws->events.emplace_back(e0, e1);
+                a.timing_start = e0;
+                a.timing_stop = e1;
+            }
+            if (mm::launch_text_walk(a, ws->stream) != 0) {
+                g_last_error = std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError());
+                return MM_ERR_HIP;
+            }
+        } else {
+            // one generic launch per record: the look-back adds the running total to each launch's first tile, so the
+            // launches append; record r's offset is that total just before its launch (a device-to-device copy)
+            std::vector<uint64_t> hs(n_records + 1);
+            MM_HIP(hipMemcpyAsync(hs.data(), d_starts, (n_records + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost,
+                                  ws->stream));
+            MM_HIP(hipStreamSynchronize(ws->stream));
+            uint64_t longest = 0;  // (records clamped into [0, n_chars], whatever the starts hold)
+            for (uint64_t q = 0; q < n_records; ++q) {
+                const uint64_t b = hs[q] < n_chars ? hs[q] : n_chars;
+                const uint64_t e = hs[q + 1] < b ? b : (hs[q + 1] < n_chars ? hs[q + 1] : n_chars);
+                if (e - b > longest) longest = e - b;
+            }
+            const uint64_t max_windows = longest >= l ? longest - l + 1 : 0;
+            const uint64_t round = max_windows < (1ull << 24) ? max_windows : (1ull << 24);
+            if (round) {
+                uint8_t *sp = reinterpret_cast<uint8_t *>(ws->scratch);
+                r = grow(sp, ws->scratch_bytes, mm::generic_scratch_bytes(round, plan->w), 1);
+                ws->scratch = sp;
+                if (r == MM_OK) r = grow_status(ws, mm::generic_status_words(round));
+                if (r) return r;
+            }
+            a.out.status = ws->status;
+            ws->status_dirty = true;
+            for (uint64_t q = 0; q < n_records; ++q) {
+                MM_HIP(hipMemcpyAsync(d_out_offsets + q, ws->total, sizeof(uint64_t), hipMemcpyDeviceToDevice, ws->stream));
+                const uint64_t b = hs[q] < n_chars ? hs[q] : n_chars;
+                const uint64_t e = hs[q + 1] < b ? b : (hs[q + 1] < n_chars ? hs[q + 1] : n_chars);
+                if (e - b < l) continue;
+                a.text = static_cast<const uint8_t *>(d_text) + b;
+                a.n = e - b;
+                a.win_begin = 0;
+                a.win_end = e - b - l + 1;
+                a.generic_round_windows = a.win_end < round ? a.win_end : round;
+                a.scratch = ws->scratch;
+                if (mm::launch_generic_text(a, ws->stream) != 0) {
+                    g_last_error = std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError());
+                    return MM_ERR_HIP;
+                }
+            }
+            MM_HIP(hipMemcpyAsync(d_out_offsets + n_records, ws->total, sizeof(uint64_t), hipMemcpyDeviceToDevice,
+                                  ws->stream));
+        }
+        ws->last_path = fused ? MM_PATH_FUSED : MM_PATH_GENERIC;
+    }
+    if (d_count)
+        MM_HIP(hipMemcpyAsync(d_count, ws->total, sizeof(unsigned long long), hipMemcpyDeviceToDevice, ws->stream));
+    return MM_OK;
+}
+
+int mm_run_text_batch_device_async(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_text, uint64_t text_bytes,
+                                   uint64_t n_records, const uint64_t *d_starts, uint64_t n_chars, uint32_t *d_out_pos,
+                                   uint32_t *d_out_sk, uint64_t capacity, uint64_t *d_out_offsets, uint64_t *d_count) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (ws) ws->async_unchecked = true;
+    return run_text_batch_async_impl(plan, ws, d_text, text_bytes, n_records, d_starts, n_chars, d_out_pos, d_out_sk,
+                                     capacity, d_out_offsets, d_count);
+}
+
+int mm_run_text_batch_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_text, uint64_t text_bytes,
+                             uint64_t n_records, const uint64_t *d_starts, uint64_t n_chars, uint32_t *d_out_pos,
+                             uint32_t *d_out_sk, uint64_t capacity, uint64_t *d_out_offsets, uint64_t *out_count) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    const int rc = text_batch_check(plan, d_text, text_bytes, n_records, d_starts, n_chars, d_out_sk, d_out_offsets);
+    if (rc) return rc;
+    if (!ws) return MM_ERR_NULL;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        // (as run_text_sync: an unchecked asynchronous run finishes before the words are reused)
+        if (ws->async_unchecked) MM_HIP(hipStreamSynchronize(ws->stream));
+        int r = run_text_batch_async_impl(plan, ws, d_text, text_bytes, n_records, d_starts, n_chars, d_out_pos,
+                                          d_out_sk, capacity, d_out_offsets, nullptr);
+        if (r) return r;
+        MM_HIP(hipMemcpyAsync(ws->h_total, ws->total, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                              ws->stream));
+        MM_HIP(hipStreamSynchronize(ws->stream));
+        const int je = judge_run_error(ws);
+        if (je < 0) return je;
+        if (je == 0) break;
+    }
+    if (out_count) *out_count = ws->h_total[0];
+    if (d_out_pos && ws->h_total[0] > capacity) return MM_ERR_CAPACITY;
+    return MM_OK;
+}
+
+int mm_run_text_batch_host(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *text, uint64_t n_records,
+                           const uint64_t *starts, uint32_t *out_pos, uint32_t *out_sk, uint64_t capacity,
+                           uint64_t *out_offsets, uint64_t *out_count) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (!plan || !out_offsets) return MM_ERR_NULL;
+    if (!plan->text) return MM_ERR_BAD_MODE;
+    if (out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;
+    if (n_records && !starts) return MM_ERR_NULL;
+    if (n_records >= (1ull << 31)) return MM_ERR_LEN_TOO_LARGE;
+    if (out_count) *out_count = 0;
+    for (uint64_t q = 0; q < n_records; ++q)
+        if (starts[q] > starts[q + 1]) return MM_ERR_UNSORTED;
+    const uint64_t n_chars = n_records ? starts[n_records] : 0;
+    if (n_chars >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
+    if (n_chars && !text) return MM_ERR_NULL;
+    if (!ws) return MM_ERR_NULL;
+    MM_HIP(set_device(ws->device));
+    // staging: [text | starts] in d_in, positions (and indices) in d_out / d_sk, offsets in d_vals
+    const uint64_t starts_at = (n_chars + 16 + 15) & ~15ull;
+    uint8_t *din = reinterpret_cast<uint8_t *>(ws->d_in);
+    int r = grow(din, ws->d_in_bytes, starts_at + (n_records + 1) * sizeof(uint64_t), 1);
+    ws->d_in = din;
+    if (r) return r;
+    const uint64_t cap = out_pos ? (capacity < n_chars ? capacity : n_chars) : 0;
+    r = grow(ws->d_out, ws->d_out_elems, cap ? cap : 1, sizeof(uint32_t));
+    if (r == MM_OK && out_sk) r = grow(ws->d_sk, ws->d_sk_elems, cap ? cap : 1, sizeof(uint32_t));
+    if (r == MM_OK) r = grow(ws->d_vals, ws->d_vals_elems, n_records + 1, sizeof(unsigned long long));
+    if (r) return r;
+    if (n_chars) MM_HIP(hipMemcpyAsync(din, text, n_chars, hipMemcpyHostToDevice, ws->stream));
+    if (n_records)
+        MM_HIP(hipMemcpyAsync(din + starts_at, starts, (n_records + 1) * sizeof(uint64_t), hipMemcpyHostToDevice,
+                              ws->stream));
+    uint64_t count = 0;
+    r = mm_run_text_batch_device(plan, ws, din, n_chars, n_records, reinterpret_cast<const uint64_t *>(din + starts_at),
+                                 n_chars, cap ? ws->d_out : nullptr, (out_sk && cap) ? ws->d_sk : nullptr, cap,
+                                 reinterpret_cast<uint64_t *>(ws->d_vals), &count);
+    if (out_count) *out_count = count;
+    if (r) return r;
+    MM_HIP(hipMemcpyAsync(out_offsets, ws->d_vals, (n_records + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
+    if (out_pos && count) {
+        MM_HIP(hipMemcpyAsync(out_pos, ws->d_out, count * sizeof(uint32_t), hipMemcpyDeviceToHost, ws->stream));
+        if (out_sk) MM_HIP(hipMemcpyAsync(out_sk, ws->d_sk, count * sizeof(uint32_t), hipMemcpyDeviceToHost, ws->stream));
+    }
+    MM_HIP(hipStreamSynchronize(ws->stream));
     return MM_OK;
 }
 

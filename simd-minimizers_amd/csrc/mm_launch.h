@@ -188,12 +188,20 @@ struct TextRunArgs {
     // (host copies of the scalars of *tables, for the fused kernel's arguments)
     bool hash_rc;
     uint32_t fw0, rc0, rot;
+    // a batch of records (fused kernel only; windows 0 .. n, win_begin = 0): records [starts[r], starts[r+1]) of the text,
+    // offsets[r] = the output index of record r's first position; tile_rec: text_batch_tiles(n) pairs of scratch
+    bool batch = false;
+    const uint64_t *starts = nullptr;
+    uint64_t n_records = 0;
+    unsigned long long *tile_rec = nullptr;
+    unsigned long long *offsets = nullptr;
 };
 int launch_generic_text(const TextRunArgs &a, hipStream_t stream);
 // ---- the fused text kernel (mm_text_walk.hip): one launch, w <= 128 and k <= 1024 (prebuilt W: 5, 11, 19)
 bool text_walk_supported(uint32_t k, uint32_t w);
 int text_prebuilt_windows(uint32_t *out, int capacity);
 uint64_t text_walk_tiles(uint64_t windows);  // = look-back words of a launch
+uint64_t text_batch_tiles(uint64_t n_chars);  // the same for a batch launch over n_chars characters
 int launch_text_walk(const TextRunArgs &a, hipStream_t stream);  // 0, -1 (HIP failure), -2 (not supported)
 
 // ---- auxiliary kernels (mm_aux.hip)

@@ -3,7 +3,7 @@
 // Prebuilt with a fixed W (unrolled minimum) for the paper's windows w = 5, 11, 19 (bench/src/bin/paper.rs:343-361), forward
 // and canonical windows, with and without the reverse-strand hash, for minimizers and both syncmer modes; every other
 // w <= kTextMaxW runs in the W = 0 instances of the same kernel (w read at run time), larger w and k > kTextMaxK take the
-// generic family's text kernels.
+// generic family's text kernels.  Each instance has a BATCH twin for mm_run_text_batch_* (records in one launch).
 #include "mm_launch.h"
 #include "mm_text_walk_impl.h"
 
@@ -13,16 +13,20 @@ namespace {
 
 typedef void (*TextWalkFn)(TextWalkParams);
 
-template <int W, bool CANON, bool HASH_RC>
+template <int W, bool CANON, bool HASH_RC, bool BATCH>
 TextWalkFn pick_mode(uint32_t mode) {
-    if (mode == 0) return text_walk_kernel<W, CANON, HASH_RC, 0>;
-    if (mode == 1) return text_walk_kernel<W, CANON, HASH_RC, 1>;
-    return text_walk_kernel<W, CANON, HASH_RC, 2>;
+    if (mode == 0) return text_walk_kernel<W, CANON, HASH_RC, 0, BATCH>;
+    if (mode == 1) return text_walk_kernel<W, CANON, HASH_RC, 1, BATCH>;
+    return text_walk_kernel<W, CANON, HASH_RC, 2, BATCH>;
+}
+template <int W, bool BATCH>
+TextWalkFn pick_strand(bool canon, bool hash_rc, uint32_t mode) {
+    if (canon) return pick_mode<W, true, true, BATCH>(mode);  // (canonical windows need a canonical hasher: mm_plan_create_text)
+    return hash_rc ? pick_mode<W, false, true, BATCH>(mode) : pick_mode<W, false, false, BATCH>(mode);
 }
 template <int W>
-TextWalkFn pick(bool canon, bool hash_rc, uint32_t mode) {
-    if (canon) return pick_mode<W, true, true>(mode);  // (canonical windows need a canonical hasher: mm_plan_create_text)
-    return hash_rc ? pick_mode<W, false, true>(mode) : pick_mode<W, false, false>(mode);
+TextWalkFn pick(bool canon, bool hash_rc, uint32_t mode, bool batch) {
+    return batch ? pick_strand<W, true>(canon, hash_rc, mode) : pick_strand<W, false>(canon, hash_rc, mode);
 }
 
 const uint32_t kTextPrebuiltW[] = {5, 11, 19};
@@ -39,6 +43,7 @@ int text_prebuilt_windows(uint32_t *out, int capacity) {
 }
 
 uint64_t text_walk_tiles(uint64_t windows) { return (windows + kTextTile - 1) / kTextTile; }
+uint64_t text_batch_tiles(uint64_t n_chars) { return text_walk_tiles(n_chars + 1); }
 
 int launch_text_walk(const TextRunArgs &a, hipStream_t stream) {
     if (!text_walk_supported(a.k, a.w)) return -2;
@@ -46,10 +51,10 @@ int launch_text_walk(const TextRunArgs &a, hipStream_t stream) {
     const bool hash_rc = a.hash_rc;
     TextWalkFn fn;
     switch (a.w) {
-        case 5: fn = pick<5>(canon, hash_rc, a.mode); break;
-        case 11: fn = pick<11>(canon, hash_rc, a.mode); break;
-        case 19: fn = pick<19>(canon, hash_rc, a.mode); break;
-        default: fn = pick<0>(canon, hash_rc, a.mode); break;
+        case 5: fn = pick<5>(canon, hash_rc, a.mode, a.batch); break;
+        case 11: fn = pick<11>(canon, hash_rc, a.mode, a.batch); break;
+        case 19: fn = pick<19>(canon, hash_rc, a.mode, a.batch); break;
+        default: fn = pick<0>(canon, hash_rc, a.mode, a.batch); break;
     }
     TextWalkParams p;
     p.text = a.text;
@@ -63,11 +68,19 @@ int launch_text_walk(const TextRunArgs &a, hipStream_t stream) {
     p.win_begin = a.win_begin;
     p.win_end = a.win_end;
     p.out = a.out;
-    const uint64_t tiles = text_walk_tiles(a.win_end - a.win_begin);
+    p.starts = a.starts;
+    p.n_records = a.n_records;
+    p.tile_rec = a.tile_rec;
+    p.offsets = a.offsets;
+    // (a batch: windows 0 .. n inclusive, so that the records that start in the last l - 1 bytes get their offsets)
+    const uint64_t tiles = a.batch ? text_batch_tiles(a.n) : text_walk_tiles(a.win_end - a.win_begin);
     // (untagged look-back words and the ticket, cleared per launch as the generic family does)
     if (hipMemsetAsync(a.out.status, 0, sizeof(unsigned long long) * tiles, stream) != hipSuccess) return -1;
     if (hipMemsetAsync(a.out.ticket, 0, sizeof(uint32_t), stream) != hipSuccess) return -1;
     if (a.timing_start) hipEventRecord(a.timing_start, stream);
+    if (a.batch)
+        hipLaunchKernelGGL(text_batch_tiles_kernel, dim3((uint32_t)((tiles + 255) / 256)), dim3(256), 0, stream, a.starts,
+                           a.n_records, a.k + a.w - 1, tiles, a.tile_rec);
     hipLaunchKernelGGL(fn, dim3((uint32_t)tiles), dim3(kTextThreads), 0, stream, p);
     if (a.timing_stop) hipEventRecord(a.timing_stop, stream);
     return hipGetLastError() == hipSuccess ? 0 : -1;

@@ -16,6 +16,15 @@
 //      across tiles (lookback_exclusive) and the stores in window order.
 // The first window of a tile dedups against the window in front of it (the tile computes one extra window), which is also
 // the seam rule of a window range.
+//
+// BATCH (mm_run_text_batch_*): the text is n_records records [starts[r], starts[r+1]) back to back, each run as if alone.
+// Stages 1-3 run straight across record boundaries (the rot-xor roll is exact, every k-mer of a valid window lies inside
+// its record); only the collect stage knows the records: window g of record r is valid iff g + l <= starts[r+1], the
+// first window of a record has no previous window, and positions / indices are record-local.  The tile's record starts
+// come from text_batch_tiles_kernel (one binary search per tile) and are staged into LDS as 16-bit tile-local offsets
+// (up to kTextBnd of them; a tile with more reads them from global memory instead); every thread finds its first
+// window's record by a search in that list and steps forward.  The thread whose windows hold g == starts[r] writes
+// offsets[r]; the grid spans windows 0 .. n_chars, so records that start in the last l - 1 bytes get theirs too.
 #pragma once
 #include "mm_common.h"
 
@@ -34,6 +43,8 @@ constexpr uint32_t kTextBytes = (kTextHashRun * kTextThreads + kTextMaxK + 32 + 
 constexpr uint32_t kTextSelStride = kTextPerThread / 2 + 1;       // dwords per thread's 32 offsets (+1: no conflicts)
 static_assert(kTextHashRun % 2 == 1, "odd runs keep the key stores of a wave on distinct banks");
 static_assert(kTextThreads == 256, "one table entry per thread");
+constexpr uint32_t kTextBnd = 2048;                               // BATCH: record starts of a tile held in LDS (4 KB)
+static_assert(kTextTile + 1 + kTextMaxW + kTextMaxK < 0xffffu, "tile-local byte offsets fit 16 bits");
 
 struct TextWalkParams {
     const uint8_t *text;       // caller's pointer (any alignment)
@@ -43,11 +54,40 @@ struct TextWalkParams {
     uint32_t k, w;             // (w: runtime value, also for the instances with a fixed W)
     uint64_t win_begin, win_end;
     OutParams out;
+    // BATCH: records [starts[r], starts[r+1]), r < n_records; tile_rec[2 t], [2 t + 1]: the first index of starts past
+    // tile t's front window, and the first past the last byte its windows reach (text_batch_tiles_kernel)
+    const uint64_t *starts;
+    uint64_t n_records;
+    const unsigned long long *tile_rec;
+    unsigned long long *offsets;  // [n_records + 1]
 };
+
+// One thread per tile of a BATCH launch: the range of record starts that tile t's collect stage needs (upper bounds of
+// its front window t * kTextTile - 1 and of the last byte it reaches, in starts[0 .. n_records]).  Records in any order
+// give some range inside [0, n_records + 1]: the walk never indexes outside it.
+__global__ __launch_bounds__(256) void text_batch_tiles_kernel(const uint64_t *starts, uint64_t n_records, uint32_t l,
+                                                               uint64_t tiles, unsigned long long *tile_rec) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= tiles) return;
+    auto upper = [&](long long x) -> uint64_t {  // first i in [0, n_records + 1) with starts[i] > x
+        uint64_t lo = 0, hi = n_records + 1;
+        while (lo < hi) {
+            const uint64_t mid = lo + (hi - lo) / 2;
+            if ((long long)starts[mid] <= x) lo = mid + 1;
+            else hi = mid;
+        }
+        return lo;
+    };
+    const long long front = (long long)(t * kTextTile) - 1;
+    const uint64_t b = t == 0 ? 0 : upper(front);
+    const uint64_t e = upper(front + kTextTile + l);
+    tile_rec[2 * t] = b;
+    tile_rec[2 * t + 1] = e > b ? e : b;
+}
 
 typedef uint32_t u32x4t __attribute__((ext_vector_type(4)));
 
-template <int W, bool CANON, bool HASH_RC, int MODE>
+template <int W, bool CANON, bool HASH_RC, int MODE, bool BATCH>
 __global__ __launch_bounds__(kTextThreads) void text_walk_kernel(TextWalkParams p) {
     __shared__ uint2 s_in[256], s_out[256];
     __shared__ __attribute__((aligned(16))) uint8_t s_text[kTextBytes];
@@ -56,6 +96,8 @@ __global__ __launch_bounds__(kTextThreads) void text_walk_kernel(TextWalkParams 
     __shared__ uint32_t s_bid;
     __shared__ uint32_t s_wave_tot[kTextThreads / kWave];
     __shared__ unsigned long long s_excl;
+    __shared__ uint16_t s_bnd[BATCH ? kTextBnd : 1];  // BATCH: the tile's record starts, tile-local (see bnd below)
+    __shared__ uint32_t s_rs0;                         // BATCH: the start of the record in front of the list
 
     const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
     const uint32_t w = W > 0 ? (uint32_t)W : p.w;
@@ -87,6 +129,20 @@ __global__ __launch_bounds__(kTextThreads) void text_walk_kernel(TextWalkParams 
         u32x4t v = {0u, 0u, 0u, 0u};
         if (o >= 0) v = __builtin_amdgcn_raw_buffer_load_b128(rs, (uint32_t)o, 0, 0);  // (past the end: zeros)
         *reinterpret_cast<u32x4t *>(s_text + 16 * c) = v;
+    }
+    // BATCH: record starts of the tile as offsets from its front window g0 (clamped: only an unordered list goes outside)
+    // (n_records < 2^31, checked by the entry points: list indices and record numbers fit 32 bits)
+    uint32_t rb = 0, nb = 0;
+    auto local_of = [&](uint64_t x) -> uint32_t {
+        const long long d = (long long)x - g0;
+        return d < 0 ? 0u : (d > 0xffff ? 0xffffu : (uint32_t)d);
+    };
+    if constexpr (BATCH) {
+        rb = (uint32_t)p.tile_rec[2 * bid];
+        nb = (uint32_t)p.tile_rec[2 * bid + 1] - rb;
+        if (nb <= kTextBnd)
+            for (uint32_t i = tid; i < nb; i += kTextThreads) s_bnd[i] = (uint16_t)local_of(p.starts[rb + i]);
+        if (tid == 0) s_rs0 = rb ? (uint32_t)p.starts[rb - 1] : 0u;
     }
     __syncthreads();
 
@@ -166,6 +222,26 @@ __global__ __launch_bounds__(kTextThreads) void text_walk_kernel(TextWalkParams 
         prev = pos_of(u_prev, *q, odd);
         have_prev = true;
     }
+    // BATCH: the record of window u is rb + i for the last list entry i with bnd(i) <= u (i = -1: the record in front
+    // of the list, starting at s_rs0); cur = bnd(i) (0 for i = -1), nxt = bnd(i + 1) (~0: past the list)
+    auto bnd = [&](uint32_t i) -> uint32_t { return nb <= kTextBnd ? (uint32_t)s_bnd[i] : local_of(p.starts[rb + i]); };
+    int ri = -1;
+    uint32_t cur = 0, nxt = ~0u;
+    if constexpr (BATCH) {
+        uint32_t lo = 0, hi = nb;
+        while (lo < hi) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (bnd(mid) <= u_prev) lo = mid + 1;
+            else hi = mid;
+        }
+        ri = (int)lo - 1;
+        cur = ri >= 0 ? bnd((uint32_t)ri) : 0u;
+        nxt = lo < nb ? bnd(lo) : ~0u;
+    }
+    const int ri0 = ri;
+    // start of window u_prev's record in text coordinates; smask bit j: a record starts at window u_first + j
+    const uint32_t rs0 = ri >= 0 ? (uint32_t)(g0 + cur) : s_rs0;
+    uint32_t smask = 0;
     uint32_t flags = 0;
     uint32_t vals[kTextPerThread];
 #pragma unroll
@@ -178,8 +254,20 @@ __global__ __launch_bounds__(kTextThreads) void text_walk_kernel(TextWalkParams 
         const uint64_t g = w0 + tid * kTextPerThread + j;
         const uint32_t pp = pos_of(u, mysel[j], odd);
         bool f = false;
-        if (g < p.win_end) {
-            if (MODE == 0) f = !have_prev || pp != prev;
+        bool in_rec = true, first_of_rec = !have_prev;
+        if constexpr (BATCH) {
+            while (nxt <= u) {
+                ++ri;
+                cur = nxt;
+                nxt = (uint32_t)(ri + 1) < nb ? bnd((uint32_t)(ri + 1)) : ~0u;
+            }
+            const int r = (int)rb + ri;
+            in_rec = r >= 0 && (uint32_t)r < (uint32_t)p.n_records && u + l <= nxt;
+            first_of_rec = u == cur;
+            smask |= (uint32_t)first_of_rec << j;
+        }
+        if (g < p.win_end && in_rec) {
+            if (MODE == 0) f = first_of_rec || pp != prev;
             else if (MODE == 1) f = (pp == (uint32_t)g) || (pp == (uint32_t)g + w - 1);
             else f = (pp == (uint32_t)g + w / 2);
         }
@@ -206,17 +294,30 @@ __global__ __launch_bounds__(kTextThreads) void text_walk_kernel(TextWalkParams 
     }
     __syncthreads();
     unsigned long long dst = s_excl + wave_base + (incl - cnt);
+    if constexpr (BATCH) {
+        // offsets of the records that start at this thread's windows: list entries ri0 + 1 .. ri, each at window bnd(i)
+        for (int i = ri0 + 1; i <= ri; ++i) {
+            const uint32_t j = bnd((uint32_t)i) - u_first;
+            if (j < kTextPerThread) p.offsets[rb + (uint32_t)i] = dst + __popc(flags & ((1u << j) - 1u));
+        }
+    }
+    uint32_t rec0 = rs0;  // (BATCH: the start of window j's record)
 #pragma unroll
     for (uint32_t j = 0; j < kTextPerThread; ++j) {
+        const uint32_t g = (uint32_t)(w0 + tid * kTextPerThread + j);
+        if (BATCH && (smask & (1u << j))) rec0 = g;
         if (flags & (1u << j)) {
             if (dst < p.out.cap) {
-                p.out.pos[dst] = vals[j];
-                if (p.out.sk) p.out.sk[dst] = (uint32_t)(w0 + tid * kTextPerThread + j);
+                p.out.pos[dst] = BATCH ? vals[j] - rec0 : vals[j];
+                if (p.out.sk) p.out.sk[dst] = BATCH ? g - rec0 : g;
             }
             ++dst;
         }
     }
-    if (tid == 0 && bid == gridDim.x - 1) *p.out.total = s_excl + block_total;
+    if (tid == 0 && bid == gridDim.x - 1) {
+        *p.out.total = s_excl + block_total;
+        if (BATCH) p.offsets[p.n_records] = s_excl + block_total;
+    }
 }
 
 }  // namespace mm
