@@ -1599,6 +1599,9 @@ static int run_reads_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, const
     if (!d_packed) return MM_ERR_NULL;
     const uint64_t span = d_read_starts ? total_bases : (n_reads - 1) * (uint64_t)read_stride + read_len;
     if (span >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
+    // bases of all reads together, which bound a lane table's lanes: reads back to back cover their span once, fixed-stride
+    // reads may OVERLAP (read_len > read_stride: 5 kbp windows every 1 kbp) and then cover it several times
+    const uint64_t read_bases = d_read_starts ? span : (span > n_reads * (uint64_t)read_len ? span : n_reads * (uint64_t)read_len);
     mm::SeqView view;
     int r = make_view(d_packed, packed_bytes, base_offset, span, &view);
     if (r) return r;
@@ -1653,12 +1656,12 @@ static int run_reads_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, const
             const uint64_t max_nw = read_len >= l ? read_len - l + 1 : 0;
             const double dens = plan->mode == MM_OPEN_SYNCMERS ? 1.0 / plan->w : (plan->mode == MM_CLOSED_SYNCMERS ? 2.0 / plan->w : 2.0 / (plan->w + 1.0));
             const uint64_t one_lane = (uint64_t)((48.0 * 1024.0 / 516.0 - 8.0) / (1.3 * dens));
-            lanes = mm::fused_segments_plan(a, span, ws->nblk, &sp) == 0 && max_nw > (sp.S > one_lane ? sp.S : one_lane);
+            lanes = mm::fused_segments_plan(a, read_bases, ws->nblk, &sp) == 0 && max_nw > (sp.S > one_lane ? sp.S : one_lane);
         }
         int lr = -3;
         if (lanes) {
             const mm::SegSource src{a.read_starts, a.read_starts ? nullptr : d_read_lens, read_stride, read_len};
-            r = run_lane_table(ws, a, src, span);
+            r = run_lane_table(ws, a, src, read_bases);
             if (r < 0) return r;
             lr = r == 0 ? 0 : -3;
         }
@@ -1690,7 +1693,7 @@ static int run_reads_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, const
                 // (reads too long for one lane each and no lane-table launch either - switched off, or no kernel)
                 if (lr == -3 && !lanes && policy != 0) {
                     const mm::SegSource src{a.read_starts, a.read_starts ? nullptr : d_read_lens, read_stride, read_len};
-                    r = run_lane_table(ws, a, src, span);
+                    r = run_lane_table(ws, a, src, read_bases);
                     if (r < 0) return r;
                     if (r == 0) lr = 0;
                 }

@@ -437,30 +437,34 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
     // so the halo after the last base needs no clamping.
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<uint32_t *>(ctx.seq_d + Q0c), 0, (int)(((long long)ctx.seq_dwords - Q0c) * 4), 0x00020000);
-    const int32_t pb = prel0 + (int32_t)ctx.lane_bases;  // first base of this lane's element 0
-    // 16-base view starting at tile-relative base position pos >= 0
-    auto view = [&](int32_t pos) -> uint32_t {
-        const auto d = __builtin_amdgcn_raw_buffer_load_b64(rsrc, ((uint32_t)pos >> 4) << 2, 0, 0);
-        return __builtin_amdgcn_alignbit(d[1], d[0], 2u * ((uint32_t)pos & 15u));
+    // Base positions of the lane are UNSIGNED offsets from the tile's origin: two lanes of one tile may lie up to 2^32 bases
+    // apart (lane-table tiles, reads at a large stride, a long first record cut to max_read_len), and a signed position at
+    // 2^31 or beyond would read as "before the buffer".
+    const uint32_t pb = (uint32_t)prel0 + ctx.lane_bases;  // first base of this lane's element 0
+    // 16-base view starting at tile-relative base position pos
+    auto view = [&](uint32_t pos) -> uint32_t {
+        const auto d = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (pos >> 4) << 2, 0, 0);
+        return __builtin_amdgcn_alignbit(d[1], d[0], 2u * (pos & 15u));
     };
-    // same, but pos may be -1 (only at a lane's start): the missing base reads as code 0
-    auto view_first = [&](int32_t pos) -> uint32_t {
-        const bool neg = pos < 0;
-        const auto d = __builtin_amdgcn_raw_buffer_load_b64(rsrc, neg ? 0u : (((uint32_t)pos >> 4) << 2), 0, 0);
-        return __builtin_amdgcn_alignbit(neg ? d[0] : d[1], neg ? 0u : d[0], 2u * ((uint32_t)pos & 15u));
+    // same, but pos may be the base before the buffer (0xffffffff: lane_bases == 0 and prel0 == -1, only at a lane's start):
+    // the missing base reads as code 0
+    auto view_first = [&](uint32_t pos) -> uint32_t {
+        const bool before = pos == 0xffffffffu;
+        const auto d = __builtin_amdgcn_raw_buffer_load_b64(rsrc, before ? 0u : ((pos >> 4) << 2), 0, 0);
+        return __builtin_amdgcn_alignbit(before ? d[0] : d[1], before ? 0u : d[0], 2u * (pos & 15u));
     };
 
     // the same in two steps, for loads issued two W-blocks ahead of their use
     using RawView = decltype(__builtin_amdgcn_raw_buffer_load_b64(rsrc, 0, 0, 0));
-    auto raw = [&](int32_t pos) -> RawView {
+    auto raw = [&](uint32_t pos) -> RawView {
 #ifdef MM_EXP_LOADSAME  // timing experiment (wrong results): every lane of the wave reads the same cache line
-        return __builtin_amdgcn_raw_buffer_load_b64(rsrc, (((uint32_t)pos >> 4) << 2) & 0x78u, 0, 0);
+        return __builtin_amdgcn_raw_buffer_load_b64(rsrc, ((pos >> 4) << 2) & 0x78u, 0, 0);
 #else
-        return __builtin_amdgcn_raw_buffer_load_b64(rsrc, ((uint32_t)pos >> 4) << 2, 0, 0);
+        return __builtin_amdgcn_raw_buffer_load_b64(rsrc, (pos >> 4) << 2, 0, 0);
 #endif
     };
-    auto aligned = [&](const RawView &d, int32_t pos) -> uint32_t {
-        return __builtin_amdgcn_alignbit(d[1], d[0], 2u * ((uint32_t)pos & 15u));
+    auto aligned = [&](const RawView &d, uint32_t pos) -> uint32_t {
+        return __builtin_amdgcn_alignbit(d[1], d[0], 2u * (pos & 15u));
     };
 
     const uint32_t rot_l = (32u - p.ht.rot) & 31u;  // alignbit amount for rotl(x, rot)
@@ -477,7 +481,7 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
 #else
     for (uint32_t g = 0; g * 16u < k; ++g) {
 #endif
-        const uint32_t wa = g == 0 ? view_first(pb) : view(pb + 16 * (int32_t)g);
+        const uint32_t wa = g == 0 ? view_first(pb) : view(pb + 16u * g);
         const uint32_t rem = k - 16u * g;
 #pragma unroll
         for (int m = 0; m < 8; ++m) {
@@ -496,8 +500,8 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
     }
 
     uint32_t ring_l[W], ring_r[W];
-    int32_t pos_in = pb + (int32_t)k;  // base entering the hash at step e: pb + k + e
-    int32_t pos_out = pb;              // base leaving the hash at step e:  pb + e
+    uint32_t pos_in = pb + k;  // base entering the hash at step e: pb + k + e
+    uint32_t pos_out = pb;     // base leaving the hash at step e:  pb + e
     // 0xffff0000 kept in a VGPR so that (h & mask) | e is one v_and_or_b32 with e in an SGPR
     uint32_t kmask;
     asm volatile("v_mov_b32 %0, 0xffff0000" : "=v"(kmask));
@@ -596,8 +600,8 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
     };
 #pragma unroll
     for (int g = 0; g < NSUB; ++g) {
-        va[g] = view(pos_in + 16 * g);
-        vr[g] = g == 0 ? view_first(pos_out) : view(pos_out + 16 * g);
+        va[g] = view(pos_in + 16u * (uint32_t)g);
+        vr[g] = g == 0 ? view_first(pos_out) : view(pos_out + 16u * (uint32_t)g);
         v2[g] = 0;
     }
 
@@ -621,9 +625,9 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
         }
 #pragma unroll
         for (int g = 0; g < NSUB; ++g) {
-            va[g] = view(pos_in + 16 * g);
-            vr[g] = view(pos_out + 16 * g);
-            if (kV2Load) v2[g] = view(pb + 1 + 16 * g);
+            va[g] = view(pos_in + 16u * (uint32_t)g);
+            vr[g] = view(pos_out + 16u * (uint32_t)g);
+            if (kV2Load) v2[g] = view(pb + 1u + 16u * (uint32_t)g);
         }
         // ... and the raw dwords of block 2: global loads run two W-blocks ahead of their use, so
         // that a burst of copy-out stores of a neighbouring workgroup in the CU's memory pipeline
@@ -633,14 +637,14 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
             for (int d = 0; d < PFD - 1; ++d)
 #pragma unroll
                 for (int g = 0; g < NSUB; ++g) {
-                    qa[d][g] = raw(pos_in + (d + 1) * W + 16 * g);
-                    qr[d][g] = raw(pos_out + (d + 1) * W + 16 * g);
-                    if (kV2Load) q2[d][g] = raw(pb + 1 + (d + 1) * W + 16 * g);
+                    qa[d][g] = raw(pos_in + (uint32_t)((d + 1) * W + 16 * g));
+                    qr[d][g] = raw(pos_out + (uint32_t)((d + 1) * W + 16 * g));
+                    if (kV2Load) q2[d][g] = raw(pb + 1u + (uint32_t)((d + 1) * W + 16 * g));
                 }
         } else {
             // wide loads: group 0 = blocks 2 .. MG + 1 (the views of block 1 were loaded above)
-            gp_in = (uint32_t)(pos_in + W);
-            gp_out = (uint32_t)(pos_out + W);
+            gp_in = pos_in + (uint32_t)W;
+            gp_out = pos_out + (uint32_t)W;
             wide_load(gp_in, Wa[1]);
 #ifndef MM_EXP_ONE_STREAM
             wide_load(gp_out, Wr[1]);
@@ -699,7 +703,7 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
     const uint32_t l = k + (uint32_t)W - 1;
     const int thr = (int)(l / 2);
     uint32_t prev;            // key of the predecessor window's k-mer (mode 0)
-    int32_t pos_r2 = pb + 1;  // window 0 -> 1 drops base pb + 1
+    uint32_t pos_r2 = pb + 1u;  // window 0 -> 1 drops base pb + 1
     if (CANON) {
         // window -1 covers bases [pb, pb + l)
         uint32_t c = 0;
@@ -708,7 +712,7 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
 #else
         for (uint32_t g = 0; g * 16u < l; ++g) {
 #endif
-            uint32_t wd = (g == 0 ? view_first(pb) : view(pb + 16 * (int32_t)g)) & 0xAAAAAAAAu;
+            uint32_t wd = (g == 0 ? view_first(pb) : view(pb + 16u * g)) & 0xAAAAAAAAu;
             const uint32_t rem = l - 16u * g;
             if (rem < 16u) wd &= (1u << (2u * rem)) - 1u;
             c += __popc(wd);
@@ -716,7 +720,7 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
         int cnt = (int)c;
         prev = (cnt > thr) ? ring_all<W, false>(ring_l) : ring_all<W, true>(ring_r);
         // move to window 0: + base pb + l, - base pb
-        cnt += (int)((view(pb + (int32_t)l) >> 1) & 1u);
+        cnt += (int)((view(pb + l) >> 1) & 1u);
         cnt -= (int)((view_first(pb) >> 1) & 1u);
         dn = cnt - thr - 1;
     } else {
@@ -808,8 +812,8 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
     // is the form the compiler picks for base + block * W.  sh_*: funnel-shift amount of the next
     // block's view (the hardware uses its low five bits); pl_*: base position of the loads that run
     // PFD - 1 blocks ahead.
-    uint32_t sh_in = 2u * (uint32_t)pos_in, sh_out = 2u * (uint32_t)pos_out;
-    uint32_t pl_in = (uint32_t)pos_in + (uint32_t)((PFD - 1) * W), pl_out = (uint32_t)pos_out + (uint32_t)((PFD - 1) * W);
+    uint32_t sh_in = 2u * pos_in, sh_out = 2u * pos_out;
+    uint32_t pl_in = pos_in + (uint32_t)((PFD - 1) * W), pl_out = pos_out + (uint32_t)((PFD - 1) * W);
 #define MM_BUMP(x, c) asm volatile("v_add_u32 %0, %1, %0" : "+v"(x) : "n"(c))
     uint32_t kn = 0;  // wide loads: index of block b + 1 within its group (wave-uniform)
     // The W-block loop.  Round 5: with wide loads the index of a block within its load group (kn) decides which dword pair
@@ -969,16 +973,16 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
         for (int g = 0; g < NSUB; ++g) {
             va[g] = __builtin_amdgcn_alignbit(qa[0][g][1], qa[0][g][0], sh_in);
             vr[g] = __builtin_amdgcn_alignbit(qr[0][g][1], qr[0][g][0], sh_out);
-            if (kV2Load) v2[g] = aligned(q2[0][g], pos_r2 + 16 * g);
+            if (kV2Load) v2[g] = aligned(q2[0][g], pos_r2 + 16u * (uint32_t)g);
 #pragma unroll
             for (int d = 0; d + 1 < PFD - 1; ++d) {
                 qa[d][g] = qa[d + 1][g];
                 qr[d][g] = qr[d + 1][g];
                 if (kV2Load) q2[d][g] = q2[d + 1][g];
             }
-            qa[PFD - 2][g] = raw((int32_t)pl_in + 16 * g);
-            qr[PFD - 2][g] = raw((int32_t)pl_out + 16 * g);
-            if (kV2Load) q2[PFD - 2][g] = raw(pos_r2 + (PFD - 1) * W + 16 * g);
+            qa[PFD - 2][g] = raw(pl_in + 16u * (uint32_t)g);
+            qr[PFD - 2][g] = raw(pl_out + 16u * (uint32_t)g);
+            if (kV2Load) q2[PFD - 2][g] = raw(pos_r2 + (uint32_t)((PFD - 1) * W + 16 * g));
         }
         if (AMBI && !kAmbiLand) {
 #pragma unroll
