@@ -63,6 +63,12 @@ typedef struct mm_device_group mm_device_group_t; /* one workspace per listed de
 typedef struct mm_plan mm_plan_t;           /* immutable (k, w, hasher, mode): the Builder     */
 typedef struct mm_workspace mm_workspace_t; /* per-stream device scratch: the thread-local CACHE
                                                of src/lib.rs:217-219, src/collect.rs:124-126   */
+/* Threads: one workspace per host thread / stream; plans are immutable and shareable.
+ *   - a plan is never written after mm_plan_create*: any number of threads may run with it at once;
+ *   - a workspace or a device group is used by ONE thread at a time (no lock inside); it may move from
+ *     one thread to another between calls;
+ *   - mm_last_error() is per thread: it tells the calling thread about its own last failure;
+ *   - an entry point restores the CALLING thread's current device before it returns. */
 
 /* One entry per assert!/panic! on the reference path. */
 enum {
@@ -148,6 +154,10 @@ int mm_workspace_kernel_time(mm_workspace_t *ws, double *total_ms, uint64_t *lau
                              int reset);
 /* Family used by the last run (mm_path_t). */
 int mm_workspace_last_path(const mm_workspace_t *ws);
+/* 1 once this workspace takes the fused kernels' tile ids from an atomic ticket (after a look-back of one of its
+ * runs timed out: workgroups were not dispatched in index order), else 0.  Read-only diagnostic: results are the
+ * same either way, the synchronous entry points repeat such a run themselves. */
+int mm_workspace_ticket_mode(const mm_workspace_t *ws);
 /* 1 when the last reads / batch run on this workspace was a LANE-TABLE launch (round 6): one launch of the reads-mode
  * kernel whose lanes are segments of the reads - a read longer than a lane takes consecutive lanes - so reads and
  * sequences of any lengths (Builder::run per read / contig, src/lib.rs:378; the reference's `short` experiment spans

@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import threading
 
 import numpy as np
 
@@ -100,10 +101,19 @@ def _text_array(seq) -> np.ndarray:
 
 
 _lib = None
+_lib_lock = threading.Lock()
 
 
 def lib():
-    """Load the HIP library; fail loudly if it has not been built."""
+    """Load the HIP library; fail loudly if it has not been built.  Threads racing on the first call load and bind
+    it once."""
+    if _lib is not None:
+        return _lib
+    with _lib_lock:
+        return _load_lib()
+
+
+def _load_lib():
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
@@ -174,6 +184,7 @@ def lib():
         L.mm_workspace_enable_timing.argtypes = [vp, C.c_int]
         L.mm_workspace_kernel_time.argtypes = [vp, C.POINTER(C.c_double), u64p, C.c_int]
         L.mm_workspace_last_path.argtypes = [vp]
+        L.mm_workspace_ticket_mode.argtypes = [vp]
         L.mm_workspace_last_lane_table.argtypes = [vp]
         if hasattr(L, "mm_prebuilt_window_sizes"):  # (absent from the round-3 library kept for A/B runs under tools/ab/)
             L.mm_prebuilt_window_sizes.argtypes = [C.c_int, C.c_int, u32p, C.c_int]
@@ -247,7 +258,8 @@ EXPORTED_SYMBOLS = [
     "mm_plan_create",
     "mm_plan_destroy", "mm_plan_value_len", "mm_workspace_create", "mm_workspace_destroy",
     "mm_workspace_sync", "mm_workspace_check", "mm_workspace_force_generic", "mm_workspace_set_blocks_per_lane",
-    "mm_workspace_enable_timing", "mm_workspace_kernel_time", "mm_workspace_last_path", "mm_workspace_last_lane_table", "mm_prebuilt_window_sizes",
+    "mm_workspace_enable_timing", "mm_workspace_kernel_time", "mm_workspace_last_path", "mm_workspace_ticket_mode",
+    "mm_workspace_last_lane_table", "mm_prebuilt_window_sizes",
     "mm_run_device_async", "mm_run_device", "mm_run_host", "mm_run_host_ascii",
     "mm_values_u64_device_async", "mm_values_u64_host", "mm_values_u128_device_async",
     "mm_values_u128_host", "mm_run_batch_device", "mm_run_reads_device_async", "mm_run_reads_device",
@@ -402,7 +414,8 @@ class AsciiSeq:
 
 
 class Workspace:
-    """Device scratch + stream (the reference's thread-local CACHE, src/lib.rs:217-219)."""
+    """Device scratch + stream (the reference's thread-local CACHE, src/lib.rs:217-219).  One thread uses a workspace at
+    a time (the library holds no lock on it); it may be handed to another thread between calls."""
 
     def __init__(self, device: int = 0, stream: int | None = None):
         L = lib()
@@ -458,6 +471,11 @@ class Workspace:
 
     def last_path(self) -> int:
         return lib().mm_workspace_last_path(self.h)
+
+    def ticket_mode(self) -> bool:
+        """The fused kernels take their tile ids from an atomic ticket on this workspace since a look-back of one of its
+        runs timed out (``mm_workspace_ticket_mode``; diagnostics only, results are the same)."""
+        return bool(lib().mm_workspace_ticket_mode(self.h))
 
     def last_lane_table(self) -> bool:
         """The last reads / batch run was ONE lane-table launch (``mm_workspace_last_lane_table``)."""
@@ -633,13 +651,18 @@ class DeviceGroup:
         return pos[:o[-1]], (sk[:o[-1]] if sk is not None else None), o
 
 
-_default_ws: dict[int, Workspace] = {}
+_default_ws = threading.local()  # .by_device: {device: Workspace} of the calling thread
 
 
 def default_workspace(device: int = 0) -> Workspace:
-    """Per-device workspace bound to torch's current stream when torch is importable, so that
-    tensor fills / copies issued through torch are ordered with the engine's kernels."""
-    if device not in _default_ws:
+    """The calling thread's workspace of ``device`` (the reference's thread-local CACHE, src/lib.rs:217-219): one per
+    (thread, device), created at the thread's first use and bound to the thread's current torch stream of that device
+    when torch is importable, so that tensor fills / copies issued through torch are ordered with the engine's kernels.
+    A workspace serves one thread at a time, so threads never share one of these."""
+    by_device = getattr(_default_ws, "by_device", None)
+    if by_device is None:
+        by_device = _default_ws.by_device = {}
+    if device not in by_device:
         stream = None
         try:
             import torch
@@ -647,8 +670,8 @@ def default_workspace(device: int = 0) -> Workspace:
                 stream = torch.cuda.current_stream(device).cuda_stream
         except ImportError:
             pass
-        _default_ws[device] = Workspace(device, stream)
-    return _default_ws[device]
+        by_device[device] = Workspace(device, stream)
+    return by_device[device]
 
 
 # -------------------------------------------------------------------- builder
@@ -765,6 +788,7 @@ class Builder:
         self._text_hasher = text_hasher  # hasher of byte text (None: TextMulHasher, the default of ``&[u8]``)
         self._plan = None
         self._text_plan = None
+        self._plan_lock = threading.Lock()  # (threads that share a builder create its plans once)
 
     def hasher(self, hasher) -> "Builder":  # src/lib.rs:327
         """A ``Hasher`` for 2-bit sequences, or a ``TextHasher`` for byte text; the other kind is kept."""
@@ -779,20 +803,28 @@ class Builder:
                        self._text_hasher)
 
     def workspace(self, ws: Workspace) -> "Builder":
-        return Builder(self.k, self.w, self.canonical, self.mode, self._hasher, self._sk, ws, self._text_hasher)
+        """The same builder on ``ws``; plans already created are shared (they do not depend on the workspace)."""
+        b = Builder(self.k, self.w, self.canonical, self.mode, self._hasher, self._sk, ws, self._text_hasher)
+        b._plan, b._text_plan = self._plan, self._text_plan
+        return b
 
     def _ws(self) -> Workspace:
         return self._workspace or default_workspace()
 
     def plan(self) -> Plan:
+        """The builder's plan, created at first use; immutable, so any number of threads may run with it."""
         if self._plan is None:
-            self._plan = Plan(self.k, self.w, self.canonical, self.mode, self._hasher)
+            with self._plan_lock:
+                if self._plan is None:
+                    self._plan = Plan(self.k, self.w, self.canonical, self.mode, self._hasher)
         return self._plan
 
     def text_plan(self) -> Plan:
-        """The plan of byte-text runs (mm_plan_create_text)."""
+        """The plan of byte-text runs (mm_plan_create_text), created at first use like ``plan``."""
         if self._text_plan is None:
-            self._text_plan = Plan(self.k, self.w, self.canonical, self.mode, self._text_hasher, text=True)
+            with self._plan_lock:
+                if self._text_plan is None:
+                    self._text_plan = Plan(self.k, self.w, self.canonical, self.mode, self._text_hasher, text=True)
         return self._text_plan
 
     # -- host sequences -------------------------------------------------

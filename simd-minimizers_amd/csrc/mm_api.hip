@@ -821,6 +821,7 @@ int mm_workspace_kernel_time(mm_workspace_t *ws, double *total_ms, uint64_t *lau
 }
 
 int mm_workspace_last_path(const mm_workspace_t *ws) { return ws ? ws->last_path : 0; }
+int mm_workspace_ticket_mode(const mm_workspace_t *ws) { return ws && ws->force_ticket ? 1 : 0; }
 int mm_workspace_last_lane_table(const mm_workspace_t *ws) { return ws && ws->last_lane_table ? 1 : 0; }
 
 // Diagnostics (no device needed when MM_TAPER_SLOTS names the workgroup slots): the launch plan of a run over

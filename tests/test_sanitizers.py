@@ -215,3 +215,9 @@ def test_host_side_under_asan_ubsan():
     tail = (r.stdout + r.stderr)[-4000:]
     assert r.returncode == 0 and "host paths ok" in r.stdout, tail
     assert "ERROR: AddressSanitizer" not in tail and "runtime error:" not in tail, tail
+    # the threaded workload (tests/thread_workload.py): 8 threads, each with its own workspace, on shared plans
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "thread_workload.py"), "--threads", "8", "--rounds",
+                        "1", "--lib", lib], env=env, capture_output=True, text=True, timeout=1200)
+    tail = (r.stdout + r.stderr)[-4000:]
+    assert r.returncode == 0 and '"ok": true' in r.stdout, tail
+    assert "ERROR: AddressSanitizer" not in tail and "runtime error:" not in tail, tail
