@@ -620,6 +620,12 @@ int mm_debug_launch_plan(uint32_t w, int canonical_windows, int mode, uint64_t n
                          uint64_t *out7, uint32_t *tile_seq, uint32_t *tile_win0, uint32_t *tile_nblk,
                          uint64_t tile_capacity, uint64_t *n_tiles);
 int mm_debug_launch_lds(uint32_t w, int canonical_windows, int mode, uint64_t n_windows, uint64_t *out2);
+/* Diagnostics: 1 when a minimizer run (positions only) of one sequence or a batch of sequences with this (k, w) and window
+ * flavour is launched with a kernel compiled for that k (one sequence load stream), 0 when it takes the
+ * kernel that reads k at run time.  Both compute the same; the GPU test-suite checks that.  No device needed.  One of the
+ * mm_debug_* family: for tests and tools, no part of the drop-in interface.  In the EXPERIMENTS build of the library the
+ * answer follows its switches - MM_NO_KC, MM_JIT_FORCE and a non-zero MM_DEBUG all make it 0. */
+int mm_debug_fixed_k_kernel(uint32_t k, uint32_t w, int canonical_windows);
 /* Diagnostics of the lane-table launches (round 6).  mm_debug_lane_plan: the lane length and grid the host
  * chooses for n_reads reads of total_bases bases - out6 = {blocks per lane, windows per lane S, entries per lane list, bytes of
  * the lane lists, upper bound of the lanes (a multiple of 256), tiles}; mode as in mm_debug_launch_plan (3: with super-k-mer

@@ -873,6 +873,10 @@ int mm_debug_launch_lds(uint32_t w, int canonical_windows, int mode, uint64_t n_
     return MM_OK;
 }
 
+int mm_debug_fixed_k_kernel(uint32_t k, uint32_t w, int canonical_windows) {
+    return mm::fused_fixed_k(k, w, canonical_windows, canonical_windows) ? 1 : 0;
+}
+
 int mm_debug_launch_plan(uint32_t w, int canonical_windows, int mode, uint64_t n_seqs, const uint64_t *n_windows,
                          uint64_t *out7, uint32_t *tile_seq, uint32_t *tile_win0, uint32_t *tile_nblk, uint64_t tile_capacity,
                          uint64_t *n_tiles) {

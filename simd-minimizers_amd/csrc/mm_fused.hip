@@ -59,6 +59,20 @@ const Instance *find_instance(uint32_t w, int canonical_windows, int hasher_cano
     return nullptr;
 }
 
+// Fixed-k instances (mm_fused_inst_kc.hip): minimizers of sequence mode whose walk keeps one load stream because k is a
+// compile-time constant.  Same results as the run-time-k kernel of the same (w, flavour); -DMM_NO_KC for the whole
+// library (A/B builds) or MM_NO_KC in the environment of the EXPERIMENTS build (A/B inside one process) leave them out.
+const FusedKcInstance *find_kc_instance(uint32_t w, uint32_t k, int canonical_windows, int hasher_canonical) {
+    if (mm_exp_env("MM_NO_KC")) return nullptr;
+    int n = 0;
+    const FusedKcInstance *inst = fused_kc_instances(&n);
+    for (int i = 0; i < n; ++i)
+        if (inst[i].w == w && inst[i].k == k && inst[i].canon == (canonical_windows != 0) &&
+            inst[i].hash_rc == (hasher_canonical != 0))
+            return &inst[i];
+    return nullptr;
+}
+
 double emit_density(uint32_t w, uint32_t mode) {
     return mode == 2 ? 1.0 / w : (mode == 1 ? 2.0 / w : 2.0 / (w + 1.0));
 }
@@ -214,10 +228,17 @@ struct KernelRef {
 
 thread_local std::string t_jit_error;
 
-KernelRef resolve_kernel(uint32_t w, int canonical_windows, int hasher_canonical, uint32_t mode, bool sk) {
+// k: the plan's k-mer length for launches that may take a fixed-k instance (FusedParams::k is then that k), 0: never
+KernelRef resolve_kernel(uint32_t w, int canonical_windows, int hasher_canonical, uint32_t mode, bool sk, uint32_t k = 0) {
     KernelRef kr;
     if (mode > 2) return kr;
     const bool force_jit = force_jit_wanted();  // tuning experiments (experiments build only)
+    if (k != 0 && mode == 0 && !sk && !force_jit) {
+        if (const FusedKcInstance *kc = find_kc_instance(w, k, canonical_windows, hasher_canonical)) {
+            kr.host = kc->fn;
+            return kr;
+        }
+    }
     const Instance *inst = force_jit ? nullptr : find_instance(w, canonical_windows, hasher_canonical);
     if (inst) {
         kr.host = inst->fn[(mode == 0 && sk) ? 3 : mode];
@@ -281,6 +302,10 @@ bool fused_supported(uint32_t k, uint32_t w, int canonical_windows, int hasher_c
     (void)k;
     if (find_instance(w, canonical_windows, hasher_canonical)) return true;
     return jit_enabled() && w >= 1 && w <= kJitMaxW;
+}
+
+bool fused_fixed_k(uint32_t k, uint32_t w, int canonical_windows, int hasher_canonical) {
+    return !force_jit_wanted() && find_kc_instance(w, k, canonical_windows, hasher_canonical) != nullptr;
 }
 
 // lower end of the lane lengths tune_whole_rounds may choose from (blocks per lane)
@@ -436,7 +461,7 @@ uint32_t fused_batch_nblk(const RunArgs &a, const uint64_t *n_windows, uint64_t 
     for (uint64_t s = 0; s < n_seqs; ++s) tiles += (n_windows[s] + g.NB - 1) / g.NB;
     g.nblocks = tiles;
     if (tiles <= 512) return 0;
-    const KernelRef kr = resolve_kernel(a.w, a.canonical_windows, (int)a.ht.canonical, a.mode, a.out.sk != nullptr);
+    const KernelRef kr = resolve_kernel(a.w, a.canonical_windows, (int)a.ht.canonical, a.mode, a.out.sk != nullptr, a.k);
     if (!kr) return 0;
     const uint32_t nb = whole_rounds_nblk(a, kr, g, [&](uint64_t S) {
         uint64_t t = 0;
@@ -531,7 +556,7 @@ bool fused_batch_tiles(const RunArgs &a0, const uint64_t *n_windows, uint64_t n_
     uint64_t zone_start = ~0ull, per_level = 1, lmax = 0;
     uint64_t fake_slots = 0;
     if (const char *e = mm_env("MM_TAPER_SLOTS")) fake_slots = (uint64_t)atoi(e) > 0 ? (uint64_t)atoi(e) : 0;
-    const KernelRef kr = (a.nblk == 0 && total && !fake_slots) ? resolve_kernel(a.w, a.canonical_windows, (int)a.ht.canonical, a.mode, a.out.sk != nullptr) : KernelRef();
+    const KernelRef kr = (a.nblk == 0 && total && !fake_slots) ? resolve_kernel(a.w, a.canonical_windows, (int)a.ht.canonical, a.mode, a.out.sk != nullptr, a.k) : KernelRef();
     int per_cu = 0, cus = 0;
     if (a.nblk == 0 && total && !mm_env("MM_NO_TAPER") && g.nblk >= kTaperMinBlocks + 4u &&
         (fake_slots || (kr && resident_slots(kr, g.lds_bytes, &per_cu, &cus)))) {
@@ -627,7 +652,7 @@ int launch_fused(const RunArgs &a, hipStream_t stream) {
     if (g.nblocks == 0) return 0;
     if (g.lds_bytes > kMaxLdsBytes) return -2;
     const KernelRef kr = resolve_kernel(a.w, a.canonical_windows, (int)a.ht.canonical, a.mode,
-                                        a.out.sk != nullptr);
+                                        a.out.sk != nullptr, a.k);
     if (!kr) return -2;
     // A run long enough for the tapered tail keeps the default (longest) lanes: the taper removes what the whole-rounds
     // tuner is there to avoid, and longer lanes pay less per-tile overhead (k=21 w=11 on 775 Mbp: 0.382 ms with the

@@ -340,6 +340,42 @@ constexpr int kWideGroup = wide_group_blocks(W);
 template <int W>
 constexpr int kWideDwords = wide_dwords(W);
 
+// Compile-time k (round 7): ONE load stream.  The base leaving the hash is the base that entered it k steps earlier, so
+// with k a template constant (KC) the hash-out views are taken from the hash-in buffers: the working buffer of the
+// current group and the one of the group before it, which stays live across the group turn in the registers the
+// hash-out buffer used to occupy.  Both are byte-normalised; when a group is a whole number of bytes (MG * W bases,
+// a multiple of 4) the earlier buffer begins exactly 2 * MG * W bits before the current one and carries the same bit
+// part s, so hash-out view (K, g) begins at bit s + off with off = 2 * W * K + 32 * g - 2 * KC of the current buffer,
+// or - off negative - at off + 2 * MG * W of the earlier one: dword pair and shift are compile-time, as for the
+// hash-in views.  The rule below says for which (W, KC) every view lies inside the bits valid for every lane of ONE
+// of the two buffers (the last view with the strand window's extra base, see wide_group_blocks_nd) and the lane's
+// warm-up can fill the earlier buffer (it begins at most one dword in front of the lane's first base).  k=21 w=11
+// passes (views of blocks 0, 1 from the earlier buffer, 2, 3 from the current one); k=31 w=51 does not: its groups
+// are one block of 51 bases, 12.75 bytes, so the distance between the two buffers differs from lane to lane.
+// -DMM_NO_KC (experiments, A/B): no walk takes this form.
+constexpr bool kc_rule(int W, int KC) {
+#ifdef MM_NO_KC
+    return false;
+#endif
+    if (KC <= 0) return false;
+    const int MG = wide_group_blocks(W), ND = wide_dwords(W);
+    if (MG < 1 || (MG * W) % 4 != 0) return false;
+    // The warm-up's earlier buffer begins at byte A = (gp_in >> 2) - MG * W / 4 of the tile's span, gp_in = pb + KC + 2 * W the
+    // first base of the lane's load group 0 and pb >= -1 the lane's element 0 (lane_walk): A is smallest at pb = -1, and
+    // the warm-up reaches at most one dword (four bytes) in front of the span.
+    if ((KC + 2 * W - 1) / 4 - MG * W / 4 < -4) return false;
+    const int nsub = (W + 15) / 16, valid = 32 * ND - 24, span = 2 * MG * W;
+    for (int K = 0; K < MG; ++K)
+        for (int g = 0; g < nsub; ++g) {
+            int off = 2 * W * K + 32 * g - 2 * KC;
+            if (off < 0) off += span;
+            if (off < 0) return false;
+            const int bases = (W - 16 * g < 16 ? W - 16 * g : 16) + (g == nsub - 1 ? 1 : 0);
+            if (off % 32 > 24 || off + 6 + 2 * bases > valid) return false;
+        }
+    return true;
+}
+
 template <int N>
 struct IntTag {
     static constexpr int value = N;
@@ -414,7 +450,9 @@ constexpr uint32_t ambi_land_bytes(int W) { return ambi_land_rule(W) ? kFusedWav
 // One lane walks its S windows.  List mode: appends emitted 16-bit values to the lane's LDS
 // list (entries past the capacity are dropped but counted).  DIRECT mode: stores final values
 // to HBM from ctx.dst on.  Returns the number of emitted windows.
-template <int W, bool CANON, bool HASH_RC, int MODE, bool SK, bool DIRECT, bool PARTIAL, bool AMBI = false, bool E8 = false>
+// KC > 0: k is this compile-time constant (the launcher's promise, FusedParams::k == KC) and the walk keeps one load
+// stream where kc_rule allows it; KC = 0: k is FusedParams::k.
+template <int W, bool CANON, bool HASH_RC, int MODE, bool SK, bool DIRECT, bool PARTIAL, bool AMBI = false, bool E8 = false, int KC = 0>
 __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCtx &ctx, bool &overflowed) {
     static_assert(!E8 || !SK, "8-bit list entries hold positions only");
     constexpr uint32_t kStride = list_stride(E8);  // bytes between consecutive entries of the lane's list
@@ -469,7 +507,8 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
 
     const uint32_t rot_l = (32u - p.ht.rot) & 31u;  // alignbit amount for rotl(x, rot)
     const uint32_t rot_r = p.ht.rot & 31u;
-    const uint32_t k = p.k;
+    constexpr bool kKC = !AMBI && kc_rule(W, KC);  // (the skip-ambiguous walk keeps its two streams)
+    const uint32_t k = kKC ? (uint32_t)KC : p.k;
     uint32_t fw = p.ht.fw0, rc = p.ht.rc0;  // (the hasher's constant XOR terms; 0 for NtHasher)
     const uint8_t *tabb = reinterpret_cast<const uint8_t *>(ctx.tab);
 
@@ -534,6 +573,7 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
     WideBuf(&Wr)[2] = Wa;
 #else
     WideBuf Wa[2], Wr[2];  // [0] working buffer of the current group, [1] landing buffer of the next one
+                           // (kKC: Wr[0] = the hash-in working buffer of the group before, Wr[1] unused)
 #endif
     constexpr bool kAmbiLand = AMBI && ambi_land_rule(W);  // (the look-ahead loads that land in LDS: see below)
     uint32_t gp_in = 0, gp_out = 0;  // first base (tile-relative) of the next group to load
@@ -588,6 +628,23 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
         for (int i = 0; i < ND; ++i)
             dst.q[i] = __builtin_amdgcn_alignbyte(i + 1 < ND ? w.q[i + 1 < ND ? i + 1 : i] : 0u, w.q[i], a);
         return w.sh & 6u;
+    };
+    // kKC: the hash-out views of block k of a group, from the earlier (`wp`) or the current (`w`) hash-in buffer; `sh` is
+    // the hash-in views' shift of the same block, s + 2 * W * k (its low five bits count)
+    auto kc_out_views = [&](const WideBuf &wp, const WideBuf &w, uint32_t sh, auto ktag, uint32_t (&v)[NSUB]) {
+        constexpr int K = decltype(ktag)::value;
+        constexpr int kSpan = 2 * W * (MG ? MG : 1);
+#pragma unroll
+        for (int g = 0; g < NSUB; ++g) {
+            constexpr int kLag = 2 * (KC > 0 ? KC : 0);
+            const int off0 = 2 * W * K + 32 * g - kLag;
+            const bool prv = off0 < 0;
+            const int off = prv ? off0 + kSpan : off0;
+            const int pp = off > 0 ? off / 32 : 0;
+            const uint32_t add = (uint32_t)(((off - 2 * W * K) % 32 + 32) % 32);  // (off - 2 W K may be negative)
+            const WideBuf &src = prv ? wp : w;
+            v[g] = __builtin_amdgcn_alignbit(pp + 1 < ND ? src.q[pp + 1 < ND ? pp + 1 : 0] : 0u, src.q[pp < ND ? pp : 0], sh + add);
+        }
     };
     // views of block k of a group (k compile-time): dword pair and shift as derived above
     auto wide_views = [&](const WideBuf &w, uint32_t sh, auto ktag, uint32_t (&v)[NSUB]) {
@@ -647,8 +704,25 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
             gp_out = pos_out + (uint32_t)W;
             wide_load(gp_in, Wa[1]);
 #ifndef MM_EXP_ONE_STREAM
-            wide_load(gp_out, Wr[1]);
+            if (!kKC) wide_load(gp_out, Wr[1]);
 #endif
+            if (kKC) {
+                // The working buffer of the group BEFORE group 0, so that the first group turn is like every other: byte-
+                // normalised, MG * W / 4 bytes in front of group 0's.  It may begin up to four bytes in front of the tile's
+                // origin (kc_rule; lane 0 of any tile whose element 0 lies in the first bytes of the tile's span, not only at
+                // the very start of a buffer): those bytes are filled with 0 instead of loaded, and no view uses them - the
+                // first hash-out view begins at the lane's base pb + W, 2 * MG * W - 2 * KC bits into this buffer.
+                const int32_t A = (int32_t)(gp_in >> 2) - (MG * W) / 4;
+                const bool before = A < 0;
+                const uint32_t off = before ? 0u : ((uint32_t)A & ~3u);
+                typedef uint32_t u32x4w __attribute__((ext_vector_type(4)));
+                const u32x4w v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0);
+                const uint32_t v4 = ND == 5 ? __builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 16, 0) : 0u;
+                const uint32_t x[6] = {before ? 0u : v.x, before ? v.x : v.y, before ? v.y : v.z, before ? v.z : v.w,
+                                       before ? v.w : v4, 0u};
+#pragma unroll
+                for (int i = 0; i < ND; ++i) Wa[0].q[i] = __builtin_amdgcn_alignbyte(i + 1 < ND ? x[i + 1] : 0u, x[i], (uint32_t)A & 3u);
+            }
             if (kAmbiLand && ND == 5) {
                 land_q4_load(gp_in, lpar, 0u);
                 land_q4_load(gp_out, lpar, 1u);
@@ -870,7 +944,7 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
         pos_out += W;
         pos_r2 += W;
         MM_BUMP(sh_in, 2 * W);
-        MM_BUMP(sh_out, 2 * W);
+        if (!kKC) MM_BUMP(sh_out, 2 * W);
         if (MG == 0) {
             MM_BUMP(pl_in, W);
             MM_BUMP(pl_out, W);
@@ -928,7 +1002,15 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
             if ((KN >= 0 ? (uint32_t)KN : kn) == 0u) {
                 // (the landing buffer [1] is shifted into the working buffer [0]; then it takes the next load)
                 // (kAmbiLand: the fifth dwords were taken out of LDS at the top of the block)
+                if (kKC) {  // the group that ends becomes the earlier buffer
+#pragma unroll
+                    for (int i = 0; i < ND; ++i) Wr[0].q[i] = Wa[0].q[i];
+                }
                 sh_in = wide_normalise(Wa[0], Wa[1]);
+                if (kKC) {
+                    wide_load(gp_in, Wa[1]);
+                    MM_BUMP(gp_in, MG * W);
+                } else {
 #ifdef MM_EXP_ONE_STREAM
                 sh_out = sh_in;
                 wide_load(gp_in, Wa[1]);
@@ -945,13 +1027,15 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
                 MM_BUMP(gp_in, MG * W);
                 MM_BUMP(gp_out, MG * W);
 #endif
+                }
             }
             switch (KN >= 0 ? (uint32_t)KN : kn) {
 #define MM_WIDE_CASE(K)                                                   \
     case K:                                                               \
         if (K < (MG ? MG : 1)) {                                          \
             wide_views(Wa[0], sh_in, IntTag<(K < (MG ? MG : 1) ? K : 0)>{}, va); \
-            wide_views(Wr[0], sh_out, IntTag<(K < (MG ? MG : 1) ? K : 0)>{}, vr); \
+            if (kKC) kc_out_views(Wr[0], Wa[0], sh_in, IntTag<(K < (MG ? MG : 1) ? K : 0)>{}, vr); \
+            else wide_views(Wr[0], sh_out, IntTag<(K < (MG ? MG : 1) ? K : 0)>{}, vr); \
         }                                                                 \
         break;
                 MM_WIDE_CASE(0)
@@ -1761,7 +1845,9 @@ __device__ __forceinline__ void copy_out_wave(const uint8_t *smem, const OutPara
 // READS = false: one sequence (range of windows), lane t walks windows [t*S, (t+1)*S) of the tile.
 // READS = true : a batch of short reads at a fixed stride, lane t walks read (tile*256 + t) alone;
 //                positions are read-local and read_offsets[] delimits the reads in the output.
-template <int W, bool CANON, bool HASH_RC, int MODE, bool SK, bool READS>
+// KC (trailing, 0 = k at run time): the walks of sequence mode (plain, range-checked and the redo; not the skip-ambiguous
+// walk, not reads mode) are compiled for k = KC, see kc_rule; the launcher picks such an instance only for that k.
+template <int W, bool CANON, bool HASH_RC, int MODE, bool SK, bool READS, int KC = 0>
 // (small W: at least 4 waves per SIMD, i.e. at most 128 VGPRs - the two-body walks sit right at that
 // limit; larger W need more registers and get no such bound)
 // Workgroups per CU the register allocation is bounded for.  Small W: 4 (128 VGPRs; the lists allow
@@ -2060,8 +2146,8 @@ __global__ __launch_bounds__(kFusedThreads, MM_MIN_BLOCKS) void fused_kernel(con
                 my_count = (partial || !kTwoBodies<W>)
                                ? lane_walk<W, CANON, HASH_RC, MODE, SK, false, true, kAmbi, kE8>(p, ctx, over)
                                : lane_walk<W, CANON, HASH_RC, MODE, SK, false, kAmbi && !kTwoBodies<W>, kAmbi, kE8>(p, ctx, over);
-            else my_count = partial ? lane_walk<W, CANON, HASH_RC, MODE, SK, false, true, false, kE8>(p, ctx, over)
-                                    : lane_walk<W, CANON, HASH_RC, MODE, SK, false, false, false, kE8>(p, ctx, over);
+            else my_count = partial ? lane_walk<W, CANON, HASH_RC, MODE, SK, false, true, false, kE8, KC>(p, ctx, over)
+                                    : lane_walk<W, CANON, HASH_RC, MODE, SK, false, false, false, kE8, KC>(p, ctx, over);
             if (over) s_overflow = 1;  // benign race: every writer stores 1
         }
     }
@@ -2146,8 +2232,8 @@ __global__ __launch_bounds__(kFusedThreads, MM_MIN_BLOCKS) void fused_kernel(con
         ctx.dst = run0 + excl;
         bool over;
         if (kAmbi && p.wamb) lane_walk<W, CANON, HASH_RC, MODE, SK, true, true, kAmbi, kE8>(p, ctx, over);
-        else if (partial) lane_walk<W, CANON, HASH_RC, MODE, SK, true, true, false, kE8>(p, ctx, over);
-        else lane_walk<W, CANON, HASH_RC, MODE, SK, true, false, false, kE8>(p, ctx, over);
+        else if (partial) lane_walk<W, CANON, HASH_RC, MODE, SK, true, true, false, kE8, KC>(p, ctx, over);
+        else lane_walk<W, CANON, HASH_RC, MODE, SK, true, false, false, kE8, KC>(p, ctx, over);
     }
     if (p.trace) {
         __syncthreads();

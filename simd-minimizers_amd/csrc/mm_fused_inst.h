@@ -35,6 +35,17 @@ const FusedInstance *fused_instances_k(int *count);
 const FusedInstance *fused_instances_l(int *count);
 const FusedInstance *fused_instances_m(int *count);
 
+// fixed-k instances (minimizers of one sequence / a batch of sequences, k a compile-time constant: kc_rule in
+// mm_fused_impl.h), mm_fused_inst_kc.hip.  The launcher takes one when the plan's (w, k, flavour) has it.
+struct FusedKcInstance {
+    uint32_t w, k;
+    bool canon, hash_rc;
+    FusedKernelFn fn;
+};
+#define MM_KC_INST(W, KC, C, R) \
+    { W, KC, C, R, &fused_kernel<W, C, R, 0, false, false, KC> }
+const FusedKcInstance *fused_kc_instances(int *count);
+
 // reads-mode instances (minimizers only), mm_fused_inst_reads_*.hip
 struct FusedReadsInstance {
     uint32_t w;

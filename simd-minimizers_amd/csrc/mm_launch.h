@@ -55,6 +55,8 @@ uint64_t fused_overread_bytes();
 
 // ---- fused family (mm_fused_*.hip): one kernel, specialised per w
 bool fused_supported(uint32_t k, uint32_t w, int canonical_windows, int hasher_canonical);
+// whether a minimizer launch (mode 0, positions only) of this plan takes a fixed-k instance (mm_fused_inst_kc.hip)
+bool fused_fixed_k(uint32_t k, uint32_t w, int canonical_windows, int hasher_canonical);
 uint64_t fused_status_words(const RunArgs &a);
 // 8-byte words reserved per tile status (the look-back words of consecutive tiles are spaced apart)
 uint64_t fused_status_stride();

@@ -5,7 +5,10 @@ walk (fast emit, no range / ambiguity checks) and counts its VALU instructions b
 (full / half rate as measured on MI355X in SHADER CYCLES, profiles/r03_valu_issue_rates.txt: 2.31 / 4.14 cycles
 per wave64 instruction - tools/ubench/valu_rate.hip reads the shader clock under every loop since round 3, the
 round-1 table assumed 2.4 GHz and read 2.5 / 4.3; any SGPR source operand makes an instruction half rate).  Writes profiles/head_isa_census.json,
-which bench.py reads for roofline.valu.issue_clk.  usage: isa_census.py [W] [canon 0|1]"""
+which bench.py reads for roofline.valu.issue_clk.  usage: isa_census.py [W] [canon 0|1] [KC]
+(KC > 0: the fixed-k flavour fused_kernel<..., KC>; default 21 for W = 11 - what the launcher runs for k=21 w=11 - and 0,
+k at run time, otherwise.  profiles/head_isa_census.json is the record of (11, canonical, 21); every other record is
+isa_census_w<W>_<canon|fwd>[_k<KC>].json.  CENSUS_OUT=<file> writes the record there instead)"""
 import collections
 import hashlib
 import json
@@ -21,12 +24,15 @@ from isa_loops import classify  # noqa: E402
 
 W = int(sys.argv[1]) if len(sys.argv) > 1 else 11
 CANON = (sys.argv[2] != "0") if len(sys.argv) > 2 else True
+# (the launcher runs the fixed-k flavour for k=21 w=11, canonical and forward: that is the default census of w = 11; KC 0 = run-time k)
+KC = int(sys.argv[3]) if len(sys.argv) > 3 else (21 if W == 11 else 0)
+KCS = f", {KC}" if KC else ""
 csrc = os.path.join(ROOT, "simd-minimizers_amd", "csrc")
 tmp = tempfile.mkdtemp(prefix="mm_census_")
 src = os.path.join(tmp, "k.hip")
 c = "true" if CANON else "false"
 open(src, "w").write('#include "mm_fused_impl.h"\n'
-                     f"template __global__ void mm::fused_kernel<{W}, {c}, {c}, 0, false, false>(const mm::FusedParams);\n")
+                     f"template __global__ void mm::fused_kernel<{W}, {c}, {c}, 0, false, false{KCS}>(const mm::FusedParams);\n")
 asm = os.path.join(tmp, "k.s")
 subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-I" + csrc, "-S",
                 "--cuda-device-only", "-o", asm, src], check=True, stderr=subprocess.DEVNULL)
@@ -131,7 +137,7 @@ full, half = cls["valu_full"], cls["valu_half"]
 # shader cycles per wave64 instruction (means over the instructions of each class in profiles/r03_valu_issue_rates.txt,
 # "by wall time at that clock"); the architectural figures are 2 and 4 (MI355X_MICROARCH.md)
 FULL, HALF = 2.31, 4.14
-rec = {"kernel": f"mm::fused_kernel<{W}, {c}, {c}, 0, false, false>", "kernel_source_sha": h.hexdigest()[:16],
+rec = {"kernel": f"mm::fused_kernel<{W}, {c}, {c}, 0, false, false{KCS}>", "kernel_source_sha": h.hexdigest()[:16],
        "main_loop_windows": NWIN, "main_loop_instructions": len(best), "wide_group_blocks": MG,
        "valu_full_rate": full, "valu_half_rate": half,
        "salu": cls["salu"], "lds": cls["lds"], "vmem": cls["vmem"],
@@ -143,6 +149,8 @@ rec = {"kernel": f"mm::fused_kernel<{W}, {c}, {c}, 0, false, false>", "kernel_so
                 "clock read under each loop (profiles/r03_valu_issue_rates.txt); ideal_clk_per_valu uses the "
                 "architectural 2 / 4",
        **meta}
-out = os.path.join(ROOT, "profiles", "head_isa_census.json" if (W, CANON) == (11, True) else f"isa_census_w{W}_{'canon' if CANON else 'fwd'}.json")
+kc_tag = f"_k{KC}" if KC else ""
+out = os.path.join(ROOT, "profiles", "head_isa_census.json" if (W, CANON, KC) == (11, True, 21) else f"isa_census_w{W}_{'canon' if CANON else 'fwd'}{kc_tag}.json")
+out = os.environ.get("CENSUS_OUT", out)
 json.dump(rec, open(out, "w"), indent=1)
 print(json.dumps(rec))

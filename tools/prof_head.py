@@ -22,6 +22,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "gpurun_out")
 os.environ["TMPDIR"] = "/tmp"
+PASS_TIMEOUT_S = 300
 
 
 def rocprof(name, pmc, cmd):
@@ -30,8 +31,15 @@ def rocprof(name, pmc, cmd):
     args = ["rocprofv3", "--kernel-trace"]
     args += ["--pmc"] + pmc if pmc else ["--stats"]
     args += ["-d", d, "-o", "r", "--"] + cmd
+    # (every profiled run under a time limit of its own; a run that fails ends the collection - nothing more is started on
+    # a device that has just faulted or hung)
     with open(os.path.join(OUT, name + ".log"), "w") as log:
-        subprocess.run(args, stdout=log, stderr=subprocess.STDOUT, cwd=ROOT)
+        try:
+            r = subprocess.run(args, stdout=log, stderr=subprocess.STDOUT, cwd=ROOT, timeout=PASS_TIMEOUT_S)
+        except subprocess.TimeoutExpired:
+            raise SystemExit(f"prof_head: {name} ran longer than {PASS_TIMEOUT_S} s; see {name}.log")
+    if r.returncode != 0:
+        raise SystemExit(f"prof_head: {name} ended with status {r.returncode}; see {name}.log")
     dbs = sorted(glob.glob(os.path.join(d, "**", "*.db"), recursive=True))
     return dbs[0] if dbs else None
 
