@@ -518,6 +518,64 @@ int mm_fastq_pack_device_async(mm_workspace_t *ws, const uint8_t *d_text, uint64
                                uint64_t *d_rec_base /* [max_records + 1] */,
                                uint64_t *d_rec_text_pos /* [max_records] or NULL */, uint64_t max_records,
                                uint64_t *d_counts /* [2] */);
+/* FASTA / FASTQ text with N: the packers above, which ALSO write the ambiguity bits of a PackedNSeq, and the
+ * skip-ambiguous run over the records they write - file -> minimizers with Builder::run_skip_ambiguous_windows per
+ * record (src/lib.rs:451-496, src/minimizers.rs:169-214) and no parsing on the CPU.
+ *
+ * d_packed, d_rec_base, d_rec_text_pos and d_counts receive exactly what the plain packer writes for the same text.
+ * d_amb receives one bit per output base in the numbering of d_packed: base i is bit i % 8 of byte i / 8, record r
+ * owns bits [d_rec_base[r], d_rec_base[r + 1]).  A bit is set for every sequence byte whose upper-cased value
+ * (c & 0xDF) is not one of A C G T - the rule of mm_pack_ascii_n_device_async; line ends, header and quality bytes
+ * are not bases and give no bit.  d_amb: not NULL and 4-byte aligned (MM_ERR_NULL otherwise, like d_packed);
+ * amb_capacity_bytes: a non-zero multiple of 4 (MM_ERR_CAPACITY otherwise); n_bytes / 8 + 8 rounded up to a multiple
+ * of 4 always suffices.  The first min(amb_capacity_bytes, that) bytes are cleared, nothing is written past
+ * amb_capacity_bytes.  Always the two-pass kernels (MM_FASTA_KERNEL does not apply).  The asynchronous FASTQ entry
+ * wants the text to start with its first '@', like mm_fastq_pack_device_async. */
+int mm_fasta_pack_n_device_async(mm_workspace_t *ws, const uint8_t *d_text, uint64_t n_bytes,
+                                 uint8_t *d_packed, uint64_t packed_capacity_bytes,
+                                 uint8_t *d_amb, uint64_t amb_capacity_bytes,
+                                 uint64_t *d_rec_base /* [max_records + 1] */,
+                                 uint64_t *d_rec_text_pos /* [max_records] or NULL */, uint64_t max_records,
+                                 uint64_t *d_counts /* [2] */);
+int mm_fastq_pack_n_device_async(mm_workspace_t *ws, const uint8_t *d_text, uint64_t n_bytes,
+                                 uint8_t *d_packed, uint64_t packed_capacity_bytes,
+                                 uint8_t *d_amb, uint64_t amb_capacity_bytes,
+                                 uint64_t *d_rec_base /* [max_records + 1] */,
+                                 uint64_t *d_rec_text_pos /* [max_records] or NULL */, uint64_t max_records,
+                                 uint64_t *d_counts /* [2] */);
+/* Synchronous; FASTQ is told from FASTA by the first non-blank byte, as mm_fasta_pack_device does.  MM_ERR_CAPACITY
+ * also when the bases did not fit d_amb (out_counts[0] against 8 * amb_capacity_bytes). */
+int mm_fasta_pack_n_device(mm_workspace_t *ws, const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_packed,
+                           uint64_t packed_capacity_bytes, uint8_t *d_amb, uint64_t amb_capacity_bytes,
+                           uint64_t *d_rec_base, uint64_t *d_rec_text_pos, uint64_t max_records,
+                           uint64_t *d_counts, uint64_t *out_counts /* [2] */);
+/* Builder::run_skip_ambiguous_windows (src/lib.rs:451-496; the skipping collect src/minimizers.rs:169-214) per record
+ * of a back-to-back buffer: mm_run_packed_reads_device with the ambiguity bits of the same bases (base j of the
+ * buffer = bit amb_offset + j of d_amb).  One launch - one lane per read or the lane table - with the window
+ * ambiguity prepared once over the whole span: a window that lies inside a record covers that record's bases only,
+ * so a neighbour's N never reaches it.  Canonical minimizer / closed-syncmer / open-syncmer plans
+ * (MM_ERR_HASHER_NOT_CANONICAL for a forward plan, MM_ERR_BAD_MODE for a text plan); no super-k-mer flavour, as the
+ * reference has none.  Positions are record-local, d_out_offsets[r] .. [r + 1] delimit record r's. */
+int mm_run_packed_reads_skip_ambiguous_device_async(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
+                                                    uint64_t packed_bytes, uint64_t base_offset, const void *d_amb,
+                                                    uint64_t amb_bytes, uint64_t amb_offset, uint64_t n_reads,
+                                                    const uint64_t *d_read_starts /* [n_reads + 1] */,
+                                                    uint64_t total_bases, uint32_t max_read_len, uint32_t *d_out_pos,
+                                                    uint64_t capacity, uint64_t *d_out_offsets /* [n_reads + 1] */,
+                                                    uint64_t *d_count);
+int mm_run_packed_reads_skip_ambiguous_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
+                                              uint64_t packed_bytes, uint64_t base_offset, const void *d_amb,
+                                              uint64_t amb_bytes, uint64_t amb_offset, uint64_t n_reads,
+                                              const uint64_t *d_read_starts, uint64_t total_bases,
+                                              uint32_t max_read_len, uint32_t *d_out_pos, uint64_t capacity,
+                                              uint64_t *d_out_offsets, uint64_t *out_count);
+/* The same from HOST memory in one call, like mm_run_packed_reads_host: `packed` and `amb` hold the reads back to back
+ * from base 0 (ceil(total / 4) and ceil(total / 8) bytes, total = read_starts[n_reads]). */
+int mm_run_packed_reads_skip_ambiguous_host(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *packed,
+                                            const uint8_t *amb, uint64_t n_reads,
+                                            const uint64_t *read_starts /* [n_reads + 1] */, uint32_t max_read_len,
+                                            uint32_t *out_pos, uint64_t capacity,
+                                            uint64_t *out_offsets /* [n_reads + 1] */, uint64_t *out_count);
 /* ------------------------------------------------------------------ several devices from one call
  * The reference's parallel driver is host code: rayon over the contigs, one Builder::run each
  * (bench/src/bin/paper.rs:442-459).  A device group holds one workspace (stream, scratch) per listed device; a

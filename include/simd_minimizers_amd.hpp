@@ -328,6 +328,41 @@ class Builder {  // src/lib.rs:225-230
         if (sk_) sk_->assign(sk.begin(), sk.begin() + n);
     }
 
+    // run_skip_ambiguous_windows (src/lib.rs:451-496) per read over MANY PackedNSeq reads in ONE call
+    // (mm_run_packed_reads_skip_ambiguous_host): codes and ambiguity bits are packed back to back on the host.  Canonical
+    // builders only, no super-k-mer indices.  pos / offsets are OVERWRITTEN, read r's read-local positions at
+    // pos[offsets[r] .. offsets[r + 1]).
+    void run_many_skip_ambiguous_windows(const std::vector<PackedNSeq> &reads, std::vector<uint32_t> &pos,
+                                         std::vector<uint64_t> &offsets) const {
+        static_assert(CANONICAL, "run_skip_ambiguous_windows() is only defined for canonical builders");
+        Workspace &ws = ws_ ? *ws_ : Workspace::thread_default();
+        std::vector<uint64_t> starts(reads.size() + 1, 0);
+        uint32_t longest = 0;
+        for (size_t r = 0; r < reads.size(); ++r) {
+            starts[r + 1] = starts[r] + reads[r].seq.len;
+            if (reads[r].seq.len > longest) longest = (uint32_t)reads[r].seq.len;
+        }
+        const uint64_t total = starts.back();
+        std::vector<uint8_t> packed((total + 3) / 4 + 16, 0), amb((total + 7) / 8 + 16, 0);
+        for (size_t r = 0; r < reads.size(); ++r)
+            for (uint64_t i = 0; i < reads[r].seq.len; ++i) {
+                const uint64_t s = reads[r].seq.offset + i, a = reads[r].amb_offset + i, d = starts[r] + i;
+                packed[d >> 2] |= (uint8_t)(((reads[r].seq.data[s >> 2] >> (2 * (s & 3))) & 3u) << (2 * (d & 3)));
+                amb[d >> 3] |= (uint8_t)(((reads[r].amb[a >> 3] >> (a & 7)) & 1u) << (d & 7));
+            }
+        mm_plan_t *plan = nullptr;
+        check(mm_plan_create(&plan, k_, w_, CANONICAL, (mm_mode_t)SYNCMER, has_hasher_ ? &hasher_ : nullptr));
+        const uint64_t cap = total ? total : 1;
+        pos.assign(cap, 0);
+        offsets.assign(reads.size() + 1, 0);
+        uint64_t n = 0;
+        const int r = mm_run_packed_reads_skip_ambiguous_host(plan, ws.get(), packed.data(), amb.data(), reads.size(),
+                                                              starts.data(), longest, pos.data(), cap, offsets.data(), &n);
+        mm_plan_destroy(plan);
+        check(r);
+        pos.resize(n);
+    }
+
     // Builder::run per record over many records of byte text (src/lib.rs:378) in ONE call (mm_run_text_batch_host):
     // pos and offsets are OVERWRITTEN, record r's record-local positions at pos[offsets[r] .. offsets[r + 1]); the
     // super-k-mer indices (super_kmers()) likewise overwrite their vector.

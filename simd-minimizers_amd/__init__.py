@@ -250,6 +250,17 @@ def _load_lib():
         L.mm_fasta_pack_device.argtypes = fasta_args + [u64p]
         if hasattr(L, "mm_fastq_pack_device_async"):
             L.mm_fastq_pack_device_async.argtypes = fasta_args
+        if hasattr(L, "mm_fasta_pack_n_device"):  # (FASTA / FASTQ with N: ambiguity bits from the packers, skipped windows)
+            fasta_n_args = fasta_args[:5] + [vp, C.c_uint64] + fasta_args[5:]
+            L.mm_fasta_pack_n_device_async.argtypes = fasta_n_args
+            L.mm_fastq_pack_n_device_async.argtypes = fasta_n_args
+            L.mm_fasta_pack_n_device.argtypes = fasta_n_args + [u64p]
+            packed_skip_args = [vp, vp, vp, C.c_uint64, C.c_uint64, vp, C.c_uint64, C.c_uint64, C.c_uint64, vp, C.c_uint64,
+                                C.c_uint32, vp, C.c_uint64, vp]
+            L.mm_run_packed_reads_skip_ambiguous_device_async.argtypes = packed_skip_args + [vp]
+            L.mm_run_packed_reads_skip_ambiguous_device.argtypes = packed_skip_args + [u64p]
+            L.mm_run_packed_reads_skip_ambiguous_host.argtypes = [vp, vp, u8p, u8p, C.c_uint64, u64p, C.c_uint32, u32p,
+                                                                  C.c_uint64, u64p, u64p]
         _lib = L
     return _lib
 
@@ -282,6 +293,9 @@ EXPORTED_SYMBOLS = [
     "mm_text_mul_hasher", "mm_text_hasher_from_dna", "mm_plan_create_text", "mm_run_text_device_async",
     "mm_run_text_device", "mm_run_text_host", "mm_text_prebuilt_window_sizes",
     "mm_run_text_batch_device_async", "mm_run_text_batch_device", "mm_run_text_batch_host",
+    "mm_fasta_pack_n_device_async", "mm_fastq_pack_n_device_async", "mm_fasta_pack_n_device",
+    "mm_run_packed_reads_skip_ambiguous_device_async", "mm_run_packed_reads_skip_ambiguous_device",
+    "mm_run_packed_reads_skip_ambiguous_host",
 ]
 
 
@@ -1116,10 +1130,11 @@ def canonical_minimizer_positions(seq, k, w):  # src/lib.rs:652
 class FastaRecords:
     """Records of a FASTA text packed on the device (``fasta_pack_device``): ``packed`` = one 2-bit buffer holding
     all sequences back to back, ``base`` = the n + 1 base offsets delimiting them, ``text_pos`` = byte offset of
-    every record's '>' in the text."""
+    every record's '>' in the text; ``amb`` (``fasta_pack_n_device`` only, else None) = one ambiguity bit per base of
+    ``packed``, in the same numbering."""
 
-    def __init__(self, packed, base, text_pos):
-        self.packed, self.base, self.text_pos = packed, base, text_pos
+    def __init__(self, packed, base, text_pos, amb=None):
+        self.packed, self.base, self.text_pos, self.amb = packed, base, text_pos, amb
 
     def __len__(self):
         return len(self.base) - 1
@@ -1142,10 +1157,8 @@ class FastaRecords:
         return text[p:len(text) if q < 0 else q].rstrip(b"\r")
 
 
-def fasta_pack_device(text, max_records: int = 1 << 16, device: int = 0) -> FastaRecords:
-    """needletail::parse_fastx_file + PackedSeqVec::from_ascii of every record (bench/src/lib.rs:51-82) on the
-    device: ``text`` = the file's bytes (bytes / numpy uint8 / torch uint8 CUDA tensor), FASTA or - since round 4,
-    told apart by the first non-blank byte like needletail does - FASTQ (four-line records)."""
+def _fasta_pack(text, max_records: int, device: int, with_amb: bool) -> FastaRecords:
+    """What ``fasta_pack_device`` and ``fasta_pack_n_device`` share: the upload, the buffers, the one call, the slicing."""
     import torch
 
     dev = f"cuda:{device}"
@@ -1158,14 +1171,18 @@ def fasta_pack_device(text, max_records: int = 1 << 16, device: int = 0) -> Fast
     n = int(t.numel())
     ws = default_workspace(device)
     packed = torch.empty((n // 4 + 8 + 3) // 4 * 4 + 64, dtype=torch.uint8, device=dev)
+    amb = torch.empty((n // 8 + 8 + 3) // 4 * 4 + 64, dtype=torch.uint8, device=dev) if with_amb else None
     rec_base = torch.zeros(max_records + 1, dtype=torch.int64, device=dev)
     rec_pos = torch.zeros(max(max_records, 1), dtype=torch.int64, device=dev)
     counts = torch.zeros(2, dtype=torch.int64, device=dev)
     torch.cuda.synchronize(device)
     out = (C.c_uint64 * 2)()
-    code = lib().mm_fasta_pack_device(ws.h, C.c_void_p(t.data_ptr()) if n else None, n, C.c_void_p(packed.data_ptr()),
-                                      packed.numel() // 4 * 4, C.c_void_p(rec_base.data_ptr()),
-                                      C.c_void_p(rec_pos.data_ptr()), max_records, C.c_void_p(counts.data_ptr()), out)
+    head = (ws.h, C.c_void_p(t.data_ptr()) if n else None, n, C.c_void_p(packed.data_ptr()), packed.numel() // 4 * 4)
+    tail = (C.c_void_p(rec_base.data_ptr()), C.c_void_p(rec_pos.data_ptr()), max_records, C.c_void_p(counts.data_ptr()), out)
+    if with_amb:
+        code = lib().mm_fasta_pack_n_device(*head, C.c_void_p(amb.data_ptr()), amb.numel() // 4 * 4, *tail)
+    else:
+        code = lib().mm_fasta_pack_device(*head, *tail)
     if code == ERR["CAPACITY"]:
         if out[1] > max_records:
             raise MinimizerError(code, f"{out[1]} records > max_records {max_records}")
@@ -1173,10 +1190,27 @@ def fasta_pack_device(text, max_records: int = 1 << 16, device: int = 0) -> Fast
     _check(code)
     n_rec = int(out[1])
     return FastaRecords(packed, rec_base[: n_rec + 1].cpu().numpy().astype(np.uint64),
-                        rec_pos[:n_rec].cpu().numpy().astype(np.uint64))
+                        rec_pos[:n_rec].cpu().numpy().astype(np.uint64), amb)
+
+
+def fasta_pack_device(text, max_records: int = 1 << 16, device: int = 0) -> FastaRecords:
+    """needletail::parse_fastx_file + PackedSeqVec::from_ascii of every record (bench/src/lib.rs:51-82) on the
+    device: ``text`` = the file's bytes (bytes / numpy uint8 / torch uint8 CUDA tensor), FASTA or - since round 4,
+    told apart by the first non-blank byte like needletail does - FASTQ (four-line records)."""
+    return _fasta_pack(text, max_records, device, False)
 
 
 fastx_pack_device = fasta_pack_device  # (the reference's loader call reads both formats)
+
+
+def fasta_pack_n_device(text, max_records: int = 1 << 16, device: int = 0) -> FastaRecords:
+    """``fasta_pack_device`` for texts with ``N``: the same records (FASTA or FASTQ) plus ``.amb``, one ambiguity bit per
+    packed base, set for every sequence byte that is not ``ACGT`` / ``acgt`` (PackedNSeqVec::from_ascii per record,
+    ``mm_fasta_pack_n_device``).  What ``run_packed_reads_skip_ambiguous_device`` takes."""
+    return _fasta_pack(text, max_records, device, True)
+
+
+fastx_pack_n_device = fasta_pack_n_device
 
 
 def run_reads_host(builder: "Builder", reads, super_kmers: bool = False):
@@ -1292,6 +1326,60 @@ def run_packed_reads_device(builder: "Builder", records: FastaRecords, out_pos, 
                                             C.c_void_p(out_sk.data_ptr()) if out_sk is not None else None,
                                             int(out_pos.numel()), C.c_void_p(out_offsets.data_ptr()), C.byref(cnt)))
     return int(cnt.value)
+
+
+def run_packed_reads_skip_ambiguous_device(builder: "Builder", records: FastaRecords, out_pos, out_offsets, max_read_len=None):
+    """``run_packed_reads_device`` over the records of ``fasta_pack_n_device`` with ``Builder::run_skip_ambiguous_windows``
+    per record (``mm_run_packed_reads_skip_ambiguous_device``): windows that hold an ambiguous base select nothing.
+    Canonical builders only, no super-k-mer indices.  Returns the number of positions."""
+    import torch
+    if records.amb is None:
+        raise ValueError("records without ambiguity bits: pack them with fasta_pack_n_device")
+    n = len(records)
+    starts = torch.from_numpy(np.ascontiguousarray(records.base, dtype=np.uint64).view(np.int64)).to(out_pos.device)
+    lens = records.lengths()
+    if max_read_len is None:
+        max_read_len = max(lens) if lens else 0
+    cnt = C.c_uint64()
+    ws = builder._ws()
+    cap = int(out_pos.numel())
+    code = lib().mm_run_packed_reads_skip_ambiguous_device(
+        builder.plan().h, ws.h, C.c_void_p(records.packed.data_ptr()), int(records.packed.numel()), 0,
+        C.c_void_p(records.amb.data_ptr()), int(records.amb.numel()), 0, n, C.c_void_p(starts.data_ptr()),
+        int(records.base[-1]) if n else 0, int(max_read_len), C.c_void_p(out_pos.data_ptr()), cap,
+        C.c_void_p(out_offsets.data_ptr()), C.byref(cnt))
+    if code == ERR["CAPACITY"]:
+        raise MinimizerError(code, f"output capacity {cap} < {cnt.value}")
+    _check(code)
+    return int(cnt.value)
+
+
+def run_reads_skip_ambiguous_host(builder: "Builder", reads):
+    """Many short host reads with ``N`` in ONE call (``mm_run_packed_reads_skip_ambiguous_host``): ``reads`` = list of
+    ASCII ``bytes``; returns (positions, offsets) - read r's read-local positions are
+    ``positions[offsets[r]:offsets[r + 1]]``, what ``run_skip_ambiguous_windows`` of ``PackedNSeqVec.from_ascii(read)``
+    returns.  Canonical builders only."""
+    arrs = [np.frombuffer(bytes(s), dtype=np.uint8) for s in reads]
+    lens = [len(a) for a in arrs]
+    starts = np.zeros(len(lens) + 1, dtype=np.uint64)
+    starts[1:] = np.cumsum(lens, dtype=np.uint64)
+    total = int(starts[-1])
+    flat = np.concatenate(arrs) if total else np.zeros(0, dtype=np.uint8)
+    q = np.concatenate([(flat >> 1) & 3, np.zeros((-total) % 4, dtype=np.uint8)]).reshape(-1, 4)
+    packed = (q[:, 0] | (q[:, 1] << 2) | (q[:, 2] << 4) | (q[:, 3] << 6)).astype(np.uint8) if total else np.zeros(1, dtype=np.uint8)
+    up = flat & 0xDF
+    bad = ~((up == 65) | (up == 67) | (up == 71) | (up == 84))
+    amb = np.packbits(bad, bitorder="little") if total else np.zeros(1, dtype=np.uint8)
+    cap = max(1, total)
+    pos = np.empty(cap, dtype=np.uint32)
+    offs = np.zeros(len(lens) + 1, dtype=np.uint64)
+    cnt = C.c_uint64()
+    ws = builder._ws()
+    _check(lib().mm_run_packed_reads_skip_ambiguous_host(builder.plan().h, ws.h, _p(packed, C.c_uint8), _p(amb, C.c_uint8),
+                                                         len(lens), _p(starts, C.c_uint64), max(lens) if lens else 0,
+                                                         _p(pos, C.c_uint32), cap, _p(offs, C.c_uint64), C.byref(cnt)))
+    n = int(cnt.value)
+    return pos[:n], [int(o) for o in offs]
 
 
 def run_fasta_device(builder: "Builder", records: FastaRecords, out_pos, out_sk=None):

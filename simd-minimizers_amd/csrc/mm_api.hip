@@ -1586,7 +1586,8 @@ static int run_reads_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, const
     // read_len is then the longest read to expect (longer ones are cut to it), read_stride is not used.
     if (!plan || !ws || !d_out_offsets) return MM_ERR_NULL;
     if (n_reads >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
-    if (d_read_starts && (amb || d_read_lens)) return MM_ERR_BAD_MODE;
+    // (back-to-back reads WITH ambiguity bits: mm_run_packed_reads_skip_ambiguous_* - bit j of the span belongs to base j)
+    if (d_read_starts && d_read_lens) return MM_ERR_BAD_MODE;
     if (amb && !plan->canonical_windows) return MM_ERR_HASHER_NOT_CANONICAL;
     if (d_out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;  // src/lib.rs:339
     if (d_out_sk && amb) return MM_ERR_BAD_MODE;  // the reference has no skip-ambiguous super-k-mer run
@@ -1728,7 +1729,7 @@ static int run_reads_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, const
             uint64_t len = d_read_lens ? (lens[i] < read_len ? lens[i] : read_len) : read_len;
             if (d_read_starts) len = starts[i + 1] - starts[i] < read_len ? starts[i + 1] - starts[i] : read_len;
             AmbArgs ra;
-            if (amb) ra = AmbArgs{amb->d_amb, amb->bytes, amb->bit_offset + i * (uint64_t)read_stride};
+            if (amb) ra = AmbArgs{amb->d_amb, amb->bytes, amb->bit_offset + (d_read_starts ? starts[i] : i * (uint64_t)read_stride)};
             r = run_device_async_impl(plan, ws, bytes + first / 4, packed_bytes - first / 4, first % 4, len,
                                       0, UINT64_MAX, d_out_pos, d_out_sk, capacity, nullptr, i != 0,
                                       amb ? &ra : nullptr);
@@ -1767,6 +1768,56 @@ int mm_run_packed_reads_device(const mm_plan_t *plan, mm_workspace_t *ws, const 
     for (int attempt = 0; attempt < 2; ++attempt) {
         int r = run_reads_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_reads, 0, max_read_len, nullptr,
                                      d_out_pos, capacity, d_out_offsets, nullptr, nullptr, d_out_sk, d_read_starts, total_bases);
+        if (r) return r;
+        MM_HIP(hipMemcpyAsync(ws->h_total, ws->total, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ws->stream));
+        MM_HIP(hipStreamSynchronize(ws->stream));
+        const int je = judge_run_error(ws);
+        if (je < 0) return je;
+        if (je == 0) break;  // (1: redo the batch in ticket mode)
+    }
+    if (out_count) *out_count = ws->h_total[0];
+    if (d_out_pos && ws->h_total[0] > capacity) return MM_ERR_CAPACITY;
+    return MM_OK;
+}
+
+// Builder::run_skip_ambiguous_windows (src/lib.rs:451-496) per record of a back-to-back buffer: what the *_pack_n packers
+// write goes straight in.  The refusals that need no device come first, the workspace last.
+static int packed_reads_skip_check(const mm_plan_t *plan, const void *d_amb, uint64_t n_reads, const uint64_t *d_read_starts) {
+    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
+    if (plan && !plan->canonical_windows) return MM_ERR_HASHER_NOT_CANONICAL;
+    if (n_reads && (!d_read_starts || !d_amb)) return MM_ERR_NULL;
+    return MM_OK;
+}
+
+int mm_run_packed_reads_skip_ambiguous_device_async(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
+                                                    uint64_t packed_bytes, uint64_t base_offset, const void *d_amb,
+                                                    uint64_t amb_bytes, uint64_t amb_offset, uint64_t n_reads,
+                                                    const uint64_t *d_read_starts, uint64_t total_bases,
+                                                    uint32_t max_read_len, uint32_t *d_out_pos, uint64_t capacity,
+                                                    uint64_t *d_out_offsets, uint64_t *d_count) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    const int c = packed_reads_skip_check(plan, d_amb, n_reads, d_read_starts);
+    if (c) return c;
+    if (ws) ws->async_unchecked = true;
+    const AmbArgs amb{d_amb, amb_bytes, amb_offset};
+    return run_reads_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_reads, 0, max_read_len, nullptr, d_out_pos,
+                                capacity, d_out_offsets, d_count, &amb, nullptr, d_read_starts, total_bases);
+}
+
+int mm_run_packed_reads_skip_ambiguous_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
+                                              uint64_t packed_bytes, uint64_t base_offset, const void *d_amb,
+                                              uint64_t amb_bytes, uint64_t amb_offset, uint64_t n_reads,
+                                              const uint64_t *d_read_starts, uint64_t total_bases,
+                                              uint32_t max_read_len, uint32_t *d_out_pos, uint64_t capacity,
+                                              uint64_t *d_out_offsets, uint64_t *out_count) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    const int c = packed_reads_skip_check(plan, d_amb, n_reads, d_read_starts);
+    if (c) return c;
+    if (!ws) return MM_ERR_NULL;
+    const AmbArgs amb{d_amb, amb_bytes, amb_offset};
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        int r = run_reads_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_reads, 0, max_read_len, nullptr,
+                                     d_out_pos, capacity, d_out_offsets, nullptr, &amb, nullptr, d_read_starts, total_bases);
         if (r) return r;
         MM_HIP(hipMemcpyAsync(ws->h_total, ws->total, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ws->stream));
         MM_HIP(hipStreamSynchronize(ws->stream));
@@ -2406,6 +2457,52 @@ int mm_run_packed_reads_host(const mm_plan_t *plan, mm_workspace_t *ws, const ui
     return MM_OK;
 }
 
+// The same with ambiguity bits (PackedNSeq reads from host memory): packed bytes and starts in d_in, the bits in d_amb.
+int mm_run_packed_reads_skip_ambiguous_host(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *packed,
+                                            const uint8_t *amb, uint64_t n_reads, const uint64_t *read_starts,
+                                            uint32_t max_read_len, uint32_t *out_pos, uint64_t capacity,
+                                            uint64_t *out_offsets, uint64_t *out_count) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    const int c = packed_reads_skip_check(plan, amb, n_reads, read_starts);
+    if (c) return c;
+    if (!plan || !ws || !out_offsets || (n_reads && !packed)) return MM_ERR_NULL;
+    if (out_count) *out_count = 0;
+    MM_HIP(set_device(ws->device));
+    const uint64_t total_bases = n_reads ? read_starts[n_reads] : 0;
+    for (uint64_t r = 0; r < n_reads; ++r)
+        if (read_starts[r] > read_starts[r + 1]) return MM_ERR_CAPACITY;  // (starts must not decrease)
+    if (total_bases >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
+    const uint64_t bytes = (total_bases + 3) / 4, abytes = (total_bases + 7) / 8;
+    const uint64_t starts_at = (bytes + 64 + 15) & ~15ull;
+    uint8_t *din = reinterpret_cast<uint8_t *>(ws->d_in);
+    int r = grow(din, ws->d_in_bytes, starts_at + (n_reads + 1) * sizeof(uint64_t), 1);
+    ws->d_in = din;
+    if (r) return r;
+    uint8_t *damb = reinterpret_cast<uint8_t *>(ws->d_amb);
+    r = grow(damb, ws->d_amb_bytes, abytes + 16, 1);
+    ws->d_amb = damb;
+    if (r) return r;
+    uint64_t cap = out_pos ? (capacity < total_bases ? capacity : total_bases) : 0;
+    r = grow(ws->d_out, ws->d_out_elems, cap ? cap : 1, sizeof(uint32_t));
+    if (r == MM_OK) r = grow(ws->d_vals, ws->d_vals_elems, n_reads + 1, sizeof(unsigned long long));
+    if (r) return r;
+    if (bytes) MM_HIP(hipMemcpyAsync(din, packed, bytes, hipMemcpyHostToDevice, ws->stream));
+    MM_HIP(hipMemsetAsync(din + bytes, 0, starts_at - bytes, ws->stream));
+    if (abytes) MM_HIP(hipMemcpyAsync(damb, amb, abytes, hipMemcpyHostToDevice, ws->stream));
+    MM_HIP(hipMemsetAsync(damb + abytes, 0, 16, ws->stream));
+    if (n_reads) MM_HIP(hipMemcpyAsync(din + starts_at, read_starts, (n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ws->stream));
+    uint64_t count = 0;
+    r = mm_run_packed_reads_skip_ambiguous_device(plan, ws, din, starts_at, 0, damb, abytes + 16, 0, n_reads,
+                                                  reinterpret_cast<const uint64_t *>(din + starts_at), total_bases, max_read_len,
+                                                  cap ? ws->d_out : nullptr, cap, reinterpret_cast<uint64_t *>(ws->d_vals), &count);
+    if (out_count) *out_count = count;
+    if (r) return r;
+    MM_HIP(hipMemcpyAsync(out_offsets, ws->d_vals, (n_reads + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
+    if (out_pos && count) MM_HIP(hipMemcpyAsync(out_pos, ws->d_out, count * sizeof(uint32_t), hipMemcpyDeviceToHost, ws->stream));
+    MM_HIP(hipStreamSynchronize(ws->stream));
+    return MM_OK;
+}
+
 int mm_run_host_ascii(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *ascii,
                       uint64_t n_bases, uint32_t *out_pos, uint32_t *out_sk, uint64_t capacity,
                       uint64_t *out_count) {
@@ -3021,10 +3118,18 @@ static int fasta_packer_choice(const mm_workspace_t *ws) {
 #endif
 }
 
-int mm_fasta_pack_device_async(mm_workspace_t *ws, const uint8_t *d_text, uint64_t n_bytes,
-                               uint8_t *d_packed, uint64_t packed_capacity_bytes, uint64_t *d_rec_base,
-                               uint64_t *d_rec_text_pos, uint64_t max_records, uint64_t *d_counts) {
-    ApiScope api_scope;  // (restores the calling thread's current device on return)
+// What the *_pack_n entry points ask of their second output, before anything else is looked at (no device needed).
+static int amb_out_check(const uint8_t *d_amb, uint64_t amb_capacity_bytes) {
+    if (!d_amb || reinterpret_cast<uintptr_t>(d_amb) % 4 != 0) return MM_ERR_NULL;
+    if (amb_capacity_bytes == 0 || amb_capacity_bytes % 4 != 0) return MM_ERR_CAPACITY;
+    return MM_OK;
+}
+
+// (d_amb: the ambiguity bits of mm_fasta_pack_n_*, checked by the caller - always the two-pass kernels; null: the plain packer)
+static int fasta_pack_async(mm_workspace_t *ws, const uint8_t *d_text, uint64_t n_bytes,
+                            uint8_t *d_packed, uint64_t packed_capacity_bytes, uint64_t *d_rec_base,
+                            uint64_t *d_rec_text_pos, uint64_t max_records, uint64_t *d_counts, uint8_t *d_amb,
+                            uint64_t amb_capacity_bytes) {
     // (the synchronous wrapper below checks the error word itself; a direct asynchronous caller asks mm_workspace_check)
     if (!ws || !d_counts || !d_rec_base) return MM_ERR_NULL;
     if (n_bytes >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
@@ -3033,6 +3138,7 @@ int mm_fasta_pack_device_async(mm_workspace_t *ws, const uint8_t *d_text, uint64
     if (n_bytes == 0) {
         MM_HIP(hipMemsetAsync(d_counts, 0, 2 * sizeof(uint64_t), ws->stream));
         MM_HIP(hipMemsetAsync(d_rec_base, 0, sizeof(uint64_t), ws->stream));
+        if (d_amb) MM_HIP(hipMemsetAsync(d_amb, 0, amb_capacity_bytes < 8 ? amb_capacity_bytes : 8, ws->stream));
         return MM_OK;
     }
     if (!d_text || (!d_packed && packed_capacity_bytes)) return MM_ERR_NULL;
@@ -3046,12 +3152,13 @@ int mm_fasta_pack_device_async(mm_workspace_t *ws, const uint8_t *d_text, uint64
     const int r = grow(sp, ws->scratch_bytes, need_a > need_b ? need_a : need_b, 1);
     ws->scratch = sp;
     if (r) return r;
-    const int choice = fasta_packer_choice(ws);
+    const int choice = d_amb ? 0 : fasta_packer_choice(ws);
     if (choice == 0) {
         if (mm::launch_fasta_pack2(d_text, n_bytes, d_packed, packed_capacity_bytes & ~3ull,
                                    reinterpret_cast<unsigned long long *>(d_rec_base),
                                    reinterpret_cast<unsigned long long *>(d_rec_text_pos), max_records,
-                                   reinterpret_cast<unsigned long long *>(d_counts), ws->scratch, ws->stream))
+                                   reinterpret_cast<unsigned long long *>(d_counts), ws->scratch, ws->stream, d_amb,
+                                   amb_capacity_bytes))
             return hip_fail(hipGetLastError(), "fasta_pack2");
         return MM_OK;
     }
@@ -3075,12 +3182,32 @@ int mm_fasta_pack_device_async(mm_workspace_t *ws, const uint8_t *d_text, uint64
 #endif
 }
 
+int mm_fasta_pack_device_async(mm_workspace_t *ws, const uint8_t *d_text, uint64_t n_bytes,
+                               uint8_t *d_packed, uint64_t packed_capacity_bytes, uint64_t *d_rec_base,
+                               uint64_t *d_rec_text_pos, uint64_t max_records, uint64_t *d_counts) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    return fasta_pack_async(ws, d_text, n_bytes, d_packed, packed_capacity_bytes, d_rec_base, d_rec_text_pos, max_records,
+                            d_counts, nullptr, 0);
+}
+
+int mm_fasta_pack_n_device_async(mm_workspace_t *ws, const uint8_t *d_text, uint64_t n_bytes,
+                                 uint8_t *d_packed, uint64_t packed_capacity_bytes, uint8_t *d_amb,
+                                 uint64_t amb_capacity_bytes, uint64_t *d_rec_base, uint64_t *d_rec_text_pos,
+                                 uint64_t max_records, uint64_t *d_counts) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    const int c = amb_out_check(d_amb, amb_capacity_bytes);
+    if (c) return c;
+    return fasta_pack_async(ws, d_text, n_bytes, d_packed, packed_capacity_bytes, d_rec_base, d_rec_text_pos, max_records,
+                            d_counts, d_amb, amb_capacity_bytes);
+}
+
 // FASTQ (round 4): four-line records, the sequence of every record packed like a FASTA record's (mm_fastq.hip).
 // The packer tells a byte's role from the number of newlines in front of it, so the text has to START with its first
 // record's '@': `pos_bias` is what a caller that cut blank bytes off the front adds back to the records' text positions.
 static int fastq_pack_async(mm_workspace_t *ws, const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_packed,
                             uint64_t packed_capacity_bytes, uint64_t *d_rec_base, uint64_t *d_rec_text_pos,
-                            uint64_t max_records, uint64_t *d_counts, uint64_t pos_bias) {
+                            uint64_t max_records, uint64_t *d_counts, uint64_t pos_bias, uint8_t *d_amb = nullptr,
+                            uint64_t amb_capacity_bytes = 0) {
     if (!ws || !d_counts || !d_rec_base) return MM_ERR_NULL;
     if (n_bytes >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
     if (reinterpret_cast<uintptr_t>(d_packed) % 4 != 0) return MM_ERR_NULL;
@@ -3088,6 +3215,7 @@ static int fastq_pack_async(mm_workspace_t *ws, const uint8_t *d_text, uint64_t 
     if (n_bytes == 0) {
         MM_HIP(hipMemsetAsync(d_counts, 0, 2 * sizeof(uint64_t), ws->stream));
         MM_HIP(hipMemsetAsync(d_rec_base, 0, sizeof(uint64_t), ws->stream));
+        if (d_amb) MM_HIP(hipMemsetAsync(d_amb, 0, amb_capacity_bytes < 8 ? amb_capacity_bytes : 8, ws->stream));
         return MM_OK;
     }
     if (!d_text || (!d_packed && packed_capacity_bytes)) return MM_ERR_NULL;
@@ -3098,7 +3226,8 @@ static int fastq_pack_async(mm_workspace_t *ws, const uint8_t *d_text, uint64_t 
     if (mm::launch_fastq_pack(d_text, n_bytes, d_packed, packed_capacity_bytes & ~3ull,
                               reinterpret_cast<unsigned long long *>(d_rec_base),
                               reinterpret_cast<unsigned long long *>(d_rec_text_pos), max_records,
-                              reinterpret_cast<unsigned long long *>(d_counts), ws->scratch, ws->stream, pos_bias))
+                              reinterpret_cast<unsigned long long *>(d_counts), ws->scratch, ws->stream, pos_bias, d_amb,
+                              amb_capacity_bytes))
         return hip_fail(hipGetLastError(), "fastq_pack");
     return MM_OK;
 }
@@ -3111,10 +3240,21 @@ int mm_fastq_pack_device_async(mm_workspace_t *ws, const uint8_t *d_text, uint64
                             d_counts, 0);
 }
 
-int mm_fasta_pack_device(mm_workspace_t *ws, const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_packed,
-                         uint64_t packed_capacity_bytes, uint64_t *d_rec_base, uint64_t *d_rec_text_pos,
-                         uint64_t max_records, uint64_t *d_counts, uint64_t *out_counts) {
+int mm_fastq_pack_n_device_async(mm_workspace_t *ws, const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_packed,
+                                 uint64_t packed_capacity_bytes, uint8_t *d_amb, uint64_t amb_capacity_bytes,
+                                 uint64_t *d_rec_base, uint64_t *d_rec_text_pos, uint64_t max_records, uint64_t *d_counts) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
+    const int c = amb_out_check(d_amb, amb_capacity_bytes);
+    if (c) return c;
+    return fastq_pack_async(ws, d_text, n_bytes, d_packed, packed_capacity_bytes, d_rec_base, d_rec_text_pos, max_records,
+                            d_counts, 0, d_amb, amb_capacity_bytes);
+}
+
+// (d_amb: mm_fasta_pack_n_device, checked by it; null: the plain packers)
+static int fasta_pack_sync(mm_workspace_t *ws, const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_packed,
+                           uint64_t packed_capacity_bytes, uint64_t *d_rec_base, uint64_t *d_rec_text_pos,
+                           uint64_t max_records, uint64_t *d_counts, uint64_t *out_counts, uint8_t *d_amb,
+                           uint64_t amb_capacity_bytes) {
     if (!out_counts || !ws) return MM_ERR_NULL;  // (a null workspace used to reach the error branch below)
     // whatever way this call ends, the per-call three-pass flag does not outlive it
     struct ClearOnce {
@@ -3136,21 +3276,29 @@ int mm_fasta_pack_device(mm_workspace_t *ws, const uint8_t *d_text, uint64_t n_b
             // front of the first record used to shift every line's role by one: ADVICE r4) and adds the cut back to the
             // records' text positions
             const int r = fastq_pack_async(ws, d_text + i, n_bytes - i, d_packed, packed_capacity_bytes, d_rec_base,
-                                           d_rec_text_pos, max_records, d_counts, i);
+                                           d_rec_text_pos, max_records, d_counts, i, d_amb, amb_capacity_bytes);
             if (r) return r;
+            if (d_amb && i) {
+                // (the packer cleared what the text behind the cut can fill; the header promises what the whole text can)
+                const uint64_t cut = ((n_bytes - i) / 8 + 8 + 3) & ~3ull, whole = (n_bytes / 8 + 8 + 3) & ~3ull;
+                const uint64_t from = cut < amb_capacity_bytes ? cut : amb_capacity_bytes;
+                const uint64_t to = whole < amb_capacity_bytes ? whole : amb_capacity_bytes;
+                if (to > from) MM_HIP(hipMemsetAsync(d_amb + from, 0, to - from, ws->stream));
+            }
             MM_HIP(hipMemcpyAsync(out_counts, d_counts, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
             MM_HIP(hipStreamSynchronize(ws->stream));
             if (out_counts[0] > (packed_capacity_bytes & ~3ull) * 4 || out_counts[1] > max_records) return MM_ERR_CAPACITY;
+            if (d_amb && out_counts[0] > amb_capacity_bytes * 8) return MM_ERR_CAPACITY;
             return MM_OK;
         }
     }
     for (int attempt = 0; attempt < 2; ++attempt) {
-        const int r = mm_fasta_pack_device_async(ws, d_text, n_bytes, d_packed, packed_capacity_bytes, d_rec_base,
-                                                 d_rec_text_pos, max_records, d_counts);
+        const int r = fasta_pack_async(ws, d_text, n_bytes, d_packed, packed_capacity_bytes, d_rec_base, d_rec_text_pos,
+                                       max_records, d_counts, d_amb, amb_capacity_bytes);
         if (r) return r;
         // (only an attempt that launched the one-pass kernel cleared the error word and may consult it: the three-pass
         // kernels neither clear nor raise it, and a word left by an earlier failed run is not theirs - ADVICE r3)
-        const bool was_one_pass = n_bytes != 0 && fasta_packer_choice(ws) == 1;
+        const bool was_one_pass = !d_amb && n_bytes != 0 && fasta_packer_choice(ws) == 1;
         MM_HIP(hipMemcpyAsync(out_counts, d_counts, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
         MM_HIP(hipMemcpyAsync(ws->h_total + 1, ws->total + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost,
                               ws->stream));
@@ -3163,7 +3311,27 @@ int mm_fasta_pack_device(mm_workspace_t *ws, const uint8_t *d_text, uint64_t n_b
         if (!ws->async_unchecked) MM_HIP(hipMemsetAsync(ws->total + 2, 0, sizeof(unsigned long long), ws->stream));
     }
     if (out_counts[0] > (packed_capacity_bytes & ~3ull) * 4 || out_counts[1] > max_records) return MM_ERR_CAPACITY;
+    if (d_amb && out_counts[0] > amb_capacity_bytes * 8) return MM_ERR_CAPACITY;
     return MM_OK;
+}
+
+int mm_fasta_pack_device(mm_workspace_t *ws, const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_packed,
+                         uint64_t packed_capacity_bytes, uint64_t *d_rec_base, uint64_t *d_rec_text_pos,
+                         uint64_t max_records, uint64_t *d_counts, uint64_t *out_counts) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    return fasta_pack_sync(ws, d_text, n_bytes, d_packed, packed_capacity_bytes, d_rec_base, d_rec_text_pos, max_records,
+                           d_counts, out_counts, nullptr, 0);
+}
+
+int mm_fasta_pack_n_device(mm_workspace_t *ws, const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_packed,
+                           uint64_t packed_capacity_bytes, uint8_t *d_amb, uint64_t amb_capacity_bytes,
+                           uint64_t *d_rec_base, uint64_t *d_rec_text_pos, uint64_t max_records, uint64_t *d_counts,
+                           uint64_t *out_counts) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    const int c = amb_out_check(d_amb, amb_capacity_bytes);
+    if (c) return c;
+    return fasta_pack_sync(ws, d_text, n_bytes, d_packed, packed_capacity_bytes, d_rec_base, d_rec_text_pos, max_records,
+                           d_counts, out_counts, d_amb, amb_capacity_bytes);
 }
 
 static const uint32_t kProbeGroups = 16;

@@ -284,16 +284,26 @@ __global__ __launch_bounds__(kFaGroup) void fasta2_resolve_kernel(FaScratch sc, 
     }
 }
 
-// K2: pack
+// K2: pack.  AMB (mm_fasta_pack_n_*): also one ambiguity bit per output base into amb32 - the thread's "not ACGT" mask
+// goes through the rule its codes go through (one run, two runs, byte by byte) and into a second LDS area (mm_text.h);
+// the plain instantiation holds none of it.
+template <bool AMB>
 __global__ __launch_bounds__(kFqThreads) void fasta2_pack_kernel(const uint8_t *__restrict__ text, uint64_t n, const FaScratch sc,
                                                                  uint32_t *__restrict__ out32, uint64_t out_dwords,
                                                                  unsigned long long *__restrict__ rec_base,
-                                                                 unsigned long long *__restrict__ rec_pos, uint64_t max_records) {
+                                                                 unsigned long long *__restrict__ rec_pos, uint64_t max_records,
+                                                                 uint32_t *__restrict__ amb32, uint64_t amb_dwords) {
     __shared__ uint32_t s_part[kFqPieces][kFqWaves];
     // the chunk's output, assembled in LDS (see fastq_pack_kernel): at most 16 384 bases = 1024 dwords + 1 + 2
     constexpr uint32_t kOutDwords = kFqChunk / 16u + 4u;
     __shared__ uint32_t s_out[kOutDwords];
     for (uint32_t i = threadIdx.x; i < kOutDwords; i += kFqThreads) s_out[i] = 0u;  // (ordered by fa_read_chunk's barriers)
+    uint32_t *s_amb = nullptr;
+    if constexpr (AMB) {
+        __shared__ uint32_t s_amb_area[kAmbDwords];
+        s_amb = s_amb_area;
+        for (uint32_t i = threadIdx.x; i < kAmbDwords; i += kFqThreads) s_amb[i] = 0u;
+    }
     const uint64_t c0 = (uint64_t)blockIdx.x * kFqChunk;
     const uint64_t grp = blockIdx.x / kFaGroup;
     const uint32_t gs = sc.g_state[grp], gh = gs & 1u, gst = (gs >> 1) & 1u;
@@ -330,22 +340,33 @@ __global__ __launch_bounds__(kFqThreads) void fasta2_pack_kernel(const uint8_t *
                 return (codes >> (2u * first)) & (len >= 32u ? ~0ull : ((1ull << (2u * len)) - 1ull));
             };
             unsigned long long bits = field(f1, l1);
+            // (AMB: the same bytes' ambiguity flags, one bit each where the codes take two)
+            uint32_t na = 0, abits = 0;
+            auto afield = [&](uint32_t first, uint32_t len) { return (na >> first) & (len >= 32u ? ~0u : ((1u << len) - 1u)); };
+            if constexpr (AMB) {
+                na = not_acgt32(v) & sm;
+                abits = afield(f1, l1);
+            }
             if (rest) {
                 const uint32_t f2 = (uint32_t)__builtin_ctz(rest), t2 = rest >> f2, l2 = t2 == 0xffffffffu ? 32u : (uint32_t)__builtin_ctz(~t2);
                 const uint32_t rest2 = l2 + f2 >= 32u ? 0u : (rest >> (f2 + l2)) << (f2 + l2);
                 if (rest2 == 0u) {
                     bits |= field(f2, l2) << (2u * l1);
+                    if constexpr (AMB) abits |= afield(f2, l2) << l1;
                 } else {  // (lines shorter than the piece, '\r' inside a line: byte by byte)
                     bits = 0;
+                    abits = 0;
                     uint32_t k = 0;
 #pragma unroll
                     for (int i = 0; i < (int)kFqBytesPerThread; ++i)
                         if ((sm >> i) & 1u) {
                             bits |= ((codes >> (2 * i)) & 3ull) << (2u * k);
+                            if constexpr (AMB) abits |= ((na >> i) & 1u) << k;
                             ++k;
                         }
                 }
             }
+            if constexpr (AMB) amb_or_lds(s_amb, seq0, o0, abits);
             const uint32_t q = (uint32_t)((o0 >> 4) - q0);
             const uint32_t sh = 2u * (uint32_t)(o0 & 15ull);
             const unsigned long long lo = bits << sh;                              // (64 bits shifted by at most 30:
@@ -375,6 +396,7 @@ __global__ __launch_bounds__(kFqThreads) void fasta2_pack_kernel(const uint8_t *
         if (i == 0 || i + 1 == nd) atomicOr(&out32[q], w);
         else out32[q] = w;
     }
+    if constexpr (AMB) amb_flush(s_amb, seq0, chunk_seq, amb32, amb_dwords);
 }
 
 __global__ void fasta2_finish_kernel(const FaScratch sc, uint64_t groups, unsigned long long *rec_base, uint64_t max_records,
@@ -397,7 +419,9 @@ uint64_t fasta2_scratch_bytes(uint64_t n_bytes) {
 
 int launch_fasta_pack2(const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_packed, uint64_t packed_capacity_bytes,
                        unsigned long long *d_rec_base, unsigned long long *d_rec_pos, uint64_t max_records,
-                       unsigned long long *d_counts, void *scratch, hipStream_t stream) {
+                       unsigned long long *d_counts, void *scratch, hipStream_t stream, uint8_t *d_amb,
+                       uint64_t amb_capacity_bytes) {
+    // (d_amb: the ambiguity bits of mm_fasta_pack_n_*, amb_capacity_bytes a multiple of 4; null: the plain packer)
     const uint64_t chunks = fa2_chunks(n_bytes), groups = fa2_groups(chunks);
     if (chunks == 0 || chunks >= (1ull << 31)) return -1;
     unsigned long long *q = static_cast<unsigned long long *>(scratch);
@@ -414,11 +438,22 @@ int launch_fasta_pack2(const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_packe
     // the packed bytes are OR-ed together where chunks meet: clear what the text can fill at most
     const uint64_t clear = packed_capacity_bytes < (n_bytes + 3) / 4 + 8 ? packed_capacity_bytes : (n_bytes + 3) / 4 + 8;
     if (clear && hipMemsetAsync(d_packed, 0, clear, stream) != hipSuccess) return -1;
+    const uint64_t amb_dwords = amb_capacity_bytes / 4;
+    if (d_amb) {  // (OR-ed together where chunks meet, like the codes: one bit per text byte at most)
+        const uint64_t aclear = amb_capacity_bytes < ((n_bytes / 8 + 8 + 3) & ~3ull) ? amb_capacity_bytes : ((n_bytes / 8 + 8 + 3) & ~3ull);
+        if (aclear && hipMemsetAsync(d_amb, 0, aclear, stream) != hipSuccess) return -1;
+    }
     hipLaunchKernelGGL(fasta2_count_kernel, dim3((uint32_t)chunks), dim3(kFqThreads), 0, stream, d_text, n_bytes, sc.fn);
     hipLaunchKernelGGL(fasta2_groups_kernel, dim3((uint32_t)groups), dim3(kFaGroup), 0, stream, sc, chunks);
     hipLaunchKernelGGL(fasta2_resolve_kernel, dim3(1), dim3(kFaGroup), 0, stream, sc, groups);
-    hipLaunchKernelGGL(fasta2_pack_kernel, dim3((uint32_t)chunks), dim3(kFqThreads), 0, stream, d_text, n_bytes, sc,
-                       reinterpret_cast<uint32_t *>(d_packed), out_dwords, d_rec_base, d_rec_pos, max_records);
+    if (d_amb)
+        hipLaunchKernelGGL(fasta2_pack_kernel<true>, dim3((uint32_t)chunks), dim3(kFqThreads), 0, stream, d_text, n_bytes, sc,
+                           reinterpret_cast<uint32_t *>(d_packed), out_dwords, d_rec_base, d_rec_pos, max_records,
+                           reinterpret_cast<uint32_t *>(d_amb), amb_dwords);
+    else
+        hipLaunchKernelGGL(fasta2_pack_kernel<false>, dim3((uint32_t)chunks), dim3(kFqThreads), 0, stream, d_text, n_bytes, sc,
+                           reinterpret_cast<uint32_t *>(d_packed), out_dwords, d_rec_base, d_rec_pos, max_records,
+                           (uint32_t *)nullptr, (uint64_t)0);
     hipLaunchKernelGGL(fasta2_finish_kernel, dim3(1), dim3(1), 0, stream, sc, groups, d_rec_base, max_records, d_counts);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -236,12 +236,15 @@ __global__ __launch_bounds__(kFqGroup) void fastq_resolve_kernel(FqScratch sc, u
     }
 }
 
-// K2: pack
+// K2: pack.  AMB (mm_fastq_pack_n_*): also one ambiguity bit per output base into amb32, as in fasta2_pack_kernel
+// (mm_fasta2.hip); the plain instantiation holds none of it.
+template <bool AMB>
 __global__ __launch_bounds__(kFqThreads) void fastq_pack_kernel(const uint8_t *__restrict__ text, uint64_t n, const FqScratch sc,
                                                                 uint32_t *__restrict__ out32, uint64_t out_dwords,
                                                                 unsigned long long *__restrict__ rec_base,
                                                                 unsigned long long *__restrict__ rec_pos,
-                                                                uint64_t max_records, uint64_t pos_bias) {
+                                                                uint64_t max_records, uint64_t pos_bias,
+                                                                uint32_t *__restrict__ amb32, uint64_t amb_dwords) {
     __shared__ uint32_t s_part[kFqPieces][kFqWaves];
     // The chunk's output is assembled in LDS (at most 16 384 bases = 1024 dwords, + 1 for its bit offset, + 2 for the
     // last thread's three-dword OR) and leaves as whole dwords; only the first and the last dword, which the chunk
@@ -251,6 +254,12 @@ __global__ __launch_bounds__(kFqThreads) void fastq_pack_kernel(const uint8_t *_
     constexpr uint32_t kOutDwords = kFqChunk / 16u + 4u;
     __shared__ uint32_t s_out[kOutDwords];
     for (uint32_t i = threadIdx.x; i < kOutDwords; i += kFqThreads) s_out[i] = 0u;  // (ordered by read_chunk's barriers)
+    uint32_t *s_amb = nullptr;
+    if constexpr (AMB) {
+        __shared__ uint32_t s_amb_area[kAmbDwords];
+        s_amb = s_amb_area;
+        for (uint32_t i = threadIdx.x; i < kAmbDwords; i += kFqThreads) s_amb[i] = 0u;
+    }
     const uint64_t c0 = (uint64_t)blockIdx.x * kFqChunk;
     const uint64_t grp = blockIdx.x / kFqGroup;
     const uint32_t gphase = (uint32_t)(sc.g_nl[grp] & 3ull);  // phase the chunk's group starts in
@@ -284,9 +293,12 @@ __global__ __launch_bounds__(kFqThreads) void fastq_pack_kernel(const uint8_t *_
             const unsigned long long codes = (unsigned long long)clo | ((unsigned long long)chi << 32);
             const uint32_t first = (uint32_t)__builtin_ctz(sm), run = sm >> first;
             unsigned long long bits;
+            uint32_t na = 0, abits = 0;  // (AMB: the same bytes' ambiguity flags, one bit each where the codes take two)
+            if constexpr (AMB) na = not_acgt32(v) & sm;
             if ((run & (run + 1u)) == 0u) {  // ONE run of bytes (the rule: a piece of one sequence line)
                 const uint32_t len = (uint32_t)__popc(sm);
                 bits = (codes >> (2u * first)) & (len >= 32u ? ~0ull : ((1ull << (2u * len)) - 1ull));
+                if constexpr (AMB) abits = na >> first;  // (na lies inside sm: nothing above the run)
             } else {  // ('\r' inside a line, or reads shorter than a piece)
                 bits = 0;
                 uint32_t k = 0;
@@ -294,9 +306,11 @@ __global__ __launch_bounds__(kFqThreads) void fastq_pack_kernel(const uint8_t *_
                 for (int i = 0; i < (int)kFqBytesPerThread; ++i)
                     if ((sm >> i) & 1u) {
                         bits |= ((codes >> (2 * i)) & 3ull) << (2u * k);
+                        if constexpr (AMB) abits |= ((na >> i) & 1u) << k;
                         ++k;
                     }
             }
+            if constexpr (AMB) amb_or_lds(s_amb, seq0, o0, abits);
             const uint32_t q = (uint32_t)((o0 >> 4) - q0);
             const uint32_t sh = 2u * (uint32_t)(o0 & 15ull);
             const unsigned long long lo = bits << sh;                              // (64 bits shifted by at most 30:
@@ -326,6 +340,7 @@ __global__ __launch_bounds__(kFqThreads) void fastq_pack_kernel(const uint8_t *_
         if (i == 0 || i + 1 == nd) atomicOr(&out32[q], w);
         else out32[q] = w;
     }
+    if constexpr (AMB) amb_flush(s_amb, seq0, chunk_seq, amb32, amb_dwords);
 }
 
 __global__ void fastq_finish_kernel(const FqScratch sc, uint64_t groups, unsigned long long *rec_base, uint64_t max_records,
@@ -348,7 +363,9 @@ uint64_t fastq_scratch_bytes(uint64_t n_bytes) {
 
 int launch_fastq_pack(const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_packed, uint64_t packed_capacity_bytes,
                       unsigned long long *d_rec_base, unsigned long long *d_rec_pos, uint64_t max_records,
-                      unsigned long long *d_counts, void *scratch, hipStream_t stream, uint64_t pos_bias) {
+                      unsigned long long *d_counts, void *scratch, hipStream_t stream, uint64_t pos_bias, uint8_t *d_amb,
+                      uint64_t amb_capacity_bytes) {
+    // (d_amb: the ambiguity bits of mm_fastq_pack_n_*, amb_capacity_bytes a multiple of 4; null: the plain packer)
     // (pos_bias: added to every record's text position - the caller passed the text from its first '@' on)
     const uint64_t chunks = fastq_chunks(n_bytes), groups = fastq_groups(chunks);
     if (chunks == 0 || chunks >= (1ull << 31)) return -1;
@@ -366,12 +383,23 @@ int launch_fastq_pack(const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_packed
     sc.g_rec0 = q, q += groups + 1;
     const uint64_t out_dwords = packed_capacity_bytes / 4;
     if (out_dwords && hipMemsetAsync(d_packed, 0, out_dwords * 4, stream) != hipSuccess) return -1;
+    const uint64_t amb_dwords = amb_capacity_bytes / 4;
+    if (d_amb) {  // (one bit per text byte at most)
+        const uint64_t aclear = amb_capacity_bytes < ((n_bytes / 8 + 8 + 3) & ~3ull) ? amb_capacity_bytes : ((n_bytes / 8 + 8 + 3) & ~3ull);
+        if (aclear && hipMemsetAsync(d_amb, 0, aclear, stream) != hipSuccess) return -1;
+    }
     hipLaunchKernelGGL(fastq_count_kernel, dim3((uint32_t)chunks), dim3(kFqThreads), 0, stream, d_text, n_bytes, sc.nl, sc.seq,
                        sc.rec);
     hipLaunchKernelGGL(fastq_groups_kernel, dim3((uint32_t)groups), dim3(kFqGroup), 0, stream, sc, chunks);
     hipLaunchKernelGGL(fastq_resolve_kernel, dim3(1), dim3(kFqGroup), 0, stream, sc, groups);
-    hipLaunchKernelGGL(fastq_pack_kernel, dim3((uint32_t)chunks), dim3(kFqThreads), 0, stream, d_text, n_bytes, sc,
-                       reinterpret_cast<uint32_t *>(d_packed), out_dwords, d_rec_base, d_rec_pos, max_records, pos_bias);
+    if (d_amb)
+        hipLaunchKernelGGL(fastq_pack_kernel<true>, dim3((uint32_t)chunks), dim3(kFqThreads), 0, stream, d_text, n_bytes, sc,
+                           reinterpret_cast<uint32_t *>(d_packed), out_dwords, d_rec_base, d_rec_pos, max_records, pos_bias,
+                           reinterpret_cast<uint32_t *>(d_amb), amb_dwords);
+    else
+        hipLaunchKernelGGL(fastq_pack_kernel<false>, dim3((uint32_t)chunks), dim3(kFqThreads), 0, stream, d_text, n_bytes, sc,
+                           reinterpret_cast<uint32_t *>(d_packed), out_dwords, d_rec_base, d_rec_pos, max_records, pos_bias,
+                           (uint32_t *)nullptr, (uint64_t)0);
     hipLaunchKernelGGL(fastq_finish_kernel, dim3(1), dim3(1), 0, stream, sc, groups, d_rec_base, max_records, d_counts);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

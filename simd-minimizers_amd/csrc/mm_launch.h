@@ -227,13 +227,15 @@ int launch_fasta_pack(const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_packed
 uint64_t fasta2_scratch_bytes(uint64_t n_bytes);
 int launch_fasta_pack2(const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_packed, uint64_t packed_capacity_bytes,
                        unsigned long long *d_rec_base, unsigned long long *d_rec_pos, uint64_t max_records,
-                       unsigned long long *d_counts, void *scratch, hipStream_t stream);
+                       unsigned long long *d_counts, void *scratch, hipStream_t stream, uint8_t *d_amb = nullptr,
+                       uint64_t amb_capacity_bytes = 0);
 
 // ---- FASTQ text -> packed records (mm_fastq.hip): four-line records, the sequences of lines 4r + 1
 uint64_t fastq_scratch_bytes(uint64_t n_bytes);
 int launch_fastq_pack(const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_packed, uint64_t packed_capacity_bytes,
                       unsigned long long *d_rec_base, unsigned long long *d_rec_pos, uint64_t max_records,
-                      unsigned long long *d_counts, void *scratch, hipStream_t stream, uint64_t pos_bias = 0);
+                      unsigned long long *d_counts, void *scratch, hipStream_t stream, uint64_t pos_bias = 0,
+                      uint8_t *d_amb = nullptr, uint64_t amb_capacity_bytes = 0);
 // copies to / from page-locked host memory by a kernel (mm_aux.hip; the host entry point's alternative mechanisms)
 int launch_copy_range(const uint32_t *d_src, uint32_t *dst_host_alias, const unsigned long long *d_range, uint64_t cap,
                       uint32_t workgroups, hipStream_t stream);

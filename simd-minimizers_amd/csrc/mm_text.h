@@ -75,6 +75,51 @@ __device__ __forceinline__ uint32_t any_eq32(const Text32 &v, uint32_t pat) {
     }
     return m;
 }
+// 32-bit mask of the bytes whose upper-cased value (c & 0xDF) is none of A C G T: the ambiguity rule of
+// PackedNSeqVec::from_ascii (pack_ascii_n_kernel, mm_aux.hip).  Four exact zero-byte tests per dword, one gather.
+__device__ __forceinline__ uint32_t not_acgt32(const Text32 &v) {
+    uint32_t m = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const uint32_t x = v.d[i] & 0xdfdfdfdfu;
+        uint32_t is = 0;
+#pragma unroll
+        for (uint32_t pat : {0x41414141u, 0x43434343u, 0x47474747u, 0x54545454u}) {
+            const uint32_t z = x ^ pat;
+            is |= ~(((z & 0x7f7f7f7fu) + 0x7f7f7f7fu) | z | 0x7f7f7f7fu);  // 0x80 where the byte matches
+        }
+        m |= ((is * 0x00204081u) >> 28) << (4 * i);
+    }
+    return ~m;
+}
+
+// The packers' second output (the *_pack_n entry points): one ambiguity bit per output base, in the numbering of the
+// 2-bit codes.  A chunk's bits are assembled in LDS like its codes and leave as whole dwords; a dword holds 32 bases
+// where a code dword holds 16, so the chunk's first and last dword - the two it may share with its neighbours, OR-ed
+// into the cleared buffer - are found from seq0 >> 5, not from the code dwords' seams.
+constexpr uint32_t kAmbDwords = kFqChunk / 32u + 2u;  // 16 384 bases = 512 dwords, + 1 for the bit offset, + 1 for the last thread's spill
+// a thread's (at most 32, consecutive) bits, the first at output base o0
+__device__ __forceinline__ void amb_or_lds(uint32_t *s_amb, unsigned long long seq0, unsigned long long o0, uint32_t bits) {
+    if (bits == 0u) return;
+    const uint32_t q = (uint32_t)((o0 >> 5) - (seq0 >> 5)), sh = (uint32_t)(o0 & 31ull);
+    const unsigned long long x = (unsigned long long)bits << sh;
+    if ((uint32_t)x) atomicOr(&s_amb[q], (uint32_t)x);
+    if ((uint32_t)(x >> 32)) atomicOr(&s_amb[q + 1], (uint32_t)(x >> 32));
+}
+// after a barrier: the chunk's dwords to the cleared buffer (amb_dwords: its capacity)
+__device__ __forceinline__ void amb_flush(const uint32_t *s_amb, unsigned long long seq0, uint32_t chunk_seq,
+                                          uint32_t *__restrict__ amb32, uint64_t amb_dwords) {
+    const uint32_t nd = chunk_seq ? (uint32_t)(((seq0 & 31ull) + chunk_seq + 31ull) >> 5) : 0u;  // dwords the chunk touches
+    const uint64_t q0 = seq0 >> 5;
+    for (uint32_t i = threadIdx.x; i < nd; i += kFqThreads) {
+        const uint32_t w = s_amb[i];
+        const uint64_t q = q0 + i;
+        if (w == 0u || q >= amb_dwords) continue;
+        if (i == 0 || i + 1 == nd) atomicOr(&amb32[q], w);
+        else amb32[q] = w;
+    }
+}
+
 // inclusive prefix sum over the 64 lanes of a wave with DPP row shifts / broadcasts (also of packed 16-bit fields whose
 // sums stay below 2^16)
 __device__ __forceinline__ uint32_t fq_wave_scan(uint32_t v) {
