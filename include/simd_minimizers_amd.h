@@ -338,6 +338,59 @@ int mm_values_u128_host(mm_workspace_t *ws, const uint8_t *packed, uint64_t base
                         uint64_t n_bases, uint32_t len, int canonical, const uint32_t *pos,
                         uint64_t n_pos, uint64_t *values);
 
+/* Output::values_u64 / values_u128 (src/lib.rs:584-629) of EVERY read of one packed buffer in one launch: what a
+ * loop over Builder::run (src/lib.rs:378) and Output::values_* per read computes.  The inputs are what the reads entry
+ * points (mm_run_reads_*, mm_run_packed_reads_*) take and write:
+ *   d_packed / packed_bytes / base_offset   the packed buffer; no byte outside it is loaded, whatever d_pos holds
+ *   n_reads, and the layout: d_read_starts [n_reads + 1] (device; read r starts at base d_read_starts[r], the
+ *                            mm_run_packed_reads_* layout), or NULL and read_stride (read r starts at base
+ *                            r * read_stride, a 64-bit product: the mm_run_reads_* layout)
+ *   d_pos                    the read-local positions, back to back (any 4-byte boundary)
+ *   d_out_offsets [n_reads + 1]   as the reads entry points write them: value i belongs to the read r with
+ *                            d_out_offsets[r] <= i < d_out_offsets[r + 1] (empty reads are skipped) and is the k-mer
+ *                            at base base_offset + start(r) + d_pos[i] of the buffer (64-bit: a read may start at or
+ *                            beyond base 2^32); a position with pos + len past its read's end gives an unspecified value
+ *   n_pos_max                what d_pos and d_values hold; the TRUE count is d_out_offsets[n_reads], read on the
+ *                            device: values at or past it (or past n_pos_max) are not written, so the call can be
+ *                            queued behind the packer and the reads run on one stream with no host wait
+ *   d_values                 8-byte aligned; u64: n_pos_max words, u128: 2 * n_pos_max words ({lo, hi} per value)
+ * len / canonical as for mm_values_u64_device_async (len = mm_plan_value_len).  MM_ERR_NULL for a NULL workspace, and for
+ * NULL d_packed / d_pos / d_out_offsets / d_values when there is work; MM_ERR_VALUE_LEN for len == 0, len > 32 (u64) or
+ * len > 64 (u128); MM_ERR_CAPACITY when base_offset, or a fixed-stride layout's last read, starts past packed_bytes;
+ * n_reads == 0 or n_pos_max == 0 returns MM_OK with nothing launched.  Not covered: mm_run_batch_device's separately
+ * allocated sequences, byte text. */
+int mm_values_u64_reads_device_async(mm_workspace_t *ws, const void *d_packed, uint64_t packed_bytes,
+                                     uint64_t base_offset, uint64_t n_reads,
+                                     const uint64_t *d_read_starts /* [n_reads + 1] or NULL */, uint32_t read_stride,
+                                     uint32_t len, int canonical, const uint32_t *d_pos,
+                                     const uint64_t *d_out_offsets /* [n_reads + 1] */, uint64_t n_pos_max,
+                                     uint64_t *d_values);
+int mm_values_u128_reads_device_async(mm_workspace_t *ws, const void *d_packed, uint64_t packed_bytes,
+                                      uint64_t base_offset, uint64_t n_reads,
+                                      const uint64_t *d_read_starts /* [n_reads + 1] or NULL */, uint32_t read_stride,
+                                      uint32_t len, int canonical, const uint32_t *d_pos,
+                                      const uint64_t *d_out_offsets /* [n_reads + 1] */, uint64_t n_pos_max,
+                                      uint64_t *d_values);
+/* The same from HOST memory (Output::values_* per read, src/lib.rs:584-629, of a loop over Builder::run,
+ * src/lib.rs:378): one upload of the packed bytes, the starts, the positions and the offsets, one launch, one download
+ * of offsets[n_reads] values.  Starts or offsets that decrease return MM_ERR_UNSORTED before anything is touched;
+ * MM_ERR_CAPACITY when read_starts[n_reads] (or a fixed-stride layout's last read) lies past packed_bytes. */
+int mm_values_u64_reads_host(mm_workspace_t *ws, const uint8_t *packed, uint64_t packed_bytes, uint64_t base_offset,
+                             uint64_t n_reads, const uint64_t *read_starts /* [n_reads + 1] or NULL */,
+                             uint32_t read_stride, uint32_t len, int canonical, const uint32_t *pos,
+                             const uint64_t *offsets /* [n_reads + 1] */, uint64_t *values);
+int mm_values_u128_reads_host(mm_workspace_t *ws, const uint8_t *packed, uint64_t packed_bytes, uint64_t base_offset,
+                              uint64_t n_reads, const uint64_t *read_starts /* [n_reads + 1] or NULL */,
+                              uint32_t read_stride, uint32_t len, int canonical, const uint32_t *pos,
+                              const uint64_t *offsets /* [n_reads + 1] */, uint64_t *values);
+/* Diagnostics of the reads values kernels (Output::values_*, src/lib.rs:584-629, per read of src/lib.rs:378; no device
+ * needed).  mm_debug_values_read_of runs the kernel's read lookup on the host: out_read[j] = the largest r in
+ * [0, n_reads] with offsets[r] <= idx[j], -1 if there is none.  mm_values_reads_lds_stage: the number of offsets a
+ * workgroup stages in LDS; a workgroup whose values span more reads searches global memory instead. */
+int mm_debug_values_read_of(const uint64_t *offsets /* [n_reads + 1] */, uint64_t n_reads, const uint64_t *idx,
+                            uint64_t n, int64_t *out_read);
+uint32_t mm_values_reads_lds_stage(void);
+
 /* Page-locked host memory for the host entry points.  Any host pointer works; with buffers from
  * mm_host_alloc the copies to and from the device run in both directions at once (97 GB/s aggregate
  * against 56 GB/s for pageable memory on the round-1 box), which the pipelined long-sequence path

@@ -328,6 +328,21 @@ class Builder {  // src/lib.rs:225-230
         if (sk_) sk_->assign(sk.begin(), sk.begin() + n);
     }
 
+    // Output::values_u64 / values_u128 (src/lib.rs:584-629) of EVERY read of run_many in ONE call (mm_values_u64_reads_host /
+    // mm_values_u128_reads_host): `reads`, `pos` and `offsets` as run_many took and wrote them; read r's values are
+    // [offsets[r] .. offsets[r + 1]) of the result, what run(reads[r], ..).values_u64() returns.
+    std::vector<uint64_t> values_u64_many(const std::vector<PackedSeq> &reads, const std::vector<uint32_t> &pos,
+                                          const std::vector<uint64_t> &offsets) const {
+        return values_many_raw(reads, pos, offsets, false);
+    }
+    std::vector<u128> values_u128_many(const std::vector<PackedSeq> &reads, const std::vector<uint32_t> &pos,
+                                       const std::vector<uint64_t> &offsets) const {
+        const std::vector<uint64_t> raw = values_many_raw(reads, pos, offsets, true);
+        std::vector<u128> v(raw.size() / 2);
+        for (size_t i = 0; i < v.size(); ++i) v[i] = ((u128)raw[2 * i + 1] << 64) | raw[2 * i];
+        return v;
+    }
+
     // run_skip_ambiguous_windows (src/lib.rs:451-496) per read over MANY PackedNSeq reads in ONE call
     // (mm_run_packed_reads_skip_ambiguous_host): codes and ambiguity bits are packed back to back on the host.  Canonical
     // builders only, no super-k-mer indices.  pos / offsets are OVERWRITTEN, read r's read-local positions at
@@ -414,6 +429,29 @@ class Builder {  // src/lib.rs:225-230
         mm_plan_destroy(plan);
         check(r);
         return n;
+    }
+
+    std::vector<uint64_t> values_many_raw(const std::vector<PackedSeq> &reads, const std::vector<uint32_t> &pos,
+                                          const std::vector<uint64_t> &offsets, bool wide) const {
+        if (offsets.size() != reads.size() + 1) throw Error(MM_ERR_NULL);
+        Workspace &ws = ws_ ? *ws_ : Workspace::thread_default();
+        std::vector<uint64_t> starts(reads.size() + 1, 0);
+        for (size_t r = 0; r < reads.size(); ++r) starts[r + 1] = starts[r] + reads[r].len;
+        const uint64_t total = starts.back();
+        std::vector<uint8_t> packed((total + 3) / 4 + 1, 0);
+        for (size_t r = 0; r < reads.size(); ++r)  // (base by base: any source offset to any destination offset)
+            for (uint64_t i = 0; i < reads[r].len; ++i) {
+                const uint64_t s = reads[r].offset + i, d = starts[r] + i;
+                packed[d >> 2] |= (uint8_t)(((reads[r].data[s >> 2] >> (2 * (s & 3))) & 3u) << (2 * (d & 3)));
+            }
+        const uint64_t n = offsets.back();
+        if (pos.size() < n) throw Error(MM_ERR_CAPACITY);
+        std::vector<uint64_t> v((wide ? 2 : 1) * n);
+        const uint32_t len = SYNCMER ? k_ + w_ - 1 : k_;
+        check((wide ? mm_values_u128_reads_host : mm_values_u64_reads_host)(
+            ws.get(), packed.data(), packed.size(), 0, reads.size(), starts.data(), 0, len, CANONICAL, pos.data(),
+            offsets.data(), v.data()));
+        return v;
     }
 
     uint32_t k_, w_;

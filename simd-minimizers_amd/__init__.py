@@ -218,6 +218,17 @@ def _load_lib():
                                                   C.c_uint32, C.c_int, vp, C.c_uint64, vp]
         L.mm_values_u128_host.argtypes = [vp, u8p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, u32p,
                                           C.c_uint64, u64p]
+        values_reads_args = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, vp, C.c_uint32, C.c_uint32, C.c_int, vp, vp,
+                             C.c_uint64, vp]
+        L.mm_values_u64_reads_device_async.argtypes = values_reads_args
+        L.mm_values_u128_reads_device_async.argtypes = values_reads_args
+        values_reads_host_args = [vp, u8p, C.c_uint64, C.c_uint64, C.c_uint64, u64p, C.c_uint32, C.c_uint32, C.c_int,
+                                  u32p, u64p, u64p]
+        L.mm_values_u64_reads_host.argtypes = values_reads_host_args
+        L.mm_values_u128_reads_host.argtypes = values_reads_host_args
+        L.mm_debug_values_read_of.argtypes = [u64p, C.c_uint64, u64p, C.c_uint64, C.POINTER(C.c_int64)]
+        L.mm_values_reads_lds_stage.argtypes = []
+        L.mm_values_reads_lds_stage.restype = C.c_uint32
         L.mm_run_batch_device.argtypes = [vp, vp, C.c_uint64, C.POINTER(vp), u64p, u64p, u64p, vp, vp,
                                           C.c_uint64, u64p]
         reads_args = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp,
@@ -296,6 +307,8 @@ EXPORTED_SYMBOLS = [
     "mm_fasta_pack_n_device_async", "mm_fastq_pack_n_device_async", "mm_fasta_pack_n_device",
     "mm_run_packed_reads_skip_ambiguous_device_async", "mm_run_packed_reads_skip_ambiguous_device",
     "mm_run_packed_reads_skip_ambiguous_host",
+    "mm_values_u64_reads_device_async", "mm_values_u128_reads_device_async", "mm_values_u64_reads_host",
+    "mm_values_u128_reads_host", "mm_debug_values_read_of", "mm_values_reads_lds_stage",
 ]
 
 
@@ -1380,6 +1393,98 @@ def run_reads_skip_ambiguous_host(builder: "Builder", reads):
                                                          _p(pos, C.c_uint32), cap, _p(offs, C.c_uint64), C.byref(cnt)))
     n = int(cnt.value)
     return pos[:n], [int(o) for o in offs]
+
+
+def _value_len(builder: "Builder") -> int:
+    """What ``Output.values_u64`` reads per position: k for minimizers, k + w - 1 for syncmers."""
+    return builder.k if builder.mode == MM_MINIMIZERS else builder.k + builder.w - 1
+
+
+def values_read_of(offsets, idx) -> np.ndarray:
+    """The reads values kernels' lookup on the host (``mm_debug_values_read_of``, no GPU): for every value index in
+    ``idx`` the read r with ``offsets[r] <= idx < offsets[r + 1]`` = ``np.searchsorted(offsets, idx, 'right') - 1``."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    idx = np.ascontiguousarray(idx, dtype=np.uint64)
+    out = np.empty(len(idx), dtype=np.int64)
+    _check(lib().mm_debug_values_read_of(_p(offsets, C.c_uint64), len(offsets) - 1, _p(idx, C.c_uint64), len(idx),
+                                         out.ctypes.data_as(C.POINTER(C.c_int64))))
+    return out
+
+
+def values_reads_lds_stage() -> int:
+    """Offsets a workgroup of the reads values kernels stages in LDS (``mm_values_reads_lds_stage``); a workgroup whose
+    values span more reads searches global memory."""
+    return int(lib().mm_values_reads_lds_stage())
+
+
+def values_reads_device(builder: "Builder", d_packed, n_reads, d_pos, d_out_offsets, read_starts=None, read_stride=0,
+                        base_offset=0, n_pos_max=None, out=None, u128=False):
+    """K-mer values of EVERY read's positions in one launch (``mm_values_u64_reads_device_async`` /
+    ``mm_values_u128_reads_device_async``): ``d_packed`` the packed uint8 CUDA tensor the reads run took, ``d_pos`` its
+    read-local positions (int32 tensor), ``d_out_offsets`` its n_reads + 1 offsets (int64 tensor), and the same layout -
+    ``read_starts`` (int64 tensor of n_reads + 1 starts: reads back to back) or ``read_stride``.  ``len`` and
+    ``canonical`` come from the builder like ``Output.values_u64`` takes them.  The true count is read on the device:
+    nothing waits for the host, values at or past it stay as they were.  Fills ``out`` (int64 tensor of ``n_pos_max``
+    words, twice that for ``u128``: {lo, hi}) or returns a new zero-filled one; the call is asynchronous on the
+    builder's workspace (``Workspace.sync``)."""
+    import torch
+    if n_pos_max is None:
+        n_pos_max = int(d_pos.numel())
+    per = 2 if u128 else 1
+    if out is None:
+        out = torch.zeros(per * n_pos_max, dtype=torch.int64, device=d_pos.device)
+        torch.cuda.synchronize(d_pos.device)
+    elif out.numel() < per * n_pos_max:
+        raise ValueError(f"out holds {out.numel()} words, {per * n_pos_max} needed")
+    if d_pos.numel() < n_pos_max:
+        raise ValueError(f"d_pos holds {d_pos.numel()} positions, n_pos_max is {n_pos_max}")
+    f = lib().mm_values_u128_reads_device_async if u128 else lib().mm_values_u64_reads_device_async
+    _check(f(builder._ws().h, C.c_void_p(d_packed.data_ptr()), int(d_packed.numel()), int(base_offset), int(n_reads),
+             C.c_void_p(read_starts.data_ptr()) if read_starts is not None else None, int(read_stride),
+             _value_len(builder), int(builder.canonical), C.c_void_p(d_pos.data_ptr()),
+             C.c_void_p(d_out_offsets.data_ptr()), int(n_pos_max), C.c_void_p(out.data_ptr())))
+    return out
+
+
+def _pack_reads(reads):
+    """Reads (``PackedSeq`` views / ASCII ``bytes``) -> (packed bytes, starts): the reads packed back to back."""
+    codes = []
+    for s in reads:
+        if isinstance(s, (bytes, bytearray)):
+            codes.append((np.frombuffer(bytes(s), dtype=np.uint8) >> 1) & 3)
+        else:  # PackedSeq view
+            codes.append(s.codes())
+    starts = np.zeros(len(codes) + 1, dtype=np.uint64)
+    starts[1:] = np.cumsum([len(c) for c in codes], dtype=np.uint64)
+    total = int(starts[-1])
+    if not total:
+        return np.zeros(1, dtype=np.uint8), starts
+    q = np.concatenate(codes + [np.zeros((-total) % 4, dtype=np.uint8)]).astype(np.uint8).reshape(-1, 4)
+    return (q[:, 0] | (q[:, 1] << 2) | (q[:, 2] << 4) | (q[:, 3] << 6)).astype(np.uint8), starts
+
+
+def values_reads_host(builder: "Builder", reads, pos, offsets, u128=False):
+    """K-mer values of many host reads in ONE call (``mm_values_u64_reads_host`` / ``mm_values_u128_reads_host``):
+    ``reads`` as ``run_reads_host`` takes them, ``pos`` / ``offsets`` as it returns them.  Returns a uint64 array (one
+    value per position), or a list of Python ints for ``u128`` - read r's values are ``[offsets[r]:offsets[r + 1]]``,
+    what ``Output.values_u64`` of ``Builder.run(read)`` returns."""
+    packed, starts = _pack_reads(reads)
+    pos = np.ascontiguousarray(pos, dtype=np.uint32)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    if len(offsets) != len(starts):
+        raise ValueError(f"{len(starts) - 1} reads need {len(starts)} offsets, not {len(offsets)}")
+    n = int(offsets[-1]) if len(offsets) else 0
+    if len(pos) < n:
+        raise ValueError(f"offsets end at {n}, pos holds {len(pos)}")
+    per = 2 if u128 else 1
+    vals = np.zeros(max(1, per * n), dtype=np.uint64)
+    f = lib().mm_values_u128_reads_host if u128 else lib().mm_values_u64_reads_host
+    _check(f(builder._ws().h, _p(packed, C.c_uint8), len(packed), 0, len(starts) - 1, _p(starts, C.c_uint64), 0,
+             _value_len(builder), int(builder.canonical), _p(pos, C.c_uint32) if len(pos) else None,
+             _p(offsets, C.c_uint64), _p(vals, C.c_uint64)))
+    if u128:
+        return [int(vals[2 * i]) | (int(vals[2 * i + 1]) << 64) for i in range(n)]
+    return vals[:n]
 
 
 def run_fasta_device(builder: "Builder", records: FastaRecords, out_pos, out_sk=None):

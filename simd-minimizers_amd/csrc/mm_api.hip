@@ -19,6 +19,7 @@
 #include "../../include/simd_minimizers_amd.h"
 #include "mm_env.h"
 #include "mm_launch.h"
+#include "mm_values_reads.h"
 
 namespace {
 
@@ -3087,6 +3088,142 @@ int mm_values_u128_host(mm_workspace_t *ws, const uint8_t *packed, uint64_t base
     MM_HIP(hipStreamSynchronize(ws->stream));
     return MM_OK;
 }
+
+// ---- Output::values_u64 / values_u128 (src/lib.rs:584-629) of every read of one packed buffer in ONE launch: what a loop
+// over Builder::run (src/lib.rs:378) and Output::values_* per read computes, from the read-local positions and offsets the
+// reads entry points write (mm_values_reads.hip).  The true count is d_out_offsets[n_reads], read on the device.
+static int values_reads_async_impl(mm_workspace_t *ws, const void *d_packed, uint64_t packed_bytes, uint64_t base_offset,
+                                   uint64_t n_reads, const uint64_t *d_read_starts, uint32_t read_stride, uint32_t len,
+                                   int canonical, const uint32_t *d_pos, const uint64_t *d_out_offsets, uint64_t n_pos_max,
+                                   uint64_t *d_values, bool u128) {
+    if (!ws) return MM_ERR_NULL;
+    if (len == 0 || len > (u128 ? 64u : 32u)) return MM_ERR_VALUE_LEN;
+    if (n_reads == 0 || n_pos_max == 0) return MM_OK;
+    if (!d_packed || !d_pos || !d_out_offsets || !d_values) return MM_ERR_NULL;
+    if (n_reads >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
+    if (packed_bytes >= (1ull << 60)) return MM_ERR_LEN_TOO_LARGE;
+    // what the host can prove about the layout: the buffer's first base, and a fixed-stride layout's last read, lie
+    // inside the buffer (starts in device memory are the kernel's to bound: no load leaves the buffer whatever they hold)
+    const uint64_t buffer_bases = 4 * packed_bytes;
+    if (base_offset > buffer_bases) return MM_ERR_CAPACITY;
+    if (!d_read_starts && (n_reads - 1) * (uint64_t)read_stride > buffer_bases - base_offset) return MM_ERR_CAPACITY;
+    MM_HIP(set_device(ws->device));
+    mm::ValuesReadsArgs a;
+    const uintptr_t addr = reinterpret_cast<uintptr_t>(d_packed);
+    const uint64_t byte_shift = addr & 3u;
+    a.view.d = reinterpret_cast<const uint32_t *>(addr - byte_shift);
+    a.view.byte_lo = byte_shift;
+    a.view.byte_hi = byte_shift + packed_bytes;
+    a.view.q_lo = byte_shift ? 1 : 0;
+    a.view.q_hi = a.view.byte_hi / 4;
+    a.view.base0 = base_offset + 4 * byte_shift;
+    a.n_reads = n_reads;
+    a.read_starts = reinterpret_cast<const unsigned long long *>(d_read_starts);
+    a.read_stride = read_stride;
+    a.len = len;
+    a.canonical = canonical ? 1 : 0;
+    a.pos = d_pos;
+    a.offsets = reinterpret_cast<const unsigned long long *>(d_out_offsets);
+    a.n_pos_max = n_pos_max;
+    a.out = reinterpret_cast<unsigned long long *>(d_values);
+    const int r = mm::launch_values_reads(a, u128, ws->stream);
+    if (r == -3) return MM_ERR_LEN_TOO_LARGE;
+    if (r) return hip_fail(hipGetLastError(), u128 ? "values_u128_reads" : "values_u64_reads");
+    return MM_OK;
+}
+
+int mm_values_u64_reads_device_async(mm_workspace_t *ws, const void *d_packed, uint64_t packed_bytes, uint64_t base_offset,
+                                     uint64_t n_reads, const uint64_t *d_read_starts, uint32_t read_stride, uint32_t len,
+                                     int canonical, const uint32_t *d_pos, const uint64_t *d_out_offsets,
+                                     uint64_t n_pos_max, uint64_t *d_values) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    return values_reads_async_impl(ws, d_packed, packed_bytes, base_offset, n_reads, d_read_starts, read_stride, len,
+                                   canonical, d_pos, d_out_offsets, n_pos_max, d_values, false);
+}
+
+int mm_values_u128_reads_device_async(mm_workspace_t *ws, const void *d_packed, uint64_t packed_bytes, uint64_t base_offset,
+                                      uint64_t n_reads, const uint64_t *d_read_starts, uint32_t read_stride, uint32_t len,
+                                      int canonical, const uint32_t *d_pos, const uint64_t *d_out_offsets,
+                                      uint64_t n_pos_max, uint64_t *d_values) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    return values_reads_async_impl(ws, d_packed, packed_bytes, base_offset, n_reads, d_read_starts, read_stride, len,
+                                   canonical, d_pos, d_out_offsets, n_pos_max, d_values, true);
+}
+
+// The same from HOST memory: one upload (packed bytes, starts, positions, offsets), one launch, one download.
+static int values_reads_host_impl(mm_workspace_t *ws, const uint8_t *packed, uint64_t packed_bytes, uint64_t base_offset,
+                                  uint64_t n_reads, const uint64_t *read_starts, uint32_t read_stride, uint32_t len,
+                                  int canonical, const uint32_t *pos, const uint64_t *offsets, uint64_t *values, bool u128) {
+    if (!ws) return MM_ERR_NULL;
+    if (len == 0 || len > (u128 ? 64u : 32u)) return MM_ERR_VALUE_LEN;
+    if (n_reads == 0) return MM_OK;
+    if (!offsets) return MM_ERR_NULL;
+    if (n_reads >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
+    for (uint64_t r = 0; r < n_reads; ++r) {
+        if (read_starts && read_starts[r] > read_starts[r + 1]) return MM_ERR_UNSORTED;
+        if (offsets[r] > offsets[r + 1]) return MM_ERR_UNSORTED;
+    }
+    const uint64_t n_pos = offsets[n_reads];
+    if (n_pos == 0) return MM_OK;
+    if (!packed || !pos || !values) return MM_ERR_NULL;
+    if (packed_bytes >= (1ull << 60)) return MM_ERR_LEN_TOO_LARGE;
+    if (base_offset > 4 * packed_bytes) return MM_ERR_CAPACITY;
+    if (read_starts && read_starts[n_reads] > 4 * packed_bytes - base_offset) return MM_ERR_CAPACITY;
+    if (!read_starts && (n_reads - 1) * (uint64_t)read_stride > 4 * packed_bytes - base_offset) return MM_ERR_CAPACITY;
+    MM_HIP(set_device(ws->device));
+    // staging: [packed bytes | starts | offsets] in d_in, positions in d_out, values in d_vals
+    const uint64_t words = n_reads + 1, per = u128 ? 2 : 1;
+    const uint64_t starts_at = (packed_bytes + 15) & ~15ull;
+    const uint64_t offsets_at = starts_at + (read_starts ? words * sizeof(uint64_t) : 0);
+    uint8_t *din = reinterpret_cast<uint8_t *>(ws->d_in);
+    int r = grow(din, ws->d_in_bytes, offsets_at + words * sizeof(uint64_t), 1);
+    ws->d_in = din;
+    if (r) return r;
+    r = grow(ws->d_out, ws->d_out_elems, n_pos, sizeof(uint32_t));
+    if (r) return r;
+    r = grow(ws->d_vals, ws->d_vals_elems, per * n_pos, sizeof(unsigned long long));
+    if (r) return r;
+    MM_HIP(hipMemcpyAsync(din, packed, packed_bytes, hipMemcpyHostToDevice, ws->stream));
+    if (read_starts)
+        MM_HIP(hipMemcpyAsync(din + starts_at, read_starts, words * sizeof(uint64_t), hipMemcpyHostToDevice, ws->stream));
+    MM_HIP(hipMemcpyAsync(din + offsets_at, offsets, words * sizeof(uint64_t), hipMemcpyHostToDevice, ws->stream));
+    MM_HIP(hipMemcpyAsync(ws->d_out, pos, n_pos * sizeof(uint32_t), hipMemcpyHostToDevice, ws->stream));
+    r = values_reads_async_impl(ws, din, packed_bytes, base_offset, n_reads,
+                                read_starts ? reinterpret_cast<const uint64_t *>(din + starts_at) : nullptr, read_stride, len,
+                                canonical, ws->d_out, reinterpret_cast<const uint64_t *>(din + offsets_at), n_pos,
+                                reinterpret_cast<uint64_t *>(ws->d_vals), u128);
+    if (r) return r;
+    MM_HIP(hipMemcpyAsync(values, ws->d_vals, per * n_pos * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
+    MM_HIP(hipStreamSynchronize(ws->stream));
+    return MM_OK;
+}
+
+int mm_values_u64_reads_host(mm_workspace_t *ws, const uint8_t *packed, uint64_t packed_bytes, uint64_t base_offset,
+                             uint64_t n_reads, const uint64_t *read_starts, uint32_t read_stride, uint32_t len, int canonical,
+                             const uint32_t *pos, const uint64_t *offsets, uint64_t *values) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    return values_reads_host_impl(ws, packed, packed_bytes, base_offset, n_reads, read_starts, read_stride, len, canonical,
+                                  pos, offsets, values, false);
+}
+
+int mm_values_u128_reads_host(mm_workspace_t *ws, const uint8_t *packed, uint64_t packed_bytes, uint64_t base_offset,
+                              uint64_t n_reads, const uint64_t *read_starts, uint32_t read_stride, uint32_t len, int canonical,
+                              const uint32_t *pos, const uint64_t *offsets, uint64_t *values) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    return values_reads_host_impl(ws, packed, packed_bytes, base_offset, n_reads, read_starts, read_stride, len, canonical,
+                                  pos, offsets, values, true);
+}
+
+// The kernel's read lookup on the host (no device): out_read[j] = the read of value idx[j], the largest r in
+// [0, n_reads] with offsets[r] <= idx[j] (-1 if there is none) = searchsorted(offsets, idx[j], 'right') - 1.
+int mm_debug_values_read_of(const uint64_t *offsets, uint64_t n_reads, const uint64_t *idx, uint64_t n, int64_t *out_read) {
+    if (!offsets || (n && (!idx || !out_read))) return MM_ERR_NULL;
+    for (uint64_t j = 0; j < n; ++j)
+        out_read[j] = idx[j] < offsets[0] ? -1 : (int64_t)mm::values_read_of(offsets, (uint64_t)0, n_reads, idx[j]);
+    return MM_OK;
+}
+
+uint32_t mm_values_reads_lds_stage(void) { return mm::kValuesReadsStage; }
 
 int mm_pack_ascii_device_async(mm_workspace_t *ws, const uint8_t *d_ascii, uint64_t n_bases,
                                uint8_t *d_packed) {

@@ -3,6 +3,7 @@
 // (PackedSeqVec::from_ascii, call site src/lib.rs:110) and the synthetic input generator.
 #include "mm_common.h"
 #include "mm_launch.h"
+#include "mm_values.h"  // value_of, value128_of
 
 namespace mm {
 
@@ -17,20 +18,6 @@ namespace mm {
 // window order, so the 256 positions of a wave fall into a few hundred bytes of sequence: the sequence loads hit the
 // same two or three lines.
 constexpr int kValuesPerThread = 4;
-
-__device__ __forceinline__ unsigned long long value_of(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t sh, uint32_t len,
-                                                       int canonical, unsigned long long mask) {
-    const uint32_t lo = __builtin_amdgcn_alignbit(w1, w0, sh), hi = __builtin_amdgcn_alignbit(w2, w1, sh);
-    unsigned long long v = (((unsigned long long)hi << 32) | lo) & mask;
-    if (canonical) {
-        unsigned long long r = __brevll(v);  // reverses bit order: pairs reversed and bit-swapped
-        r = ((r & 0xAAAAAAAAAAAAAAAAull) >> 1) | ((r & 0x5555555555555555ull) << 1);
-        r >>= (64u - 2u * len);
-        r ^= 0xAAAAAAAAAAAAAAAAull & mask;  // complement: code ^ 2
-        v = r < v ? r : v;
-    }
-    return v;
-}
 
 __global__ __launch_bounds__(kBlockThreads) void values_u64_kernel(SeqView seq, uint32_t len,
                                                                    int canonical,
@@ -100,35 +87,8 @@ __global__ __launch_bounds__(kBlockThreads) void values_u128_kernel(SeqView seq,
     unsigned long long w[5];
 #pragma unroll
     for (int t = 0; t < 5; ++t) w[t] = load_dword_clamped(seq, q + t);
-    unsigned long long a = w[0] | (w[1] << 32), b = w[2] | (w[3] << 32);
-    unsigned long long lo = sh ? (a >> sh) | (b << (64u - sh)) : a;
-    unsigned long long hi = sh ? (b >> sh) | (w[4] << (64u - sh)) : b;
-    const uint32_t bits = 2u * len;  // 2 .. 128
-    if (bits <= 64) {
-        hi = 0;
-        if (bits < 64) lo &= (1ull << bits) - 1ull;
-    } else if (bits < 128) {
-        hi &= (1ull << (bits - 64u)) - 1ull;
-    }
-    if (canonical) {
-        // reverse the 2-bit groups of the 128-bit value, align to bit 0, complement (code ^ 2)
-        auto revpairs = [](unsigned long long x) {
-            x = __brevll(x);
-            return ((x & 0xAAAAAAAAAAAAAAAAull) >> 1) | ((x & 0x5555555555555555ull) << 1);
-        };
-        unsigned long long rhi = revpairs(lo), rlo = revpairs(hi);  // 128-bit reversal
-        const uint32_t s = 128u - bits;                              // shift right by s (0 .. 126)
-        unsigned long long clo, chi;
-        if (s == 0) { clo = rlo; chi = rhi; }
-        else if (s < 64) { clo = (rlo >> s) | (rhi << (64u - s)); chi = rhi >> s; }
-        else if (s == 64) { clo = rhi; chi = 0; }
-        else { clo = rhi >> (s - 64u); chi = 0; }
-        unsigned long long mlo = bits >= 64 ? ~0ull : (1ull << bits) - 1ull;
-        unsigned long long mhi = bits <= 64 ? 0ull : (bits >= 128 ? ~0ull : (1ull << (bits - 64u)) - 1ull);
-        clo ^= 0xAAAAAAAAAAAAAAAAull & mlo;
-        chi ^= 0xAAAAAAAAAAAAAAAAull & mhi;
-        if (chi < hi || (chi == hi && clo < lo)) { lo = clo; hi = chi; }
-    }
+    unsigned long long lo, hi;
+    value128_of(w, sh, len, canonical, lo, hi);
     out[2 * i] = lo;
     out[2 * i + 1] = hi;
 }

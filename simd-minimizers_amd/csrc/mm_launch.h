@@ -211,6 +211,28 @@ int launch_values_u64(SeqView seq, uint32_t len, int canonical, const uint32_t *
                       uint64_t n_pos, unsigned long long *d_values, hipStream_t stream);
 int launch_values_u128(SeqView seq, uint32_t len, int canonical, const uint32_t *d_pos,
                        uint64_t n_pos, unsigned long long *d_values, hipStream_t stream);
+// ---- values of every read's positions in one launch (mm_values_reads.hip)
+// The packed buffer as whole dwords plus its byte range: d = d_packed rounded down to a dword, bytes [byte_lo, byte_hi)
+// of d are the caller's, dwords [q_lo, q_hi) lie wholly inside them; base0 = base_offset + 4 * byte_lo.
+struct PackedView {
+    const uint32_t *d;
+    unsigned long long q_lo, q_hi;
+    unsigned long long byte_lo, byte_hi;
+    unsigned long long base0;
+};
+struct ValuesReadsArgs {
+    PackedView view;
+    unsigned long long n_reads;                // > 0
+    const unsigned long long *read_starts;     // [n_reads + 1], or null: read r starts at r * read_stride
+    uint32_t read_stride;
+    uint32_t len;
+    int canonical;
+    const uint32_t *pos;                       // read-local positions, back to back
+    const unsigned long long *offsets;         // [n_reads + 1]; offsets[n_reads] = the true count
+    unsigned long long n_pos_max;              // what pos / out hold: the grid's size
+    unsigned long long *out;                   // u64: one word per value; u128: {lo, hi}
+};
+int launch_values_reads(const ValuesReadsArgs &a, bool u128, hipStream_t stream);  // 0, -1 (HIP failure), -3 (grid too large)
 int launch_pack_ascii(const uint8_t *d_ascii, uint64_t n, uint8_t *d_packed, hipStream_t stream);
 int launch_pack_ascii_n(const uint8_t *d_ascii, uint64_t n, uint8_t *d_packed, uint8_t *d_amb,
                         hipStream_t stream);

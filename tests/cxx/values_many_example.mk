@@ -1,0 +1,8 @@
+# Compiles values_many_example.cpp against the in-tree library (compile/link check; run on a GPU box):
+#   make -C tests/cxx -f values_many_example.mk
+ROOT := ../..
+all: values_many_example
+values_many_example: values_many_example.cpp $(ROOT)/include/simd_minimizers_amd.hpp $(ROOT)/include/simd_minimizers_amd.h
+	g++ -std=c++17 -O2 -I$(ROOT)/include -o $@ values_many_example.cpp -L$(ROOT)/simd-minimizers_amd -lsimd_minimizers_amd -Wl,-rpath,'$$ORIGIN/../../simd-minimizers_amd' -Wl,-rpath,/opt/rocm/lib
+clean:
+	rm -f values_many_example
