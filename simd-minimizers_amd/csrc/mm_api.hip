@@ -278,6 +278,17 @@ int grow(T *&ptr, uint64_t &have, uint64_t need, size_t elem) {
     return MM_OK;
 }
 
+// The workspace's byte buffers (d_in, d_amb, d_ascii, scratch) are void *: grow() for them.
+int grow_bytes(void *&ptr, uint64_t &have, uint64_t need) {
+    uint8_t *p = static_cast<uint8_t *>(ptr);
+    const int r = grow(p, have, need, 1);
+    ptr = p;
+    return r;
+}
+
+// The first check of every DNA entry point: a text plan runs through mm_run_text_* only.
+inline int dna_plan_only(const mm_plan_t *plan) { return plan && plan->text ? MM_ERR_BAD_MODE : MM_OK; }
+
 // The tile status words.  MM_STATUS_TIGHT=1 (tests) allocates exactly what the launcher asked for, without
 // the slack of grow(), so that an under-sized request cannot hide behind it.
 int grow_status(mm_workspace *ws, uint64_t need) {
@@ -418,6 +429,58 @@ int judge_run_error(mm_workspace *ws) {
                                             : "kernel error 0x%x (bad batch table)", code);
     g_last_error = buf;
     return MM_ERR_HIP;
+}
+
+// The synchronous form of every run: `issue(&host_written)` queues one attempt; the words total[0..1] come to h_total
+// (a 16-byte copy, unless the kernel stores them into the page-locked words itself: host_written), the stream is waited
+// for and the error word judged.  A look-back spin that ran out (1: workgroups were not dispatched in index order)
+// repeats the run once, with tile ids taken from an atomic ticket, which defines the order itself.
+template <class Issue>
+int run_sync(mm_workspace_t *ws, uint64_t capacity, bool wants_positions, uint64_t *out_count, Issue issue) {
+    if (!ws) return MM_ERR_NULL;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        // (an *_async run that is still executing on this stream stores its error code into the same page-locked
+        // word: let it finish before the words are reused for THIS run, or its error would be taken for ours - the
+        // sticky word keeps it for mm_workspace_check.  ADVICE r4)
+        if (ws->async_unchecked) MM_HIP(hipStreamSynchronize(ws->stream));
+        bool host_written = false;
+        const int r = issue(&host_written);
+        if (r) return r;
+        if (!host_written)
+            MM_HIP(hipMemcpyAsync(ws->h_total, ws->total, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ws->stream));
+        MM_HIP(hipStreamSynchronize(ws->stream));
+        const int je = judge_run_error(ws);
+        if (je < 0) return je;
+        if (je == 0) break;
+    }
+    if (out_count) *out_count = ws->h_total[0];
+    if (wants_positions && ws->h_total[0] > capacity) return MM_ERR_CAPACITY;
+    return MM_OK;
+}
+
+// Staging of the host entry points' results: room in d_out / d_sk for `cap` positions (and indices), cap being what the
+// caller's buffer takes of the `bound` positions a run can give (0 when no positions are asked for) ...
+uint64_t capped(const void *out_pos, uint64_t capacity, uint64_t bound) {
+    return out_pos ? (capacity < bound ? capacity : bound) : 0;
+}
+int stage_outputs(mm_workspace_t *ws, uint64_t cap, bool want_sk) {
+    int r = grow(ws->d_out, ws->d_out_elems, cap ? cap : 1, sizeof(uint32_t));
+    if (r == MM_OK && want_sk) r = grow(ws->d_sk, ws->d_sk_elems, cap ? cap : 1, sizeof(uint32_t));
+    return r;
+}
+
+// ... and their way back: `n_offsets` offsets from d_vals (batches), `count` positions (and indices) if they were asked
+// for, and one wait when anything was queued.
+int download_positions(mm_workspace_t *ws, uint32_t *out_pos, uint32_t *out_sk, uint64_t count,
+                       uint64_t *out_offsets = nullptr, uint64_t n_offsets = 0) {
+    if (out_offsets)
+        MM_HIP(hipMemcpyAsync(out_offsets, ws->d_vals, n_offsets * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
+    if (out_pos && count) {
+        MM_HIP(hipMemcpyAsync(out_pos, ws->d_out, count * sizeof(uint32_t), hipMemcpyDeviceToHost, ws->stream));
+        if (out_sk) MM_HIP(hipMemcpyAsync(out_sk, ws->d_sk, count * sizeof(uint32_t), hipMemcpyDeviceToHost, ws->stream));
+    }
+    if (out_offsets || (out_pos && count)) MM_HIP(hipStreamSynchronize(ws->stream));
+    return MM_OK;
 }
 
 }  // namespace
@@ -1126,10 +1189,7 @@ static int run_device_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, cons
         if (!fused) {
             const uint64_t nwin = win_end - win_begin;
             a.generic_round_windows = nwin < (1ull << 24) ? nwin : (1ull << 24);
-            uint64_t need_scratch = mm::generic_scratch_bytes(a.generic_round_windows, plan->w);
-            uint8_t *sp = reinterpret_cast<uint8_t *>(ws->scratch);
-            r = grow(sp, ws->scratch_bytes, need_scratch, 1);
-            ws->scratch = sp;
+            r = grow_bytes(ws->scratch, ws->scratch_bytes, mm::generic_scratch_bytes(a.generic_round_windows, plan->w));
             if (r) return r;
             a.scratch = ws->scratch;
             r = grow_status(ws, mm::generic_status_words(a.generic_round_windows));
@@ -1160,7 +1220,7 @@ int mm_run_device_async(const mm_plan_t *plan, mm_workspace_t *ws, const void *d
                         uint64_t win_begin, uint64_t win_end, uint32_t *d_out_pos,
                         uint32_t *d_out_sk, uint64_t capacity, uint64_t *d_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
-    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
+    if (const int bad = dna_plan_only(plan)) return bad;
     if (ws) ws->async_unchecked = true;
     return run_device_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_bases, win_begin,
                                  win_end, d_out_pos, d_out_sk, capacity, d_count, false);
@@ -1528,7 +1588,7 @@ int mm_run_batch_device(const mm_plan_t *plan, mm_workspace_t *ws, uint64_t n_se
                         uint32_t *d_out_pos, uint32_t *d_out_sk, uint64_t capacity,
                         uint64_t *out_offsets) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
-    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
+    if (const int bad = dna_plan_only(plan)) return bad;
     if (!plan || !ws || !out_offsets) return MM_ERR_NULL;
     if (n_seqs && (!d_packed || !packed_bytes || !n_bases)) return MM_ERR_NULL;
     MM_HIP(set_device(ws->device));
@@ -1745,6 +1805,19 @@ static int run_reads_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, const
     return MM_OK;
 }
 
+static int run_reads_sync(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
+                          uint64_t packed_bytes, uint64_t base_offset, uint64_t n_reads,
+                          uint32_t read_stride, uint32_t read_len, const uint32_t *d_read_lens,
+                          uint32_t *d_out_pos, uint64_t capacity, uint64_t *d_out_offsets,
+                          uint64_t *out_count, const AmbArgs *amb, uint32_t *d_out_sk = nullptr,
+                          const uint64_t *d_read_starts = nullptr, uint64_t total_bases = 0) {
+    return run_sync(ws, capacity, d_out_pos != nullptr, out_count, [&](bool *) {
+        return run_reads_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_reads, read_stride, read_len,
+                                    d_read_lens, d_out_pos, capacity, d_out_offsets, nullptr, amb, d_out_sk,
+                                    d_read_starts, total_bases);
+    });
+}
+
 // Reads packed back to back (the FASTQ / FASTA packers' layout): read r = bases [d_read_starts[r], d_read_starts[r + 1]).
 int mm_run_packed_reads_device_async(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
                                      uint64_t packed_bytes, uint64_t base_offset, uint64_t n_reads,
@@ -1752,7 +1825,7 @@ int mm_run_packed_reads_device_async(const mm_plan_t *plan, mm_workspace_t *ws, 
                                      uint32_t *d_out_pos, uint32_t *d_out_sk, uint64_t capacity, uint64_t *d_out_offsets,
                                      uint64_t *d_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
-    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
+    if (const int bad = dna_plan_only(plan)) return bad;
     if (!d_read_starts && n_reads) return MM_ERR_NULL;
     if (ws) ws->async_unchecked = true;
     return run_reads_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_reads, 0, max_read_len, nullptr, d_out_pos,
@@ -1764,27 +1837,16 @@ int mm_run_packed_reads_device(const mm_plan_t *plan, mm_workspace_t *ws, const 
                                uint32_t max_read_len, uint32_t *d_out_pos, uint32_t *d_out_sk, uint64_t capacity,
                                uint64_t *d_out_offsets, uint64_t *out_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
-    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
+    if (const int bad = dna_plan_only(plan)) return bad;
     if (!ws || (!d_read_starts && n_reads)) return MM_ERR_NULL;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        int r = run_reads_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_reads, 0, max_read_len, nullptr,
-                                     d_out_pos, capacity, d_out_offsets, nullptr, nullptr, d_out_sk, d_read_starts, total_bases);
-        if (r) return r;
-        MM_HIP(hipMemcpyAsync(ws->h_total, ws->total, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ws->stream));
-        MM_HIP(hipStreamSynchronize(ws->stream));
-        const int je = judge_run_error(ws);
-        if (je < 0) return je;
-        if (je == 0) break;  // (1: redo the batch in ticket mode)
-    }
-    if (out_count) *out_count = ws->h_total[0];
-    if (d_out_pos && ws->h_total[0] > capacity) return MM_ERR_CAPACITY;
-    return MM_OK;
+    return run_reads_sync(plan, ws, d_packed, packed_bytes, base_offset, n_reads, 0, max_read_len, nullptr, d_out_pos, capacity,
+                          d_out_offsets, out_count, nullptr, d_out_sk, d_read_starts, total_bases);
 }
 
 // Builder::run_skip_ambiguous_windows (src/lib.rs:451-496) per record of a back-to-back buffer: what the *_pack_n packers
 // write goes straight in.  The refusals that need no device come first, the workspace last.
 static int packed_reads_skip_check(const mm_plan_t *plan, const void *d_amb, uint64_t n_reads, const uint64_t *d_read_starts) {
-    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
+    if (const int bad = dna_plan_only(plan)) return bad;
     if (plan && !plan->canonical_windows) return MM_ERR_HASHER_NOT_CANONICAL;
     if (n_reads && (!d_read_starts || !d_amb)) return MM_ERR_NULL;
     return MM_OK;
@@ -1814,21 +1876,9 @@ int mm_run_packed_reads_skip_ambiguous_device(const mm_plan_t *plan, mm_workspac
     ApiScope api_scope;  // (restores the calling thread's current device on return)
     const int c = packed_reads_skip_check(plan, d_amb, n_reads, d_read_starts);
     if (c) return c;
-    if (!ws) return MM_ERR_NULL;
     const AmbArgs amb{d_amb, amb_bytes, amb_offset};
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        int r = run_reads_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_reads, 0, max_read_len, nullptr,
-                                     d_out_pos, capacity, d_out_offsets, nullptr, &amb, nullptr, d_read_starts, total_bases);
-        if (r) return r;
-        MM_HIP(hipMemcpyAsync(ws->h_total, ws->total, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ws->stream));
-        MM_HIP(hipStreamSynchronize(ws->stream));
-        const int je = judge_run_error(ws);
-        if (je < 0) return je;
-        if (je == 0) break;  // (1: redo the batch in ticket mode)
-    }
-    if (out_count) *out_count = ws->h_total[0];
-    if (d_out_pos && ws->h_total[0] > capacity) return MM_ERR_CAPACITY;
-    return MM_OK;
+    return run_reads_sync(plan, ws, d_packed, packed_bytes, base_offset, n_reads, 0, max_read_len, nullptr, d_out_pos, capacity,
+                          d_out_offsets, out_count, &amb, nullptr, d_read_starts, total_bases);
 }
 
 int mm_run_reads_device_async(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
@@ -1837,33 +1887,10 @@ int mm_run_reads_device_async(const mm_plan_t *plan, mm_workspace_t *ws, const v
                               uint32_t *d_out_pos, uint64_t capacity, uint64_t *d_out_offsets,
                               uint64_t *d_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
-    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
+    if (const int bad = dna_plan_only(plan)) return bad;
     if (ws) ws->async_unchecked = true;
     return run_reads_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_reads, read_stride,
                                 read_len, d_read_lens, d_out_pos, capacity, d_out_offsets, d_count);
-}
-
-static int run_reads_sync(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
-                          uint64_t packed_bytes, uint64_t base_offset, uint64_t n_reads,
-                          uint32_t read_stride, uint32_t read_len, const uint32_t *d_read_lens,
-                          uint32_t *d_out_pos, uint64_t capacity, uint64_t *d_out_offsets,
-                          uint64_t *out_count, const AmbArgs *amb, uint32_t *d_out_sk = nullptr) {
-    if (!ws) return MM_ERR_NULL;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        int r = run_reads_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_reads, read_stride,
-                                     read_len, d_read_lens, d_out_pos, capacity, d_out_offsets, nullptr, amb,
-                                     d_out_sk);
-        if (r) return r;
-        MM_HIP(hipMemcpyAsync(ws->h_total, ws->total, 2 * sizeof(unsigned long long),
-                              hipMemcpyDeviceToHost, ws->stream));
-        MM_HIP(hipStreamSynchronize(ws->stream));
-        const int je = judge_run_error(ws);
-        if (je < 0) return je;
-        if (je == 0) break;  // (1: redo the batch in ticket mode)
-    }
-    if (out_count) *out_count = ws->h_total[0];
-    if (d_out_pos && ws->h_total[0] > capacity) return MM_ERR_CAPACITY;
-    return MM_OK;
 }
 
 int mm_run_reads_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
@@ -1872,7 +1899,7 @@ int mm_run_reads_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d
                         uint32_t *d_out_pos, uint64_t capacity, uint64_t *d_out_offsets,
                         uint64_t *out_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
-    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
+    if (const int bad = dna_plan_only(plan)) return bad;
     return run_reads_sync(plan, ws, d_packed, packed_bytes, base_offset, n_reads, read_stride, read_len,
                           d_read_lens, d_out_pos, capacity, d_out_offsets, out_count, nullptr);
 }
@@ -1883,7 +1910,7 @@ int mm_run_reads_superkmers_device_async(const mm_plan_t *plan, mm_workspace_t *
                                          uint32_t *d_out_pos, uint32_t *d_out_sk, uint64_t capacity,
                                          uint64_t *d_out_offsets, uint64_t *d_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
-    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
+    if (const int bad = dna_plan_only(plan)) return bad;
     if (ws) ws->async_unchecked = true;
     if (!d_out_sk) return MM_ERR_NULL;
     return run_reads_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_reads, read_stride,
@@ -1897,7 +1924,7 @@ int mm_run_reads_superkmers_device(const mm_plan_t *plan, mm_workspace_t *ws, co
                                    uint32_t *d_out_pos, uint32_t *d_out_sk, uint64_t capacity,
                                    uint64_t *d_out_offsets, uint64_t *out_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
-    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
+    if (const int bad = dna_plan_only(plan)) return bad;
     if (!d_out_sk) return MM_ERR_NULL;
     return run_reads_sync(plan, ws, d_packed, packed_bytes, base_offset, n_reads, read_stride, read_len,
                           d_read_lens, d_out_pos, capacity, d_out_offsets, out_count, nullptr, d_out_sk);
@@ -1911,7 +1938,7 @@ int mm_run_reads_skip_ambiguous_device_async(const mm_plan_t *plan, mm_workspace
                                              uint32_t *d_out_pos, uint64_t capacity,
                                              uint64_t *d_out_offsets, uint64_t *d_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
-    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
+    if (const int bad = dna_plan_only(plan)) return bad;
     if (ws) ws->async_unchecked = true;
     const AmbArgs amb{d_amb, amb_bytes, amb_offset};
     return run_reads_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_reads, read_stride,
@@ -1925,7 +1952,7 @@ int mm_run_reads_skip_ambiguous_device(const mm_plan_t *plan, mm_workspace_t *ws
                                        const uint32_t *d_read_lens, uint32_t *d_out_pos,
                                        uint64_t capacity, uint64_t *d_out_offsets, uint64_t *out_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
-    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
+    if (const int bad = dna_plan_only(plan)) return bad;
     const AmbArgs amb{d_amb, amb_bytes, amb_offset};
     return run_reads_sync(plan, ws, d_packed, packed_bytes, base_offset, n_reads, read_stride, read_len,
                           d_read_lens, d_out_pos, capacity, d_out_offsets, out_count, &amb);
@@ -1938,7 +1965,7 @@ int mm_run_skip_ambiguous_device_async(const mm_plan_t *plan, mm_workspace_t *ws
                                        uint64_t win_begin, uint64_t win_end, uint32_t *d_out_pos,
                                        uint64_t capacity, uint64_t *d_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
-    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
+    if (const int bad = dna_plan_only(plan)) return bad;
     if (ws) ws->async_unchecked = true;
     const AmbArgs amb{d_amb, amb_bytes, amb_offset};
     return run_device_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_bases, win_begin,
@@ -1949,38 +1976,19 @@ static int run_device_sync(const mm_plan_t *plan, mm_workspace_t *ws, const void
                            uint64_t packed_bytes, uint64_t base_offset, uint64_t n_bases,
                            uint64_t win_begin, uint64_t win_end, uint32_t *d_out_pos, uint32_t *d_out_sk,
                            uint64_t capacity, uint64_t *out_count, const AmbArgs *amb) {
-    if (!ws) return MM_ERR_NULL;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        // One stream operation per call when the fused kernel runs: its last tile stores the total straight into the
-        // page-locked word h_total[0] and a tile that raises an error stores the code into h_total[1] (flag_error),
-        // so the host only waits for the stream.  (Rounds 1-3: two clears, the kernel, a copy - about 33 us a call.)
-        bool host_written = false;
-        // (an *_async run that is still executing on this stream stores its error code into the same page-locked
-        // word: let it finish before the word is cleared for THIS run, or its error would be taken for ours - the
-        // sticky word keeps it for mm_workspace_check.  ADVICE r4)
-        if (ws->async_unchecked) MM_HIP(hipStreamSynchronize(ws->stream));
+    // One stream operation per call when the fused kernel runs: its last tile stores the total straight into the
+    // page-locked word h_total[0] and a tile that raises an error stores the code into h_total[1] (flag_error),
+    // so the host only waits for the stream.  (Rounds 1-3: two clears, the kernel, a copy - about 33 us a call.)
+    // The split path, the generic family and empty runs leave host_written false: the device words, cleared by the
+    // run itself, are copied.
+    return run_sync(ws, capacity, d_out_pos != nullptr, out_count, [&](bool *host_written) -> int {
         ws->h_total[0] = 0;
         ws->h_total[1] = 0;
-        // (no mapped host words on this runtime: the device's error word is read back below, so clear it first)
+        // (no mapped host words on this runtime: the device's error word is read back, so clear it first)
         if (!ws->h_total_dev) MM_HIP(hipMemsetAsync(ws->total + 1, 0, sizeof(unsigned long long), ws->stream));
-        int r = run_device_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_bases, win_begin,
-                                      win_end, d_out_pos, d_out_sk, capacity, nullptr, false, amb, &host_written);
-        if (r) return r;
-        if (!host_written) {
-            // (split path, generic family, empty run: the device words, cleared by the run itself)
-            MM_HIP(hipMemcpyAsync(ws->h_total, ws->total, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                                  ws->stream));
-        }
-        MM_HIP(hipStreamSynchronize(ws->stream));
-        // (1: a look-back spin ran out - workgroups were not dispatched in index order.  Redo the run
-        // with tile ids taken from an atomic ticket, which defines the order itself.)
-        const int je = judge_run_error(ws);
-        if (je < 0) return je;
-        if (je == 0) break;
-    }
-    if (out_count) *out_count = ws->h_total[0];
-    if (d_out_pos && ws->h_total[0] > capacity) return MM_ERR_CAPACITY;
-    return MM_OK;
+        return run_device_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_bases, win_begin, win_end,
+                                     d_out_pos, d_out_sk, capacity, nullptr, false, amb, host_written);
+    });
 }
 
 int mm_run_skip_ambiguous_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
@@ -1989,7 +1997,7 @@ int mm_run_skip_ambiguous_device(const mm_plan_t *plan, mm_workspace_t *ws, cons
                                  uint64_t win_begin, uint64_t win_end, uint32_t *d_out_pos,
                                  uint64_t capacity, uint64_t *out_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
-    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
+    if (const int bad = dna_plan_only(plan)) return bad;
     const AmbArgs amb{d_amb, amb_bytes, amb_offset};
     return run_device_sync(plan, ws, d_packed, packed_bytes, base_offset, n_bases, win_begin, win_end,
                            d_out_pos, nullptr, capacity, out_count, &amb);
@@ -2000,7 +2008,7 @@ int mm_run_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packe
                   uint64_t win_begin, uint64_t win_end, uint32_t *d_out_pos, uint32_t *d_out_sk,
                   uint64_t capacity, uint64_t *out_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
-    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
+    if (const int bad = dna_plan_only(plan)) return bad;
     return run_device_sync(plan, ws, d_packed, packed_bytes, base_offset, n_bases, win_begin, win_end,
                            d_out_pos, d_out_sk, capacity, out_count, nullptr);
 }
@@ -2011,28 +2019,15 @@ static int run_host_common(const mm_plan_t *plan, mm_workspace_t *ws, const void
                            uint64_t *out_count, const AmbArgs *amb = nullptr) {
     const uint64_t l = (uint64_t)plan->k + plan->w - 1;
     const uint64_t n_w = n_bases >= l ? n_bases - l + 1 : 0;
-    uint64_t cap = out_pos ? (capacity < n_w ? capacity : n_w) : 0;
-    int r = grow(ws->d_out, ws->d_out_elems, cap ? cap : 1, sizeof(uint32_t));
+    const uint64_t cap = capped(out_pos, capacity, n_w);
+    int r = stage_outputs(ws, cap, out_sk != nullptr);
     if (r) return r;
-    if (out_sk) {
-        r = grow(ws->d_sk, ws->d_sk_elems, cap ? cap : 1, sizeof(uint32_t));
-        if (r) return r;
-    }
     uint64_t count = 0;
     r = run_device_sync(plan, ws, d_packed, packed_bytes, base_offset, n_bases, 0, UINT64_MAX,
                         cap ? ws->d_out : nullptr, (out_sk && cap) ? ws->d_sk : nullptr, cap, &count, amb);
     if (out_count) *out_count = count;
-    if (r == MM_ERR_CAPACITY) return r;
     if (r) return r;
-    if (out_pos && count) {
-        MM_HIP(hipMemcpyAsync(out_pos, ws->d_out, count * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                              ws->stream));
-        if (out_sk)
-            MM_HIP(hipMemcpyAsync(out_sk, ws->d_sk, count * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                                  ws->stream));
-        MM_HIP(hipStreamSynchronize(ws->stream));
-    }
-    return MM_OK;
+    return download_positions(ws, out_pos, out_sk, count);
 }
 
 // Host entry point for long sequences, pipelined: the window range is cut into chunks; while chunk c is computed,
@@ -2386,7 +2381,7 @@ int mm_run_host(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *packed
                 uint64_t base_offset, uint64_t n_bases, uint32_t *out_pos, uint32_t *out_sk,
                 uint64_t capacity, uint64_t *out_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
-    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
+    if (const int bad = dna_plan_only(plan)) return bad;
     if (!plan || !ws) return MM_ERR_NULL;
     if (n_bases >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
     if (out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;
@@ -2397,9 +2392,7 @@ int mm_run_host(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *packed
         const int rs = run_host_small(plan, ws, packed, base_offset, n_bases, out_pos, out_sk, capacity, out_count);
         if (rs != MM_SMALL_NOT_TAKEN) return rs;
     }
-    uint8_t *din = reinterpret_cast<uint8_t *>(ws->d_in);
-    int r = grow(din, ws->d_in_bytes, bytes + 16, 1);
-    ws->d_in = din;
+    int r = grow_bytes(ws->d_in, ws->d_in_bytes, bytes + 16);
     if (r) return r;
     if (bytes) {
         if (!packed) return MM_ERR_NULL;
@@ -2411,62 +2404,11 @@ int mm_run_host(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *packed
                            capacity, out_count);
 }
 
-// Many short sequences from HOST memory in one call (round 4): what a caller that looped Builder::run over its reads
-// (src/lib.rs:378; 2-20 ns per base on the reference's CPU, about 28 us per CALL here) does instead - the reads packed
-// back to back, their starts, one upload, ONE launch of the reads-mode kernel, one download.
-int mm_run_packed_reads_host(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *packed, uint64_t n_reads,
-                             const uint64_t *read_starts, uint32_t max_read_len, uint32_t *out_pos, uint32_t *out_sk,
-                             uint64_t capacity, uint64_t *out_offsets, uint64_t *out_count) {
-    ApiScope api_scope;  // (restores the calling thread's current device on return)
-    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
-    if (!plan || !ws || !out_offsets) return MM_ERR_NULL;
-    if (n_reads && (!read_starts || !packed)) return MM_ERR_NULL;
-    if (out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;
-    if (out_count) *out_count = 0;
-    MM_HIP(set_device(ws->device));
-    const uint64_t total_bases = n_reads ? read_starts[n_reads] : 0;
-    for (uint64_t r = 0; r < n_reads; ++r)
-        if (read_starts[r] > read_starts[r + 1]) return MM_ERR_CAPACITY;  // (starts must not decrease)
-    if (total_bases >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
-    const uint64_t bytes = (total_bases + 3) / 4;
-    // staging: [packed bytes + slack | starts] in d_in, positions (and indices) in d_out / d_sk, offsets in d_vals
-    const uint64_t starts_at = (bytes + 64 + 15) & ~15ull;
-    uint8_t *din = reinterpret_cast<uint8_t *>(ws->d_in);
-    int r = grow(din, ws->d_in_bytes, starts_at + (n_reads + 1) * sizeof(uint64_t), 1);
-    ws->d_in = din;
-    if (r) return r;
-    uint64_t cap = out_pos ? (capacity < total_bases ? capacity : total_bases) : 0;
-    r = grow(ws->d_out, ws->d_out_elems, cap ? cap : 1, sizeof(uint32_t));
-    if (r == MM_OK && out_sk) r = grow(ws->d_sk, ws->d_sk_elems, cap ? cap : 1, sizeof(uint32_t));
-    if (r == MM_OK) r = grow(ws->d_vals, ws->d_vals_elems, n_reads + 1, sizeof(unsigned long long));
-    if (r) return r;
-    if (bytes) MM_HIP(hipMemcpyAsync(din, packed, bytes, hipMemcpyHostToDevice, ws->stream));
-    MM_HIP(hipMemsetAsync(din + bytes, 0, starts_at - bytes, ws->stream));
-    if (n_reads) MM_HIP(hipMemcpyAsync(din + starts_at, read_starts, (n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ws->stream));
-    uint64_t count = 0;
-    r = mm_run_packed_reads_device(plan, ws, din, starts_at, 0, n_reads, reinterpret_cast<const uint64_t *>(din + starts_at),
-                                   total_bases, max_read_len, cap ? ws->d_out : nullptr, (out_sk && cap) ? ws->d_sk : nullptr, cap,
-                                   reinterpret_cast<uint64_t *>(ws->d_vals), &count);
-    if (out_count) *out_count = count;
-    if (r) return r;
-    MM_HIP(hipMemcpyAsync(out_offsets, ws->d_vals, (n_reads + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
-    if (out_pos && count) {
-        MM_HIP(hipMemcpyAsync(out_pos, ws->d_out, count * sizeof(uint32_t), hipMemcpyDeviceToHost, ws->stream));
-        if (out_sk) MM_HIP(hipMemcpyAsync(out_sk, ws->d_sk, count * sizeof(uint32_t), hipMemcpyDeviceToHost, ws->stream));
-    }
-    MM_HIP(hipStreamSynchronize(ws->stream));
-    return MM_OK;
-}
-
-// The same with ambiguity bits (PackedNSeq reads from host memory): packed bytes and starts in d_in, the bits in d_amb.
-int mm_run_packed_reads_skip_ambiguous_host(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *packed,
-                                            const uint8_t *amb, uint64_t n_reads, const uint64_t *read_starts,
-                                            uint32_t max_read_len, uint32_t *out_pos, uint64_t capacity,
-                                            uint64_t *out_offsets, uint64_t *out_count) {
-    ApiScope api_scope;  // (restores the calling thread's current device on return)
-    const int c = packed_reads_skip_check(plan, amb, n_reads, read_starts);
-    if (c) return c;
-    if (!plan || !ws || !out_offsets || (n_reads && !packed)) return MM_ERR_NULL;
+// The staging of both packed-reads host entry points, behind their own argument checks: [packed bytes + slack | starts] in
+// d_in, the ambiguity bits (amb != null: PackedNSeq reads) in d_amb, positions (and indices) in d_out / d_sk, offsets in d_vals.
+static int packed_reads_host_impl(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *packed, const uint8_t *amb,
+                                  uint64_t n_reads, const uint64_t *read_starts, uint32_t max_read_len, uint32_t *out_pos,
+                                  uint32_t *out_sk, uint64_t capacity, uint64_t *out_offsets, uint64_t *out_count) {
     if (out_count) *out_count = 0;
     MM_HIP(set_device(ws->device));
     const uint64_t total_bases = n_reads ? read_starts[n_reads] : 0;
@@ -2475,60 +2417,100 @@ int mm_run_packed_reads_skip_ambiguous_host(const mm_plan_t *plan, mm_workspace_
     if (total_bases >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
     const uint64_t bytes = (total_bases + 3) / 4, abytes = (total_bases + 7) / 8;
     const uint64_t starts_at = (bytes + 64 + 15) & ~15ull;
-    uint8_t *din = reinterpret_cast<uint8_t *>(ws->d_in);
-    int r = grow(din, ws->d_in_bytes, starts_at + (n_reads + 1) * sizeof(uint64_t), 1);
-    ws->d_in = din;
+    int r = grow_bytes(ws->d_in, ws->d_in_bytes, starts_at + (n_reads + 1) * sizeof(uint64_t));
+    if (r == MM_OK && amb) r = grow_bytes(ws->d_amb, ws->d_amb_bytes, abytes + 16);
     if (r) return r;
-    uint8_t *damb = reinterpret_cast<uint8_t *>(ws->d_amb);
-    r = grow(damb, ws->d_amb_bytes, abytes + 16, 1);
-    ws->d_amb = damb;
-    if (r) return r;
-    uint64_t cap = out_pos ? (capacity < total_bases ? capacity : total_bases) : 0;
-    r = grow(ws->d_out, ws->d_out_elems, cap ? cap : 1, sizeof(uint32_t));
+    const uint64_t cap = capped(out_pos, capacity, total_bases);
+    r = stage_outputs(ws, cap, out_sk != nullptr);
     if (r == MM_OK) r = grow(ws->d_vals, ws->d_vals_elems, n_reads + 1, sizeof(unsigned long long));
     if (r) return r;
+    uint8_t *const din = static_cast<uint8_t *>(ws->d_in), *const damb = static_cast<uint8_t *>(ws->d_amb);
     if (bytes) MM_HIP(hipMemcpyAsync(din, packed, bytes, hipMemcpyHostToDevice, ws->stream));
     MM_HIP(hipMemsetAsync(din + bytes, 0, starts_at - bytes, ws->stream));
-    if (abytes) MM_HIP(hipMemcpyAsync(damb, amb, abytes, hipMemcpyHostToDevice, ws->stream));
-    MM_HIP(hipMemsetAsync(damb + abytes, 0, 16, ws->stream));
+    if (amb) {
+        if (abytes) MM_HIP(hipMemcpyAsync(damb, amb, abytes, hipMemcpyHostToDevice, ws->stream));
+        MM_HIP(hipMemsetAsync(damb + abytes, 0, 16, ws->stream));
+    }
     if (n_reads) MM_HIP(hipMemcpyAsync(din + starts_at, read_starts, (n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ws->stream));
+    const AmbArgs a{damb, abytes + 16, 0};
     uint64_t count = 0;
-    r = mm_run_packed_reads_skip_ambiguous_device(plan, ws, din, starts_at, 0, damb, abytes + 16, 0, n_reads,
-                                                  reinterpret_cast<const uint64_t *>(din + starts_at), total_bases, max_read_len,
-                                                  cap ? ws->d_out : nullptr, cap, reinterpret_cast<uint64_t *>(ws->d_vals), &count);
+    r = run_reads_sync(plan, ws, din, starts_at, 0, n_reads, 0, max_read_len, nullptr, cap ? ws->d_out : nullptr, cap,
+                       reinterpret_cast<uint64_t *>(ws->d_vals), &count, amb ? &a : nullptr, (out_sk && cap) ? ws->d_sk : nullptr,
+                       reinterpret_cast<const uint64_t *>(din + starts_at), total_bases);
     if (out_count) *out_count = count;
     if (r) return r;
-    MM_HIP(hipMemcpyAsync(out_offsets, ws->d_vals, (n_reads + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
-    if (out_pos && count) MM_HIP(hipMemcpyAsync(out_pos, ws->d_out, count * sizeof(uint32_t), hipMemcpyDeviceToHost, ws->stream));
-    MM_HIP(hipStreamSynchronize(ws->stream));
-    return MM_OK;
+    return download_positions(ws, out_pos, out_sk, count, out_offsets, n_reads + 1);
+}
+
+// Many short sequences from HOST memory in one call (round 4): what a caller that looped Builder::run over its reads
+// (src/lib.rs:378; 2-20 ns per base on the reference's CPU, about 28 us per CALL here) does instead - the reads packed
+// back to back, their starts, one upload, ONE launch of the reads-mode kernel, one download.
+int mm_run_packed_reads_host(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *packed, uint64_t n_reads,
+                             const uint64_t *read_starts, uint32_t max_read_len, uint32_t *out_pos, uint32_t *out_sk,
+                             uint64_t capacity, uint64_t *out_offsets, uint64_t *out_count) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (const int bad = dna_plan_only(plan)) return bad;
+    if (!plan || !ws || !out_offsets) return MM_ERR_NULL;
+    if (n_reads && (!read_starts || !packed)) return MM_ERR_NULL;
+    if (out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;
+    return packed_reads_host_impl(plan, ws, packed, nullptr, n_reads, read_starts, max_read_len, out_pos, out_sk, capacity,
+                                  out_offsets, out_count);
+}
+
+// The same with ambiguity bits (PackedNSeq reads from host memory).
+int mm_run_packed_reads_skip_ambiguous_host(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *packed,
+                                            const uint8_t *amb, uint64_t n_reads, const uint64_t *read_starts,
+                                            uint32_t max_read_len, uint32_t *out_pos, uint64_t capacity,
+                                            uint64_t *out_offsets, uint64_t *out_count) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    const int c = packed_reads_skip_check(plan, amb, n_reads, read_starts);
+    if (c) return c;
+    if (!plan || !ws || !out_offsets || (n_reads && !packed)) return MM_ERR_NULL;
+    // (no reads: the bits are not looked at, like the device entry point's - but the launch still takes the skip path)
+    static const uint8_t no_bits = 0;
+    return packed_reads_host_impl(plan, ws, packed, amb ? amb : &no_bits, n_reads, read_starts, max_read_len, out_pos, nullptr,
+                                  capacity, out_offsets, out_count);
+}
+
+// The staging of the sequence host entry points other than mm_run_host, behind their own argument checks: `src` is packed
+// bytes or (ascii) one byte per base, packed on the device; `skip` runs the skip-ambiguous windows over the bits of `amb`
+// (packed source) or over the bits the ASCII packer writes.
+static int run_host_staged(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *src, bool ascii, uint64_t base_offset,
+                           bool skip, const uint8_t *amb, uint64_t amb_offset, uint64_t n_bases, uint32_t *out_pos,
+                           uint32_t *out_sk, uint64_t capacity, uint64_t *out_count) {
+    MM_HIP(set_device(ws->device));
+    const uint64_t bytes = (base_offset + n_bases + 3) / 4, abytes = (amb_offset + n_bases + 7) / 8;
+    int r = grow_bytes(ws->d_in, ws->d_in_bytes, bytes + 16);
+    if (r == MM_OK && skip) r = grow_bytes(ws->d_amb, ws->d_amb_bytes, abytes + 16);
+    if (r == MM_OK && ascii) r = grow_bytes(ws->d_ascii, ws->d_ascii_bytes, n_bases + 16);
+    if (r) return r;
+    uint8_t *const din = static_cast<uint8_t *>(ws->d_in), *const damb = static_cast<uint8_t *>(ws->d_amb);
+    if (n_bases) {
+        if (!src || (skip && !ascii && !amb)) return MM_ERR_NULL;
+        if (ascii) {
+            const uint8_t *const dasc = static_cast<const uint8_t *>(ws->d_ascii);
+            MM_HIP(hipMemcpyAsync(ws->d_ascii, src, n_bases, hipMemcpyHostToDevice, ws->stream));
+            if (skip ? mm::launch_pack_ascii_n(dasc, n_bases, din, damb, ws->stream) : mm::launch_pack_ascii(dasc, n_bases, din, ws->stream))
+                return hip_fail(hipGetLastError(), skip ? "pack_ascii_n" : "pack_ascii");
+        } else {
+            MM_HIP(hipMemcpyAsync(ws->d_in, src, bytes, hipMemcpyHostToDevice, ws->stream));
+            if (skip) MM_HIP(hipMemcpyAsync(ws->d_amb, amb, abytes, hipMemcpyHostToDevice, ws->stream));
+        }
+    }
+    const AmbArgs a{ws->d_amb, abytes + 16, amb_offset};
+    return run_host_common(plan, ws, ws->d_in, bytes + 16, base_offset, n_bases, out_pos, out_sk, capacity, out_count,
+                           skip ? &a : nullptr);
 }
 
 int mm_run_host_ascii(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *ascii,
                       uint64_t n_bases, uint32_t *out_pos, uint32_t *out_sk, uint64_t capacity,
                       uint64_t *out_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
-    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
+    if (const int bad = dna_plan_only(plan)) return bad;
     if (!plan || !ws) return MM_ERR_NULL;
     if (n_bases >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
     if (out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;
-    MM_HIP(set_device(ws->device));
-    const uint64_t bytes = (n_bases + 3) / 4;
-    uint8_t *din = reinterpret_cast<uint8_t *>(ws->d_in);
-    int r = grow(din, ws->d_in_bytes, bytes + 16, 1);
-    ws->d_in = din;
-    if (r) return r;
-    uint8_t *dasc = reinterpret_cast<uint8_t *>(ws->d_ascii);
-    r = grow(dasc, ws->d_ascii_bytes, n_bases + 16, 1);
-    ws->d_ascii = dasc;
-    if (r) return r;
-    if (n_bases) {
-        if (!ascii) return MM_ERR_NULL;
-        MM_HIP(hipMemcpyAsync(ws->d_ascii, ascii, n_bases, hipMemcpyHostToDevice, ws->stream));
-        if (mm::launch_pack_ascii(dasc, n_bases, din, ws->stream)) return hip_fail(hipGetLastError(), "pack_ascii");
-    }
-    return run_host_common(plan, ws, ws->d_in, bytes + 16, 0, n_bases, out_pos, out_sk, capacity,
-                           out_count);
+    return run_host_staged(plan, ws, ascii, true, 0, false, nullptr, 0, n_bases, out_pos, out_sk, capacity, out_count);
 }
 
 // ------------------------------------------------------------------- text
@@ -2608,9 +2590,7 @@ static int run_text_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, const 
             if (r) return r;
         } else {
             a.generic_round_windows = nwin < (1ull << 24) ? nwin : (1ull << 24);
-            uint8_t *sp = reinterpret_cast<uint8_t *>(ws->scratch);
-            r = grow(sp, ws->scratch_bytes, mm::generic_scratch_bytes(a.generic_round_windows, plan->w), 1);
-            ws->scratch = sp;
+            r = grow_bytes(ws->scratch, ws->scratch_bytes, mm::generic_scratch_bytes(a.generic_round_windows, plan->w));
             if (r) return r;
             a.scratch = ws->scratch;
             r = grow_status(ws, mm::generic_status_words(a.generic_round_windows));
@@ -2649,23 +2629,9 @@ int mm_run_text_device_async(const mm_plan_t *plan, mm_workspace_t *ws, const vo
 static int run_text_sync(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_text, uint64_t text_bytes,
                          uint64_t n, uint64_t win_begin, uint64_t win_end, uint32_t *d_out_pos, uint32_t *d_out_sk,
                          uint64_t capacity, uint64_t *out_count) {
-    if (!ws) return MM_ERR_NULL;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        // (as run_device_sync: an unchecked asynchronous run finishes before the words are reused)
-        if (ws->async_unchecked) MM_HIP(hipStreamSynchronize(ws->stream));
-        int r = run_text_async_impl(plan, ws, d_text, text_bytes, n, win_begin, win_end, d_out_pos, d_out_sk,
-                                    capacity, nullptr);
-        if (r) return r;
-        MM_HIP(hipMemcpyAsync(ws->h_total, ws->total, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                              ws->stream));
-        MM_HIP(hipStreamSynchronize(ws->stream));
-        const int je = judge_run_error(ws);
-        if (je < 0) return je;
-        if (je == 0) break;
-    }
-    if (out_count) *out_count = ws->h_total[0];
-    if (d_out_pos && ws->h_total[0] > capacity) return MM_ERR_CAPACITY;
-    return MM_OK;
+    return run_sync(ws, capacity, d_out_pos != nullptr, out_count, [&](bool *) {
+        return run_text_async_impl(plan, ws, d_text, text_bytes, n, win_begin, win_end, d_out_pos, d_out_sk, capacity, nullptr);
+    });
 }
 
 int mm_run_text_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_text, uint64_t text_bytes,
@@ -2687,25 +2653,17 @@ int mm_run_text_host(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *t
     MM_HIP(set_device(ws->device));
     const uint64_t l = (uint64_t)plan->k + plan->w - 1;
     const uint64_t n_w = n >= l ? n - l + 1 : 0;
-    const uint64_t cap = out_pos ? (capacity < n_w ? capacity : n_w) : 0;
-    uint8_t *dtext = reinterpret_cast<uint8_t *>(ws->d_ascii);
-    int r = grow(dtext, ws->d_ascii_bytes, n + 16, 1);
-    ws->d_ascii = dtext;
-    if (r == MM_OK) r = grow(ws->d_out, ws->d_out_elems, cap ? cap : 1, sizeof(uint32_t));
-    if (r == MM_OK && out_sk) r = grow(ws->d_sk, ws->d_sk_elems, cap ? cap : 1, sizeof(uint32_t));
+    const uint64_t cap = capped(out_pos, capacity, n_w);
+    int r = grow_bytes(ws->d_ascii, ws->d_ascii_bytes, n + 16);
+    if (r == MM_OK) r = stage_outputs(ws, cap, out_sk != nullptr);
     if (r) return r;
-    if (n) MM_HIP(hipMemcpyAsync(dtext, text, n, hipMemcpyHostToDevice, ws->stream));
+    if (n) MM_HIP(hipMemcpyAsync(ws->d_ascii, text, n, hipMemcpyHostToDevice, ws->stream));
     uint64_t count = 0;
-    r = run_text_sync(plan, ws, dtext, n, n, 0, UINT64_MAX, cap ? ws->d_out : nullptr, (out_sk && cap) ? ws->d_sk : nullptr,
+    r = run_text_sync(plan, ws, ws->d_ascii, n, n, 0, UINT64_MAX, cap ? ws->d_out : nullptr, (out_sk && cap) ? ws->d_sk : nullptr,
                       cap, &count);
     if (out_count) *out_count = count;
     if (r) return r;
-    if (out_pos && count) {
-        MM_HIP(hipMemcpyAsync(out_pos, ws->d_out, count * sizeof(uint32_t), hipMemcpyDeviceToHost, ws->stream));
-        if (out_sk) MM_HIP(hipMemcpyAsync(out_sk, ws->d_sk, count * sizeof(uint32_t), hipMemcpyDeviceToHost, ws->stream));
-        MM_HIP(hipStreamSynchronize(ws->stream));
-    }
-    return MM_OK;
+    return download_positions(ws, out_pos, out_sk, count);
 }
 
 // ------------------------------------------------------------- text batch
@@ -2805,9 +2763,7 @@ static int run_text_batch_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, 
             const uint64_t max_windows = longest >= l ? longest - l + 1 : 0;
             const uint64_t round = max_windows < (1ull << 24) ? max_windows : (1ull << 24);
             if (round) {
-                uint8_t *sp = reinterpret_cast<uint8_t *>(ws->scratch);
-                r = grow(sp, ws->scratch_bytes, mm::generic_scratch_bytes(round, plan->w), 1);
-                ws->scratch = sp;
+                r = grow_bytes(ws->scratch, ws->scratch_bytes, mm::generic_scratch_bytes(round, plan->w));
                 if (r == MM_OK) r = grow_status(ws, mm::generic_status_words(round));
                 if (r) return r;
             }
@@ -2854,23 +2810,10 @@ int mm_run_text_batch_device(const mm_plan_t *plan, mm_workspace_t *ws, const vo
     ApiScope api_scope;  // (restores the calling thread's current device on return)
     const int rc = text_batch_check(plan, d_text, text_bytes, n_records, d_starts, n_chars, d_out_sk, d_out_offsets);
     if (rc) return rc;
-    if (!ws) return MM_ERR_NULL;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        // (as run_text_sync: an unchecked asynchronous run finishes before the words are reused)
-        if (ws->async_unchecked) MM_HIP(hipStreamSynchronize(ws->stream));
-        int r = run_text_batch_async_impl(plan, ws, d_text, text_bytes, n_records, d_starts, n_chars, d_out_pos,
-                                          d_out_sk, capacity, d_out_offsets, nullptr);
-        if (r) return r;
-        MM_HIP(hipMemcpyAsync(ws->h_total, ws->total, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                              ws->stream));
-        MM_HIP(hipStreamSynchronize(ws->stream));
-        const int je = judge_run_error(ws);
-        if (je < 0) return je;
-        if (je == 0) break;
-    }
-    if (out_count) *out_count = ws->h_total[0];
-    if (d_out_pos && ws->h_total[0] > capacity) return MM_ERR_CAPACITY;
-    return MM_OK;
+    return run_sync(ws, capacity, d_out_pos != nullptr, out_count, [&](bool *) {
+        return run_text_batch_async_impl(plan, ws, d_text, text_bytes, n_records, d_starts, n_chars, d_out_pos, d_out_sk,
+                                         capacity, d_out_offsets, nullptr);
+    });
 }
 
 int mm_run_text_batch_host(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *text, uint64_t n_records,
@@ -2892,15 +2835,13 @@ int mm_run_text_batch_host(const mm_plan_t *plan, mm_workspace_t *ws, const uint
     MM_HIP(set_device(ws->device));
     // staging: [text | starts] in d_in, positions (and indices) in d_out / d_sk, offsets in d_vals
     const uint64_t starts_at = (n_chars + 16 + 15) & ~15ull;
-    uint8_t *din = reinterpret_cast<uint8_t *>(ws->d_in);
-    int r = grow(din, ws->d_in_bytes, starts_at + (n_records + 1) * sizeof(uint64_t), 1);
-    ws->d_in = din;
+    int r = grow_bytes(ws->d_in, ws->d_in_bytes, starts_at + (n_records + 1) * sizeof(uint64_t));
     if (r) return r;
-    const uint64_t cap = out_pos ? (capacity < n_chars ? capacity : n_chars) : 0;
-    r = grow(ws->d_out, ws->d_out_elems, cap ? cap : 1, sizeof(uint32_t));
-    if (r == MM_OK && out_sk) r = grow(ws->d_sk, ws->d_sk_elems, cap ? cap : 1, sizeof(uint32_t));
+    const uint64_t cap = capped(out_pos, capacity, n_chars);
+    r = stage_outputs(ws, cap, out_sk != nullptr);
     if (r == MM_OK) r = grow(ws->d_vals, ws->d_vals_elems, n_records + 1, sizeof(unsigned long long));
     if (r) return r;
+    uint8_t *const din = static_cast<uint8_t *>(ws->d_in);
     if (n_chars) MM_HIP(hipMemcpyAsync(din, text, n_chars, hipMemcpyHostToDevice, ws->stream));
     if (n_records)
         MM_HIP(hipMemcpyAsync(din + starts_at, starts, (n_records + 1) * sizeof(uint64_t), hipMemcpyHostToDevice,
@@ -2911,13 +2852,7 @@ int mm_run_text_batch_host(const mm_plan_t *plan, mm_workspace_t *ws, const uint
                                  reinterpret_cast<uint64_t *>(ws->d_vals), &count);
     if (out_count) *out_count = count;
     if (r) return r;
-    MM_HIP(hipMemcpyAsync(out_offsets, ws->d_vals, (n_records + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
-    if (out_pos && count) {
-        MM_HIP(hipMemcpyAsync(out_pos, ws->d_out, count * sizeof(uint32_t), hipMemcpyDeviceToHost, ws->stream));
-        if (out_sk) MM_HIP(hipMemcpyAsync(out_sk, ws->d_sk, count * sizeof(uint32_t), hipMemcpyDeviceToHost, ws->stream));
-    }
-    MM_HIP(hipStreamSynchronize(ws->stream));
-    return MM_OK;
+    return download_positions(ws, out_pos, out_sk, count, out_offsets, n_records + 1);
 }
 
 int mm_run_skip_ambiguous_host(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *packed,
@@ -2925,62 +2860,23 @@ int mm_run_skip_ambiguous_host(const mm_plan_t *plan, mm_workspace_t *ws, const 
                                uint64_t n_bases, uint32_t *out_pos, uint64_t capacity,
                                uint64_t *out_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
-    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
+    if (const int bad = dna_plan_only(plan)) return bad;
     if (!plan || !ws) return MM_ERR_NULL;
     if (n_bases >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
     if (!plan->canonical_windows) return MM_ERR_HASHER_NOT_CANONICAL;
-    MM_HIP(set_device(ws->device));
-    const uint64_t bytes = (base_offset + n_bases + 3) / 4;
-    const uint64_t abytes = (amb_offset + n_bases + 7) / 8;
-    uint8_t *din = reinterpret_cast<uint8_t *>(ws->d_in);
-    int r = grow(din, ws->d_in_bytes, bytes + 16, 1);
-    ws->d_in = din;
-    if (r) return r;
-    uint8_t *damb = reinterpret_cast<uint8_t *>(ws->d_amb);
-    r = grow(damb, ws->d_amb_bytes, abytes + 16, 1);
-    ws->d_amb = damb;
-    if (r) return r;
-    if (n_bases) {
-        if (!packed || !amb) return MM_ERR_NULL;
-        MM_HIP(hipMemcpyAsync(ws->d_in, packed, bytes, hipMemcpyHostToDevice, ws->stream));
-        MM_HIP(hipMemcpyAsync(ws->d_amb, amb, abytes, hipMemcpyHostToDevice, ws->stream));
-    }
-    const AmbArgs a{ws->d_amb, abytes + 16, amb_offset};
-    return run_host_common(plan, ws, ws->d_in, bytes + 16, base_offset, n_bases, out_pos, nullptr,
-                           capacity, out_count, &a);
+    return run_host_staged(plan, ws, packed, false, base_offset, true, amb, amb_offset, n_bases, out_pos, nullptr, capacity,
+                           out_count);
 }
 
 int mm_run_skip_ambiguous_host_ascii(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *ascii,
                                      uint64_t n_bases, uint32_t *out_pos, uint64_t capacity,
                                      uint64_t *out_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
-    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
+    if (const int bad = dna_plan_only(plan)) return bad;
     if (!plan || !ws) return MM_ERR_NULL;
     if (n_bases >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
     if (!plan->canonical_windows) return MM_ERR_HASHER_NOT_CANONICAL;
-    MM_HIP(set_device(ws->device));
-    const uint64_t bytes = (n_bases + 3) / 4, abytes = (n_bases + 7) / 8;
-    uint8_t *din = reinterpret_cast<uint8_t *>(ws->d_in);
-    int r = grow(din, ws->d_in_bytes, bytes + 16, 1);
-    ws->d_in = din;
-    if (r) return r;
-    uint8_t *damb = reinterpret_cast<uint8_t *>(ws->d_amb);
-    r = grow(damb, ws->d_amb_bytes, abytes + 16, 1);
-    ws->d_amb = damb;
-    if (r) return r;
-    uint8_t *dasc = reinterpret_cast<uint8_t *>(ws->d_ascii);
-    r = grow(dasc, ws->d_ascii_bytes, n_bases + 16, 1);
-    ws->d_ascii = dasc;
-    if (r) return r;
-    if (n_bases) {
-        if (!ascii) return MM_ERR_NULL;
-        MM_HIP(hipMemcpyAsync(ws->d_ascii, ascii, n_bases, hipMemcpyHostToDevice, ws->stream));
-        if (mm::launch_pack_ascii_n(dasc, n_bases, din, damb, ws->stream))
-            return hip_fail(hipGetLastError(), "pack_ascii_n");
-    }
-    const AmbArgs a{ws->d_amb, abytes + 16, 0};
-    return run_host_common(plan, ws, ws->d_in, bytes + 16, 0, n_bases, out_pos, nullptr, capacity,
-                           out_count, &a);
+    return run_host_staged(plan, ws, ascii, true, 0, true, nullptr, 0, n_bases, out_pos, nullptr, capacity, out_count);
 }
 
 int mm_pack_ascii_n_device_async(mm_workspace_t *ws, const uint8_t *d_ascii, uint64_t n_bases,
@@ -2995,51 +2891,64 @@ int mm_pack_ascii_n_device_async(mm_workspace_t *ws, const uint8_t *d_ascii, uin
     return MM_OK;
 }
 
-int mm_values_u64_device_async(mm_workspace_t *ws, const void *d_packed, uint64_t packed_bytes,
-                               uint64_t base_offset, uint64_t n_bases, uint32_t len,
-                               int canonical, const uint32_t *d_pos, uint64_t n_pos,
-                               uint64_t *d_values) {
-    ApiScope api_scope;  // (restores the calling thread's current device on return)
+// ---- Output::values_u64 / values_u128 (src/lib.rs:584-629): `words` 64-bit words per value, 1 or 2
+static int values_async_impl(mm_workspace_t *ws, const void *d_packed, uint64_t packed_bytes, uint64_t base_offset,
+                             uint64_t n_bases, uint32_t len, int canonical, const uint32_t *d_pos, uint64_t n_pos,
+                             uint64_t *d_values, int words) {
     if (!ws) return MM_ERR_NULL;
-    if (len == 0 || len > 32) return MM_ERR_VALUE_LEN;
+    if (len == 0 || len > 32u * words) return MM_ERR_VALUE_LEN;
     if (n_pos == 0) return MM_OK;
     if (!d_packed || !d_pos || !d_values) return MM_ERR_NULL;
     MM_HIP(set_device(ws->device));
     mm::SeqView v;
     int r = make_view(d_packed, packed_bytes, base_offset, n_bases, &v);
     if (r) return r;
-    if (mm::launch_values_u64(v, len, canonical, d_pos, n_pos,
-                              reinterpret_cast<unsigned long long *>(d_values), ws->stream))
-        return hip_fail(hipGetLastError(), "values_u64");
+    unsigned long long *const out = reinterpret_cast<unsigned long long *>(d_values);
+    if (words == 2 ? mm::launch_values_u128(v, len, canonical, d_pos, n_pos, out, ws->stream)
+                   : mm::launch_values_u64(v, len, canonical, d_pos, n_pos, out, ws->stream))
+        return hip_fail(hipGetLastError(), words == 2 ? "values_u128" : "values_u64");
     return MM_OK;
+}
+
+// The same from HOST memory: packed bytes (+ slack for the loads behind the last value) in d_in, positions in d_out,
+// values in d_vals.
+static int values_host_impl(mm_workspace_t *ws, const uint8_t *packed, uint64_t base_offset, uint64_t n_bases, uint32_t len,
+                            int canonical, const uint32_t *pos, uint64_t n_pos, uint64_t *values, int words) {
+    if (!ws) return MM_ERR_NULL;
+    if (len == 0 || len > 32u * words) return MM_ERR_VALUE_LEN;
+    if (n_pos == 0) return MM_OK;
+    if (!packed || !pos || !values) return MM_ERR_NULL;
+    MM_HIP(set_device(ws->device));
+    const uint64_t bytes = (base_offset + n_bases + 3) / 4, slack = 16 * words;
+    int r = grow_bytes(ws->d_in, ws->d_in_bytes, bytes + slack);
+    if (r) return r;
+    r = grow(ws->d_out, ws->d_out_elems, n_pos, sizeof(uint32_t));
+    if (r) return r;
+    r = grow(ws->d_vals, ws->d_vals_elems, words * n_pos, sizeof(unsigned long long));
+    if (r) return r;
+    MM_HIP(hipMemcpyAsync(ws->d_in, packed, bytes, hipMemcpyHostToDevice, ws->stream));
+    MM_HIP(hipMemcpyAsync(ws->d_out, pos, n_pos * sizeof(uint32_t), hipMemcpyHostToDevice, ws->stream));
+    r = values_async_impl(ws, ws->d_in, bytes + slack, base_offset, n_bases, len, canonical, ws->d_out, n_pos,
+                          reinterpret_cast<uint64_t *>(ws->d_vals), words);
+    if (r) return r;
+    MM_HIP(hipMemcpyAsync(values, ws->d_vals, words * n_pos * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
+    MM_HIP(hipStreamSynchronize(ws->stream));
+    return MM_OK;
+}
+
+int mm_values_u64_device_async(mm_workspace_t *ws, const void *d_packed, uint64_t packed_bytes,
+                               uint64_t base_offset, uint64_t n_bases, uint32_t len,
+                               int canonical, const uint32_t *d_pos, uint64_t n_pos,
+                               uint64_t *d_values) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    return values_async_impl(ws, d_packed, packed_bytes, base_offset, n_bases, len, canonical, d_pos, n_pos, d_values, 1);
 }
 
 int mm_values_u64_host(mm_workspace_t *ws, const uint8_t *packed, uint64_t base_offset,
                        uint64_t n_bases, uint32_t len, int canonical, const uint32_t *pos,
                        uint64_t n_pos, uint64_t *values) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
-    if (!ws) return MM_ERR_NULL;
-    if (len == 0 || len > 32) return MM_ERR_VALUE_LEN;
-    if (n_pos == 0) return MM_OK;
-    if (!packed || !pos || !values) return MM_ERR_NULL;
-    MM_HIP(set_device(ws->device));
-    const uint64_t bytes = (base_offset + n_bases + 3) / 4;
-    uint8_t *din = reinterpret_cast<uint8_t *>(ws->d_in);
-    int r = grow(din, ws->d_in_bytes, bytes + 16, 1);
-    ws->d_in = din;
-    if (r) return r;
-    r = grow(ws->d_out, ws->d_out_elems, n_pos, sizeof(uint32_t));
-    if (r) return r;
-    r = grow(ws->d_vals, ws->d_vals_elems, n_pos, sizeof(unsigned long long));
-    if (r) return r;
-    MM_HIP(hipMemcpyAsync(ws->d_in, packed, bytes, hipMemcpyHostToDevice, ws->stream));
-    MM_HIP(hipMemcpyAsync(ws->d_out, pos, n_pos * sizeof(uint32_t), hipMemcpyHostToDevice, ws->stream));
-    r = mm_values_u64_device_async(ws, ws->d_in, bytes + 16, base_offset, n_bases, len, canonical,
-                                   ws->d_out, n_pos, reinterpret_cast<uint64_t *>(ws->d_vals));
-    if (r) return r;
-    MM_HIP(hipMemcpyAsync(values, ws->d_vals, n_pos * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
-    MM_HIP(hipStreamSynchronize(ws->stream));
-    return MM_OK;
+    return values_host_impl(ws, packed, base_offset, n_bases, len, canonical, pos, n_pos, values, 1);
 }
 
 int mm_values_u128_device_async(mm_workspace_t *ws, const void *d_packed, uint64_t packed_bytes,
@@ -3047,46 +2956,14 @@ int mm_values_u128_device_async(mm_workspace_t *ws, const void *d_packed, uint64
                                 int canonical, const uint32_t *d_pos, uint64_t n_pos,
                                 uint64_t *d_values) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
-    if (!ws) return MM_ERR_NULL;
-    if (len == 0 || len > 64) return MM_ERR_VALUE_LEN;
-    if (n_pos == 0) return MM_OK;
-    if (!d_packed || !d_pos || !d_values) return MM_ERR_NULL;
-    MM_HIP(set_device(ws->device));
-    mm::SeqView v;
-    int r = make_view(d_packed, packed_bytes, base_offset, n_bases, &v);
-    if (r) return r;
-    if (mm::launch_values_u128(v, len, canonical, d_pos, n_pos,
-                               reinterpret_cast<unsigned long long *>(d_values), ws->stream))
-        return hip_fail(hipGetLastError(), "values_u128");
-    return MM_OK;
+    return values_async_impl(ws, d_packed, packed_bytes, base_offset, n_bases, len, canonical, d_pos, n_pos, d_values, 2);
 }
 
 int mm_values_u128_host(mm_workspace_t *ws, const uint8_t *packed, uint64_t base_offset,
                         uint64_t n_bases, uint32_t len, int canonical, const uint32_t *pos,
                         uint64_t n_pos, uint64_t *values) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
-    if (!ws) return MM_ERR_NULL;
-    if (len == 0 || len > 64) return MM_ERR_VALUE_LEN;
-    if (n_pos == 0) return MM_OK;
-    if (!packed || !pos || !values) return MM_ERR_NULL;
-    MM_HIP(set_device(ws->device));
-    const uint64_t bytes = (base_offset + n_bases + 3) / 4;
-    uint8_t *din = reinterpret_cast<uint8_t *>(ws->d_in);
-    int r = grow(din, ws->d_in_bytes, bytes + 32, 1);
-    ws->d_in = din;
-    if (r) return r;
-    r = grow(ws->d_out, ws->d_out_elems, n_pos, sizeof(uint32_t));
-    if (r) return r;
-    r = grow(ws->d_vals, ws->d_vals_elems, 2 * n_pos, sizeof(unsigned long long));
-    if (r) return r;
-    MM_HIP(hipMemcpyAsync(ws->d_in, packed, bytes, hipMemcpyHostToDevice, ws->stream));
-    MM_HIP(hipMemcpyAsync(ws->d_out, pos, n_pos * sizeof(uint32_t), hipMemcpyHostToDevice, ws->stream));
-    r = mm_values_u128_device_async(ws, ws->d_in, bytes + 32, base_offset, n_bases, len, canonical,
-                                    ws->d_out, n_pos, reinterpret_cast<uint64_t *>(ws->d_vals));
-    if (r) return r;
-    MM_HIP(hipMemcpyAsync(values, ws->d_vals, 2 * n_pos * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
-    MM_HIP(hipStreamSynchronize(ws->stream));
-    return MM_OK;
+    return values_host_impl(ws, packed, base_offset, n_bases, len, canonical, pos, n_pos, values, 2);
 }
 
 // ---- Output::values_u64 / values_u128 (src/lib.rs:584-629) of every read of one packed buffer in ONE launch: what a loop
@@ -3175,10 +3052,9 @@ static int values_reads_host_impl(mm_workspace_t *ws, const uint8_t *packed, uin
     const uint64_t words = n_reads + 1, per = u128 ? 2 : 1;
     const uint64_t starts_at = (packed_bytes + 15) & ~15ull;
     const uint64_t offsets_at = starts_at + (read_starts ? words * sizeof(uint64_t) : 0);
-    uint8_t *din = reinterpret_cast<uint8_t *>(ws->d_in);
-    int r = grow(din, ws->d_in_bytes, offsets_at + words * sizeof(uint64_t), 1);
-    ws->d_in = din;
+    int r = grow_bytes(ws->d_in, ws->d_in_bytes, offsets_at + words * sizeof(uint64_t));
     if (r) return r;
+    uint8_t *const din = static_cast<uint8_t *>(ws->d_in);
     r = grow(ws->d_out, ws->d_out_elems, n_pos, sizeof(uint32_t));
     if (r) return r;
     r = grow(ws->d_vals, ws->d_vals_elems, per * n_pos, sizeof(unsigned long long));
@@ -3262,12 +3138,12 @@ static int amb_out_check(const uint8_t *d_amb, uint64_t amb_capacity_bytes) {
     return MM_OK;
 }
 
-// (d_amb: the ambiguity bits of mm_fasta_pack_n_*, checked by the caller - always the two-pass kernels; null: the plain packer)
-static int fasta_pack_async(mm_workspace_t *ws, const uint8_t *d_text, uint64_t n_bytes,
-                            uint8_t *d_packed, uint64_t packed_capacity_bytes, uint64_t *d_rec_base,
-                            uint64_t *d_rec_text_pos, uint64_t max_records, uint64_t *d_counts, uint8_t *d_amb,
-                            uint64_t amb_capacity_bytes) {
-    // (the synchronous wrapper below checks the error word itself; a direct asynchronous caller asks mm_workspace_check)
+// What the FASTA and the FASTQ packer do before they differ: the argument checks, the workspace's device, and an empty text's
+// answer (no base, no record).  Returns MM_PACK_GO_ON when there is a text to pack, else the call's result.
+static const int MM_PACK_GO_ON = 1;
+static int pack_prologue(mm_workspace_t *ws, const uint8_t *d_text, uint64_t n_bytes, const uint8_t *d_packed,
+                         uint64_t packed_capacity_bytes, uint64_t *d_rec_base, uint64_t *d_counts, uint8_t *d_amb,
+                         uint64_t amb_capacity_bytes) {
     if (!ws || !d_counts || !d_rec_base) return MM_ERR_NULL;
     if (n_bytes >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
     if (reinterpret_cast<uintptr_t>(d_packed) % 4 != 0) return MM_ERR_NULL;
@@ -3279,15 +3155,32 @@ static int fasta_pack_async(mm_workspace_t *ws, const uint8_t *d_text, uint64_t 
         return MM_OK;
     }
     if (!d_text || (!d_packed && packed_capacity_bytes)) return MM_ERR_NULL;
-    uint8_t *sp = reinterpret_cast<uint8_t *>(ws->scratch);
+    return MM_PACK_GO_ON;
+}
+
+// ... and what their synchronous callers ask of the two counts (bases, records) once they are on the host.
+static int pack_counts_check(const uint64_t *out_counts, uint64_t packed_capacity_bytes, uint64_t max_records,
+                             const uint8_t *d_amb, uint64_t amb_capacity_bytes) {
+    if (out_counts[0] > (packed_capacity_bytes & ~3ull) * 4 || out_counts[1] > max_records) return MM_ERR_CAPACITY;
+    if (d_amb && out_counts[0] > amb_capacity_bytes * 8) return MM_ERR_CAPACITY;
+    return MM_OK;
+}
+
+// (d_amb: the ambiguity bits of mm_fasta_pack_n_*, checked by the caller - always the two-pass kernels; null: the plain packer)
+static int fasta_pack_async(mm_workspace_t *ws, const uint8_t *d_text, uint64_t n_bytes,
+                            uint8_t *d_packed, uint64_t packed_capacity_bytes, uint64_t *d_rec_base,
+                            uint64_t *d_rec_text_pos, uint64_t max_records, uint64_t *d_counts, uint8_t *d_amb,
+                            uint64_t amb_capacity_bytes) {
+    // (the synchronous wrapper below checks the error word itself; a direct asynchronous caller asks mm_workspace_check)
+    const int p = pack_prologue(ws, d_text, n_bytes, d_packed, packed_capacity_bytes, d_rec_base, d_counts, d_amb, amb_capacity_bytes);
+    if (p != MM_PACK_GO_ON) return p;
 #ifdef MM_EXPERIMENTS
     const uint64_t need_a = mm::fasta_scratch_bytes(n_bytes);
 #else
     const uint64_t need_a = 0;
 #endif
     const uint64_t need_b = mm::fasta2_scratch_bytes(n_bytes);
-    const int r = grow(sp, ws->scratch_bytes, need_a > need_b ? need_a : need_b, 1);
-    ws->scratch = sp;
+    const int r = grow_bytes(ws->scratch, ws->scratch_bytes, need_a > need_b ? need_a : need_b);
     if (r) return r;
     const int choice = d_amb ? 0 : fasta_packer_choice(ws);
     if (choice == 0) {
@@ -3345,20 +3238,9 @@ static int fastq_pack_async(mm_workspace_t *ws, const uint8_t *d_text, uint64_t 
                             uint64_t packed_capacity_bytes, uint64_t *d_rec_base, uint64_t *d_rec_text_pos,
                             uint64_t max_records, uint64_t *d_counts, uint64_t pos_bias, uint8_t *d_amb = nullptr,
                             uint64_t amb_capacity_bytes = 0) {
-    if (!ws || !d_counts || !d_rec_base) return MM_ERR_NULL;
-    if (n_bytes >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
-    if (reinterpret_cast<uintptr_t>(d_packed) % 4 != 0) return MM_ERR_NULL;
-    MM_HIP(set_device(ws->device));
-    if (n_bytes == 0) {
-        MM_HIP(hipMemsetAsync(d_counts, 0, 2 * sizeof(uint64_t), ws->stream));
-        MM_HIP(hipMemsetAsync(d_rec_base, 0, sizeof(uint64_t), ws->stream));
-        if (d_amb) MM_HIP(hipMemsetAsync(d_amb, 0, amb_capacity_bytes < 8 ? amb_capacity_bytes : 8, ws->stream));
-        return MM_OK;
-    }
-    if (!d_text || (!d_packed && packed_capacity_bytes)) return MM_ERR_NULL;
-    uint8_t *sp = reinterpret_cast<uint8_t *>(ws->scratch);
-    const int r = grow(sp, ws->scratch_bytes, mm::fastq_scratch_bytes(n_bytes), 1);
-    ws->scratch = sp;
+    const int p = pack_prologue(ws, d_text, n_bytes, d_packed, packed_capacity_bytes, d_rec_base, d_counts, d_amb, amb_capacity_bytes);
+    if (p != MM_PACK_GO_ON) return p;
+    const int r = grow_bytes(ws->scratch, ws->scratch_bytes, mm::fastq_scratch_bytes(n_bytes));
     if (r) return r;
     if (mm::launch_fastq_pack(d_text, n_bytes, d_packed, packed_capacity_bytes & ~3ull,
                               reinterpret_cast<unsigned long long *>(d_rec_base),
@@ -3424,9 +3306,7 @@ static int fasta_pack_sync(mm_workspace_t *ws, const uint8_t *d_text, uint64_t n
             }
             MM_HIP(hipMemcpyAsync(out_counts, d_counts, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
             MM_HIP(hipStreamSynchronize(ws->stream));
-            if (out_counts[0] > (packed_capacity_bytes & ~3ull) * 4 || out_counts[1] > max_records) return MM_ERR_CAPACITY;
-            if (d_amb && out_counts[0] > amb_capacity_bytes * 8) return MM_ERR_CAPACITY;
-            return MM_OK;
+            return pack_counts_check(out_counts, packed_capacity_bytes, max_records, d_amb, amb_capacity_bytes);
         }
     }
     for (int attempt = 0; attempt < 2; ++attempt) {
@@ -3447,9 +3327,7 @@ static int fasta_pack_sync(mm_workspace_t *ws, const uint8_t *d_text, uint64_t n
         else ws->fasta_three_pass = true;
         if (!ws->async_unchecked) MM_HIP(hipMemsetAsync(ws->total + 2, 0, sizeof(unsigned long long), ws->stream));
     }
-    if (out_counts[0] > (packed_capacity_bytes & ~3ull) * 4 || out_counts[1] > max_records) return MM_ERR_CAPACITY;
-    if (d_amb && out_counts[0] > amb_capacity_bytes * 8) return MM_ERR_CAPACITY;
-    return MM_OK;
+    return pack_counts_check(out_counts, packed_capacity_bytes, max_records, d_amb, amb_capacity_bytes);
 }
 
 int mm_fasta_pack_device(mm_workspace_t *ws, const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_packed,
@@ -3840,7 +3718,7 @@ int mm_run_sharded_host(const mm_plan_t *plan, mm_device_group_t *g, const uint8
                         uint64_t n_bases, uint32_t *out_pos, uint32_t *out_sk, uint64_t capacity,
                         uint64_t *out_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
-    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
+    if (const int bad = dna_plan_only(plan)) return bad;
     if (!plan || !g || g->ws.empty()) return MM_ERR_NULL;
     if (n_bases >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
     if (out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;
@@ -3866,10 +3744,10 @@ int mm_run_sharded_host(const mm_plan_t *plan, mm_device_group_t *g, const uint8
             r.err = g_last_error;
         };
         if (set_device(ws->device) != hipSuccess) return fail(MM_ERR_HIP);
-        uint8_t *din = reinterpret_cast<uint8_t *>(ws->d_in);
-        int rc = grow(din, ws->d_in_bytes, bytes + 16, 1);  // (the whole extent, so that positions stay absolute;
-        ws->d_in = din;                                     // only this shard's slice of it is filled)
+        // (the whole extent, so that positions stay absolute; only this shard's slice of it is filled)
+        int rc = grow_bytes(ws->d_in, ws->d_in_bytes, bytes + 16);
         if (rc) return fail(rc);
+        uint8_t *const din = static_cast<uint8_t *>(ws->d_in);
         // element 0 of the first lane is the k-mer before window a; the walk's loads run a few dwords ahead
         const uint64_t b0 = a ? ((base_offset + a - 1) / 4) & ~15ull : 0;
         uint64_t b1 = (base_offset + e + l - 2) / 4 + 1 + 64 + plan->w / 2;
@@ -3940,7 +3818,7 @@ int mm_run_sharded_host(const mm_plan_t *plan, mm_device_group_t *g, const uint8
 int mm_run_sharded_device(const mm_plan_t *plan, mm_device_group_t *g, uint64_t base_offset, uint64_t n_bases,
                           int want_superkmers, uint64_t *counts, uint64_t *total) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
-    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
+    if (const int bad = dna_plan_only(plan)) return bad;
     if (!plan || !g || g->ws.empty()) return MM_ERR_NULL;
     if (g->seq_bytes == 0) {
         g_last_error = "mm_run_sharded_device: no resident sequence (mm_device_group_upload / _adopt first)";
@@ -4154,7 +4032,7 @@ int mm_device_group_upload_batch(mm_device_group_t *g, uint64_t n_seqs, const ui
 int mm_run_batch_sharded_device(const mm_plan_t *plan, mm_device_group_t *g, const uint64_t *base_offsets,
                                 const uint64_t *n_bases, int want_superkmers, uint64_t *out_counts, uint64_t *total) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
-    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
+    if (const int bad = dna_plan_only(plan)) return bad;
     if (!plan || !g || g->ws.empty() || g->batch.size() != g->ws.size() || !n_bases) return MM_ERR_NULL;
     if (want_superkmers && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;
     const uint64_t N = g->ws.size(), n_seqs = g->seq_entry.size();
@@ -4336,7 +4214,7 @@ int mm_run_batch_sharded_host(const mm_plan_t *plan, mm_device_group_t *g, uint6
                               const uint8_t *const *packed, const uint64_t *base_offsets, const uint64_t *n_bases,
                               uint32_t *out_pos, uint32_t *out_sk, uint64_t capacity, uint64_t *out_offsets) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
-    if (plan && plan->text) return MM_ERR_BAD_MODE;  // (a text plan runs through mm_run_text_* only)
+    if (const int bad = dna_plan_only(plan)) return bad;
     if (!plan || !g || g->ws.empty() || !out_offsets) return MM_ERR_NULL;
     if (n_seqs && (!packed || !n_bases)) return MM_ERR_NULL;
     if (out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;
@@ -4380,10 +4258,9 @@ int mm_run_batch_sharded_host(const mm_plan_t *plan, mm_device_group_t *g, uint6
             total += (nbytes[j] + 16 + 15) & ~15ull;
             windows += n_bases[s] >= l ? n_bases[s] - l + 1 : 0;
         }
-        uint8_t *din = reinterpret_cast<uint8_t *>(ws->d_in);
-        int rc = grow(din, ws->d_in_bytes, total + 16, 1);
-        ws->d_in = din;
+        int rc = grow_bytes(ws->d_in, ws->d_in_bytes, total + 16);
         if (rc) return fail(rc);
+        uint8_t *const din = static_cast<uint8_t *>(ws->d_in);
         std::vector<const void *> dptr(my.size());
         std::vector<uint64_t> dbytes(my.size()), offs(my.size()), lens(my.size());
         for (size_t j = 0; j < my.size(); ++j) {
