@@ -173,6 +173,49 @@ int mm_workspace_last_lane_table(const mm_workspace_t *ws);
  * order to `out` (may be null) and returns how many there are.  No GPU needed.  The test-suite takes its list of
  * instances to compare with the oracle from here, so that none can ship untested. */
 int mm_prebuilt_window_sizes(int canonical_windows, int reads_mode, uint32_t *out, int capacity);
+/* The same list PER FLAVOUR: `mode` and `super_kmers` (minimizers with super-k-mer indices; 0 sizes with a syncmer mode)
+ * select the kernel.  A sequence-mode instance carries all four flavours, so reads_mode == 0 gives the list above for
+ * each of them; in reads mode minimizer positions have the list above, and closed syncmers, open syncmers and
+ * minimizers + super-k-mers are prebuilt for w = 5, 7, 11, 15, 17, 19, 21, 31.  Every other (flavour, w <= 128) is
+ * compiled at its first use - or ahead of it by mm_plan_prepare - which Builder::run (src/lib.rs:378), being compiled
+ * code, never is.  A table look-up: no GPU needed, none touched. */
+int mm_prebuilt_flavour_window_sizes(int canonical_windows, int reads_mode, mm_mode_t mode, int super_kmers,
+                                     uint32_t *out, int capacity);
+
+/* ----------------------------------------------------------- first call */
+
+/* The reference's Builder::run (src/lib.rs:378) is ordinary compiled code: its first call costs what its thousandth
+ * does.  Here the first run of a plan loads its kernels onto the device and, for a (flavour, w) without a prebuilt
+ * kernel, compiles one with hiprtc - seconds.  mm_plan_prepare restores the reference's behaviour for a caller that
+ * wants it: it obtains every kernel the plan's runs can dispatch to under `what`, exactly as their first launch would
+ * (the launcher's own choice: fixed-k instance, prebuilt instance, else the run-time compiler and its disk cache), on
+ * the workspace's device, and launches nothing; the calling thread's current device is what it was on return.
+ *   MM_PREPARE_SEQUENCE    mm_run_device*, mm_run_host*, mm_run_skip_ambiguous_*, tiled mm_run_batch_device launches
+ *   MM_PREPARE_READS       mm_run_reads_*, mm_run_packed_reads_* and lane-table launches (with the table's kernels)
+ *   MM_PREPARE_SUPERKMERS  also the kernels of the same runs with super-k-mer indices (d_out_sk); MM_ERR_BAD_MODE for a
+ *                          syncmer plan, as the runs themselves reject d_out_sk there (src/lib.rs:339)
+ * A text plan (mm_plan_create_text) has its fused text kernels - or the generic family's - loaded; none is compiled.
+ * report (may be NULL): `kernels` = kernels looked at; of them `compiled` were compiled by hiprtc in this call,
+ * `from_disk` were loaded from MM_JIT_CACHE_DIR, `unavailable` cannot be had (MM_JIT=0, w > 128, a compile failure) -
+ * the rest were prebuilt or already loaded.  Runs of a plan with unavailable kernels take the generic family, as they
+ * do without prepare: the call still returns MM_OK, loads that family, and mm_last_error() carries the reason.
+ * After MM_OK with unavailable == 0, no run of this plan in the prepared families on this device compiles anything.
+ * what == 0, or MM_PREPARE_SUPERKMERS alone (no family named) on a minimizer plan: MM_OK and a zero report; the
+ * syncmer-plan check comes first, so MM_PREPARE_SUPERKMERS alone on a syncmer plan is still MM_ERR_BAD_MODE.  Bits of
+ * `what` other than the three above: MM_ERR_BAD_MODE.  MM_ERR_NULL for a null plan or workspace (checked before
+ * anything else; the report, when given, is zeroed first).  MM_ERR_HIP when the runtime cannot load a prebuilt kernel
+ * (mm_last_error() names the call and the cause). */
+typedef struct mm_prepare_report {
+    uint32_t kernels, compiled, from_disk, unavailable;
+} mm_prepare_report_t;
+enum { MM_PREPARE_SEQUENCE = 1, MM_PREPARE_READS = 2, MM_PREPARE_SUPERKMERS = 4 };
+int mm_plan_prepare(const mm_plan_t *plan, mm_workspace_t *ws, uint32_t what, mm_prepare_report_t *report);
+/* Process-wide counters of the run-time compiler since the library was loaded: out[0] hiprtc compiles, out[1] kernels
+ * loaded from the disk cache, out[2] requests answered with a kernel already loaded, out[3] compiles or loads that
+ * failed.  Nothing resets them: take differences.  With them a caller can check what Builder::run (src/lib.rs:378)
+ * guarantees by construction - that a call compiled nothing.  A request for a loaded kernel never waits for another
+ * thread's compile, and different kernels compile side by side.  No GPU needed. */
+int mm_jit_stats(uint64_t out[4]);
 /* Bytes behind the last base of a run's last window that a launch of the fused family may still TOUCH (never use: a lane
  * that starts inside the window range walks its whole length with the windows past the range masked, and its loads run
  * ahead).  The launcher's own bound: mm_device_group_upload_range keeps that much resident behind every entry's share and

@@ -185,6 +185,20 @@ class Builder {  // src/lib.rs:225-230
         b.ws_ = ws;
         return b;
     }
+    // The reference's `run` (src/lib.rs:378) is compiled code: its first call costs what every call costs.  Here a
+    // builder's first run loads - and for some (flavour, w) compiles - its kernels; prepare() does that part ahead of
+    // the first run, on this builder's workspace, and launches nothing (mm_plan_prepare).  `what`: MM_PREPARE_SEQUENCE
+    // for run / run_scalar / run_once, MM_PREPARE_READS for run_many; a builder with .super_kmers() prepares those
+    // kernels as well.  Returns the report: kernels looked at, compiled, loaded from the disk cache, unavailable.
+    mm_prepare_report_t prepare(unsigned what = MM_PREPARE_SEQUENCE) const {
+        Workspace &ws = ws_ ? *ws_ : Workspace::thread_default();
+        mm_plan_t *plan = make_plan();
+        mm_prepare_report_t rep{0, 0, 0, 0};
+        const int r = mm_plan_prepare(plan, ws.get(), what | (sk_ && what ? (unsigned)MM_PREPARE_SUPERKMERS : 0u), &rep);
+        mm_plan_destroy(plan);
+        check(r);
+        return rep;
+    }
     Output<CANONICAL> run(PackedSeq seq, std::vector<uint32_t> &min_pos) const {  // src/lib.rs:378
         Workspace &ws = ws_ ? *ws_ : Workspace::thread_default();
         std::vector<uint32_t> pos, sk;

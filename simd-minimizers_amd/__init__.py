@@ -89,6 +89,15 @@ class TextHasher(C.Structure):
 _TEXT_TYPES = (bytes, bytearray, memoryview)
 
 
+class PrepareReport(C.Structure):
+    """``mm_prepare_report_t``."""
+    _fields_ = [("kernels", C.c_uint32), ("compiled", C.c_uint32), ("from_disk", C.c_uint32),
+                ("unavailable", C.c_uint32)]
+
+
+PREPARE_SEQUENCE, PREPARE_READS, PREPARE_SUPERKMERS = 1, 2, 4
+
+
 def _is_text(seq) -> bool:
     """``&[u8]`` input: bytes, bytearray or a uint8 numpy array (one character per byte, all 256 values legal)."""
     return isinstance(seq, _TEXT_TYPES) or (isinstance(seq, np.ndarray) and seq.dtype == np.uint8)
@@ -190,6 +199,11 @@ def _load_lib():
         if hasattr(L, "mm_prebuilt_window_sizes"):  # (absent from the round-3 library kept for A/B runs under tools/ab/)
             L.mm_prebuilt_window_sizes.argtypes = [C.c_int, C.c_int, u32p, C.c_int]
             L.mm_prebuilt_window_sizes.restype = C.c_int
+        if hasattr(L, "mm_plan_prepare"):  # (absent from older libraries loaded through MM_LIB_PATH for A/B runs)
+            L.mm_prebuilt_flavour_window_sizes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, u32p, C.c_int]
+            L.mm_prebuilt_flavour_window_sizes.restype = C.c_int
+            L.mm_plan_prepare.argtypes = [vp, vp, C.c_uint32, C.POINTER(PrepareReport)]
+            L.mm_jit_stats.argtypes = [u64p]
         L.mm_run_device_async.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
                                           C.c_uint64, vp, vp, C.c_uint64, vp]
         L.mm_run_device.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
@@ -309,6 +323,7 @@ EXPORTED_SYMBOLS = [
     "mm_run_packed_reads_skip_ambiguous_host",
     "mm_values_u64_reads_device_async", "mm_values_u128_reads_device_async", "mm_values_u64_reads_host",
     "mm_values_u128_reads_host", "mm_debug_values_read_of", "mm_values_reads_lds_stage",
+    "mm_prebuilt_flavour_window_sizes", "mm_plan_prepare", "mm_jit_stats",
 ]
 
 
@@ -319,6 +334,23 @@ def prebuilt_window_sizes(canonical: bool, reads: bool = False) -> list:
     buf = (C.c_uint32 * max(1, n))()
     L.mm_prebuilt_window_sizes(int(canonical), int(reads), buf, n)
     return [int(x) for x in buf[:n]]
+
+
+def prebuilt_flavour_window_sizes(canonical: bool, reads: bool = False, mode: int = 0, super_kmers: bool = False) -> list:
+    """Window sizes with a prebuilt fused kernel of one flavour (mm_prebuilt_flavour_window_sizes): ``mode`` is
+    MM_MINIMIZERS / MM_CLOSED_SYNCMERS / MM_OPEN_SYNCMERS, ``super_kmers`` minimizers with super-k-mer indices."""
+    L = lib()
+    n = L.mm_prebuilt_flavour_window_sizes(int(canonical), int(reads), int(mode), int(super_kmers), None, 0)
+    buf = (C.c_uint32 * max(1, n))()
+    L.mm_prebuilt_flavour_window_sizes(int(canonical), int(reads), int(mode), int(super_kmers), buf, n)
+    return [int(x) for x in buf[:n]]
+
+
+def jit_stats() -> dict:
+    """Process-wide counters of the run-time compiler (mm_jit_stats); nothing resets them, take differences."""
+    out = (C.c_uint64 * 4)()
+    _check(lib().mm_jit_stats(out))
+    return {"compiled": int(out[0]), "from_disk": int(out[1]), "hits": int(out[2]), "failed": int(out[3])}
 
 
 def text_prebuilt_window_sizes(canonical: bool) -> list:
@@ -854,6 +886,21 @@ class Builder:
                 if self._text_plan is None:
                     self._text_plan = Plan(self.k, self.w, self.canonical, self.mode, self._text_hasher, text=True)
         return self._text_plan
+
+    def prepare(self, ws=None, sequence=True, reads=False, super_kmers=None, text=False) -> dict:
+        """Get every kernel this builder's runs dispatch to ready on the workspace's device before the first run
+        (mm_plan_prepare): loads prebuilt kernels, compiles the others or reads them from the disk cache, launches
+        nothing.  ``super_kmers=None``: as this builder was configured.  ``text``: the byte-text plan instead.
+        Returns the report: kernels, compiled, from_disk, unavailable."""
+        if super_kmers is None:
+            super_kmers = self._sk is not None
+        what = ((PREPARE_SEQUENCE if sequence else 0) | (PREPARE_READS if reads else 0) |
+                (PREPARE_SUPERKMERS if super_kmers else 0))
+        rep = PrepareReport()
+        plan = self.text_plan() if text else self.plan()
+        _check(lib().mm_plan_prepare(plan.h, (ws or self._ws()).h, what, C.byref(rep)))
+        return {"kernels": rep.kernels, "compiled": rep.compiled, "from_disk": rep.from_disk,
+                "unavailable": rep.unavailable}
 
     # -- host sequences -------------------------------------------------
     def run(self, seq, min_pos: list) -> Output:

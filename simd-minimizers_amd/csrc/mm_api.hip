@@ -1027,6 +1027,53 @@ int mm_prebuilt_window_sizes(int canonical_windows, int reads_mode, uint32_t *ou
     return mm::fused_prebuilt_windows(canonical_windows != 0, reads_mode != 0, out, capacity < 0 ? 0 : capacity);
 }
 
+int mm_prebuilt_flavour_window_sizes(int canonical_windows, int reads_mode, mm_mode_t mode, int super_kmers, uint32_t *out,
+                                     int capacity) {
+    if ((int)mode < 0 || (int)mode > 2) return 0;
+    return mm::fused_prebuilt_flavour_windows(canonical_windows != 0, reads_mode != 0, (uint32_t)mode, super_kmers != 0, out,
+                                              capacity < 0 ? 0 : capacity);
+}
+
+int mm_jit_stats(uint64_t out[4]) {
+    if (!out) return MM_ERR_NULL;
+    mm::jit_stats(out);
+    return MM_OK;
+}
+
+// Builder::run (src/lib.rs:378) is compiled code whose first call costs what every call costs; here a plan's first run
+// loads its kernels' code objects and may compile one.  mm_plan_prepare does exactly that part of a first run - through
+// the launcher's own choice of kernel, so the two cannot disagree - and launches nothing.
+int mm_plan_prepare(const mm_plan_t *plan, mm_workspace_t *ws, uint32_t what, mm_prepare_report_t *report) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (report) *report = mm_prepare_report_t{0, 0, 0, 0};
+    if (!plan || !ws) return MM_ERR_NULL;
+    if (what & ~(uint32_t)(MM_PREPARE_SEQUENCE | MM_PREPARE_READS | MM_PREPARE_SUPERKMERS)) return MM_ERR_BAD_MODE;
+    if ((what & MM_PREPARE_SUPERKMERS) && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;  // src/lib.rs:339
+    const bool sequence = (what & MM_PREPARE_SEQUENCE) != 0, reads = (what & MM_PREPARE_READS) != 0;
+    if (!sequence && !reads) return MM_OK;
+    MM_HIP(set_device(ws->device));
+    mm::PrepareCounts c;
+    if (plan->text) {
+        // byte text: every kernel is prebuilt - the fused text kernel with its batch twin, or the generic family's
+        if (!ws->force_generic && mm::text_walk_supported(plan->k, plan->w))
+            MM_HIP(mm::text_walk_prepare(plan->w, plan->canonical_windows != 0, plan->tt.canonical != 0, plan->mode, &c.kernels));
+        else
+            MM_HIP(mm::generic_prepare(true, &c.kernels));
+    } else if (ws->force_generic) {
+        MM_HIP(mm::generic_prepare(false, &c.kernels));
+    } else {
+        MM_HIP(mm::fused_prepare(plan->k, plan->w, plan->canonical_windows, (int)plan->ht.canonical, plan->mode, sequence, reads,
+                                 (what & MM_PREPARE_SUPERKMERS) != 0, &c));
+        if (c.unavailable) {
+            // such runs take the generic family (reads one launch per read): have it loaded, and say why
+            MM_HIP(mm::generic_prepare(false, &c.kernels));
+            g_last_error = std::string("fused kernel unavailable, generic family used: ") + mm::fused_unavailable_reason();
+        }
+    }
+    if (report) *report = mm_prepare_report_t{c.kernels, c.compiled, c.from_disk, c.unavailable};
+    return MM_OK;
+}
+
 // Ambiguity bits of a PackedNSeq as they cross the ABI (null d_amb = plain PackedSeq).
 struct AmbArgs {
     const void *d_amb;
@@ -1373,7 +1420,7 @@ static int batch_issue(const mm_plan_t *plan, mm_workspace_t *ws, uint64_t n_seq
         const uint64_t per_seq_limit = 8 * tile_w < 750000ull ? 8 * tile_w : 750000ull;
         const bool short_seqs = total_w / nonempty < per_seq_limit;
         if ((short_seqs || lane_table_policy() == 1) &&
-            mm::fused_reads_supported(plan->w, plan->canonical_windows, (int)plan->ht.canonical, d_out_sk ? 1u : plan->mode)) {
+            mm::fused_reads_supported(plan->w, plan->canonical_windows, (int)plan->ht.canonical, plan->mode, d_out_sk != nullptr)) {
             uintptr_t lo = ~(uintptr_t)0, hi = 0;
             uint32_t max_len = 0;
             for (uint64_t s = 0; s < n_seqs; ++s) {
@@ -1673,11 +1720,8 @@ static int run_reads_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, const
     int r = make_view(d_packed, packed_bytes, base_offset, span, &view);
     if (r) return r;
 
-    // (super-k-mer indices: run-time specialised kernel, like the syncmer modes)
-    bool fast = !ws->force_generic &&
-                (d_out_sk ? mm::fused_reads_supported(plan->w, plan->canonical_windows, (int)plan->ht.canonical, 1)
-                          : mm::fused_reads_supported(plan->w, plan->canonical_windows, (int)plan->ht.canonical,
-                                                      plan->mode));
+    bool fast = !ws->force_generic && mm::fused_reads_supported(plan->w, plan->canonical_windows, (int)plan->ht.canonical,
+                                                                plan->mode, d_out_sk != nullptr);
     if (fast) {
         mm::ReadsArgs a;
         a.seq = view;

@@ -229,8 +229,11 @@ struct KernelRef {
 thread_local std::string t_jit_error;
 
 // k: the plan's k-mer length for launches that may take a fixed-k instance (FusedParams::k is then that k), 0: never
-KernelRef resolve_kernel(uint32_t w, int canonical_windows, int hasher_canonical, uint32_t mode, bool sk, uint32_t k = 0) {
+// how (optional): kJitHit for a prebuilt instance, else what jit_fused_kernel did
+KernelRef resolve_kernel(uint32_t w, int canonical_windows, int hasher_canonical, uint32_t mode, bool sk, uint32_t k = 0,
+                         int *how = nullptr) {
     KernelRef kr;
+    if (how) *how = kJitHit;
     if (mode > 2) return kr;
     const bool force_jit = force_jit_wanted();  // tuning experiments (experiments build only)
     if (k != 0 && mode == 0 && !sk && !force_jit) {
@@ -245,7 +248,7 @@ KernelRef resolve_kernel(uint32_t w, int canonical_windows, int hasher_canonical
         return kr;
     }
     kr.mod = jit_fused_kernel(w, canonical_windows != 0, hasher_canonical != 0, (int)mode, mode == 0 && sk,
-                              false, &t_jit_error);
+                              false, &t_jit_error, false, how);
     return kr;
 }
 
@@ -945,12 +948,46 @@ const FusedReadsInstance *find_reads_instance(uint32_t w, int canonical_windows,
     }
     return nullptr;
 }
+
+// closed syncmers, open syncmers, minimizers + super-k-mers of reads mode (mm_fused_inst_reads_f.hip .. _m.hip)
+const FusedReadsFlavourInstance *find_reads_flavour_instance(uint32_t w, int canonical_windows, int hasher_canonical) {
+    using Getter = const FusedReadsFlavourInstance *(*)(int *);
+    static const Getter kGroups[] = {fused_reads_flavours_f, fused_reads_flavours_g, fused_reads_flavours_h,
+                                     fused_reads_flavours_i, fused_reads_flavours_j, fused_reads_flavours_k,
+                                     fused_reads_flavours_l, fused_reads_flavours_m};
+    for (Getter get : kGroups) {
+        int n = 0;
+        const FusedReadsFlavourInstance *inst = get(&n);
+        for (int i = 0; i < n; ++i)
+            if (inst[i].w == w && inst[i].canon == (canonical_windows != 0) &&
+                inst[i].hash_rc == (hasher_canonical != 0))
+                return &inst[i];
+    }
+    return nullptr;
+}
+
+// the prebuilt reads-mode kernel of a flavour, or null (sk: minimizers with super-k-mer indices)
+KernelFn find_reads_kernel(uint32_t w, int canonical_windows, int hasher_canonical, uint32_t mode, bool sk) {
+    if (mode > 2) return nullptr;
+    if (mode == 0 && !sk) {
+        const FusedReadsInstance *inst = find_reads_instance(w, canonical_windows, hasher_canonical);
+        return inst ? inst->fn : nullptr;
+    }
+    const FusedReadsFlavourInstance *inst = find_reads_flavour_instance(w, canonical_windows, hasher_canonical);
+    return inst ? inst->fn[mode == 0 ? 2 : mode - 1] : nullptr;
+}
 }  // namespace
 
 int fused_prebuilt_windows(bool canonical, bool reads, uint32_t *out, int capacity) {
+    return fused_prebuilt_flavour_windows(canonical, reads, 0, false, out, capacity);
+}
+
+int fused_prebuilt_flavour_windows(bool canonical, bool reads, uint32_t mode, bool sk, uint32_t *out, int capacity) {
     int n = 0;
+    if (mode > 2 || (sk && mode != 0)) return 0;
     for (uint32_t w = 1; w <= kJitMaxW; ++w) {
-        const bool have = reads ? find_reads_instance(w, canonical, canonical) != nullptr
+        // (a sequence-mode instance carries all four flavours)
+        const bool have = reads ? find_reads_kernel(w, canonical, canonical, mode, sk) != nullptr
                                 : find_instance(w, canonical, canonical) != nullptr;
         if (!have) continue;
         if (out && n < capacity) out[n] = w;
@@ -959,10 +996,10 @@ int fused_prebuilt_windows(bool canonical, bool reads, uint32_t *out, int capaci
     return n;
 }
 
-bool fused_reads_supported(uint32_t w, int canonical_windows, int hasher_canonical, uint32_t mode) {
+bool fused_reads_supported(uint32_t w, int canonical_windows, int hasher_canonical, uint32_t mode, bool sk) {
     if (mode > 2) return false;
-    // (syncmer modes have no prebuilt reads-mode kernels: compiled at first use, cached on disk)
-    if (mode == 0 && find_reads_instance(w, canonical_windows, hasher_canonical)) return true;
+    // (flavours and window sizes without a prebuilt reads-mode kernel: compiled at first use, cached on disk)
+    if (find_reads_kernel(w, canonical_windows, hasher_canonical, mode, sk && mode == 0)) return true;
     return jit_enabled() && w >= 1 && w <= kJitMaxW;
 }
 
@@ -972,20 +1009,55 @@ uint64_t fused_reads_status_words(const ReadsArgs &a) {
 uint64_t fused_status_stride() { return status_stride_host(); }
 
 namespace {
-KernelRef resolve_reads_kernel(const ReadsArgs &a) {
+// how: as for resolve_kernel
+KernelRef resolve_reads_kernel(uint32_t w, int canonical_windows, int hasher_canonical, uint32_t mode, bool sk,
+                               int *how = nullptr) {
     KernelRef kr;
-    const bool sk = a.out.sk != nullptr && a.mode == 0;
+    if (how) *how = kJitHit;
+    if (mode > 2) return kr;
+    sk = sk && mode == 0;
     // (experiments build: MM_JIT_FORCE / MM_DEBUG route the reads-mode launches through the run-time specialisation too)
-    const FusedReadsInstance *inst =
-        (a.mode == 0 && !sk && !force_jit_wanted()) ? find_reads_instance(a.w, a.canonical_windows, (int)a.ht.canonical) : nullptr;
-    if (inst)
-        kr.host = inst->fn;
-    else
-        kr.mod = jit_fused_kernel(a.w, a.canonical_windows != 0, a.ht.canonical != 0, (int)a.mode, sk, true,
-                                  &t_jit_error);
+    kr.host = force_jit_wanted() ? nullptr : find_reads_kernel(w, canonical_windows, hasher_canonical, mode, sk);
+    if (!kr.host)
+        kr.mod = jit_fused_kernel(w, canonical_windows != 0, hasher_canonical != 0, (int)mode, sk, true, &t_jit_error,
+                                  false, how);
     return kr;
 }
+KernelRef resolve_reads_kernel(const ReadsArgs &a) {
+    return resolve_reads_kernel(a.w, a.canonical_windows, (int)a.ht.canonical, a.mode, a.out.sk != nullptr);
+}
 }  // namespace
+
+// ---- mm_plan_prepare: obtain every kernel a plan's runs dispatch to, as their first launch would, without a launch
+namespace {
+hipError_t account(const KernelRef &kr, int how, PrepareCounts *c) {
+    if (kr.host) return load_kernels({reinterpret_cast<const void *>(kr.host)}, &c->kernels);
+    ++c->kernels;
+    if (!kr) ++c->unavailable;
+    c->compiled += how == kJitCompiled ? 1u : 0u;
+    c->from_disk += how == kJitFromDisk ? 1u : 0u;
+    return hipSuccess;
+}
+}  // namespace
+
+hipError_t fused_prepare(uint32_t k, uint32_t w, int canonical_windows, int hasher_canonical, uint32_t mode, bool sequence,
+                         bool reads, bool sk, PrepareCounts *c) {
+    if (mode > 2) return hipSuccess;
+    t_jit_error.clear();
+    int how = kJitHit;
+    for (int with_sk = 0; with_sk <= (sk && mode == 0 ? 1 : 0); ++with_sk) {
+        if (sequence) {
+            // (w > kJitMaxW has neither instance nor run-time specialisation: resolve_kernel's jit call says so)
+            const KernelRef kr = resolve_kernel(w, canonical_windows, hasher_canonical, mode, with_sk != 0, k, &how);
+            if (const hipError_t e = account(kr, how, c)) return e;
+        }
+        if (reads) {
+            const KernelRef kr = resolve_reads_kernel(w, canonical_windows, hasher_canonical, mode, with_sk != 0, &how);
+            if (const hipError_t e = account(kr, how, c)) return e;
+        }
+    }
+    return reads ? lane_table_prepare(&c->kernels) : hipSuccess;
+}
 
 // ---- lane-table launches (round 6; mm_lanes.hip, FusedParams::lane_segs)
 // Lane length: the default lanes of the sequence mode with 16-bit list entries (the reads-mode kernels keep 16 bits) -

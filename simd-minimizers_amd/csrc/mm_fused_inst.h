@@ -61,6 +61,33 @@ const FusedReadsInstance *fused_reads_instances_c(int *count);
 const FusedReadsInstance *fused_reads_instances_d(int *count);
 const FusedReadsInstance *fused_reads_instances_e(int *count);
 
+// the other three flavours of reads mode (closed syncmers, open syncmers, minimizers + super-k-mer indices) for the
+// window sizes 5, 7, 11, 15, 17, 19, 21, 31 - each of them also in the minimizer table above; every other window size
+// of these flavours is specialised at first use.  mm_fused_inst_reads_f.hip .. _m.hip: a canonical window size and a
+// forward one per file, the large canonical walks beside the small forward ones, so that the files compile in about
+// the same time.
+struct FusedReadsFlavourInstance {
+    uint32_t w;
+    bool canon;
+    bool hash_rc;
+    FusedKernelFn fn[3];  // closed syncmers, open syncmers, minimizers + super-k-mers
+};
+#define MM_READS_FLAVOURS(W, C, R)                                                         \
+    {                                                                                      \
+        W, C, R, {                                                                         \
+            &fused_kernel<W, C, R, 1, false, true>, &fused_kernel<W, C, R, 2, false, true>, \
+                &fused_kernel<W, C, R, 0, true, true>                                      \
+        }                                                                                  \
+    }
+const FusedReadsFlavourInstance *fused_reads_flavours_f(int *count);
+const FusedReadsFlavourInstance *fused_reads_flavours_g(int *count);
+const FusedReadsFlavourInstance *fused_reads_flavours_h(int *count);
+const FusedReadsFlavourInstance *fused_reads_flavours_i(int *count);
+const FusedReadsFlavourInstance *fused_reads_flavours_j(int *count);
+const FusedReadsFlavourInstance *fused_reads_flavours_k(int *count);
+const FusedReadsFlavourInstance *fused_reads_flavours_l(int *count);
+const FusedReadsFlavourInstance *fused_reads_flavours_m(int *count);
+
 // walk kernels of the split path (walk_kernel), mm_walk_inst.hip
 struct WalkInstance {
     uint32_t w;

@@ -294,4 +294,14 @@ uint64_t generic_status_words(uint64_t round_windows) {
     return (round_windows + kWinPerBlockC - 1) / kWinPerBlockC + 1;
 }
 
+// mm_plan_prepare: this family's kernels, loaded on the current device without a launch
+hipError_t generic_prepare(bool text, uint32_t *kernels) {
+    return load_kernels({text ? reinterpret_cast<const void *>(generic_text_hash_kernel)
+                              : reinterpret_cast<const void *>(generic_hash_kernel),
+                         text ? reinterpret_cast<const void *>(generic_text_window_kernel)
+                              : reinterpret_cast<const void *>(generic_window_kernel),
+                         reinterpret_cast<const void *>(generic_compact_kernel)},
+                        kernels);
+}
+
 }  // namespace mm

@@ -9,9 +9,11 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -107,9 +109,20 @@ void write_file_atomic(const std::string &dir, const std::string &path, const st
     if (!ok || rename(tmp.c_str(), path.c_str()) != 0) remove(tmp.c_str());
 }
 
+// One entry per "<device>:<kernel name>|<defs>".  g_mu guards the map alone and is held for a look-up or an insert, never
+// across a compile; an entry's own mutex is held by the thread that compiles or loads it.  So a thread that asks for a
+// kernel that is already loaded takes two uncontended locks, threads that ask for the same missing kernel compile it once
+// (the others wait on the entry and then count as hits), and threads that ask for different kernels compile side by side.
+struct JitEntry {
+    std::mutex mu;
+    bool done = false;
+    hipFunction_t fn = nullptr;  // null once done: the compile or the load failed, `err` says why (never retried)
+    std::string err;
+};
 std::mutex g_mu;
-std::map<std::string, hipFunction_t> g_functions;  // "<device>:<kernel name>"
-std::map<std::string, std::string> g_failed;       // kernel name -> why (do not retry)
+std::map<std::string, std::shared_ptr<JitEntry>> g_entries;
+// process-wide counters (mm_jit_stats): compiles, loads from the disk cache, hits, failures
+std::atomic<uint64_t> g_n_compiled{0}, g_n_from_disk{0}, g_n_hits{0}, g_n_failed{0};
 
 // "gfx950" of the current device's gcnArchName ("gfx950:sramecc+:xnack-")
 std::string device_arch() {
@@ -190,9 +203,10 @@ std::string fused_kernel_name(uint32_t w, bool canon, bool hash_rc, int mode, bo
 
 // Compiled-and-loaded kernel for the current device, or nullptr (then *err says why).
 hipFunction_t jit_fused_kernel(uint32_t w, bool canon, bool hash_rc, int mode, bool sk, bool reads,
-                               std::string *err, bool walk) {
+                               std::string *err, bool walk, int *how) {
     std::string local_err;
     if (!err) err = &local_err;
+    if (how) *how = kJitFailed;
     if (!jit_enabled() || w == 0 || w > kJitMaxW) {
         *err = "run-time specialisation disabled or w out of its range";
         return nullptr;
@@ -211,14 +225,29 @@ hipFunction_t jit_fused_kernel(uint32_t w, bool canon, bool hash_rc, int mode, b
     const char *defs = user_defs;  // (always null: the product compiles the source as it is)
 #endif
     const std::string key = std::to_string(device) + ":" + name + "|" + (defs ? defs : "");
-    std::lock_guard<std::mutex> lock(g_mu);
-    auto it = g_functions.find(key);
-    if (it != g_functions.end()) return it->second;
-    auto bad = g_failed.find(key);
-    if (bad != g_failed.end()) {
-        *err = bad->second;
-        return nullptr;
+    std::shared_ptr<JitEntry> entry;
+    {
+        std::lock_guard<std::mutex> lock(g_mu);
+        std::shared_ptr<JitEntry> &slot = g_entries[key];
+        if (!slot) slot = std::make_shared<JitEntry>();
+        entry = slot;
     }
+    std::lock_guard<std::mutex> lock(entry->mu);
+    if (entry->done) {
+        if (!entry->fn) {
+            *err = entry->err;
+            return nullptr;
+        }
+        g_n_hits.fetch_add(1, std::memory_order_relaxed);
+        if (how) *how = kJitHit;
+        return entry->fn;
+    }
+    auto fail = [&]() -> hipFunction_t {
+        entry->err = *err;
+        entry->done = true;
+        g_n_failed.fetch_add(1, std::memory_order_relaxed);
+        return nullptr;
+    };
 
     // disk cache: <hash of source, name, compiler>.hsaco + .name (the lowered symbol)
     int rtc_major = 0, rtc_minor = 0;
@@ -238,10 +267,7 @@ hipFunction_t jit_fused_kernel(uint32_t w, bool canon, bool hash_rc, int mode, b
         from_disk = true;
     }
     if (!from_disk) {
-        if (!compile(name, code, lowered, err)) {
-            g_failed[key] = *err;
-            return nullptr;
-        }
+        if (!compile(name, code, lowered, err)) return fail();
         if (!path.empty()) {
             write_file_atomic(dir, path, code);
             write_file_atomic(dir, path + ".name", std::vector<char>(lowered.begin(), lowered.end()));
@@ -254,6 +280,7 @@ hipFunction_t jit_fused_kernel(uint32_t w, bool canon, bool hash_rc, int mode, b
     if (e != hipSuccess && from_disk) {
         // a stale or damaged cache entry: compile afresh once
         code.clear();
+        from_disk = false;
         if (compile(name, code, lowered, err)) {
             write_file_atomic(dir, path, code);
             write_file_atomic(dir, path + ".name", std::vector<char>(lowered.begin(), lowered.end()));
@@ -263,11 +290,20 @@ hipFunction_t jit_fused_kernel(uint32_t w, bool canon, bool hash_rc, int mode, b
     }
     if (e != hipSuccess || !fn) {
         *err = std::string("loading the specialised kernel failed: ") + hipGetErrorString(e);
-        g_failed[key] = *err;
-        return nullptr;
+        return fail();
     }
-    g_functions[key] = fn;
+    entry->fn = fn;
+    entry->done = true;
+    (from_disk ? g_n_from_disk : g_n_compiled).fetch_add(1, std::memory_order_relaxed);
+    if (how) *how = from_disk ? kJitFromDisk : kJitCompiled;
     return fn;
+}
+
+void jit_stats(uint64_t out[4]) {
+    out[0] = g_n_compiled.load(std::memory_order_relaxed);
+    out[1] = g_n_from_disk.load(std::memory_order_relaxed);
+    out[2] = g_n_hits.load(std::memory_order_relaxed);
+    out[3] = g_n_failed.load(std::memory_order_relaxed);
 }
 
 }  // namespace mm

@@ -220,4 +220,11 @@ int launch_lane_table(const SegSource &src, uint64_t n_reads, uint32_t l, const 
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// mm_plan_prepare: the table's four kernels, loaded on the current device without a launch
+hipError_t lane_table_prepare(uint32_t *kernels) {
+    return load_kernels({reinterpret_cast<const void *>(seg_count_kernel), reinterpret_cast<const void *>(seg_scan_kernel),
+                         reinterpret_cast<const void *>(seg_first_kernel), reinterpret_cast<const void *>(seg_fill_kernel)},
+                        kernels);
+}
+
 }  // namespace mm

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -79,6 +80,37 @@ int launch_fused(const RunArgs &a, hipStream_t stream);
 const char *fused_unavailable_reason();
 // window sizes with a prebuilt instance (sequence mode / reads mode), ascending; returns their number
 int fused_prebuilt_windows(bool canonical, bool reads, uint32_t *out, int capacity);
+// the same per flavour: mode 0 / 1 / 2, sk = minimizers with super-k-mer indices (mode 0 only; 0 sizes otherwise)
+int fused_prebuilt_flavour_windows(bool canonical, bool reads, uint32_t mode, bool sk, uint32_t *out, int capacity);
+
+// ---- mm_plan_prepare: every kernel a plan's runs dispatch to is obtained as their first launch would obtain it -
+// prebuilt instances are loaded onto the current device, the others compiled or read from the disk cache - and nothing
+// is launched.  `sequence` / `reads`: the kernels of sequence (and tiled batch) runs / of reads-mode and lane-table
+// launches with the table's own kernels; `sk`: the super-k-mer twins as well (mode 0).  Adds to *c; returns the first HIP
+// error.  A kernel that cannot be had counts as unavailable and fused_unavailable_reason() says why.
+struct PrepareCounts {
+    uint32_t kernels = 0, compiled = 0, from_disk = 0, unavailable = 0;
+};
+// Makes the runtime load the code objects that hold these prebuilt kernels (host symbols) on the current device, without
+// a launch; adds their number to *kernels.  Returns the first HIP error.
+inline hipError_t load_kernels(std::initializer_list<const void *> fns, uint32_t *kernels) {
+    for (const void *fn : fns) {
+        hipFuncAttributes fa{};
+        const hipError_t e = hipFuncGetAttributes(&fa, fn);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return e;
+        }
+        ++*kernels;
+    }
+    return hipSuccess;
+}
+hipError_t fused_prepare(uint32_t k, uint32_t w, int canonical_windows, int hasher_canonical, uint32_t mode, bool sequence,
+                         bool reads, bool sk, PrepareCounts *c);
+// the prebuilt kernels of the other families, loaded the same way (*kernels: their number is added)
+hipError_t lane_table_prepare(uint32_t *kernels);
+hipError_t generic_prepare(bool text, uint32_t *kernels);
+hipError_t text_walk_prepare(uint32_t w, bool canon, bool hash_rc, uint32_t mode, uint32_t *kernels);
 
 // ---- split path of the fused family (walk_kernel in mm_fused_impl.h + mm_split.hip): the walk dumps its lists
 // and exits, persistent expander workgroups on a second stream turn them into positions
@@ -106,7 +138,7 @@ struct ReadsArgs {
     SeqView seq;
     HashTables ht;
     uint32_t k, w;
-    uint32_t mode;  // 0 minimizers (prebuilt instances), 1 / 2 closed / open syncmers (run-time specialised)
+    uint32_t mode;  // 0 minimizers, 1 / 2 closed / open syncmers (prebuilt at some window sizes, else run-time specialised)
     int canonical_windows;
     uint64_t n_reads;
     uint32_t read_stride, read_len;
@@ -120,7 +152,7 @@ struct ReadsArgs {
     uint32_t status_epoch = 0;  // as in RunArgs
     hipEvent_t timing_start, timing_stop;
 };
-bool fused_reads_supported(uint32_t w, int canonical_windows, int hasher_canonical, uint32_t mode = 0);
+bool fused_reads_supported(uint32_t w, int canonical_windows, int hasher_canonical, uint32_t mode = 0, bool sk = false);
 uint64_t fused_reads_status_words(const ReadsArgs &a);
 // returns 0, -1 (HIP failure), -2 (no instance), -3 (reads too long for the LDS lists)
 int launch_fused_reads(const ReadsArgs &a, hipStream_t stream);
@@ -158,8 +190,13 @@ int launch_fused_segments(const ReadsArgs &a, const SegSource &src, const SegPla
 constexpr uint32_t kJitMaxW = 128;  // ring registers: 256 VGPRs + AGPRs still hold W = 128 without scratch
 bool jit_enabled();                 // MM_JIT=0 switches it off (then such w take the generic family)
 // walk = true: mm::walk_kernel (the split path's walk) instead of mm::fused_kernel
+// *how (optional): what the call did to obtain the kernel
+enum JitHow { kJitFailed = -1, kJitHit = 0, kJitCompiled = 1, kJitFromDisk = 2 };
 hipFunction_t jit_fused_kernel(uint32_t w, bool canon, bool hash_rc, int mode, bool sk, bool reads,
-                               std::string *err, bool walk = false);
+                               std::string *err, bool walk = false, int *how = nullptr);
+// process-wide counters since the library was loaded: hiprtc compiles, loads from the disk cache, requests answered with
+// a kernel that was already loaded, compiles or loads that failed.  Nothing resets them.
+void jit_stats(uint64_t out[4]);
 
 // ---- generic family (mm_generic.hip): any k / w
 uint64_t generic_scratch_bytes(uint64_t round_windows, uint32_t w);

@@ -45,17 +45,31 @@ int text_prebuilt_windows(uint32_t *out, int capacity) {
 uint64_t text_walk_tiles(uint64_t windows) { return (windows + kTextTile - 1) / kTextTile; }
 uint64_t text_batch_tiles(uint64_t n_chars) { return text_walk_tiles(n_chars + 1); }
 
+namespace {
+TextWalkFn pick_window(uint32_t w, bool canon, bool hash_rc, uint32_t mode, bool batch) {
+    switch (w) {
+        case 5: return pick<5>(canon, hash_rc, mode, batch);
+        case 11: return pick<11>(canon, hash_rc, mode, batch);
+        case 19: return pick<19>(canon, hash_rc, mode, batch);
+        default: return pick<0>(canon, hash_rc, mode, batch);
+    }
+}
+}  // namespace
+
+// mm_plan_prepare: the kernels of a text plan's single and batch launches, loaded on the current device without a launch
+// (every instance is prebuilt: nothing to compile)
+hipError_t text_walk_prepare(uint32_t w, bool canon, bool hash_rc, uint32_t mode, uint32_t *kernels) {
+    return load_kernels({reinterpret_cast<const void *>(pick_window(w, canon, hash_rc, mode, false)),
+                         reinterpret_cast<const void *>(pick_window(w, canon, hash_rc, mode, true)),
+                         reinterpret_cast<const void *>(text_batch_tiles_kernel)},
+                        kernels);
+}
+
 int launch_text_walk(const TextRunArgs &a, hipStream_t stream) {
     if (!text_walk_supported(a.k, a.w)) return -2;
     const bool canon = a.canonical_windows != 0;
     const bool hash_rc = a.hash_rc;
-    TextWalkFn fn;
-    switch (a.w) {
-        case 5: fn = pick<5>(canon, hash_rc, a.mode, a.batch); break;
-        case 11: fn = pick<11>(canon, hash_rc, a.mode, a.batch); break;
-        case 19: fn = pick<19>(canon, hash_rc, a.mode, a.batch); break;
-        default: fn = pick<0>(canon, hash_rc, a.mode, a.batch); break;
-    }
+    const TextWalkFn fn = pick_window(a.w, canon, hash_rc, a.mode, a.batch);
     TextWalkParams p;
     p.text = a.text;
     p.n = a.n;
