@@ -400,8 +400,8 @@ int mm_values_u128_host(mm_workspace_t *ws, const uint8_t *packed, uint64_t base
  * len / canonical as for mm_values_u64_device_async (len = mm_plan_value_len).  MM_ERR_NULL for a NULL workspace, and for
  * NULL d_packed / d_pos / d_out_offsets / d_values when there is work; MM_ERR_VALUE_LEN for len == 0, len > 32 (u64) or
  * len > 64 (u128); MM_ERR_CAPACITY when base_offset, or a fixed-stride layout's last read, starts past packed_bytes;
- * n_reads == 0 or n_pos_max == 0 returns MM_OK with nothing launched.  Not covered: mm_run_batch_device's separately
- * allocated sequences, byte text. */
+ * n_reads == 0 or n_pos_max == 0 returns MM_OK with nothing launched.  mm_run_batch_device's separately allocated
+ * sequences have their own call, mm_values_u64_batch_device_async below.  Not covered: byte text. */
 int mm_values_u64_reads_device_async(mm_workspace_t *ws, const void *d_packed, uint64_t packed_bytes,
                                      uint64_t base_offset, uint64_t n_reads,
                                      const uint64_t *d_read_starts /* [n_reads + 1] or NULL */, uint32_t read_stride,
@@ -433,6 +433,47 @@ int mm_values_u128_reads_host(mm_workspace_t *ws, const uint8_t *packed, uint64_
 int mm_debug_values_read_of(const uint64_t *offsets /* [n_reads + 1] */, uint64_t n_reads, const uint64_t *idx,
                             uint64_t n, int64_t *out_read);
 uint32_t mm_values_reads_lds_stage(void);
+
+/* Output::values_u64 / values_u128 (src/lib.rs:584-629) of EVERY sequence of a device batch in one launch: what the loop
+ * over the contigs (bench/src/bin/paper.rs:410-431: Builder::run per sequence) and Output::values_* per sequence computes,
+ * in place of one mm_values_*_device_async call per sequence.  The inputs are what mm_run_batch_device takes and returns;
+ * every array but d_pos and d_values is a HOST array:
+ *   n_seqs, d_packed [n_seqs], packed_bytes [n_seqs], base_offsets [n_seqs] or NULL, n_bases [n_seqs]
+ *                            the sequences as mm_run_batch_device took them: separate device buffers at any byte
+ *                            alignment, in any address order, any distance apart
+ *   d_pos                    the sequence-local positions, back to back (device; any 4-byte boundary)
+ *   offsets [n_seqs + 1]     as mm_run_batch_device wrote them (offsets[0] == 0): value i belongs to the sequence s with
+ *                            offsets[s] <= i < offsets[s + 1] and is the k-mer at base base_offsets[s] + d_pos[i] of
+ *                            d_packed[s]; the count is offsets[n_seqs]
+ *   d_values                 device, 8-byte aligned; u64: offsets[n_seqs] words, u128: twice that ({lo, hi} per value);
+ *                            nothing past them is written
+ * len / canonical as for mm_values_u64_device_async (len = mm_plan_value_len).  No byte outside [d_packed[s], d_packed[s] +
+ * packed_bytes[s]) is loaded, whatever d_pos holds: a position with pos + len > n_bases[s] gives the value of the sequence's
+ * bytes zero-extended past packed_bytes[s], and otherwise whatever the bytes hold.  A sequence without values is never
+ * dereferenced: its pointer may be NULL and its packed_bytes 0.
+ * The kernel is queued on the workspace's stream and the call does not wait for it; the host arrays are the caller's again
+ * on return (the tables are staged through page-locked memory of the workspace's own).
+ * Refused before anything is touched: MM_ERR_NULL for a NULL workspace, for NULL arrays when there is work and for a NULL
+ * d_packed[s] of a sequence that has values; MM_ERR_VALUE_LEN for len == 0, len > 32 (u64) or len > 64 (u128);
+ * MM_ERR_UNSORTED for offsets that decrease; MM_ERR_CAPACITY for a sequence with values whose (base_offset + n_bases + 3) / 4
+ * exceeds its packed_bytes; MM_ERR_LEN_TOO_LARGE for n_seqs >= 2^32.  n_seqs == 0 or offsets[n_seqs] == 0 returns MM_OK with
+ * nothing launched.  Not covered: byte text. */
+int mm_values_u64_batch_device_async(mm_workspace_t *ws, uint64_t n_seqs, const void *const *d_packed,
+                                     const uint64_t *packed_bytes, const uint64_t *base_offsets /* or NULL */,
+                                     const uint64_t *n_bases, uint32_t len, int canonical, const uint32_t *d_pos,
+                                     const uint64_t *offsets /* host, [n_seqs + 1] */, uint64_t *d_values);
+int mm_values_u128_batch_device_async(mm_workspace_t *ws, uint64_t n_seqs, const void *const *d_packed,
+                                      const uint64_t *packed_bytes, const uint64_t *base_offsets /* or NULL */,
+                                      const uint64_t *n_bases, uint32_t len, int canonical, const uint32_t *d_pos,
+                                      const uint64_t *offsets /* host, [n_seqs + 1] */, uint64_t *d_values);
+/* Diagnostics of the batch values kernels (Output::values_*, src/lib.rs:584-629, per sequence of the loop
+ * bench/src/bin/paper.rs:410-431; no device needed).  mm_values_batch_lds_stage: the entries (an offset and a 32-byte
+ * sequence descriptor each) a workgroup stages in LDS; a workgroup whose values span more sequences searches global memory
+ * instead.  mm_debug_values_batch_view: the view the host derives for one sequence at device address `address`, out6 =
+ * {address rounded down to a dword, byte_lo, byte_hi, q_lo, q_hi, base0}: bytes [byte_lo, byte_hi) of the rounded address are
+ * the sequence's, dwords [q_lo, q_hi) lie wholly inside them, base0 = base_offset + 4 * byte_lo. */
+uint32_t mm_values_batch_lds_stage(void);
+int mm_debug_values_batch_view(uint64_t address, uint64_t packed_bytes, uint64_t base_offset, uint64_t out6[6]);
 
 /* Page-locked host memory for the host entry points.  Any host pointer works; with buffers from
  * mm_host_alloc the copies to and from the device run in both directions at once (97 GB/s aggregate
@@ -756,6 +797,18 @@ int mm_device_group_batch_result(const mm_device_group_t *group, uint64_t seq, i
                                  uint32_t **d_sk, uint64_t *count);
 int mm_device_group_gather_batch(mm_device_group_t *group, int root, uint32_t *d_dst_pos, uint32_t *d_dst_sk /* or NULL */,
                                  uint64_t capacity, uint64_t *out_offsets /* [n_seqs + 1] */);
+/* Output::values_u64 / values_u128 (src/lib.rs:584-629) of the positions of the last mm_run_batch_sharded_device, in place
+ * of Output::values_* per contig of the loop bench/src/bin/paper.rs:410-431: ONE launch of the batch values kernel per
+ * entry over its resident sequences and result positions (the group owns the uploaded copies, so no per-sequence call could
+ * reach them).  The launches are issued from the calling thread one after the other and then waited for; the values land in
+ * a buffer the group owns on the entry's device.  len / canonical as for mm_values_u64_device_async; want_u128: {lo, hi}
+ * per value.  *total (may be NULL) receives the number of values.  MM_ERR_NULL without a finished batch run.
+ * mm_device_group_batch_values hands out where sequence seq's values lie: *d_values on the device of *entry, *count values
+ * (2 * *count words after want_u128).  The next upload or run on the group invalidates them (MM_ERR_NULL until the next
+ * mm_device_group_values_batch).  Out of scope: a gather of the values across devices. */
+int mm_device_group_values_batch(mm_device_group_t *group, uint32_t len, int canonical, int want_u128, uint64_t *total);
+int mm_device_group_batch_values(const mm_device_group_t *group, uint64_t seq, int *entry, uint64_t **d_values,
+                                 uint64_t *count);
 
 /* Diagnostics: the launch plan of the fused kernel as the host lays it out - lane length, tiles, the tapered tail
  * (DESIGN.md 4.1 "Launch geometry").  With MM_TAPER_SLOTS=<workgroup slots> in the environment no device is needed:

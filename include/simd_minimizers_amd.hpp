@@ -585,6 +585,26 @@ class DeviceGroup {
         check(r);
         return counts;
     }
+    // Output::values_u64 / values_u128 (src/lib.rs:584-629) of the last run_batch_device's positions, every entry's
+    // sequences in ONE launch (mm_device_group_values_batch); the values stay on the devices.  Returns their number.
+    template <bool CANONICAL, int SYNCMER>
+    uint64_t values_batch(const Builder<CANONICAL, SYNCMER> &b, bool u128 = false) const {
+        const uint32_t len = SYNCMER ? b.k() + b.w() - 1 : b.k();
+        uint64_t total = 0;
+        check(mm_device_group_values_batch(g_, len, CANONICAL ? 1 : 0, u128 ? 1 : 0, &total));
+        return total;
+    }
+    struct BatchValues {
+        int entry = 0;                 // the entry whose device holds them
+        uint64_t *d_values = nullptr;  // device pointer: count words, 2 * count ({lo, hi}) after values_batch(b, true)
+        uint64_t count = 0;
+    };
+    // where sequence `seq`'s values lie, until the next upload or run on the group
+    BatchValues batch_values(uint64_t seq) const {
+        BatchValues v;
+        check(mm_device_group_batch_values(g_, seq, &v.entry, &v.d_values, &v.count));
+        return v;
+    }
     // all sequences, input order, into device memory of entry `root`; returns the n + 1 offsets
     std::vector<uint64_t> gather_batch(int root, size_t n_seqs, uint32_t *d_dst_pos, uint64_t capacity) const {
         std::vector<uint64_t> offs(n_seqs + 1);

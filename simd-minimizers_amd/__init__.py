@@ -243,6 +243,14 @@ def _load_lib():
         L.mm_debug_values_read_of.argtypes = [u64p, C.c_uint64, u64p, C.c_uint64, C.POINTER(C.c_int64)]
         L.mm_values_reads_lds_stage.argtypes = []
         L.mm_values_reads_lds_stage.restype = C.c_uint32
+        values_batch_args = [vp, C.c_uint64, C.POINTER(vp), u64p, u64p, u64p, C.c_uint32, C.c_int, vp, u64p, vp]
+        L.mm_values_u64_batch_device_async.argtypes = values_batch_args
+        L.mm_values_u128_batch_device_async.argtypes = values_batch_args
+        L.mm_values_batch_lds_stage.argtypes = []
+        L.mm_values_batch_lds_stage.restype = C.c_uint32
+        L.mm_debug_values_batch_view.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, u64p]
+        L.mm_device_group_values_batch.argtypes = [vp, C.c_uint32, C.c_int, C.c_int, u64p]
+        L.mm_device_group_batch_values.argtypes = [vp, C.c_uint64, C.POINTER(C.c_int), C.POINTER(u64p), u64p]
         L.mm_run_batch_device.argtypes = [vp, vp, C.c_uint64, C.POINTER(vp), u64p, u64p, u64p, vp, vp,
                                           C.c_uint64, u64p]
         reads_args = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp,
@@ -323,6 +331,8 @@ EXPORTED_SYMBOLS = [
     "mm_run_packed_reads_skip_ambiguous_host",
     "mm_values_u64_reads_device_async", "mm_values_u128_reads_device_async", "mm_values_u64_reads_host",
     "mm_values_u128_reads_host", "mm_debug_values_read_of", "mm_values_reads_lds_stage",
+    "mm_values_u64_batch_device_async", "mm_values_u128_batch_device_async", "mm_values_batch_lds_stage",
+    "mm_debug_values_batch_view", "mm_device_group_values_batch", "mm_device_group_batch_values",
     "mm_prebuilt_flavour_window_sizes", "mm_plan_prepare", "mm_jit_stats",
 ]
 
@@ -552,6 +562,8 @@ class DeviceGroup:
         arr = (C.c_int * len(devices))(*devices)
         _check(lib().mm_device_group_create(C.byref(self.h), arr, len(devices)))
         self._batch_n = None  # sequences of the resident batch (upload_batch), None: no batch uploaded yet
+        self._devices = [int(d) for d in devices]
+        self._batch_u128 = False  # the last values_batch() wrote {lo, hi} pairs
 
     def __len__(self):
         return lib().mm_device_group_size(self.h)
@@ -676,6 +688,30 @@ class DeviceGroup:
                                                  counts, C.byref(total)))
         return [int(c) for c in counts[:n]]
 
+    def values_batch(self, builder: "Builder", u128=False) -> int:
+        """``mm_device_group_values_batch``: the k-mer values (``Output.values_u64`` / ``values_u128`` per sequence) of the
+        last ``run_batch_device``'s positions, one launch per entry over its resident sequences; ``len`` and
+        ``canonical`` come from the builder.  The values stay on the devices (``batch_values``) until the next upload or
+        run.  Returns their number."""
+        total = C.c_uint64()
+        _check(lib().mm_device_group_values_batch(self.h, _value_len(builder), int(builder.canonical), int(bool(u128)),
+                                                  C.byref(total)))
+        self._batch_u128 = bool(u128)
+        return int(total.value)
+
+    def batch_values(self, seq: int):
+        """``mm_device_group_batch_values``: (entry, values) of sequence ``seq`` after ``values_batch`` - an int64 CUDA
+        tensor on the entry's device that ALIASES the group's buffer (``count`` words, ``2 * count`` after ``u128``:
+        {lo, hi} per value), valid until the next upload or run on the group."""
+        import torch
+        entry, dv, cnt = C.c_int(), C.POINTER(C.c_uint64)(), C.c_uint64()
+        _check(lib().mm_device_group_batch_values(self.h, int(seq), C.byref(entry), C.byref(dv), C.byref(cnt)))
+        words = int(cnt.value) * (2 if self._batch_u128 else 1)
+        device = torch.device("cuda", self._devices[entry.value])
+        if words == 0:
+            return entry.value, torch.empty(0, dtype=torch.int64, device=device)
+        return entry.value, torch.as_tensor(_DeviceWords(C.cast(dv, C.c_void_p).value, words), device=device)
+
     def gather_batch(self, root: int, d_dst_pos, d_dst_sk=None):
         """All sequences' positions, input order, into device tensors on the root entry's device; returns the offsets."""
         n = self._batch_count()
@@ -709,6 +745,13 @@ class DeviceGroup:
         _check(code)
         o = [int(x) for x in out_offsets]
         return pos[:o[-1]], (sk[:o[-1]] if sk is not None else None), o
+
+
+class _DeviceWords:
+    """``n`` 64-bit words of device memory at ``address`` for ``torch.as_tensor`` (no copy, no ownership)."""
+
+    def __init__(self, address: int, n: int):
+        self.__cuda_array_interface__ = {"shape": (n,), "typestr": "<i8", "data": (address, False), "version": 2}
 
 
 _default_ws = threading.local()  # .by_device: {device: Workspace} of the calling thread
@@ -1462,6 +1505,51 @@ def values_reads_lds_stage() -> int:
     """Offsets a workgroup of the reads values kernels stages in LDS (``mm_values_reads_lds_stage``); a workgroup whose
     values span more reads searches global memory."""
     return int(lib().mm_values_reads_lds_stage())
+
+
+def values_batch_lds_stage() -> int:
+    """Entries (an offset and a sequence descriptor each) a workgroup of the batch values kernels stages in LDS
+    (``mm_values_batch_lds_stage``); a workgroup whose values span more sequences searches global memory."""
+    return int(lib().mm_values_batch_lds_stage())
+
+
+def values_batch_view(address: int, packed_bytes: int, base_offset: int = 0) -> dict:
+    """The view the batch values kernels' host side derives for one sequence (``mm_debug_values_batch_view``, no GPU)."""
+    out = (C.c_uint64 * 6)()
+    _check(lib().mm_debug_values_batch_view(int(address), int(packed_bytes), int(base_offset), out))
+    return dict(zip(("address", "byte_lo", "byte_hi", "q_lo", "q_hi", "base0"), (int(x) for x in out)))
+
+
+def values_batch_device(builder: "Builder", d_seqs, n_bases, d_pos, offsets, base_offsets=None, u128=False, out=None):
+    """K-mer values of EVERY sequence of a device batch in one launch (``mm_values_u64_batch_device_async`` /
+    ``mm_values_u128_batch_device_async``): ``d_seqs`` (list of torch uint8 CUDA tensors; ``None`` for a sequence without
+    values), ``n_bases`` and ``base_offsets`` as ``run_batch_device`` took them, ``d_pos`` the positions it wrote (int32
+    tensor) and ``offsets`` the n_seqs + 1 offsets it returned.  ``len`` and ``canonical`` come from the builder like
+    ``Output.values_u64`` takes them.  Fills ``out`` (int64 tensor of ``offsets[-1]`` words, twice that for ``u128``:
+    {lo, hi}) or returns a new zero-filled one; the call is asynchronous on the builder's workspace (``Workspace.sync``)."""
+    import torch
+    n = len(d_seqs)
+    offsets = [int(o) for o in offsets]
+    if len(offsets) != n + 1 or len(n_bases) != n or (base_offsets is not None and len(base_offsets) != n):
+        raise ValueError(f"{n} sequences need {n} lengths (and base offsets) and {n + 1} offsets")
+    count = offsets[-1]
+    per = 2 if u128 else 1
+    if out is None:
+        out = torch.zeros(per * count, dtype=torch.int64, device=d_pos.device)
+        torch.cuda.synchronize(d_pos.device)
+    elif out.numel() < per * count:
+        raise ValueError(f"out holds {out.numel()} words, {per * count} needed")
+    if d_pos.numel() < count:
+        raise ValueError(f"d_pos holds {d_pos.numel()} positions, offsets end at {count}")
+    ptrs = (C.c_void_p * max(n, 1))(*[t.data_ptr() if t is not None and t.numel() else None for t in d_seqs])
+    nbytes = (C.c_uint64 * max(n, 1))(*[int(t.numel()) if t is not None else 0 for t in d_seqs])
+    lens = (C.c_uint64 * max(n, 1))(*[int(x) for x in n_bases])
+    bases = (C.c_uint64 * max(n, 1))(*[int(x) for x in base_offsets]) if base_offsets is not None else None
+    offs = (C.c_uint64 * (n + 1))(*offsets)
+    f = lib().mm_values_u128_batch_device_async if u128 else lib().mm_values_u64_batch_device_async
+    _check(f(builder._ws().h, n, ptrs, nbytes, bases, lens, _value_len(builder), int(builder.canonical),
+             C.c_void_p(d_pos.data_ptr()), offs, C.c_void_p(out.data_ptr())))
+    return out
 
 
 def values_reads_device(builder: "Builder", d_packed, n_reads, d_pos, d_out_offsets, read_starts=None, read_stride=0,

@@ -19,6 +19,7 @@
 #include "../../include/simd_minimizers_amd.h"
 #include "mm_env.h"
 #include "mm_launch.h"
+#include "mm_values_batch.h"
 #include "mm_values_reads.h"
 
 namespace {
@@ -248,6 +249,16 @@ struct mm_workspace {
     // text batches (mm_run_text_batch_*): per tile, the range of record starts its collect stage reads
     unsigned long long *d_text_tiles = nullptr;
     uint64_t d_text_tiles_elems = 0;
+    // batch values (mm_values_*_batch_device_async): the device tables - [n_seqs + 1 offsets | n_seqs descriptors] - and
+    // two page-locked staging areas used in turn; an area is rewritten only after the event of its last upload
+    uint8_t *d_vbatch = nullptr;
+    uint64_t d_vbatch_bytes = 0;
+    static const int kValuesBatchSlots = 2;
+    uint8_t *h_vbatch[kValuesBatchSlots] = {};
+    uint64_t h_vbatch_bytes[kValuesBatchSlots] = {};
+    hipEvent_t ev_vbatch[kValuesBatchSlots] = {};
+    bool vbatch_slot_used[kValuesBatchSlots] = {};
+    int vbatch_slot_next = 0;
     // knobs / diagnostics
     bool force_generic = false;
     uint32_t nblk = 0;
@@ -800,6 +811,11 @@ void mm_workspace_destroy(mm_workspace_t *ws) {
     if (ws->h_text_tables) hipHostFree(ws->h_text_tables);
     for (int i = 0; i < mm_workspace::kTextTableSlots; ++i)
         if (ws->ev_text_tables[i]) hipEventDestroy(ws->ev_text_tables[i]);
+    if (ws->d_vbatch) hipFree(ws->d_vbatch);
+    for (int i = 0; i < mm_workspace::kValuesBatchSlots; ++i) {
+        if (ws->h_vbatch[i]) hipHostFree(ws->h_vbatch[i]);
+        if (ws->ev_vbatch[i]) hipEventDestroy(ws->ev_vbatch[i]);
+    }
     if (ws->own_stream && ws->stream) hipStreamDestroy(ws->stream);
     delete ws;
 }
@@ -3145,6 +3161,130 @@ int mm_debug_values_read_of(const uint64_t *offsets, uint64_t n_reads, const uin
 
 uint32_t mm_values_reads_lds_stage(void) { return mm::kValuesReadsStage; }
 
+// ---- Output::values_u64 / values_u128 (src/lib.rs:584-629) of every sequence of a device batch in ONE launch: what the
+// loop over Builder::run per contig (bench/src/bin/paper.rs:410-431) and Output::values_* per sequence computes, from the
+// arrays mm_run_batch_device takes and the offsets it returns (mm_values_batch.hip).
+// The checks that need no device, in the order the header lists them; *count = offsets[n_seqs].  MM_OK with *count == 0:
+// nothing to do.
+static int values_batch_check(uint64_t n_seqs, const void *const *d_packed, const uint64_t *packed_bytes,
+                              const uint64_t *base_offsets, const uint64_t *n_bases, uint32_t len, const uint32_t *d_pos,
+                              const uint64_t *offsets, const uint64_t *d_values, bool u128, uint64_t *count) {
+    *count = 0;
+    if (len == 0 || len > (u128 ? 64u : 32u)) return MM_ERR_VALUE_LEN;
+    if (n_seqs == 0) return MM_OK;
+    if (!offsets) return MM_ERR_NULL;
+    if (n_seqs >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
+    for (uint64_t s = 0; s < n_seqs; ++s)
+        if (offsets[s] > offsets[s + 1]) return MM_ERR_UNSORTED;
+    const uint64_t total = offsets[n_seqs];  // (offsets[0] is 0, as mm_run_batch_device writes it)
+    if (total == 0) return MM_OK;
+    if (!d_packed || !packed_bytes || !n_bases || !d_pos || !d_values) return MM_ERR_NULL;
+    for (uint64_t s = 0; s < n_seqs; ++s) {
+        if (offsets[s] == offsets[s + 1]) continue;  // (a sequence without values is never looked at)
+        if (!d_packed[s]) return MM_ERR_NULL;
+        const uint64_t off = base_offsets ? base_offsets[s] : 0;
+        if (packed_bytes[s] >= (1ull << 60) || off >= (1ull << 62) || n_bases[s] >= (1ull << 62)) return MM_ERR_LEN_TOO_LARGE;
+        if ((off + n_bases[s] + 3) / 4 > packed_bytes[s]) return MM_ERR_CAPACITY;
+    }
+    *count = total;
+    return MM_OK;
+}
+
+static int values_batch_async_impl(mm_workspace_t *ws, uint64_t n_seqs, const void *const *d_packed,
+                                   const uint64_t *packed_bytes, const uint64_t *base_offsets, const uint64_t *n_bases,
+                                   uint32_t len, int canonical, const uint32_t *d_pos, const uint64_t *offsets,
+                                   uint64_t *d_values, bool u128) {
+    if (!ws) return MM_ERR_NULL;
+    uint64_t total = 0;
+    int r = values_batch_check(n_seqs, d_packed, packed_bytes, base_offsets, n_bases, len, d_pos, offsets, d_values, u128, &total);
+    if (r || total == 0) return r;
+    const uint64_t per_block = u128 ? 256 : 1024;
+    if ((total + per_block - 1) / per_block > 0x7fffffffull) return MM_ERR_LEN_TOO_LARGE;  // (more workgroups than a grid holds)
+    MM_HIP(set_device(ws->device));
+    // the tables: [n_seqs + 1 offsets | pad to 16 bytes | n_seqs descriptors], built in a page-locked area that is the
+    // workspace's own - the caller's arrays are the caller's again on return - and copied to the device tables on the
+    // stream (behind every earlier launch that reads them)
+    const uint64_t seqs_at = ((n_seqs + 1) * sizeof(uint64_t) + 15) & ~15ull;
+    const uint64_t bytes = seqs_at + n_seqs * sizeof(mm::ValuesBatchSeq);
+    const int slot = ws->vbatch_slot_next;
+    ws->vbatch_slot_next = (slot + 1) % mm_workspace::kValuesBatchSlots;
+    if (!ws->ev_vbatch[slot]) MM_HIP(hipEventCreateWithFlags(&ws->ev_vbatch[slot], hipEventDisableTiming));
+    // (the area is rewritten - or replaced by a larger one - only after its previous upload has left it)
+    if (ws->vbatch_slot_used[slot]) MM_HIP(hipEventSynchronize(ws->ev_vbatch[slot]));
+    ws->vbatch_slot_used[slot] = false;
+    if (ws->h_vbatch_bytes[slot] < bytes) {
+        if (ws->h_vbatch[slot]) MM_HIP(hipHostFree(ws->h_vbatch[slot]));
+        ws->h_vbatch[slot] = nullptr;
+        ws->h_vbatch_bytes[slot] = 0;
+        const uint64_t want = bytes + bytes / 8 + 4096;
+        void *hp = nullptr;
+        MM_HIP(hipHostMalloc(&hp, want, hipHostMallocDefault));
+        ws->h_vbatch[slot] = static_cast<uint8_t *>(hp);
+        ws->h_vbatch_bytes[slot] = want;
+    }
+    r = grow(ws->d_vbatch, ws->d_vbatch_bytes, bytes, 1);
+    if (r) return r;
+    uint8_t *const h = ws->h_vbatch[slot];
+    uint64_t *const h_offsets = reinterpret_cast<uint64_t *>(h);
+    mm::ValuesBatchSeq *const h_seqs = reinterpret_cast<mm::ValuesBatchSeq *>(h + seqs_at);
+    memcpy(h_offsets, offsets, (n_seqs + 1) * sizeof(uint64_t));
+    for (uint64_t s = 0; s < n_seqs; ++s)
+        h_seqs[s] = offsets[s] == offsets[s + 1]
+                        ? mm::ValuesBatchSeq{0, 0, 0, 0}
+                        : mm::values_batch_seq((uint64_t)reinterpret_cast<uintptr_t>(d_packed[s]), packed_bytes[s],
+                                               base_offsets ? base_offsets[s] : 0);
+    MM_HIP(hipMemcpyAsync(ws->d_vbatch, h, bytes, hipMemcpyHostToDevice, ws->stream));
+    MM_HIP(hipEventRecord(ws->ev_vbatch[slot], ws->stream));
+    ws->vbatch_slot_used[slot] = true;
+    mm::ValuesBatchArgs a;
+    a.n_seqs = n_seqs;
+    a.seqs = reinterpret_cast<const mm::ValuesBatchSeq *>(ws->d_vbatch + seqs_at);
+    a.offsets = reinterpret_cast<const unsigned long long *>(ws->d_vbatch);
+    a.total = total;
+    a.len = len;
+    a.canonical = canonical ? 1 : 0;
+    a.pos = d_pos;
+    a.out = reinterpret_cast<unsigned long long *>(d_values);
+    r = mm::launch_values_batch(a, u128, ws->stream);
+    if (r == -3) return MM_ERR_LEN_TOO_LARGE;
+    if (r) return hip_fail(hipGetLastError(), u128 ? "values_u128_batch" : "values_u64_batch");
+    return MM_OK;
+}
+
+int mm_values_u64_batch_device_async(mm_workspace_t *ws, uint64_t n_seqs, const void *const *d_packed,
+                                     const uint64_t *packed_bytes, const uint64_t *base_offsets, const uint64_t *n_bases,
+                                     uint32_t len, int canonical, const uint32_t *d_pos, const uint64_t *offsets,
+                                     uint64_t *d_values) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    return values_batch_async_impl(ws, n_seqs, d_packed, packed_bytes, base_offsets, n_bases, len, canonical, d_pos, offsets,
+                                   d_values, false);
+}
+
+int mm_values_u128_batch_device_async(mm_workspace_t *ws, uint64_t n_seqs, const void *const *d_packed,
+                                      const uint64_t *packed_bytes, const uint64_t *base_offsets, const uint64_t *n_bases,
+                                      uint32_t len, int canonical, const uint32_t *d_pos, const uint64_t *offsets,
+                                      uint64_t *d_values) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    return values_batch_async_impl(ws, n_seqs, d_packed, packed_bytes, base_offsets, n_bases, len, canonical, d_pos, offsets,
+                                   d_values, true);
+}
+
+uint32_t mm_values_batch_lds_stage(void) { return mm::kValuesBatchStage; }
+
+// The view the host derives for one sequence of a batch (no device): out6 = {aligned address, byte_lo, byte_hi, q_lo, q_hi,
+// base0}, what the kernel reads out of the sequence's descriptor.
+int mm_debug_values_batch_view(uint64_t address, uint64_t packed_bytes, uint64_t base_offset, uint64_t out6[6]) {
+    if (!out6) return MM_ERR_NULL;
+    const mm::ValuesBatchSeq s = mm::values_batch_seq(address, packed_bytes, base_offset);
+    out6[0] = s.d;
+    out6[1] = s.byte_lo;
+    out6[2] = s.byte_hi;
+    out6[3] = mm::values_batch_q_lo(s);
+    out6[4] = mm::values_batch_q_hi(s);
+    out6[5] = s.base0;
+    return MM_OK;
+}
+
 int mm_pack_ascii_device_async(mm_workspace_t *ws, const uint8_t *d_ascii, uint64_t n_bases,
                                uint8_t *d_packed) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
@@ -3570,11 +3710,15 @@ struct mm_device_group {
         std::vector<uint64_t> seqs;         // sequences of this entry, input order
         std::vector<uint64_t> at, nbytes;   // where each lies in d_buf, its packed bytes
         std::vector<uint64_t> offs;         // offsets of its sequences' positions in the entry's result buffer (last run)
+        std::vector<uint64_t> run_base, run_len;  // base_offsets / n_bases of its sequences in the last run
+        uint64_t *d_vals = nullptr;         // values of the last run's positions (mm_device_group_values_batch), grown as needed
+        uint64_t vals_cap = 0;              // ... in 64-bit words
     };
     std::vector<BatchEntry> batch;
     std::vector<int> seq_entry;             // entry of every sequence
     std::vector<uint64_t> seq_slot;         // its index among the entry's sequences
     bool batch_ran = false;
+    int batch_vals_words = 0;               // 64-bit words per value in d_vals (1 or 2); 0: no values of the last run
 };
 
 namespace {
@@ -3654,9 +3798,10 @@ void mm_device_group_destroy(mm_device_group_t *g) {
     }
     if (!g->d_seq.empty()) group_drop_sequence(g);
     for (size_t i = 0; i < g->batch.size() && i < g->ws.size(); ++i)
-        if (g->batch[i].d_buf) {
+        if (g->batch[i].d_buf || g->batch[i].d_vals) {
             set_device(g->ws[i]->device);
-            hipFree(g->batch[i].d_buf);
+            if (g->batch[i].d_buf) hipFree(g->batch[i].d_buf);
+            if (g->batch[i].d_vals) hipFree(g->batch[i].d_vals);
         }
     for (mm_workspace_t *ws : g->ws) mm_workspace_destroy(ws);
     delete g;
@@ -3877,6 +4022,7 @@ int mm_run_sharded_device(const mm_plan_t *plan, mm_device_group_t *g, uint64_t 
     if (total) *total = 0;
     g->ran = true;
     g->batch_ran = false;  // (the result buffers are shared between the two resident modes: ADVICE r4)
+    g->batch_vals_words = 0;
     // expected positions per window (+ 15 % and a constant): a shard that needs more is run again with what it needs
     const double dens = plan->mode == MM_OPEN_SYNCMERS ? 1.0 / plan->w
                         : plan->mode == MM_CLOSED_SYNCMERS ? 2.0 / plan->w : 2.0 / (plan->w + 1.0);
@@ -4037,6 +4183,7 @@ int mm_device_group_upload_batch(mm_device_group_t *g, uint64_t n_seqs, const ui
     g->seq_entry.assign(n_seqs, 0);
     g->seq_slot.assign(n_seqs, 0);
     g->batch_ran = false;
+    g->batch_vals_words = 0;
     for (uint64_t s : order) {
         uint64_t best = 0;
         for (uint64_t i = 1; i < N; ++i)
@@ -4098,6 +4245,7 @@ int mm_run_batch_sharded_device(const mm_plan_t *plan, mm_device_group_t *g, con
     std::vector<Entry> ent(N);
     g->ran = false;  // (the result buffers now hold a batch: mm_device_group_result / _gather must not read them as shards)
     g->batch_ran = false;
+    g->batch_vals_words = 0;
     // (an error on a later entry must not leave the earlier entries' launches - and their uploads out of `ent`'s
     // host vectors - in flight when `ent` is destroyed: every issued entry is waited for and its error words consumed
     // before the first error is returned)
@@ -4201,6 +4349,11 @@ int mm_run_batch_sharded_device(const mm_plan_t *plan, mm_device_group_t *g, con
         sum += c;
     }
     if (total) *total = sum;
+    // (what mm_device_group_values_batch needs of this run: where every sequence's first base lies and how many follow)
+    for (uint64_t i = 0; i < N; ++i) {
+        g->batch[i].run_base = ent[i].offs;
+        g->batch[i].run_len = ent[i].lens;
+    }
     g->batch_ran = true;
     return MM_OK;
 }
@@ -4216,6 +4369,66 @@ int mm_device_group_batch_result(const mm_device_group_t *g, uint64_t seq, int *
     if (entry) *entry = e;
     if (d_pos) *d_pos = sh.d_pos ? sh.d_pos + b.offs[j] : nullptr;
     if (d_sk) *d_sk = (sh.has_sk && sh.d_sk) ? sh.d_sk + b.offs[j] : nullptr;
+    if (count) *count = b.offs[j + 1] - b.offs[j];
+    return MM_OK;
+}
+
+// ---- Output::values_u64 / values_u128 (src/lib.rs:584-629) of the last batch run's positions, per entry in ONE launch of
+// the batch values kernel over the entry's resident sequences (what a loop over the contigs, bench/src/bin/paper.rs:410-431,
+// would ask of Output::values_* one by one).  Issued from this thread one entry after the other, then waited for.
+int mm_device_group_values_batch(mm_device_group_t *g, uint32_t len, int canonical, int want_u128, uint64_t *total) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (!g || !g->batch_ran || g->batch.size() != g->ws.size()) return MM_ERR_NULL;
+    if (len == 0 || len > (want_u128 ? 64u : 32u)) return MM_ERR_VALUE_LEN;
+    const uint64_t N = g->ws.size(), words = want_u128 ? 2 : 1;
+    g->batch_vals_words = 0;
+    uint64_t sum = 0;
+    int rc = MM_OK;
+    for (uint64_t i = 0; i < N && rc == MM_OK; ++i) {
+        mm_device_group::BatchEntry &b = g->batch[i];
+        const size_t m = b.seqs.size();
+        const uint64_t count = m ? b.offs[m] : 0;
+        if (count == 0) continue;
+        if (b.run_base.size() != m || b.run_len.size() != m) {
+            rc = MM_ERR_NULL;
+            break;
+        }
+        if (set_device(g->ws[i]->device) != hipSuccess) {
+            rc = hip_fail(hipGetLastError(), "hipSetDevice");
+            break;
+        }
+        rc = grow(b.d_vals, b.vals_cap, words * count, sizeof(uint64_t));
+        if (rc) break;
+        // the sequences as they lie in the entry's buffer, with the bytes that were uploaded for each (the zeros the upload
+        // put behind them are what a position past a sequence's end reads anyway)
+        std::vector<const void *> dptr(m);
+        for (size_t j = 0; j < m; ++j) dptr[j] = b.d_buf + b.at[j];
+        // (the tables are copied into the workspace's page-locked area before the call returns: dptr may go)
+        rc = values_batch_async_impl(g->ws[i], m, dptr.data(), b.nbytes.data(), b.run_base.data(), b.run_len.data(), len,
+                                     canonical, g->shard[i].d_pos, b.offs.data(), b.d_vals, want_u128 != 0);
+        sum += count;
+    }
+    // every entry that may have a launch in flight is waited for, also when a later one failed
+    for (uint64_t i = 0; i < N; ++i) {
+        if (g->batch[i].seqs.empty()) continue;
+        hipError_t e = set_device(g->ws[i]->device);
+        if (e == hipSuccess) e = hipStreamSynchronize(g->ws[i]->stream);
+        if (e != hipSuccess && rc == MM_OK) rc = hip_fail(e, "values_batch sync");
+    }
+    if (rc) return rc;
+    if (total) *total = sum;
+    g->batch_vals_words = (int)words;
+    return MM_OK;
+}
+
+int mm_device_group_batch_values(const mm_device_group_t *g, uint64_t seq, int *entry, uint64_t **d_values, uint64_t *count) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (!g || !g->batch_ran || !g->batch_vals_words || seq >= g->seq_entry.size()) return MM_ERR_NULL;
+    const int e = g->seq_entry[seq];
+    const mm_device_group::BatchEntry &b = g->batch[(size_t)e];
+    const uint64_t j = g->seq_slot[seq];
+    if (entry) *entry = e;
+    if (d_values) *d_values = b.d_vals ? b.d_vals + (uint64_t)g->batch_vals_words * b.offs[j] : nullptr;
     if (count) *count = b.offs[j + 1] - b.offs[j];
     return MM_OK;
 }

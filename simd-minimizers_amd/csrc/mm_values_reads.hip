@@ -22,6 +22,7 @@
 #include "mm_common.h"
 #include "mm_launch.h"
 #include "mm_values.h"
+#include "mm_values_load.h"
 #include "mm_values_reads.h"
 
 namespace mm {
@@ -29,31 +30,6 @@ namespace mm {
 namespace {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// dword q of the buffer by the edge rules: whole dwords inside come from one load, others byte by byte
-__device__ __forceinline__ uint32_t edge_dword(const PackedView &v, unsigned long long q) {
-    if (q >= v.q_lo && q < v.q_hi) return v.d[q];
-    if (q > v.q_hi) return 0u;  // (q_hi may be the partial last dword; nothing lies past it.  Also keeps 4 * q from wrapping.)
-    const uint8_t *bytes = reinterpret_cast<const uint8_t *>(v.d);
-    uint32_t r = 0;
-    for (uint32_t b = 0; b < 4u; ++b) {
-        const unsigned long long at = 4ull * q + b;
-        if (at >= v.byte_lo && at < v.byte_hi) r |= (uint32_t)bytes[at] << (8u * b);
-    }
-    return r;
-}
-
-// the N dwords from dword q on
-template <int N>
-__device__ __forceinline__ void load_dwords(const PackedView &v, unsigned long long q, uint32_t (&w)[N]) {
-    if (q >= v.q_lo && q < v.q_hi && v.q_hi - q >= (unsigned long long)N) {
-#pragma unroll
-        for (int t = 0; t < N; ++t) w[t] = v.d[q + t];
-    } else {  // (rare: kept rolled, the hot path above is what the registers are for)
-#pragma nounroll
-        for (int t = 0; t < N; ++t) w[t] = edge_dword(v, q + (unsigned long long)t);
-    }
-}
 
 __device__ __forceinline__ unsigned long long read_start(const ValuesReadsArgs &a, unsigned long long r) {
     return a.read_starts ? a.read_starts[r] : r * (unsigned long long)a.read_stride;
