@@ -83,7 +83,8 @@ enum {
     MM_ERR_CAPACITY = -8,             /* caller's output buffer too small; *out_count holds the need */
     MM_ERR_BAD_MODE = -9,             /* src/lib.rs:437; super-k-mers with syncmers, src/lib.rs:339 */
     MM_ERR_NULL = -10,
-    MM_ERR_VALUE_LEN = -11,           /* values_u64 needs len <= 32, values_u128 len <= 64 */
+    MM_ERR_VALUE_LEN = -11,           /* values_u64 needs len <= 32, values_u128 len <= 64; of byte text as `&[u8]`
+                                         (MM_TEXT_VALUES_BYTES) len <= 8 and len <= 16 */
     MM_ERR_FORMAT = -12,              /* mm_fasta_pack_device: the text is FASTQ ('@' first), not FASTA */
     MM_ERR_NO_DEVICE = -20,           /* no HIP device: the engine has no CPU fallback */
     MM_ERR_HIP = -21,                 /* a HIP call failed; see mm_last_error() */
@@ -401,7 +402,8 @@ int mm_values_u128_host(mm_workspace_t *ws, const uint8_t *packed, uint64_t base
  * NULL d_packed / d_pos / d_out_offsets / d_values when there is work; MM_ERR_VALUE_LEN for len == 0, len > 32 (u64) or
  * len > 64 (u128); MM_ERR_CAPACITY when base_offset, or a fixed-stride layout's last read, starts past packed_bytes;
  * n_reads == 0 or n_pos_max == 0 returns MM_OK with nothing launched.  mm_run_batch_device's separately allocated
- * sequences have their own call, mm_values_u64_batch_device_async below.  Not covered: byte text. */
+ * sequences have their own call, mm_values_u64_batch_device_async below; byte text has mm_values_u64_text_device_async
+ * and mm_values_u64_text_batch_device_async. */
 int mm_values_u64_reads_device_async(mm_workspace_t *ws, const void *d_packed, uint64_t packed_bytes,
                                      uint64_t base_offset, uint64_t n_reads,
                                      const uint64_t *d_read_starts /* [n_reads + 1] or NULL */, uint32_t read_stride,
@@ -457,7 +459,7 @@ uint32_t mm_values_reads_lds_stage(void);
  * d_packed[s] of a sequence that has values; MM_ERR_VALUE_LEN for len == 0, len > 32 (u64) or len > 64 (u128);
  * MM_ERR_UNSORTED for offsets that decrease; MM_ERR_CAPACITY for a sequence with values whose (base_offset + n_bases + 3) / 4
  * exceeds its packed_bytes; MM_ERR_LEN_TOO_LARGE for n_seqs >= 2^32.  n_seqs == 0 or offsets[n_seqs] == 0 returns MM_OK with
- * nothing launched.  Not covered: byte text. */
+ * nothing launched.  Byte text: mm_values_u64_text_device_async / mm_values_u64_text_batch_device_async below. */
 int mm_values_u64_batch_device_async(mm_workspace_t *ws, uint64_t n_seqs, const void *const *d_packed,
                                      const uint64_t *packed_bytes, const uint64_t *base_offsets /* or NULL */,
                                      const uint64_t *n_bases, uint32_t len, int canonical, const uint32_t *d_pos,
@@ -474,6 +476,73 @@ int mm_values_u128_batch_device_async(mm_workspace_t *ws, uint64_t n_seqs, const
  * the sequence's, dwords [q_lo, q_hi) lie wholly inside them, base0 = base_offset + 4 * byte_lo. */
 uint32_t mm_values_batch_lds_stage(void);
 int mm_debug_values_batch_view(uint64_t address, uint64_t packed_bytes, uint64_t base_offset, uint64_t out6[6]);
+
+/* Output::values_u64 / values_u128 (src/lib.rs:584-629) of BYTE TEXT, at the positions the mm_run_text_* entry points
+ * write.  `encoding` names the reference Seq the text stands for:
+ *   MM_TEXT_VALUES_BYTES  `&[u8]` (src/lib.rs:59-60), 8 bits per character: value = sum over j < len of text[p + j] << 8j
+ *                         (first character in the low byte); len <= 8 (u64) / 16 (u128), else MM_ERR_VALUE_LEN;
+ *                         canonical != 0 is MM_ERR_BAD_MODE (general text has no reverse complement).
+ *                         PARITY UNPINNED: layout inferred - packed-seq is not in the reference tree.
+ *   MM_TEXT_VALUES_DNA    packed-seq AsciiSeq (src/lib.rs:59, :85-100), 2 bits per character, code(c) = (c >> 1) & 3:
+ *                         fwd = sum code(text[p + j]) << 2j, rc = sum (code(text[p + len - 1 - j]) ^ 2) << 2j, value =
+ *                         canonical ? min(fwd, rc) : fwd; len <= 32 (u64) / 64 (u128).  Bit for bit what
+ *                         mm_values_u64_device_async / mm_values_u128_device_async return on
+ *                         PackedSeqVec::from_ascii(text) at the same positions, without the packed copy.
+ * Any other encoding: MM_ERR_BAD_MODE.  len = mm_plan_value_len(plan); u128 values are stored {lo, hi}. */
+#define MM_TEXT_VALUES_BYTES 0
+#define MM_TEXT_VALUES_DNA 1
+/* A single text: the contract of mm_values_u64_device_async, on bytes.  d_text: n characters at any alignment, text_bytes
+ * readable bytes (n > text_bytes: MM_ERR_CAPACITY; n >= 2^32: MM_ERR_LEN_TOO_LARGE); d_pos: n_pos ABSOLUTE text positions,
+ * as mm_run_text_device_async writes them (also for a window range); d_values: 8-byte aligned, n_pos words (u128: twice
+ * that).  n_pos == 0 returns MM_OK with nothing launched.  No byte outside [d_text, d_text + text_bytes) is loaded whatever
+ * d_pos holds: a k-mer that reaches past text_bytes gets the missing characters as byte 0.  MM_ERR_NULL for a NULL
+ * workspace (first, whatever else is wrong) and for NULL arrays when there is work; MM_ERR_VALUE_LEN for len == 0.  The
+ * caller's current device is restored on return; completion status comes from mm_workspace_check. */
+int mm_values_u64_text_device_async(mm_workspace_t *ws, const void *d_text, uint64_t text_bytes, uint64_t n, int encoding,
+                                    uint32_t len, int canonical, const uint32_t *d_pos, uint64_t n_pos, uint64_t *d_values);
+int mm_values_u128_text_device_async(mm_workspace_t *ws, const void *d_text, uint64_t text_bytes, uint64_t n, int encoding,
+                                     uint32_t len, int canonical, const uint32_t *d_pos, uint64_t n_pos, uint64_t *d_values);
+/* The same from HOST memory: one upload, one launch, one download (text_bytes = n). */
+int mm_values_u64_text_host(mm_workspace_t *ws, const uint8_t *text, uint64_t n, int encoding, uint32_t len, int canonical,
+                            const uint32_t *pos, uint64_t n_pos, uint64_t *values);
+int mm_values_u128_text_host(mm_workspace_t *ws, const uint8_t *text, uint64_t n, int encoding, uint32_t len, int canonical,
+                             const uint32_t *pos, uint64_t n_pos, uint64_t *values);
+/* EVERY record of a text batch in one launch: the contract of mm_values_u64_reads_device_async, on what
+ * mm_run_text_batch_device_async takes and writes - what a loop over Builder::run (src/lib.rs:378) and Output::values_* per
+ * record computes.  Record r is bytes [d_starts[r], d_starts[r + 1]); value i belongs to the record r with
+ * d_out_offsets[r] <= i < d_out_offsets[r + 1] (empty records are skipped) and is the k-mer at byte d_starts[r] + d_pos[i].
+ * The TRUE count is d_out_offsets[n_records], read on the device: nothing at or past it, or past n_pos_max, is written, so
+ * a text batch run followed by its values queues on one stream with no host wait.  n_chars >= 2^32 or n_records >= 2^31:
+ * MM_ERR_LEN_TOO_LARGE; n_chars > text_bytes: MM_ERR_CAPACITY.  No byte outside [d_text, d_text + text_bytes) is loaded
+ * whatever d_pos, d_starts and d_out_offsets hold; a position whose k-mer runs past its record but stays inside the buffer
+ * gives whatever the bytes hold (unspecified).  Otherwise as the single-text call. */
+int mm_values_u64_text_batch_device_async(mm_workspace_t *ws, const void *d_text, uint64_t text_bytes, uint64_t n_records,
+                                          const uint64_t *d_starts /* [n_records + 1] */, uint64_t n_chars, int encoding,
+                                          uint32_t len, int canonical, const uint32_t *d_pos,
+                                          const uint64_t *d_out_offsets /* [n_records + 1] */, uint64_t n_pos_max,
+                                          uint64_t *d_values);
+int mm_values_u128_text_batch_device_async(mm_workspace_t *ws, const void *d_text, uint64_t text_bytes, uint64_t n_records,
+                                           const uint64_t *d_starts /* [n_records + 1] */, uint64_t n_chars, int encoding,
+                                           uint32_t len, int canonical, const uint32_t *d_pos,
+                                           const uint64_t *d_out_offsets /* [n_records + 1] */, uint64_t n_pos_max,
+                                           uint64_t *d_values);
+/* The same from HOST memory (the text is bytes 0 .. starts[n_records], the count offsets[n_records]).  Starts or offsets
+ * that decrease return MM_ERR_UNSORTED before anything is touched. */
+int mm_values_u64_text_batch_host(mm_workspace_t *ws, const uint8_t *text, uint64_t n_records,
+                                  const uint64_t *starts /* [n_records + 1] */, int encoding, uint32_t len, int canonical,
+                                  const uint32_t *pos, const uint64_t *offsets /* [n_records + 1] */, uint64_t *values);
+int mm_values_u128_text_batch_host(mm_workspace_t *ws, const uint8_t *text, uint64_t n_records,
+                                   const uint64_t *starts /* [n_records + 1] */, int encoding, uint32_t len, int canonical,
+                                   const uint32_t *pos, const uint64_t *offsets /* [n_records + 1] */, uint64_t *values);
+/* Diagnostics of the text values kernels (Output::values_*, src/lib.rs:584-629; no device needed).
+ * mm_values_text_lds_stage: the offsets a workgroup of the batch kernels stages in LDS; a workgroup whose values span more
+ * records searches global memory instead.  mm_debug_values_text: the values at the ABSOLUTE positions abs_pos[0 .. n) of a
+ * HOST buffer, by the very functions the kernels call for one value - the gather from whole dwords and edge bytes, the
+ * 2-bit compression, the assembly and the canonical step; out holds n words (want_u128: 2n, {lo, hi}).  The refusals of
+ * the device calls for encoding, canonical and len. */
+uint32_t mm_values_text_lds_stage(void);
+int mm_debug_values_text(const uint8_t *text, uint64_t text_bytes, int encoding, uint32_t len, int canonical, int want_u128,
+                         const uint64_t *abs_pos, uint64_t n, uint64_t *out);
 
 /* Page-locked host memory for the host entry points.  Any host pointer works; with buffers from
  * mm_host_alloc the copies to and from the device run in both directions at once (97 GB/s aggregate

@@ -267,7 +267,7 @@ class Builder {  // src/lib.rs:225-230
         return v;
     }
     // src/lib.rs:378 on &[u8] text (mm_run_text_host): positions are APPENDED to min_pos with the last() rule.
-    // (No Output: k-mer values of byte text are not defined by this engine.)
+    // (No Output: the k-mer values of the positions come from values_u64 / values_u128 (TextSeq, pos, encoding) below.)
     std::vector<uint32_t> &run(TextSeq seq, std::vector<uint32_t> &min_pos) const {
         Workspace &ws = ws_ ? *ws_ : Workspace::thread_default();
         mm_plan_t *plan = nullptr;
@@ -419,6 +419,28 @@ class Builder {  // src/lib.rs:225-230
         if (sk_) sk_->assign(sk.begin(), sk.begin() + n);
     }
 
+    // Output::values_u64 / values_u128 (src/lib.rs:584-629) of byte text (mm_values_u64_text_host /
+    // mm_values_u128_text_host): `pos` as run(TextSeq, ..) wrote them; `encoding` names the Seq the text stands for,
+    // MM_TEXT_VALUES_BYTES (`&[u8]`, 8 bits per character, len <= 8 / 16, forward builders only) or MM_TEXT_VALUES_DNA
+    // (AsciiSeq, 2 bits per character, len <= 32 / 64).
+    std::vector<uint64_t> values_u64(TextSeq seq, const std::vector<uint32_t> &pos, int encoding) const {
+        return values_text_raw(seq, pos, encoding, false);
+    }
+    std::vector<u128> values_u128(TextSeq seq, const std::vector<uint32_t> &pos, int encoding) const {
+        return widen(values_text_raw(seq, pos, encoding, true));
+    }
+    // The same of EVERY record of run_many(records, ..) in ONE call (mm_values_u64_text_batch_host /
+    // mm_values_u128_text_batch_host): `pos` and `offsets` as run_many wrote them; record r's values are
+    // [offsets[r] .. offsets[r + 1]) of the result, what values_u64(records[r], ..) returns for it alone.
+    std::vector<uint64_t> values_u64_many(const std::vector<TextSeq> &records, const std::vector<uint32_t> &pos,
+                                          const std::vector<uint64_t> &offsets, int encoding) const {
+        return values_text_many_raw(records, pos, offsets, encoding, false);
+    }
+    std::vector<u128> values_u128_many(const std::vector<TextSeq> &records, const std::vector<uint32_t> &pos,
+                                       const std::vector<uint64_t> &offsets, int encoding) const {
+        return widen(values_text_many_raw(records, pos, offsets, encoding, true));
+    }
+
     // the immutable plan of this builder (caller destroys it); k and w
     mm_plan_t *make_plan() const {
         mm_plan_t *plan = nullptr;
@@ -465,6 +487,39 @@ class Builder {  // src/lib.rs:225-230
         check((wide ? mm_values_u128_reads_host : mm_values_u64_reads_host)(
             ws.get(), packed.data(), packed.size(), 0, reads.size(), starts.data(), 0, len, CANONICAL, pos.data(),
             offsets.data(), v.data()));
+        return v;
+    }
+
+    static std::vector<u128> widen(const std::vector<uint64_t> &raw) {
+        std::vector<u128> v(raw.size() / 2);
+        for (size_t i = 0; i < v.size(); ++i) v[i] = ((u128)raw[2 * i + 1] << 64) | raw[2 * i];
+        return v;
+    }
+
+    std::vector<uint64_t> values_text_raw(TextSeq seq, const std::vector<uint32_t> &pos, int encoding, bool wide) const {
+        Workspace &ws = ws_ ? *ws_ : Workspace::thread_default();
+        std::vector<uint64_t> v((wide ? 2 : 1) * pos.size());
+        const uint32_t len = SYNCMER ? k_ + w_ - 1 : k_;
+        check((wide ? mm_values_u128_text_host : mm_values_u64_text_host)(ws.get(), seq.data, seq.len, encoding, len, CANONICAL,
+                                                                         pos.data(), pos.size(), v.data()));
+        return v;
+    }
+
+    std::vector<uint64_t> values_text_many_raw(const std::vector<TextSeq> &records, const std::vector<uint32_t> &pos,
+                                               const std::vector<uint64_t> &offsets, int encoding, bool wide) const {
+        if (offsets.size() != records.size() + 1) throw Error(MM_ERR_NULL);
+        Workspace &ws = ws_ ? *ws_ : Workspace::thread_default();
+        std::vector<uint64_t> starts(records.size() + 1, 0);
+        for (size_t r = 0; r < records.size(); ++r) starts[r + 1] = starts[r] + records[r].len;
+        std::vector<uint8_t> text(starts.back() ? starts.back() : 1);
+        for (size_t r = 0; r < records.size(); ++r)
+            if (records[r].len) memcpy(text.data() + starts[r], records[r].data, records[r].len);
+        const uint64_t n = offsets.back();
+        if (pos.size() < n) throw Error(MM_ERR_CAPACITY);
+        std::vector<uint64_t> v((wide ? 2 : 1) * n);
+        const uint32_t len = SYNCMER ? k_ + w_ - 1 : k_;
+        check((wide ? mm_values_u128_text_batch_host : mm_values_u64_text_batch_host)(
+            ws.get(), text.data(), records.size(), starts.data(), encoding, len, CANONICAL, pos.data(), offsets.data(), v.data()));
         return v;
     }
 

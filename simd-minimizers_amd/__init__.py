@@ -96,6 +96,9 @@ class PrepareReport(C.Structure):
 
 
 PREPARE_SEQUENCE, PREPARE_READS, PREPARE_SUPERKMERS = 1, 2, 4
+# which reference Seq a byte text stands for when its k-mer values are asked (MM_TEXT_VALUES_*): ``&[u8]`` at 8 bits per
+# character, or packed-seq ``AsciiSeq`` at 2
+TEXT_VALUES_BYTES, TEXT_VALUES_DNA = 0, 1
 
 
 def _is_text(seq) -> bool:
@@ -251,6 +254,22 @@ def _load_lib():
         L.mm_debug_values_batch_view.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, u64p]
         L.mm_device_group_values_batch.argtypes = [vp, C.c_uint32, C.c_int, C.c_int, u64p]
         L.mm_device_group_batch_values.argtypes = [vp, C.c_uint64, C.POINTER(C.c_int), C.POINTER(u64p), u64p]
+        values_text_args = [vp, vp, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, C.c_int, vp, C.c_uint64, vp]
+        L.mm_values_u64_text_device_async.argtypes = values_text_args
+        L.mm_values_u128_text_device_async.argtypes = values_text_args
+        values_text_host_args = [vp, u8p, C.c_uint64, C.c_int, C.c_uint32, C.c_int, u32p, C.c_uint64, u64p]
+        L.mm_values_u64_text_host.argtypes = values_text_host_args
+        L.mm_values_u128_text_host.argtypes = values_text_host_args
+        values_text_batch_args = [vp, vp, C.c_uint64, C.c_uint64, vp, C.c_uint64, C.c_int, C.c_uint32, C.c_int, vp, vp,
+                                  C.c_uint64, vp]
+        L.mm_values_u64_text_batch_device_async.argtypes = values_text_batch_args
+        L.mm_values_u128_text_batch_device_async.argtypes = values_text_batch_args
+        values_text_batch_host_args = [vp, u8p, C.c_uint64, u64p, C.c_int, C.c_uint32, C.c_int, u32p, u64p, u64p]
+        L.mm_values_u64_text_batch_host.argtypes = values_text_batch_host_args
+        L.mm_values_u128_text_batch_host.argtypes = values_text_batch_host_args
+        L.mm_values_text_lds_stage.argtypes = []
+        L.mm_values_text_lds_stage.restype = C.c_uint32
+        L.mm_debug_values_text.argtypes = [vp, C.c_uint64, C.c_int, C.c_uint32, C.c_int, C.c_int, u64p, C.c_uint64, u64p]
         L.mm_run_batch_device.argtypes = [vp, vp, C.c_uint64, C.POINTER(vp), u64p, u64p, u64p, vp, vp,
                                           C.c_uint64, u64p]
         reads_args = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp,
@@ -334,6 +353,9 @@ EXPORTED_SYMBOLS = [
     "mm_values_u64_batch_device_async", "mm_values_u128_batch_device_async", "mm_values_batch_lds_stage",
     "mm_debug_values_batch_view", "mm_device_group_values_batch", "mm_device_group_batch_values",
     "mm_prebuilt_flavour_window_sizes", "mm_plan_prepare", "mm_jit_stats",
+    "mm_values_u64_text_device_async", "mm_values_u128_text_device_async", "mm_values_u64_text_host",
+    "mm_values_u128_text_host", "mm_values_u64_text_batch_device_async", "mm_values_u128_text_batch_device_async",
+    "mm_values_u64_text_batch_host", "mm_values_u128_text_batch_host", "mm_values_text_lds_stage", "mm_debug_values_text",
 ]
 
 
@@ -831,11 +853,6 @@ class Plan:
         return lib().mm_plan_value_len(self.h)
 
 
-def _no_text_values(seq):
-    if _is_text(seq):
-        raise MinimizerError(ERR["BAD_MODE"], "k-mer values of byte text are not supported (2-bit sequences only)")
-
-
 class Output:
     """``Output`` of src/lib.rs:232-237: positions + lazily computed k-mer values."""
 
@@ -858,7 +875,11 @@ class Output:
         pos = np.ascontiguousarray(self.min_pos, dtype=np.uint32)
         vals = np.zeros(2 * len(pos), dtype=np.uint64)
         seq = self.seq
-        _no_text_values(seq)
+        if _is_text(seq):  # ``&[u8]``: 8 bits per character (a canonical builder or len > 16 raises the C ABI's code)
+            text = _text_array(seq)
+            _check(lib().mm_values_u128_text_host(self._ws.h, _p(text, C.c_uint8), len(text), TEXT_VALUES_BYTES, self.len,
+                                                  int(self.canonical), _p(pos, C.c_uint32), len(pos), _p(vals, C.c_uint64)))
+            return pos, [int(vals[2 * i]) | (int(vals[2 * i + 1]) << 64) for i in range(len(pos))]
         if isinstance(seq, AsciiSeq):
             seq = PackedSeqVec.from_ascii(seq.seq)
         if len(pos):
@@ -872,7 +893,11 @@ class Output:
         pos = np.ascontiguousarray(self.min_pos, dtype=np.uint32)
         vals = np.zeros(len(pos), dtype=np.uint64)
         seq = self.seq
-        _no_text_values(seq)
+        if _is_text(seq):  # ``&[u8]``: 8 bits per character (a canonical builder or len > 8 raises the C ABI's code)
+            text = _text_array(seq)
+            _check(lib().mm_values_u64_text_host(self._ws.h, _p(text, C.c_uint8), len(text), TEXT_VALUES_BYTES, self.len,
+                                                 int(self.canonical), _p(pos, C.c_uint32), len(pos), _p(vals, C.c_uint64)))
+            return pos, vals
         if isinstance(seq, AsciiSeq):
             seq = PackedSeqVec.from_ascii(seq.seq)
         if len(pos):
@@ -1579,6 +1604,106 @@ def values_reads_device(builder: "Builder", d_packed, n_reads, d_pos, d_out_offs
              _value_len(builder), int(builder.canonical), C.c_void_p(d_pos.data_ptr()),
              C.c_void_p(d_out_offsets.data_ptr()), int(n_pos_max), C.c_void_p(out.data_ptr())))
     return out
+
+
+def values_text_lds_stage() -> int:
+    """Offsets a workgroup of the text batch values kernels stages in LDS (``mm_values_text_lds_stage``); a workgroup whose
+    values span more records searches global memory."""
+    return int(lib().mm_values_text_lds_stage())
+
+
+def debug_values_text(text, encoding, length, canonical=False, u128=False, abs_pos=(), address_shift=0):
+    """The text values kernels' arithmetic for one value, on the host (``mm_debug_values_text``, no GPU): the values at
+    the absolute positions ``abs_pos`` of ``text``, whose first byte is placed ``address_shift`` (0..3) bytes past a
+    4-byte boundary.  Returns a uint64 array, or a list of Python ints for ``u128``."""
+    text = _text_array(text)
+    buf = np.zeros(len(text) + 8, dtype=np.uint8)
+    at = (-buf.ctypes.data) % 4 + int(address_shift)
+    buf[at:at + len(text)] = text
+    pos = np.ascontiguousarray(abs_pos, dtype=np.uint64)
+    per = 2 if u128 else 1
+    out = np.zeros(max(1, per * len(pos)), dtype=np.uint64)
+    _check(lib().mm_debug_values_text(C.c_void_p(buf.ctypes.data + at), len(text), int(encoding), int(length),
+                                      int(canonical), int(u128), _p(pos, C.c_uint64), len(pos), _p(out, C.c_uint64)))
+    if u128:
+        return [int(out[2 * i]) | (int(out[2 * i + 1]) << 64) for i in range(len(pos))]
+    return out[:len(pos)]
+
+
+def values_text_device(builder: "Builder", d_text, n, d_pos, n_pos, encoding, u128=False, out=None):
+    """K-mer values of device-resident byte text (``mm_values_u64_text_device_async`` /
+    ``mm_values_u128_text_device_async``): ``d_text`` the uint8 CUDA tensor a text run took (``n`` characters; every byte
+    of the tensor is readable, nothing past it is), ``d_pos`` the ABSOLUTE positions it wrote (int32 tensor, ``n_pos`` of
+    them).  ``encoding``: ``TEXT_VALUES_BYTES`` (``&[u8]``, 8 bits per character) or ``TEXT_VALUES_DNA`` (``AsciiSeq``, 2
+    bits).  ``len`` and ``canonical`` come from the builder like ``Output.values_u64`` takes them.  Fills ``out`` (int64
+    tensor of ``n_pos`` words, twice that for ``u128``: {lo, hi}) or returns a new zero-filled one; the call is
+    asynchronous on the builder's workspace (``Workspace.sync``)."""
+    import torch
+    n_pos = int(n_pos)
+    per = 2 if u128 else 1
+    if out is None:
+        out = torch.zeros(per * n_pos, dtype=torch.int64, device=d_pos.device)
+        torch.cuda.synchronize(d_pos.device)
+    elif out.numel() < per * n_pos:
+        raise ValueError(f"out holds {out.numel()} words, {per * n_pos} needed")
+    if d_pos.numel() < n_pos:
+        raise ValueError(f"d_pos holds {d_pos.numel()} positions, n_pos is {n_pos}")
+    f = lib().mm_values_u128_text_device_async if u128 else lib().mm_values_u64_text_device_async
+    _check(f(builder._ws().h, C.c_void_p(d_text.data_ptr()), int(d_text.numel()), int(n), int(encoding),
+             _value_len(builder), int(builder.canonical), C.c_void_p(d_pos.data_ptr()), n_pos,
+             C.c_void_p(out.data_ptr())))
+    return out
+
+
+def values_text_batch_device(builder: "Builder", d_text, d_starts, n_chars, d_pos, d_out_offsets, n_pos_max, encoding,
+                             u128=False, out=None):
+    """K-mer values of EVERY record of a device text batch in one launch (``mm_values_u64_text_batch_device_async`` /
+    ``mm_values_u128_text_batch_device_async``): ``d_text`` / ``d_starts`` / ``n_chars`` as ``run_text_batch_device`` took
+    them, ``d_pos`` the record-local positions and ``d_out_offsets`` the n + 1 offsets it wrote.  The true count is read
+    on the device: nothing waits for the host, values at or past it (or past ``n_pos_max``) stay as they were.
+    ``encoding`` / ``u128`` / ``out`` as for ``values_text_device`` (``out`` holds ``n_pos_max`` values)."""
+    import torch
+    n_rec = d_starts.numel() - 1
+    if n_rec < 0 or d_out_offsets.numel() != n_rec + 1:
+        raise ValueError("d_starts and d_out_offsets hold n + 1 entries each")
+    n_pos_max = int(n_pos_max)
+    per = 2 if u128 else 1
+    if out is None:
+        out = torch.zeros(per * n_pos_max, dtype=torch.int64, device=d_pos.device)
+        torch.cuda.synchronize(d_pos.device)
+    elif out.numel() < per * n_pos_max:
+        raise ValueError(f"out holds {out.numel()} words, {per * n_pos_max} needed")
+    if d_pos.numel() < n_pos_max:
+        raise ValueError(f"d_pos holds {d_pos.numel()} positions, n_pos_max is {n_pos_max}")
+    f = lib().mm_values_u128_text_batch_device_async if u128 else lib().mm_values_u64_text_batch_device_async
+    _check(f(builder._ws().h, C.c_void_p(d_text.data_ptr()), int(d_text.numel()), n_rec, C.c_void_p(d_starts.data_ptr()),
+             int(n_chars), int(encoding), _value_len(builder), int(builder.canonical), C.c_void_p(d_pos.data_ptr()),
+             C.c_void_p(d_out_offsets.data_ptr()), n_pos_max, C.c_void_p(out.data_ptr())))
+    return out
+
+
+def values_text_batch_host(builder: "Builder", records, pos, offsets, encoding, u128=False):
+    """K-mer values of many host records of byte text in ONE call (``mm_values_u64_text_batch_host`` /
+    ``mm_values_u128_text_batch_host``): ``records`` as ``run_text_batch_host`` takes them, ``pos`` / ``offsets`` as it
+    returns them.  Returns a uint64 array (one value per position), or a list of Python ints for ``u128`` - record r's
+    values are ``[offsets[r]:offsets[r + 1]]``, what ``Output.values_u64`` of ``Builder.run(record)`` returns."""
+    text, starts = _text_records(records)
+    pos = np.ascontiguousarray(pos, dtype=np.uint32)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    if len(offsets) != len(starts):
+        raise ValueError(f"{len(starts) - 1} records need {len(starts)} offsets, not {len(offsets)}")
+    n = int(offsets[-1]) if len(offsets) else 0
+    if len(pos) < n:
+        raise ValueError(f"offsets end at {n}, pos holds {len(pos)}")
+    per = 2 if u128 else 1
+    vals = np.zeros(max(1, per * n), dtype=np.uint64)
+    f = lib().mm_values_u128_text_batch_host if u128 else lib().mm_values_u64_text_batch_host
+    _check(f(builder._ws().h, _p(text, C.c_uint8), len(starts) - 1, _p(starts, C.c_uint64), int(encoding),
+             _value_len(builder), int(builder.canonical), _p(pos, C.c_uint32) if len(pos) else None,
+             _p(offsets, C.c_uint64), _p(vals, C.c_uint64)))
+    if u128:
+        return [int(vals[2 * i]) | (int(vals[2 * i + 1]) << 64) for i in range(n)]
+    return vals[:n]
 
 
 def _pack_reads(reads):

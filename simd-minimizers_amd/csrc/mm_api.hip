@@ -21,6 +21,7 @@
 #include "mm_launch.h"
 #include "mm_values_batch.h"
 #include "mm_values_reads.h"
+#include "mm_values_text.h"
 
 namespace {
 
@@ -3282,6 +3283,212 @@ int mm_debug_values_batch_view(uint64_t address, uint64_t packed_bytes, uint64_t
     out6[3] = mm::values_batch_q_lo(s);
     out6[4] = mm::values_batch_q_hi(s);
     out6[5] = s.base0;
+    return MM_OK;
+}
+
+// ---- Output::values_u64 / values_u128 (src/lib.rs:584-629) of byte text, at the positions the text entry points write
+// (mm_values_text.hip).  `encoding` names the reference Seq the text stands for: `&[u8]` (src/lib.rs:59-60) at 8 bits per
+// character, or packed-seq AsciiSeq (src/lib.rs:59, :85-100) at 2.
+static int values_text_mode_check(int encoding, uint32_t len, int canonical, bool u128) {
+    if (encoding != MM_TEXT_VALUES_BYTES && encoding != MM_TEXT_VALUES_DNA) return MM_ERR_BAD_MODE;
+    if (encoding == MM_TEXT_VALUES_BYTES && canonical) return MM_ERR_BAD_MODE;  // (general text has no reverse complement)
+    const uint32_t most = (encoding == MM_TEXT_VALUES_DNA ? 32u : 8u) * (u128 ? 2u : 1u);
+    if (len == 0 || len > most) return MM_ERR_VALUE_LEN;
+    return MM_OK;
+}
+
+static int values_text_async_impl(mm_workspace_t *ws, const void *d_text, uint64_t text_bytes, uint64_t n, int encoding,
+                                  uint32_t len, int canonical, const uint32_t *d_pos, uint64_t n_pos, uint64_t *d_values,
+                                  bool u128) {
+    if (!ws) return MM_ERR_NULL;
+    if (const int bad = values_text_mode_check(encoding, len, canonical, u128)) return bad;
+    if (n_pos == 0) return MM_OK;
+    if (!d_text || !d_pos || !d_values) return MM_ERR_NULL;
+    if (n >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
+    if (n > text_bytes) return MM_ERR_CAPACITY;
+    MM_HIP(set_device(ws->device));
+    mm::ValuesTextArgs a;
+    a.view = mm::text_view((uint64_t)reinterpret_cast<uintptr_t>(d_text), text_bytes);
+    a.n_records = 0;
+    a.starts = nullptr;
+    a.len = len;
+    a.canonical = canonical ? 1 : 0;
+    a.pos = d_pos;
+    a.offsets = nullptr;
+    a.n_pos_max = n_pos;
+    a.out = reinterpret_cast<unsigned long long *>(d_values);
+    const int r = mm::launch_values_text(a, encoding, u128, false, ws->stream);
+    if (r == -3) return MM_ERR_LEN_TOO_LARGE;
+    if (r) return hip_fail(hipGetLastError(), u128 ? "values_u128_text" : "values_u64_text");
+    return MM_OK;
+}
+
+// The same from HOST memory: the text in d_in (text_bytes = n: a k-mer past the end reads zeros), positions in d_out,
+// values in d_vals.
+static int values_text_host_impl(mm_workspace_t *ws, const uint8_t *text, uint64_t n, int encoding, uint32_t len,
+                                 int canonical, const uint32_t *pos, uint64_t n_pos, uint64_t *values, bool u128) {
+    if (!ws) return MM_ERR_NULL;
+    if (const int bad = values_text_mode_check(encoding, len, canonical, u128)) return bad;
+    if (n_pos == 0) return MM_OK;
+    if ((n && !text) || !pos || !values) return MM_ERR_NULL;
+    if (n >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
+    MM_HIP(set_device(ws->device));
+    const uint64_t per = u128 ? 2 : 1;
+    int r = grow_bytes(ws->d_in, ws->d_in_bytes, n ? n : 1);
+    if (r) return r;
+    r = grow(ws->d_out, ws->d_out_elems, n_pos, sizeof(uint32_t));
+    if (r) return r;
+    r = grow(ws->d_vals, ws->d_vals_elems, per * n_pos, sizeof(unsigned long long));
+    if (r) return r;
+    if (n) MM_HIP(hipMemcpyAsync(ws->d_in, text, n, hipMemcpyHostToDevice, ws->stream));
+    MM_HIP(hipMemcpyAsync(ws->d_out, pos, n_pos * sizeof(uint32_t), hipMemcpyHostToDevice, ws->stream));
+    r = values_text_async_impl(ws, ws->d_in, n, n, encoding, len, canonical, ws->d_out, n_pos,
+                               reinterpret_cast<uint64_t *>(ws->d_vals), u128);
+    if (r) return r;
+    MM_HIP(hipMemcpyAsync(values, ws->d_vals, per * n_pos * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
+    MM_HIP(hipStreamSynchronize(ws->stream));
+    return MM_OK;
+}
+
+int mm_values_u64_text_device_async(mm_workspace_t *ws, const void *d_text, uint64_t text_bytes, uint64_t n, int encoding,
+                                    uint32_t len, int canonical, const uint32_t *d_pos, uint64_t n_pos, uint64_t *d_values) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    return values_text_async_impl(ws, d_text, text_bytes, n, encoding, len, canonical, d_pos, n_pos, d_values, false);
+}
+
+int mm_values_u128_text_device_async(mm_workspace_t *ws, const void *d_text, uint64_t text_bytes, uint64_t n, int encoding,
+                                     uint32_t len, int canonical, const uint32_t *d_pos, uint64_t n_pos, uint64_t *d_values) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    return values_text_async_impl(ws, d_text, text_bytes, n, encoding, len, canonical, d_pos, n_pos, d_values, true);
+}
+
+int mm_values_u64_text_host(mm_workspace_t *ws, const uint8_t *text, uint64_t n, int encoding, uint32_t len, int canonical,
+                            const uint32_t *pos, uint64_t n_pos, uint64_t *values) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    return values_text_host_impl(ws, text, n, encoding, len, canonical, pos, n_pos, values, false);
+}
+
+int mm_values_u128_text_host(mm_workspace_t *ws, const uint8_t *text, uint64_t n, int encoding, uint32_t len, int canonical,
+                             const uint32_t *pos, uint64_t n_pos, uint64_t *values) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    return values_text_host_impl(ws, text, n, encoding, len, canonical, pos, n_pos, values, true);
+}
+
+// Every record of a text batch in ONE launch: what a loop over Builder::run per record (src/lib.rs:378) and
+// Output::values_* per record computes, from the record-local positions and offsets mm_run_text_batch_device_async
+// writes.  The true count is d_out_offsets[n_records], read on the device.
+static int values_text_batch_async_impl(mm_workspace_t *ws, const void *d_text, uint64_t text_bytes, uint64_t n_records,
+                                        const uint64_t *d_starts, uint64_t n_chars, int encoding, uint32_t len, int canonical,
+                                        const uint32_t *d_pos, const uint64_t *d_out_offsets, uint64_t n_pos_max,
+                                        uint64_t *d_values, bool u128) {
+    if (!ws) return MM_ERR_NULL;
+    if (const int bad = values_text_mode_check(encoding, len, canonical, u128)) return bad;
+    if (n_records == 0 || n_pos_max == 0) return MM_OK;
+    if (!d_text || !d_starts || !d_pos || !d_out_offsets || !d_values) return MM_ERR_NULL;
+    if (n_chars >= (1ull << 32) || n_records >= (1ull << 31)) return MM_ERR_LEN_TOO_LARGE;
+    if (n_chars > text_bytes) return MM_ERR_CAPACITY;
+    MM_HIP(set_device(ws->device));
+    mm::ValuesTextArgs a;
+    a.view = mm::text_view((uint64_t)reinterpret_cast<uintptr_t>(d_text), text_bytes);
+    a.n_records = n_records;
+    a.starts = reinterpret_cast<const unsigned long long *>(d_starts);
+    a.len = len;
+    a.canonical = canonical ? 1 : 0;
+    a.pos = d_pos;
+    a.offsets = reinterpret_cast<const unsigned long long *>(d_out_offsets);
+    a.n_pos_max = n_pos_max;
+    a.out = reinterpret_cast<unsigned long long *>(d_values);
+    const int r = mm::launch_values_text(a, encoding, u128, true, ws->stream);
+    if (r == -3) return MM_ERR_LEN_TOO_LARGE;
+    if (r) return hip_fail(hipGetLastError(), u128 ? "values_u128_text_batch" : "values_u64_text_batch");
+    return MM_OK;
+}
+
+// The same from HOST memory: one upload ([text | starts | offsets] in d_in, positions in d_out), one launch, one download.
+static int values_text_batch_host_impl(mm_workspace_t *ws, const uint8_t *text, uint64_t n_records, const uint64_t *starts,
+                                       int encoding, uint32_t len, int canonical, const uint32_t *pos, const uint64_t *offsets,
+                                       uint64_t *values, bool u128) {
+    if (!ws) return MM_ERR_NULL;
+    if (const int bad = values_text_mode_check(encoding, len, canonical, u128)) return bad;
+    if (n_records == 0) return MM_OK;
+    if (!starts || !offsets) return MM_ERR_NULL;
+    if (n_records >= (1ull << 31)) return MM_ERR_LEN_TOO_LARGE;
+    for (uint64_t r = 0; r < n_records; ++r)
+        if (starts[r] > starts[r + 1] || offsets[r] > offsets[r + 1]) return MM_ERR_UNSORTED;
+    const uint64_t n_pos = offsets[n_records], n_chars = starts[n_records];
+    if (n_pos == 0) return MM_OK;
+    if (!text || !pos || !values) return MM_ERR_NULL;
+    if (n_chars >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
+    MM_HIP(set_device(ws->device));
+    const uint64_t words = n_records + 1, per = u128 ? 2 : 1;
+    const uint64_t starts_at = (n_chars + 15) & ~15ull, offsets_at = starts_at + words * sizeof(uint64_t);
+    int r = grow_bytes(ws->d_in, ws->d_in_bytes, offsets_at + words * sizeof(uint64_t));
+    if (r) return r;
+    uint8_t *const din = static_cast<uint8_t *>(ws->d_in);
+    r = grow(ws->d_out, ws->d_out_elems, n_pos, sizeof(uint32_t));
+    if (r) return r;
+    r = grow(ws->d_vals, ws->d_vals_elems, per * n_pos, sizeof(unsigned long long));
+    if (r) return r;
+    if (n_chars) MM_HIP(hipMemcpyAsync(din, text, n_chars, hipMemcpyHostToDevice, ws->stream));
+    MM_HIP(hipMemcpyAsync(din + starts_at, starts, words * sizeof(uint64_t), hipMemcpyHostToDevice, ws->stream));
+    MM_HIP(hipMemcpyAsync(din + offsets_at, offsets, words * sizeof(uint64_t), hipMemcpyHostToDevice, ws->stream));
+    MM_HIP(hipMemcpyAsync(ws->d_out, pos, n_pos * sizeof(uint32_t), hipMemcpyHostToDevice, ws->stream));
+    // (text_bytes = n_chars: a k-mer that leaves the last record reads zeros, not the staged starts)
+    r = values_text_batch_async_impl(ws, din, n_chars, n_records, reinterpret_cast<const uint64_t *>(din + starts_at), n_chars,
+                                     encoding, len, canonical, ws->d_out, reinterpret_cast<const uint64_t *>(din + offsets_at),
+                                     n_pos, reinterpret_cast<uint64_t *>(ws->d_vals), u128);
+    if (r) return r;
+    MM_HIP(hipMemcpyAsync(values, ws->d_vals, per * n_pos * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
+    MM_HIP(hipStreamSynchronize(ws->stream));
+    return MM_OK;
+}
+
+int mm_values_u64_text_batch_device_async(mm_workspace_t *ws, const void *d_text, uint64_t text_bytes, uint64_t n_records,
+                                          const uint64_t *d_starts, uint64_t n_chars, int encoding, uint32_t len,
+                                          int canonical, const uint32_t *d_pos, const uint64_t *d_out_offsets,
+                                          uint64_t n_pos_max, uint64_t *d_values) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    return values_text_batch_async_impl(ws, d_text, text_bytes, n_records, d_starts, n_chars, encoding, len, canonical, d_pos,
+                                        d_out_offsets, n_pos_max, d_values, false);
+}
+
+int mm_values_u128_text_batch_device_async(mm_workspace_t *ws, const void *d_text, uint64_t text_bytes, uint64_t n_records,
+                                           const uint64_t *d_starts, uint64_t n_chars, int encoding, uint32_t len,
+                                           int canonical, const uint32_t *d_pos, const uint64_t *d_out_offsets,
+                                           uint64_t n_pos_max, uint64_t *d_values) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    return values_text_batch_async_impl(ws, d_text, text_bytes, n_records, d_starts, n_chars, encoding, len, canonical, d_pos,
+                                        d_out_offsets, n_pos_max, d_values, true);
+}
+
+int mm_values_u64_text_batch_host(mm_workspace_t *ws, const uint8_t *text, uint64_t n_records, const uint64_t *starts,
+                                  int encoding, uint32_t len, int canonical, const uint32_t *pos, const uint64_t *offsets,
+                                  uint64_t *values) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    return values_text_batch_host_impl(ws, text, n_records, starts, encoding, len, canonical, pos, offsets, values, false);
+}
+
+int mm_values_u128_text_batch_host(mm_workspace_t *ws, const uint8_t *text, uint64_t n_records, const uint64_t *starts,
+                                   int encoding, uint32_t len, int canonical, const uint32_t *pos, const uint64_t *offsets,
+                                   uint64_t *values) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    return values_text_batch_host_impl(ws, text, n_records, starts, encoding, len, canonical, pos, offsets, values, true);
+}
+
+uint32_t mm_values_text_lds_stage(void) { return mm::kValuesTextStage; }
+
+// The kernels' arithmetic for one value on the host, of a HOST buffer (no device): out[j] (want_u128: out[2j], out[2j + 1])
+// = the value at absolute position abs_pos[j], by the functions the kernels call - the gather from whole dwords and
+// edge bytes, the 2-bit compression, the assembly and the canonical step (mm_values_text.h).
+int mm_debug_values_text(const uint8_t *text, uint64_t text_bytes, int encoding, uint32_t len, int canonical, int want_u128,
+                         const uint64_t *abs_pos, uint64_t n, uint64_t *out) {
+    if (const int bad = values_text_mode_check(encoding, len, canonical, want_u128 != 0)) return bad;
+    if (n == 0) return MM_OK;
+    if ((text_bytes && !text) || !abs_pos || !out) return MM_ERR_NULL;
+    const mm::PackedView view = mm::text_view((uint64_t)reinterpret_cast<uintptr_t>(text), text_bytes);
+    const uint64_t per = want_u128 ? 2 : 1;
+    for (uint64_t j = 0; j < n; ++j)
+        mm::values_text_host_one(view, encoding, len, canonical ? 1 : 0, want_u128 != 0, abs_pos[j], out + per * j);
     return MM_OK;
 }
 

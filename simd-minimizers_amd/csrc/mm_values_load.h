@@ -1,5 +1,5 @@
 // mm_values_load.h — the bounds-checked sequence loads of the one-launch value kernels (mm_values_reads.hip,
-// mm_values_batch.hip): the dwords that hold a k-mer, out of a PackedView (mm_launch.h).  Whole dwords inside the view come
+// mm_values_batch.hip, mm_values_text.hip): the dwords that hold a k-mer, out of a PackedView (mm_launch.h).  Whole dwords inside the view come
 // from plain global loads; anything else takes the edge path, which reads single bytes inside the view and zeros outside.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -10,7 +10,7 @@
 namespace mm {
 
 // dword q of the buffer by the edge rules: whole dwords inside come from one load, others byte by byte
-__device__ __forceinline__ uint32_t edge_dword(const PackedView &v, unsigned long long q) {
+__host__ __device__ __forceinline__ uint32_t edge_dword(const PackedView &v, unsigned long long q) {
     if (q >= v.q_lo && q < v.q_hi) return v.d[q];
     if (q > v.q_hi) return 0u;  // (q_hi may be the partial last dword; nothing lies past it.  Also keeps 4 * q from wrapping.)
     const uint8_t *bytes = reinterpret_cast<const uint8_t *>(v.d);
@@ -22,10 +22,16 @@ __device__ __forceinline__ uint32_t edge_dword(const PackedView &v, unsigned lon
     return r;
 }
 
+// whether the N dwords from dword q on lie wholly inside the view
+template <int N>
+__host__ __device__ __forceinline__ bool dwords_inside(const PackedView &v, unsigned long long q) {
+    return q >= v.q_lo && q < v.q_hi && v.q_hi - q >= (unsigned long long)N;
+}
+
 // the N dwords from dword q on
 template <int N>
-__device__ __forceinline__ void load_dwords(const PackedView &v, unsigned long long q, uint32_t (&w)[N]) {
-    if (q >= v.q_lo && q < v.q_hi && v.q_hi - q >= (unsigned long long)N) {
+__host__ __device__ __forceinline__ void load_dwords(const PackedView &v, unsigned long long q, uint32_t (&w)[N]) {
+    if (dwords_inside<N>(v, q)) {
 #pragma unroll
         for (int t = 0; t < N; ++t) w[t] = v.d[q + t];
     } else {  // (rare: kept rolled, the hot path above is what the registers are for)

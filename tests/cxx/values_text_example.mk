@@ -1,0 +1,9 @@
+# Compiles values_text_example.cpp against the in-tree library (compile/link check; run on a GPU box):
+#   make -C tests/cxx -f values_text_example.mk
+ROOT := ../..
+ROCM ?= /opt/rocm
+all: values_text_example
+values_text_example: values_text_example.cpp $(ROOT)/include/simd_minimizers_amd.hpp $(ROOT)/include/simd_minimizers_amd.h
+	g++ -std=c++17 -O2 -I$(ROOT)/include -o $@ values_text_example.cpp -L$(ROOT)/simd-minimizers_amd -lsimd_minimizers_amd -Wl,-rpath,'$$ORIGIN/../../simd-minimizers_amd' -Wl,-rpath,$(ROCM)/lib
+clean:
+	rm -f values_text_example
