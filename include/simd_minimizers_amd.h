@@ -85,7 +85,7 @@ enum {
     MM_ERR_NULL = -10,
     MM_ERR_VALUE_LEN = -11,           /* values_u64 needs len <= 32, values_u128 len <= 64; of byte text as `&[u8]`
                                          (MM_TEXT_VALUES_BYTES) len <= 8 and len <= 16 */
-    MM_ERR_FORMAT = -12,              /* mm_fasta_pack_device: the text is FASTQ ('@' first), not FASTA */
+    MM_ERR_FORMAT = -12,              /* the text is FASTQ ('@' first), not FASTA (today: mm_fasta_text_device) */
     MM_ERR_NO_DEVICE = -20,           /* no HIP device: the engine has no CPU fallback */
     MM_ERR_HIP = -21,                 /* a HIP call failed; see mm_last_error() */
     MM_ERR_ALLOC = -22,
@@ -359,6 +359,43 @@ int mm_run_text_batch_host(const mm_plan_t *plan, mm_workspace_t *ws, const uint
                            const uint64_t *starts /* host, [n_records + 1] */, uint32_t *out_pos,
                            uint32_t *out_sk /* or NULL */, uint64_t capacity,
                            uint64_t *out_offsets /* [n_records + 1] */, uint64_t *out_count);
+/* FASTA text -> records of BYTE text on the device: the loader step in front of the batch calls above and of
+ * mm_values_*_text_batch_device_async - a protein FASTA in device memory becomes their d_text / d_starts with no parsing
+ * on the CPU.  The reader is mm_fasta_pack_device's (needletail::parse_fastx_file restated as the reference's loader
+ * uses it, bench/src/lib.rs:51-82; the crate is not in the reference tree: parity unpinned): a record starts with '>'
+ * at the start of a line, its header runs to the end of that line, its sequence is every following line up to the next
+ * header line with '\n' and '\r' removed, bytes in front of the first header are ignored.  The sequence bytes are kept
+ * AS THEY ARE - no case folding, no alphabet mapping (a text hasher's 256-entry tables do that), any byte value but
+ * '\n' / '\r' may occur - and go back to back into d_seq.
+ *  d_text / n_bytes        the file's bytes, any alignment; n_bytes >= 2^32 returns MM_ERR_LEN_TOO_LARGE before anything
+ *                          is touched
+ *  d_seq                   4-byte aligned (MM_ERR_NULL otherwise, like d_packed); seq_capacity_bytes = n_bytes always
+ *                          suffices.  d_seq is NOT cleared: exactly the bytes [0, min(characters, seq_capacity_bytes))
+ *                          are written, nothing at or beyond that
+ *  d_rec_start             [max_records + 1]: record r = bytes [d_rec_start[r], d_rec_start[r + 1]) of d_seq - exactly
+ *                          the d_starts of mm_run_text_batch_device_async / mm_values_*_text_batch_device_async
+ *  d_rec_text_pos          [max_records] or NULL: byte offset of the record's '>' in the text (the caller slices the
+ *                          header from there)
+ *  d_counts                [2]: characters (their n_chars), records (their n_records); records past max_records are
+ *                          counted but not tabulated
+ * An empty text gives counts 0 and d_rec_start[0] = 0.  Everything is queued on the workspace's stream; the caller's
+ * current device is restored.  This asynchronous form does NOT look at the first byte: a FASTQ text is read by the
+ * FASTA rules (a quality line may begin with '>'), so its records are nonsense - the caller knows its format or uses
+ * the synchronous form.  Kernels: the two read passes of the packer (mm_fasta2.hip), the second writing bytes; no
+ * limits on line lengths, no order between workgroups, no failure mode of its own. */
+int mm_fasta_text_device_async(mm_workspace_t *ws, const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_seq,
+                               uint64_t seq_capacity_bytes, uint64_t *d_rec_start /* [max_records + 1] */,
+                               uint64_t *d_rec_text_pos /* [max_records] or NULL */, uint64_t max_records,
+                               uint64_t *d_counts /* [2]: characters, records */);
+/* The same, synchronous: out_counts[0..1] receive the counts.  MM_ERR_CAPACITY when the characters did not fit
+ * seq_capacity_bytes or the records did not fit max_records (out_counts holds the true counts: what is needed).
+ * MM_ERR_FORMAT when the first non-blank byte is '@': FASTQ to byte records is not provided, and nothing is written. */
+int mm_fasta_text_device(mm_workspace_t *ws, const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_seq,
+                         uint64_t seq_capacity_bytes, uint64_t *d_rec_start, uint64_t *d_rec_text_pos,
+                         uint64_t max_records, uint64_t *d_counts, uint64_t *out_counts /* [2] */);
+/* The per-thread step of that kernel on the host (no device; for tests): the bytes of in[0..32) that `mask` selects
+ * (bit i = byte i) moved together to out[0..count), zeros behind them.  Returns the count (MM_ERR_NULL for a null pointer). */
+int mm_debug_compact32(const uint8_t in[32], uint32_t mask, uint8_t out[32]);
 
 /* ----------------------------------------------------------------- values */
 

@@ -313,6 +313,10 @@ def _load_lib():
             L.mm_run_packed_reads_skip_ambiguous_device.argtypes = packed_skip_args + [u64p]
             L.mm_run_packed_reads_skip_ambiguous_host.argtypes = [vp, vp, u8p, u8p, C.c_uint64, u64p, C.c_uint32, u32p,
                                                                   C.c_uint64, u64p, u64p]
+        if hasattr(L, "mm_fasta_text_device"):  # (FASTA -> records of byte text)
+            L.mm_fasta_text_device_async.argtypes = fasta_args
+            L.mm_fasta_text_device.argtypes = fasta_args + [u64p]
+            L.mm_debug_compact32.argtypes = [u8p, C.c_uint32, u8p]
         _lib = L
     return _lib
 
@@ -356,6 +360,7 @@ EXPORTED_SYMBOLS = [
     "mm_values_u64_text_device_async", "mm_values_u128_text_device_async", "mm_values_u64_text_host",
     "mm_values_u128_text_host", "mm_values_u64_text_batch_device_async", "mm_values_u128_text_batch_device_async",
     "mm_values_u64_text_batch_host", "mm_values_u128_text_batch_host", "mm_values_text_lds_stage", "mm_debug_values_text",
+    "mm_fasta_text_device_async", "mm_fasta_text_device", "mm_debug_compact32",
 ]
 
 
@@ -1432,6 +1437,62 @@ def run_text_batch_device(builder: "Builder", d_text, d_starts, n_chars: int, ou
         raise MinimizerError(code, f"output capacity {cap} < {cnt.value}")
     _check(code)
     return int(cnt.value)
+
+
+class FastaTextRecords:
+    """Records of a FASTA text as byte text on the device (``fasta_text_device``): ``seq`` = a uint8 CUDA tensor holding
+    all sequences back to back, as they stand in the file; ``starts`` = an int64 CUDA tensor of n + 1 byte offsets
+    delimiting them - what ``run_text_batch_device`` and ``values_text_batch_device`` take as ``d_text`` / ``d_starts``;
+    ``text_pos`` = byte offset of every record's '>' in the text (host array); ``n_chars`` = ``starts[n]``."""
+
+    def __init__(self, seq, starts, text_pos, n_chars):
+        self.seq, self.starts, self.text_pos, self.n_chars = seq, starts, text_pos, int(n_chars)
+
+    def __len__(self):
+        return int(self.starts.numel()) - 1
+
+    def lengths(self):
+        s = self.starts.cpu().numpy()
+        return [int(x) for x in s[1:] - s[:-1]]
+
+    header = FastaRecords.header
+
+
+def fasta_text_device(text, max_records: int = 1 << 16, device: int = 0) -> FastaTextRecords:
+    """The records of a FASTA file as byte text, read on the device (``mm_fasta_text_device``): ``text`` = the file's
+    bytes (bytes / numpy uint8 / torch uint8 CUDA tensor).  The reader of ``fasta_pack_device``; the sequence bytes are
+    kept as they are (protein, any alphabet).  FASTQ raises ``MinimizerError`` (``MM_ERR_FORMAT``)."""
+    import torch
+
+    dev = f"cuda:{device}"
+    if isinstance(text, (bytes, bytearray)):
+        text = np.frombuffer(bytes(text), dtype=np.uint8).copy()
+    if isinstance(text, np.ndarray):
+        t = torch.from_numpy(np.ascontiguousarray(text)).to(dev) if text.size else torch.zeros(0, dtype=torch.uint8, device=dev)
+    else:
+        t = text
+    n = int(t.numel())
+    ws = default_workspace(device)
+    seq = torch.empty(max(n, 4), dtype=torch.uint8, device=dev)
+    starts = torch.zeros(max_records + 1, dtype=torch.int64, device=dev)
+    rec_pos = torch.zeros(max(max_records, 1), dtype=torch.int64, device=dev)
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    torch.cuda.synchronize(device)
+    out = (C.c_uint64 * 2)()
+    code = lib().mm_fasta_text_device(ws.h, C.c_void_p(t.data_ptr()) if n else None, n, C.c_void_p(seq.data_ptr()), n,
+                                      C.c_void_p(starts.data_ptr()), C.c_void_p(rec_pos.data_ptr()), max_records,
+                                      C.c_void_p(counts.data_ptr()), out)
+    if code == ERR["CAPACITY"]:
+        raise MinimizerError(code, f"{out[1]} records > max_records {max_records}")
+    _check(code)
+    n_chars, n_rec = int(out[0]), int(out[1])
+    return FastaTextRecords(seq[:n_chars], starts[: n_rec + 1], rec_pos[:n_rec].cpu().numpy().astype(np.uint64), n_chars)
+
+
+def run_fasta_text_device(builder: "Builder", records: FastaTextRecords, out_pos, out_offsets, out_sk=None):
+    """All records of ``fasta_text_device`` in one launch of the text plan (``run_text_batch_device`` on them): record-local
+    positions, ``out_offsets`` (int64 CUDA tensor, n + 1) delimits the records.  Returns the number of positions."""
+    return run_text_batch_device(builder, records.seq, records.starts, records.n_chars, out_pos, out_offsets, out_sk)
 
 
 def run_packed_reads_device(builder: "Builder", records: FastaRecords, out_pos, out_offsets, out_sk=None, max_read_len=None):

@@ -19,6 +19,7 @@
 #include "../../include/simd_minimizers_amd.h"
 #include "mm_env.h"
 #include "mm_launch.h"
+#include "mm_fasta_text.h"
 #include "mm_values_batch.h"
 #include "mm_values_reads.h"
 #include "mm_values_text.h"
@@ -3738,6 +3739,68 @@ int mm_fasta_pack_n_device(mm_workspace_t *ws, const uint8_t *d_text, uint64_t n
     if (c) return c;
     return fasta_pack_sync(ws, d_text, n_bytes, d_packed, packed_capacity_bytes, d_rec_base, d_rec_text_pos, max_records,
                            d_counts, out_counts, d_amb, amb_capacity_bytes);
+}
+
+// FASTA text -> records of BYTE text (mm_fasta2.hip, fasta2_text_kernel): the reader of mm_fasta_pack_device_async with the
+// sequence bytes kept as they are, in the layout mm_run_text_batch_device_async takes.  The packer's checks fit as they
+// are (d_seq for d_packed, no ambiguity output); nothing is cleared.
+static int fasta_text_async(mm_workspace_t *ws, const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_seq,
+                            uint64_t seq_capacity_bytes, uint64_t *d_rec_start, uint64_t *d_rec_text_pos,
+                            uint64_t max_records, uint64_t *d_counts) {
+    const int p = pack_prologue(ws, d_text, n_bytes, d_seq, seq_capacity_bytes, d_rec_start, d_counts, nullptr, 0);
+    if (p != MM_PACK_GO_ON) return p;
+    const int r = grow_bytes(ws->scratch, ws->scratch_bytes, mm::fasta2_scratch_bytes(n_bytes));
+    if (r) return r;
+    if (mm::launch_fasta_text(d_text, n_bytes, d_seq, seq_capacity_bytes, reinterpret_cast<unsigned long long *>(d_rec_start),
+                              reinterpret_cast<unsigned long long *>(d_rec_text_pos), max_records,
+                              reinterpret_cast<unsigned long long *>(d_counts), ws->scratch, ws->stream))
+        return hip_fail(hipGetLastError(), "fasta_text");
+    return MM_OK;
+}
+
+int mm_fasta_text_device_async(mm_workspace_t *ws, const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_seq,
+                               uint64_t seq_capacity_bytes, uint64_t *d_rec_start, uint64_t *d_rec_text_pos,
+                               uint64_t max_records, uint64_t *d_counts) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    return fasta_text_async(ws, d_text, n_bytes, d_seq, seq_capacity_bytes, d_rec_start, d_rec_text_pos, max_records, d_counts);
+}
+
+int mm_fasta_text_device(mm_workspace_t *ws, const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_seq,
+                         uint64_t seq_capacity_bytes, uint64_t *d_rec_start, uint64_t *d_rec_text_pos, uint64_t max_records,
+                         uint64_t *d_counts, uint64_t *out_counts) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (!out_counts || !ws || !d_counts || !d_rec_start) return MM_ERR_NULL;
+    if (n_bytes >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
+    if (reinterpret_cast<uintptr_t>(d_seq) % 4 != 0) return MM_ERR_NULL;
+    if (d_text && n_bytes) {
+        // FASTQ starts with '@' (mm_fasta_pack_device tells the formats apart by this byte too): not read here - a
+        // quality line may begin with '>', so the FASTA rules would return nonsense
+        unsigned char head[256];
+        const size_t nh = n_bytes < sizeof head ? (size_t)n_bytes : sizeof head;
+        MM_HIP(set_device(ws->device));
+        MM_HIP(hipMemcpyAsync(head, d_text, nh, hipMemcpyDeviceToHost, ws->stream));
+        MM_HIP(hipStreamSynchronize(ws->stream));
+        size_t i = 0;
+        while (i < nh && (head[i] == ' ' || head[i] == '\t' || head[i] == '\r' || head[i] == '\n')) ++i;
+        if (i < nh && head[i] == '@') return MM_ERR_FORMAT;
+    }
+    const int r = fasta_text_async(ws, d_text, n_bytes, d_seq, seq_capacity_bytes, d_rec_start, d_rec_text_pos, max_records,
+                                   d_counts);
+    if (r) return r;
+    MM_HIP(hipMemcpyAsync(out_counts, d_counts, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
+    MM_HIP(hipStreamSynchronize(ws->stream));
+    return (out_counts[0] > seq_capacity_bytes || out_counts[1] > max_records) ? MM_ERR_CAPACITY : MM_OK;
+}
+
+// The byte-text FASTA kernel's per-thread step on the host (mm_fasta_text.h; no device): the bytes of in[0..32) that
+// `mask` selects (bit i = byte i), moved together to out[0..count), zeros behind them; returns the count.
+int mm_debug_compact32(const uint8_t in[32], uint32_t mask, uint8_t out[32]) {
+    if (!in || !out) return MM_ERR_NULL;
+    uint32_t x[8];
+    memcpy(x, in, 32);
+    const mm::Compact32 c = mm::compact32(x, mask);
+    memcpy(out, c.d, 32);
+    return (int)c.count;
 }
 
 static const uint32_t kProbeGroups = 16;

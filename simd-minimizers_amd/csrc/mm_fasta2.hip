@@ -29,6 +29,7 @@
 #include "mm_common.h"
 #include "mm_launch.h"
 #include "mm_text.h"
+#include "mm_fasta_text.h"
 
 namespace mm {
 
@@ -399,6 +400,95 @@ __global__ __launch_bounds__(kFqThreads) void fasta2_pack_kernel(const uint8_t *
     if constexpr (AMB) amb_flush(s_amb, seq0, chunk_seq, amb32, amb_dwords);
 }
 
+// K2, third form (mm_fasta_text_device_*): the sequence BYTES themselves, compacted, where the packer writes 2-bit codes -
+// records of byte text for the text path (mm_run_text_batch_*, mm_values_*_text_batch_*).  State, first output byte,
+// first record and seq_mask exactly as above.  A thread moves the selected bytes of its piece together (compact32,
+// mm_fasta_text.h) and puts them into the chunk's LDS image at the byte offset o0 - seq0 plus the byte phase of the
+// chunk's first output address (seq0 & 3: out8 is 4-byte aligned), so that LDS dword i IS output dword (seq0 >> 2) + i:
+// dwords that lie inside the thread's bytes are plain LDS stores, the first and the last - which the neighbouring
+// threads may share - are OR-ed into the zeroed area.  After one barrier the image leaves: whole dwords as coalesced
+// dword stores, the bytes of the chunk's partial first and last dword as single byte stores - the neighbouring chunks
+// write the OTHER bytes of those dwords, so nothing is OR-ed in global memory and the output needs no clearing (a
+// memset of n bytes would be a third of the kernel's traffic).  No byte at or beyond out_bytes is written.
+__global__ __launch_bounds__(kFqThreads) void fasta2_text_kernel(const uint8_t *__restrict__ text, uint64_t n, const FaScratch sc,
+                                                                 uint8_t *__restrict__ out8, uint64_t out_bytes,
+                                                                 unsigned long long *__restrict__ rec_start,
+                                                                 unsigned long long *__restrict__ rec_pos, uint64_t max_records) {
+    __shared__ uint32_t s_part[kFqPieces][kFqWaves];
+    constexpr uint32_t kTextDwords = kFqChunk / 4u + 1u;  // at most 16 384 bytes + the byte phase (0..3)
+    __shared__ uint32_t s_out[kTextDwords];
+    for (uint32_t i = threadIdx.x; i < kTextDwords; i += kFqThreads) s_out[i] = 0u;  // (ordered by fa_read_chunk's barriers)
+    const uint64_t c0 = (uint64_t)blockIdx.x * kFqChunk;
+    const uint64_t grp = blockIdx.x / kFaGroup;
+    const uint32_t gs = sc.g_state[grp], gh = gs & 1u, gst = (gs >> 1) & 1u;
+    const FaFn pre = fa_unwords2(sc.pre0[blockIdx.x], sc.pre1[blockIdx.x]);
+    const uint32_t h_in = pre.kind ? (pre.kind == 2u ? 1u : 0u) : gh, st_in = gst | pre.rec;
+    const unsigned long long seq0 = sc.g_base[grp] + pre.K + (gst ? pre.V + (gh ? 0u : pre.U) : 0u);
+    const unsigned long long rec0 = sc.g_rec[grp] + pre.nrec;
+    FaChunk c;
+    fa_read_chunk(text, n, c0, s_part, c);
+    uint32_t seq_mask[kFqPieces], both[kFqPieces], both_before[kFqPieces];
+#pragma unroll
+    for (int p = 0; p < (int)kFqPieces; ++p) {
+        seq_mask[p] = c.kb[p] | (st_in ? c.vb[p] : 0u) | ((st_in && !h_in) ? c.ub[p] : 0u);
+        both[p] = (uint32_t)__popc(seq_mask[p]) | ((uint32_t)__popc(c.rs[p]) << 16);  // (sums stay below 2^16)
+    }
+    const uint32_t chunk_seq = chunk_exclusive(both, both_before, s_part) & 0xffffu;  // sequence bytes of the chunk
+    const uint32_t ph = (uint32_t)(seq0 & 3ull);                                      // byte phase of its first output byte
+#pragma unroll
+    for (int p = 0; p < (int)kFqPieces; ++p) {
+        const uint32_t before = both_before[p] & 0xffffu;
+        const unsigned long long o0 = seq0 + before;  // first output byte of the thread's piece
+        const unsigned long long r0 = rec0 + (both_before[p] >> 16);
+        const uint32_t sm = seq_mask[p];
+        if (sm) {
+            const Compact32 k = compact32(c.v[p].d, sm);
+            // the thread's bytes at LDS byte a: shifted up by a & 3 bytes they are whole dwords from a >> 2 on (nine at most)
+            const uint32_t a = ph + before, q = a >> 2, sh = a & 3u;
+            const uint32_t nd = (sh + k.count + 3u) >> 2;  // dwords the thread touches: 1..9
+            uint32_t w[9];
+            w[0] = k.d[0] << (8u * sh);
+#pragma unroll
+            for (int i = 1; i < 8; ++i) w[i] = sh ? __builtin_amdgcn_alignbyte(k.d[i], k.d[i - 1], 4u - sh) : k.d[i];
+            w[8] = sh ? k.d[7] >> (32u - 8u * sh) : 0u;
+#pragma unroll
+            for (int i = 0; i < 9; ++i) {
+                if ((uint32_t)i >= nd) break;
+                if (i == 0 || (uint32_t)i + 1u == nd) {
+                    if (w[i]) atomicOr(&s_out[q + i], w[i]);
+                } else {
+                    s_out[q + i] = w[i];  // (every byte of it is this thread's)
+                }
+            }
+        }
+        // record table: a record starts where its '>' is; its bytes start at the output index reached there
+        uint32_t st = c.rs[p], j = 0;
+        while (st) {
+            const uint32_t i = (uint32_t)__builtin_ctz(st);
+            st &= st - 1u;
+            const unsigned long long r = r0 + j++;
+            if (r < max_records) {
+                rec_start[r] = o0 + (uint32_t)__popc(sm & ((1u << i) - 1u));
+                if (rec_pos) rec_pos[r] = c0 + (uint64_t)p * kFqPiece + (uint64_t)threadIdx.x * kFqBytesPerThread + i;
+            }
+        }
+    }
+    __syncthreads();
+    if (seq0 >= out_bytes) return;
+    // the chunk's bytes are LDS bytes [ph, end): output byte seq0 - ph + j is LDS byte j
+    const uint32_t m = out_bytes - seq0 < chunk_seq ? (uint32_t)(out_bytes - seq0) : chunk_seq;
+    const uint32_t end = ph + m, last = end >> 2;  // `last`: the dword that holds the bytes behind the whole dwords
+    uint32_t *out32 = reinterpret_cast<uint32_t *>(out8) + (seq0 >> 2);
+    for (uint32_t i = (ph ? 1u : 0u) + threadIdx.x; i < last; i += kFqThreads) out32[i] = s_out[i];
+    if (threadIdx.x < 8u) {
+        // threads 0..3: the bytes of a partial FIRST dword; threads 4..7: the bytes behind the last whole dword
+        const bool head = threadIdx.x < 4u;
+        const uint32_t j = head ? threadIdx.x : 4u * last + (threadIdx.x - 4u);
+        const bool mine = head ? (ph != 0u && j >= ph && j < end) : (j < end && (last != 0u || ph == 0u));
+        if (mine) out8[seq0 - ph + j] = (uint8_t)(s_out[j >> 2] >> (8u * (j & 3u)));
+    }
+}
+
 __global__ void fasta2_finish_kernel(const FaScratch sc, uint64_t groups, unsigned long long *rec_base, uint64_t max_records,
                                      unsigned long long *counts) {
     const unsigned long long bases = sc.g_base[groups], recs = sc.g_rec[groups];
@@ -455,6 +545,31 @@ int launch_fasta_pack2(const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_packe
                            reinterpret_cast<uint32_t *>(d_packed), out_dwords, d_rec_base, d_rec_pos, max_records,
                            (uint32_t *)nullptr, (uint64_t)0);
     hipLaunchKernelGGL(fasta2_finish_kernel, dim3(1), dim3(1), 0, stream, sc, groups, d_rec_base, max_records, d_counts);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// FASTA text -> records of byte text: the same two read passes, the third form of K2.  d_seq is NOT cleared (see the kernel).
+int launch_fasta_text(const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_seq, uint64_t seq_capacity_bytes,
+                      unsigned long long *d_rec_start, unsigned long long *d_rec_pos, uint64_t max_records,
+                      unsigned long long *d_counts, void *scratch, hipStream_t stream) {
+    const uint64_t chunks = fa2_chunks(n_bytes), groups = fa2_groups(chunks);
+    if (chunks == 0 || chunks >= (1ull << 31)) return -1;
+    unsigned long long *q = static_cast<unsigned long long *>(scratch);
+    FaScratch sc;
+    sc.fn = q, q += chunks;
+    sc.pre0 = q, q += chunks;
+    sc.pre1 = q, q += chunks;
+    sc.grp0 = q, q += groups + 1;
+    sc.grp1 = q, q += groups + 1;
+    sc.g_base = q, q += groups + 1;
+    sc.g_rec = q, q += groups + 1;
+    sc.g_state = reinterpret_cast<uint32_t *>(q);
+    hipLaunchKernelGGL(fasta2_count_kernel, dim3((uint32_t)chunks), dim3(kFqThreads), 0, stream, d_text, n_bytes, sc.fn);
+    hipLaunchKernelGGL(fasta2_groups_kernel, dim3((uint32_t)groups), dim3(kFaGroup), 0, stream, sc, chunks);
+    hipLaunchKernelGGL(fasta2_resolve_kernel, dim3(1), dim3(kFaGroup), 0, stream, sc, groups);
+    hipLaunchKernelGGL(fasta2_text_kernel, dim3((uint32_t)chunks), dim3(kFqThreads), 0, stream, d_text, n_bytes, sc, d_seq,
+                       seq_capacity_bytes, d_rec_start, d_rec_pos, max_records);
+    hipLaunchKernelGGL(fasta2_finish_kernel, dim3(1), dim3(1), 0, stream, sc, groups, d_rec_start, max_records, d_counts);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

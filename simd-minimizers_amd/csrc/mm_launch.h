@@ -288,6 +288,11 @@ int launch_fasta_pack2(const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_packe
                        unsigned long long *d_rec_base, unsigned long long *d_rec_pos, uint64_t max_records,
                        unsigned long long *d_counts, void *scratch, hipStream_t stream, uint8_t *d_amb = nullptr,
                        uint64_t amb_capacity_bytes = 0);
+// ---- FASTA text -> records of byte text (mm_fasta2.hip: the same passes, the sequence bytes kept as they are; scratch
+// as fasta2_scratch_bytes; d_seq 4-byte aligned and not cleared)
+int launch_fasta_text(const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_seq, uint64_t seq_capacity_bytes,
+                      unsigned long long *d_rec_start, unsigned long long *d_rec_pos, uint64_t max_records,
+                      unsigned long long *d_counts, void *scratch, hipStream_t stream);
 
 // ---- FASTQ text -> packed records (mm_fastq.hip): four-line records, the sequences of lines 4r + 1
 uint64_t fastq_scratch_bytes(uint64_t n_bytes);
