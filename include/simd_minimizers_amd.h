@@ -141,6 +141,9 @@ int mm_workspace_sync(mm_workspace_t *ws);
  *                 dispatched in index order): that run's output and count are invalid; every later
  *                 run on this workspace takes its tile ids from an atomic ticket, so repeating the
  *                 runs issued since the last check gives the right result;
+ *   MM_ERR_CAPACITY  mm_run_text_batch_counts_device_async found d_counts beyond max_chars / max_records (an asynchronous
+ *                 loader that overflowed its tables): that run wrote count 0 and offsets[0] = 0, nothing else, and its
+ *                 values call wrote nothing; mm_last_error() names the call;
  *   MM_ERR_HIP    a kernel refused to run (mm_last_error() says why).
  * The synchronous entry points check (and repeat the run) themselves. */
 int mm_workspace_check(mm_workspace_t *ws);
@@ -393,6 +396,49 @@ int mm_fasta_text_device_async(mm_workspace_t *ws, const uint8_t *d_text, uint64
 int mm_fasta_text_device(mm_workspace_t *ws, const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_seq,
                          uint64_t seq_capacity_bytes, uint64_t *d_rec_start, uint64_t *d_rec_text_pos,
                          uint64_t max_records, uint64_t *d_counts, uint64_t *out_counts /* [2] */);
+/* The batch run with its two counts taken from the DEVICE: d_counts has the loader's layout above (d_counts[0] = characters,
+ * d_counts[1] = records) and is read when the kernels run, so mm_fasta_text_device_async, this call and
+ * mm_values_*_text_batch_counts_device_async queue on one stream and the caller waits once (mm_workspace_check) - file in
+ * device memory -> records -> positions -> values with no host wait in between.  The reference has no counterpart: its
+ * loader and Builder::run are synchronous host code (bench/src/lib.rs:51-82, src/lib.rs:378).
+ *  max_chars / max_records  upper bounds of the two counts, all the host knows: they size the launch.  max_chars >
+ *                         text_bytes: MM_ERR_CAPACITY; max_chars >= 2^32 or max_records >= 2^31: MM_ERR_LEN_TOO_LARGE.
+ *                         Behind the loader: seq_capacity_bytes and max_records as given to it
+ *  d_starts               [max_records + 1]; with (n_chars, n_records) = d_counts[0..1] at kernel time, entries past
+ *                         d_starts[n_records] are not read
+ *  d_out_pos / d_out_sk / d_out_offsets[0 .. n_records] / d_count
+ *                         bit for bit what mm_run_text_batch_device_async writes given n_chars and n_records as host
+ *                         arguments; d_out_offsets is [max_records + 1], entries past [n_records] are not written.
+ *                         capacity = max_chars always suffices (a window gives at most one position)
+ * No window anywhere (n_records == 0, n_chars < l = k + w - 1, max_chars == 0): count 0 and d_out_offsets[0 .. n_records]
+ * = 0, written by the kernels.  Counts BEYOND the bounds (d_counts[0] > max_chars or d_counts[1] > max_records): the run
+ * writes *d_count = 0 and d_out_offsets[0] = 0, touches nothing else, and mm_workspace_check returns MM_ERR_CAPACITY.  No
+ * byte outside [d_text, d_text + text_bytes) is loaded whatever d_counts and d_starts hold.  NULL handling and
+ * MM_ERR_BAD_MODE (a packed plan, d_out_sk with syncmers) as for mm_run_text_batch_device_async, in its order; d_counts NULL
+ * is MM_ERR_NULL.  Plans the fused text kernel does not take (w > 128, k > 1024) and mm_workspace_force_generic return
+ * MM_ERR_BAD_MODE before anything is queued - the generic family's launch per record needs the starts on the host:
+ * mm_last_error() points to mm_run_text_batch_device.  Kernels: the launches of mm_run_text_batch_device_async with a grid
+ * for max_chars; workgroups past the real tile count leave at once. */
+int mm_run_text_batch_counts_device_async(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_text,
+                                          uint64_t text_bytes, uint64_t max_chars, uint64_t max_records,
+                                          const uint64_t *d_starts /* [max_records + 1] */,
+                                          const uint64_t *d_counts /* [2]: characters, records */, uint32_t *d_out_pos,
+                                          uint32_t *d_out_sk /* or NULL */, uint64_t capacity,
+                                          uint64_t *d_out_offsets /* [max_records + 1] */, uint64_t *d_count);
+/* Same, then waits ONCE and returns out[0] = positions, out[1] = n_chars, out[2] = n_records (a look-back time-out repeats
+ * the run, as in every synchronous form).  MM_ERR_CAPACITY when the positions exceeded `capacity` (out[0]: the need) or the
+ * counts exceeded the bounds (out[0] = 0, out[1..2]: the true counts). */
+int mm_run_text_batch_counts_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_text, uint64_t text_bytes,
+                                    uint64_t max_chars, uint64_t max_records, const uint64_t *d_starts,
+                                    const uint64_t *d_counts, uint32_t *d_out_pos, uint32_t *d_out_sk, uint64_t capacity,
+                                    uint64_t *d_out_offsets, uint64_t *out /* [3]: positions, n_chars, n_records */);
+/* What the kernels of the two calls above make of counts and bounds, by the function they call themselves (no device; for
+ * tests): out[0] = real tiles (ceil((n_chars + 1) / 8192); 1 when refused), out[1] = launched tiles (the same of
+ * max_chars), out[2] = win_end = n_chars >= l ? n_chars - l + 1 : 0 (l = k + w - 1; 0 when refused), out[3] = 1 when a count
+ * exceeds its bound (refused).  The entry points' rule for the bounds: MM_ERR_LEN_TOO_LARGE for max_chars >= 2^32 or
+ * max_records >= 2^31; MM_ERR_W_ZERO, MM_ERR_NULL. */
+int mm_debug_text_counts_view(uint32_t k, uint32_t w, uint64_t max_chars, uint64_t max_records, uint64_t n_chars,
+                              uint64_t n_records, uint64_t out[4]);
 /* The per-thread step of that kernel on the host (no device; for tests): the bytes of in[0..32) that `mask` selects
  * (bit i = byte i) moved together to out[0..count), zeros behind them.  Returns the count (MM_ERR_NULL for a null pointer). */
 int mm_debug_compact32(const uint8_t in[32], uint32_t mask, uint8_t out[32]);
@@ -563,6 +609,26 @@ int mm_values_u128_text_batch_device_async(mm_workspace_t *ws, const void *d_tex
                                            uint32_t len, int canonical, const uint32_t *d_pos,
                                            const uint64_t *d_out_offsets /* [n_records + 1] */, uint64_t n_pos_max,
                                            uint64_t *d_values);
+/* The values of a counts run (mm_run_text_batch_counts_device_async; Output::values_* per record, src/lib.rs:584-629):
+ * max_chars / max_records / d_starts / d_counts as that call took them, d_pos / d_out_offsets as it wrote them.  The number
+ * of records - for the record search and for the true count d_out_offsets[n_records] - is d_counts[1], read on the device,
+ * and both counts are held against the bounds there: beyond them (the state the run refuses), or with no record, nothing
+ * is written.  max_records == 0 or n_pos_max == 0 returns MM_OK with nothing launched.  Bounds, encodings and the loads'
+ * limits as the call above and mm_values_u64_text_batch_device_async. */
+int mm_values_u64_text_batch_counts_device_async(mm_workspace_t *ws, const void *d_text, uint64_t text_bytes,
+                                                 uint64_t max_chars, uint64_t max_records,
+                                                 const uint64_t *d_starts /* [max_records + 1] */,
+                                                 const uint64_t *d_counts /* [2] */, int encoding, uint32_t len,
+                                                 int canonical, const uint32_t *d_pos,
+                                                 const uint64_t *d_out_offsets /* [max_records + 1] */, uint64_t n_pos_max,
+                                                 uint64_t *d_values);
+int mm_values_u128_text_batch_counts_device_async(mm_workspace_t *ws, const void *d_text, uint64_t text_bytes,
+                                                  uint64_t max_chars, uint64_t max_records,
+                                                  const uint64_t *d_starts /* [max_records + 1] */,
+                                                  const uint64_t *d_counts /* [2] */, int encoding, uint32_t len,
+                                                  int canonical, const uint32_t *d_pos,
+                                                  const uint64_t *d_out_offsets /* [max_records + 1] */, uint64_t n_pos_max,
+                                                  uint64_t *d_values);
 /* The same from HOST memory (the text is bytes 0 .. starts[n_records], the count offsets[n_records]).  Starts or offsets
  * that decrease return MM_ERR_UNSORTED before anything is touched. */
 int mm_values_u64_text_batch_host(mm_workspace_t *ws, const uint8_t *text, uint64_t n_records,

@@ -317,6 +317,16 @@ def _load_lib():
             L.mm_fasta_text_device_async.argtypes = fasta_args
             L.mm_fasta_text_device.argtypes = fasta_args + [u64p]
             L.mm_debug_compact32.argtypes = [u8p, C.c_uint32, u8p]
+        if hasattr(L, "mm_run_text_batch_counts_device"):  # (text batch run and values with their counts on the device)
+            counts_args = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, vp, vp, vp, vp, C.c_uint64, vp]
+            L.mm_run_text_batch_counts_device_async.argtypes = counts_args + [vp]
+            L.mm_run_text_batch_counts_device.argtypes = counts_args + [u64p]
+            values_counts_args = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, vp, vp, C.c_int, C.c_uint32, C.c_int, vp, vp,
+                                  C.c_uint64, vp]
+            L.mm_values_u64_text_batch_counts_device_async.argtypes = values_counts_args
+            L.mm_values_u128_text_batch_counts_device_async.argtypes = values_counts_args
+            L.mm_debug_text_counts_view.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
+                                                    u64p]
         _lib = L
     return _lib
 
@@ -361,6 +371,9 @@ EXPORTED_SYMBOLS = [
     "mm_values_u128_text_host", "mm_values_u64_text_batch_device_async", "mm_values_u128_text_batch_device_async",
     "mm_values_u64_text_batch_host", "mm_values_u128_text_batch_host", "mm_values_text_lds_stage", "mm_debug_values_text",
     "mm_fasta_text_device_async", "mm_fasta_text_device", "mm_debug_compact32",
+    "mm_run_text_batch_counts_device_async", "mm_run_text_batch_counts_device",
+    "mm_values_u64_text_batch_counts_device_async", "mm_values_u128_text_batch_counts_device_async",
+    "mm_debug_text_counts_view",
 ]
 
 
@@ -1493,6 +1506,163 @@ def run_fasta_text_device(builder: "Builder", records: FastaTextRecords, out_pos
     """All records of ``fasta_text_device`` in one launch of the text plan (``run_text_batch_device`` on them): record-local
     positions, ``out_offsets`` (int64 CUDA tensor, n + 1) delimits the records.  Returns the number of positions."""
     return run_text_batch_device(builder, records.seq, records.starts, records.n_chars, out_pos, out_offsets, out_sk)
+
+
+def text_counts_view(k: int, w: int, max_chars: int, max_records: int, n_chars: int, n_records: int) -> dict:
+    """What the kernels of the counts calls make of the device's counts and the caller's bounds
+    (``mm_debug_text_counts_view``: the function they call, on the host; no GPU)."""
+    out = (C.c_uint64 * 4)()
+    _check(lib().mm_debug_text_counts_view(k, w, max_chars, max_records, n_chars, n_records, out))
+    return {"real_tiles": int(out[0]), "launched_tiles": int(out[1]), "win_end": int(out[2]), "refused": bool(out[3])}
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def run_text_batch_counts_device(builder: "Builder", d_text, d_starts, d_counts, out_pos, out_offsets, out_sk=None,
+                                 max_chars=None, wait=False, d_count=None):
+    """``run_text_batch_device`` with the two counts taken from the DEVICE (``mm_run_text_batch_counts_device_async``):
+    ``d_counts`` = an int64 CUDA tensor {characters, records} as ``mm_fasta_text_device_async`` writes it, read when the
+    kernels run; ``d_starts`` / ``out_offsets`` hold ``max_records + 1`` entries, ``max_chars`` (default: all of ``d_text``)
+    bounds the characters.  Queued on the builder's workspace, nothing waits: returns None and ``Workspace.check`` reports
+    counts beyond the bounds as ``MM_ERR_CAPACITY`` (``d_count``: an optional int64 CUDA tensor that receives the number of
+    positions).  ``wait=True`` (``mm_run_text_batch_counts_device``): one wait, returns (positions, n_chars, n_records)."""
+    max_rec = d_starts.numel() - 1
+    if max_rec < 0 or out_offsets.numel() < max_rec + 1:
+        raise ValueError("d_starts and out_offsets hold max_records + 1 entries each")
+    if d_counts.numel() < 2:
+        raise ValueError("d_counts holds two words: characters, records")
+    text_bytes = d_text.numel() if d_text is not None else 0
+    if max_chars is None:
+        max_chars = text_bytes
+    cap = out_pos.numel() if out_pos is not None else 0
+    args = (builder.text_plan().h, builder._ws().h, _ptr(d_text), text_bytes, int(max_chars), max_rec, _ptr(d_starts),
+            _ptr(d_counts), _ptr(out_pos), _ptr(out_sk), cap, _ptr(out_offsets))
+    if not wait:
+        _check_counts(lib().mm_run_text_batch_counts_device_async(*args, _ptr(d_count)))
+        return None
+    out = (C.c_uint64 * 3)()
+    code = lib().mm_run_text_batch_counts_device(*args, out)
+    if code == ERR["CAPACITY"]:
+        if out_pos is not None and out[0] > cap:
+            raise MinimizerError(code, f"output capacity {cap} < {out[0]}")
+        raise MinimizerError(code, f"counts ({out[1]} characters, {out[2]} records) beyond max_chars {int(max_chars)} / "
+                                   f"max_records {max_rec}")
+    _check_counts(code)
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def _check_counts(code: int):
+    """``_check`` that also shows why a counts call refused a plan (``MM_ERR_BAD_MODE`` with ``mm_last_error``)."""
+    if code == ERR["BAD_MODE"]:
+        L = lib()
+        raise MinimizerError(code, L.mm_strerror(code).decode() + ": " + L.mm_last_error().decode())
+    _check(code)
+
+
+def values_text_batch_counts_device(builder: "Builder", d_text, d_starts, d_counts, d_pos, d_out_offsets, n_pos_max, encoding,
+                                    u128=False, out=None, max_chars=None):
+    """``values_text_batch_device`` for a counts run (``mm_values_u64_text_batch_counts_device_async`` /
+    ``mm_values_u128_text_batch_counts_device_async``): ``d_text`` / ``d_starts`` / ``d_counts`` / ``max_chars`` as
+    ``run_text_batch_counts_device`` took them, ``d_pos`` / ``d_out_offsets`` as it wrote them.  The number of records and
+    the true count are read on the device; counts beyond the bounds and the kernel writes nothing.  Asynchronous on the
+    builder's workspace."""
+    import torch
+    max_rec = d_starts.numel() - 1
+    if max_rec < 0 or d_out_offsets.numel() < max_rec + 1:
+        raise ValueError("d_starts and d_out_offsets hold max_records + 1 entries each")
+    n_pos_max = int(n_pos_max)
+    per = 2 if u128 else 1
+    if out is None:
+        out = torch.zeros(per * n_pos_max, dtype=torch.int64, device=d_pos.device)
+        torch.cuda.synchronize(d_pos.device)
+    elif out.numel() < per * n_pos_max:
+        raise ValueError(f"out holds {out.numel()} words, {per * n_pos_max} needed")
+    if d_pos.numel() < n_pos_max:
+        raise ValueError(f"d_pos holds {d_pos.numel()} positions, n_pos_max is {n_pos_max}")
+    text_bytes = d_text.numel() if d_text is not None else 0
+    if max_chars is None:
+        max_chars = text_bytes
+    f = lib().mm_values_u128_text_batch_counts_device_async if u128 else lib().mm_values_u64_text_batch_counts_device_async
+    _check(f(builder._ws().h, _ptr(d_text), text_bytes, int(max_chars), max_rec, _ptr(d_starts), _ptr(d_counts),
+             int(encoding), _value_len(builder), int(builder.canonical), _ptr(d_pos), _ptr(d_out_offsets), n_pos_max,
+             _ptr(out)))
+    return out
+
+
+class FastaTextPipeline:
+    """What ``fasta_text_pipeline_device`` queued: the device tensors of loader, run and values (``seq``, ``starts``,
+    ``rec_pos``, ``counts``, ``pos``, ``offsets``, ``count``, ``values`` or None), all still being written until
+    ``finish()`` has waited."""
+
+    def __init__(self, builder, ws, seq, starts, rec_pos, counts, pos, offsets, count, values, max_records):
+        self.builder, self.ws = builder, ws
+        self.seq, self.starts, self.rec_pos, self.counts = seq, starts, rec_pos, counts
+        self.pos, self.offsets, self.count, self.values = pos, offsets, count, values
+        self.max_records = max_records
+
+    def finish(self):
+        """The ONE wait of the pipeline: ``Workspace.check`` (``MinimizerError`` ``MM_ERR_CAPACITY`` when the file holds
+        more than ``max_records`` records), then the counts.  Returns (records, n_positions, positions, offsets, values):
+        the ``FastaTextRecords`` of ``fasta_text_device``, the count ``run_fasta_text_device`` returns with its
+        ``out_pos[:count]`` / ``out_offsets`` (CUDA tensors), and the values tensor of ``values_text_batch_device`` cut to
+        the count (None when no encoding was given)."""
+        try:
+            self.ws.check()
+        except MinimizerError as e:
+            if e.code == ERR["CAPACITY"]:
+                raise MinimizerError(e.code, f"{e} ({lib().mm_last_error().decode()}); max_records was {self.max_records}")
+            raise
+        n_chars, n_rec = (int(x) for x in self.counts.cpu().numpy())
+        cnt = int(self.count.item())
+        recs = FastaTextRecords(self.seq[:n_chars], self.starts[: n_rec + 1],
+                                self.rec_pos[:n_rec].cpu().numpy().astype(np.uint64), n_chars)
+        vals = None
+        if self.values is not None:
+            per = self.values.numel() // max(1, self.pos.numel())
+            vals = self.values[: per * cnt]
+        return recs, cnt, self.pos[:cnt], self.offsets[: n_rec + 1], vals
+
+
+def fasta_text_pipeline_device(builder: "Builder", text, max_records: int, encoding=None, u128=False) -> FastaTextPipeline:
+    """File bytes -> records -> positions (-> values) queued on ONE stream with no synchronisation in between:
+    ``mm_fasta_text_device_async``, ``mm_run_text_batch_counts_device_async`` and, with an ``encoding``
+    (``TEXT_VALUES_BYTES`` / ``TEXT_VALUES_DNA``), ``mm_values_*_text_batch_counts_device_async`` on the builder's
+    workspace; the loader's counts never visit the host.  ``text`` = the file's bytes (bytes / numpy uint8 / torch uint8
+    CUDA tensor on the workspace's device).  Returns a ``FastaTextPipeline``; its ``finish()`` waits once.  The
+    asynchronous loader does NOT look at the first byte: a FASTQ text is read by the FASTA rules (a quality line may begin
+    with '>'), so its records are nonsense - the caller knows its format or uses ``fasta_text_device``."""
+    import torch
+
+    ws = builder._ws()
+    dev = f"cuda:{ws.device}"
+    if isinstance(text, (bytes, bytearray)):
+        text = np.frombuffer(bytes(text), dtype=np.uint8).copy()
+    if isinstance(text, np.ndarray):
+        t = torch.from_numpy(np.ascontiguousarray(text)).to(dev) if text.size else torch.zeros(0, dtype=torch.uint8, device=dev)
+    else:
+        t = text
+    n = int(t.numel())
+    max_records = int(max_records)
+    seq = torch.empty(max(n, 4), dtype=torch.uint8, device=dev)
+    starts = torch.zeros(max_records + 1, dtype=torch.int64, device=dev)
+    rec_pos = torch.zeros(max(max_records, 1), dtype=torch.int64, device=dev)
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    pos = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    offsets = torch.zeros(max_records + 1, dtype=torch.int64, device=dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    per = 2 if u128 else 1
+    values = torch.zeros(per * max(n, 1), dtype=torch.int64, device=dev) if encoding is not None else None
+    torch.cuda.synchronize(ws.device)  # (the tensors above are torch's work on its own stream: before, not between)
+    _check(lib().mm_fasta_text_device_async(ws.h, _ptr(t) if n else None, n, _ptr(seq), n, _ptr(starts), _ptr(rec_pos),
+                                            max_records, _ptr(counts)))
+    seq_n = seq[:n] if n else seq[:0]
+    run_text_batch_counts_device(builder, seq_n if n else None, starts, counts, pos, offsets, max_chars=n, d_count=count)
+    if encoding is not None and n and max_records:
+        values_text_batch_counts_device(builder, seq_n, starts, counts, pos, offsets, pos.numel(), encoding, u128=u128,
+                                        out=values, max_chars=n)
+    return FastaTextPipeline(builder, ws, seq, starts, rec_pos, counts, pos, offsets, count, values, max_records)
 
 
 def run_packed_reads_device(builder: "Builder", records: FastaRecords, out_pos, out_offsets, out_sk=None, max_read_len=None):

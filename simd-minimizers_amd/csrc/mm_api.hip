@@ -20,6 +20,7 @@
 #include "mm_env.h"
 #include "mm_launch.h"
 #include "mm_fasta_text.h"
+#include "mm_text_counts.h"
 #include "mm_values_batch.h"
 #include "mm_values_reads.h"
 #include "mm_values_text.h"
@@ -403,6 +404,10 @@ int collect_timing(mm_workspace *ws) {
 // The per-run error word of a finished run (h_total[1], see OutParams::error): 0 = fine, 1 = a look-back
 // spin ran out (the caller redoes the run in ticket mode), anything else is a failed launch.
 // Returns 0 (fine), 1 (redo in ticket mode) or a negative MM_ERR_* code.
+// (kernel error 6: the counts of a text batch run, read on the device, lie beyond the bounds the caller gave)
+const char *const kTextCountsRefused =
+    "mm_run_text_batch_counts_device_async: d_counts exceed max_chars / max_records (the loader overflowed its tables?); "
+    "count 0 and offsets[0] = 0 were written, nothing else";
 int judge_run_error(mm_workspace *ws) {
     const uint32_t code = (uint32_t)ws->h_total[1];
     if (code == 0) return 0;
@@ -434,6 +439,10 @@ int judge_run_error(mm_workspace *ws) {
         g_last_error = "mm_fasta_pack_device_async: lines too short for the one-pass packer; its output is invalid, "
                        "repeat the call (three-pass kernels from now on)";
         return MM_ERR_ORDER;
+    }
+    if (code == 6u) {
+        g_last_error = kTextCountsRefused;
+        return MM_ERR_CAPACITY;
     }
     char buf[128];
     snprintf(buf, sizeof(buf), code == 2u   ? "kernel error 2: dynamic LDS does not lie behind the static LDS"
@@ -856,6 +865,10 @@ int mm_workspace_check(mm_workspace_t *ws) {
         g_last_error = "mm_fasta_pack_device_async: lines too short for the one-pass packer; its output is invalid, "
                        "repeat the call (three-pass kernels from now on)";
         return MM_ERR_ORDER;
+    }
+    if (code == 6u) {
+        g_last_error = kTextCountsRefused;
+        return MM_ERR_CAPACITY;
     }
     char buf[128];
     snprintf(buf, sizeof(buf), code == 2u   ? "kernel error 2: dynamic LDS does not lie behind the static LDS"
@@ -2878,6 +2891,143 @@ int mm_run_text_batch_device(const mm_plan_t *plan, mm_workspace_t *ws, const vo
     });
 }
 
+// --------------------------------------------- text batch, counts on the device
+// The same run with its two counts in DEVICE memory (d_counts, the layout mm_fasta_text_device_async writes: characters,
+// records), read when the kernels run: loader and run queue back to back, nothing waits for the host.  The host knows
+// upper bounds only and sizes the launch from them; the kernels do the rest (mm_text_counts.h, mm_text_walk_impl.h).  The
+// reference has no counterpart (Builder::run is synchronous host code, src/lib.rs:378); the results are those of
+// mm_run_text_batch_device_async given the counts as host arguments.
+// The argument checks, before anything is touched (no workspace needed), in the order of text_batch_check.
+static int text_batch_counts_check(const mm_plan_t *plan, const void *d_text, uint64_t text_bytes, uint64_t max_chars,
+                                   uint64_t max_records, const uint64_t *d_starts, const uint64_t *d_counts,
+                                   const uint32_t *d_out_sk, const uint64_t *d_out_offsets) {
+    if (!plan) return MM_ERR_NULL;
+    if (!plan->text) return MM_ERR_BAD_MODE;  // (a plan of mm_plan_create: packed entry points only)
+    if (max_chars >= (1ull << 32) || max_records >= (1ull << 31)) return MM_ERR_LEN_TOO_LARGE;
+    if (d_out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;  // src/lib.rs:339
+    if (!d_out_offsets || !d_counts || (max_records && !d_starts)) return MM_ERR_NULL;
+    if (max_chars > text_bytes) return MM_ERR_CAPACITY;
+    if (max_chars && !d_text) return MM_ERR_NULL;
+    if (!mm::text_walk_supported(plan->k, plan->w)) {
+        // (the generic family runs one launch per record: it needs the starts on the host)
+        g_last_error = "mm_run_text_batch_counts_device*: w > 128 or k > 1024 has no fused text kernel; read the counts back "
+                       "and call mm_run_text_batch_device";
+        return MM_ERR_BAD_MODE;
+    }
+    return MM_OK;
+}
+
+static int run_text_batch_counts_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_text,
+                                            uint64_t text_bytes, uint64_t max_chars, uint64_t max_records,
+                                            const uint64_t *d_starts, const uint64_t *d_counts, uint32_t *d_out_pos,
+                                            uint32_t *d_out_sk, uint64_t capacity, uint64_t *d_out_offsets,
+                                            uint64_t *d_count) {
+    int r = text_batch_counts_check(plan, d_text, text_bytes, max_chars, max_records, d_starts, d_counts, d_out_sk,
+                                    d_out_offsets);
+    if (r) return r;
+    if (!ws) return MM_ERR_NULL;
+    if (ws->force_generic) {
+        g_last_error = "mm_run_text_batch_counts_device*: the generic family (mm_workspace_force_generic) needs the starts on "
+                       "the host; read the counts back and call mm_run_text_batch_device";
+        return MM_ERR_BAD_MODE;
+    }
+    if (!d_out_pos) capacity = 0;
+    MM_HIP(set_device(ws->device));
+    mm::TextRunArgs a;
+    r = text_tables_on_device(ws, plan->tt, &a.tables);
+    if (r) return r;
+    // (grid, look-back words and the tiles' record ranges for the bound: max_chars == 0 is still one tile, which writes
+    // offsets[0] and the count)
+    const uint64_t tiles = mm::text_batch_tiles(max_chars);
+    r = grow_status(ws, tiles + 1);
+    if (r == MM_OK) r = grow(ws->d_text_tiles, ws->d_text_tiles_elems, 2 * tiles, sizeof(unsigned long long));
+    if (r) return r;
+    MM_HIP(hipMemsetAsync(ws->total, 0, 2 * sizeof(unsigned long long), ws->stream));
+    a.text = static_cast<const uint8_t *>(d_text);
+    a.k = plan->k;
+    a.w = plan->w;
+    a.canonical_windows = plan->canonical_windows;
+    a.mode = plan->mode;
+    a.out.pos = d_out_pos;
+    a.out.sk = d_out_sk;
+    a.out.cap = capacity;
+    a.out.total = ws->total;
+    a.out.ticket = ws->ticket;
+    a.out.error = reinterpret_cast<uint32_t *>(ws->total + 1);
+    a.out.status = ws->status;
+    ws->status_dirty = true;  // (the text kernels clear and write untagged words)
+    a.timing_start = a.timing_stop = nullptr;
+    a.hash_rc = plan->tt.canonical != 0;
+    a.fw0 = plan->tt.fw0;
+    a.rc0 = plan->tt.rc0;
+    a.rot = plan->tt.rot;
+    a.scratch = nullptr;
+    a.generic_round_windows = 0;
+    a.n = max_chars;
+    a.win_begin = 0;
+    a.win_end = 0;  // (from the counts, on the device)
+    a.batch = true;
+    a.starts = d_starts;
+    a.n_records = max_records;
+    a.tile_rec = ws->d_text_tiles;
+    a.offsets = reinterpret_cast<unsigned long long *>(d_out_offsets);
+    a.counts = d_counts;
+    if (ws->timing) {
+        hipEvent_t e0, e1;
+        MM_HIP(hipEventCreate(&e0));
+        MM_HIP(hipEventCreate(&e1));
+        ws->events.emplace_back(e0, e1);
+        a.timing_start = e0;
+        a.timing_stop = e1;
+    }
+    if (mm::launch_text_walk(a, ws->stream) != 0) {
+        g_last_error = std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError());
+        return MM_ERR_HIP;
+    }
+    ws->last_path = MM_PATH_FUSED;
+    if (d_count)
+        MM_HIP(hipMemcpyAsync(d_count, ws->total, sizeof(unsigned long long), hipMemcpyDeviceToDevice, ws->stream));
+    return MM_OK;
+}
+
+int mm_run_text_batch_counts_device_async(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_text,
+                                          uint64_t text_bytes, uint64_t max_chars, uint64_t max_records,
+                                          const uint64_t *d_starts, const uint64_t *d_counts, uint32_t *d_out_pos,
+                                          uint32_t *d_out_sk, uint64_t capacity, uint64_t *d_out_offsets,
+                                          uint64_t *d_count) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (ws) ws->async_unchecked = true;
+    return run_text_batch_counts_async_impl(plan, ws, d_text, text_bytes, max_chars, max_records, d_starts, d_counts,
+                                            d_out_pos, d_out_sk, capacity, d_out_offsets, d_count);
+}
+
+int mm_run_text_batch_counts_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_text, uint64_t text_bytes,
+                                    uint64_t max_chars, uint64_t max_records, const uint64_t *d_starts,
+                                    const uint64_t *d_counts, uint32_t *d_out_pos, uint32_t *d_out_sk, uint64_t capacity,
+                                    uint64_t *d_out_offsets, uint64_t *out) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    const int rc = text_batch_counts_check(plan, d_text, text_bytes, max_chars, max_records, d_starts, d_counts, d_out_sk,
+                                           d_out_offsets);
+    if (rc) return rc;
+    if (!ws) return MM_ERR_NULL;
+    if (out) out[0] = out[1] = out[2] = 0;
+    uint64_t count = 0;
+    // (the two counts come back with the run's words: h_total[4..5], one wait for all of them)
+    const int r = run_sync(ws, capacity, d_out_pos != nullptr, &count, [&](bool *) {
+        const int q = run_text_batch_counts_async_impl(plan, ws, d_text, text_bytes, max_chars, max_records, d_starts,
+                                                       d_counts, d_out_pos, d_out_sk, capacity, d_out_offsets, nullptr);
+        if (q) return q;
+        MM_HIP(hipMemcpyAsync(ws->h_total + 4, d_counts, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
+        return (int)MM_OK;
+    });
+    if (out && (r == MM_OK || r == MM_ERR_CAPACITY)) {
+        out[0] = count;
+        out[1] = ws->h_total[4];
+        out[2] = ws->h_total[5];
+    }
+    return r;
+}
+
 int mm_run_text_batch_host(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *text, uint64_t n_records,
                            const uint64_t *starts, uint32_t *out_pos, uint32_t *out_sk, uint64_t capacity,
                            uint64_t *out_offsets, uint64_t *out_count) {
@@ -3460,6 +3610,73 @@ int mm_values_u128_text_batch_device_async(mm_workspace_t *ws, const void *d_tex
     ApiScope api_scope;  // (restores the calling thread's current device on return)
     return values_text_batch_async_impl(ws, d_text, text_bytes, n_records, d_starts, n_chars, encoding, len, canonical, d_pos,
                                         d_out_offsets, n_pos_max, d_values, true);
+}
+
+// The values of a counts run (mm_run_text_batch_counts_device_async): the records' number comes from d_counts[1] on the
+// device - for the record search and for the true count d_out_offsets[n_records] - and both counts are held against the
+// bounds there: beyond them (the state the run refuses) or with no record, nothing is written.
+static int values_text_batch_counts_async_impl(mm_workspace_t *ws, const void *d_text, uint64_t text_bytes, uint64_t max_chars,
+                                               uint64_t max_records, const uint64_t *d_starts, const uint64_t *d_counts,
+                                               int encoding, uint32_t len, int canonical, const uint32_t *d_pos,
+                                               const uint64_t *d_out_offsets, uint64_t n_pos_max, uint64_t *d_values,
+                                               bool u128) {
+    if (!ws) return MM_ERR_NULL;
+    if (const int bad = values_text_mode_check(encoding, len, canonical, u128)) return bad;
+    if (max_records == 0 || n_pos_max == 0) return MM_OK;
+    if (!d_text || !d_starts || !d_counts || !d_pos || !d_out_offsets || !d_values) return MM_ERR_NULL;
+    if (max_chars >= (1ull << 32) || max_records >= (1ull << 31)) return MM_ERR_LEN_TOO_LARGE;
+    if (max_chars > text_bytes) return MM_ERR_CAPACITY;
+    MM_HIP(set_device(ws->device));
+    mm::ValuesTextArgs a;
+    a.view = mm::text_view((uint64_t)reinterpret_cast<uintptr_t>(d_text), text_bytes);
+    a.n_records = max_records;
+    a.starts = reinterpret_cast<const unsigned long long *>(d_starts);
+    a.len = len;
+    a.canonical = canonical ? 1 : 0;
+    a.pos = d_pos;
+    a.offsets = reinterpret_cast<const unsigned long long *>(d_out_offsets);
+    a.n_pos_max = n_pos_max;
+    a.out = reinterpret_cast<unsigned long long *>(d_values);
+    a.counts = reinterpret_cast<const unsigned long long *>(d_counts);
+    a.max_chars = max_chars;
+    const int r = mm::launch_values_text(a, encoding, u128, true, ws->stream);
+    if (r == -3) return MM_ERR_LEN_TOO_LARGE;
+    if (r) return hip_fail(hipGetLastError(), u128 ? "values_u128_text_batch_counts" : "values_u64_text_batch_counts");
+    return MM_OK;
+}
+
+int mm_values_u64_text_batch_counts_device_async(mm_workspace_t *ws, const void *d_text, uint64_t text_bytes,
+                                                 uint64_t max_chars, uint64_t max_records, const uint64_t *d_starts,
+                                                 const uint64_t *d_counts, int encoding, uint32_t len, int canonical,
+                                                 const uint32_t *d_pos, const uint64_t *d_out_offsets, uint64_t n_pos_max,
+                                                 uint64_t *d_values) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    return values_text_batch_counts_async_impl(ws, d_text, text_bytes, max_chars, max_records, d_starts, d_counts, encoding,
+                                               len, canonical, d_pos, d_out_offsets, n_pos_max, d_values, false);
+}
+
+int mm_values_u128_text_batch_counts_device_async(mm_workspace_t *ws, const void *d_text, uint64_t text_bytes,
+                                                  uint64_t max_chars, uint64_t max_records, const uint64_t *d_starts,
+                                                  const uint64_t *d_counts, int encoding, uint32_t len, int canonical,
+                                                  const uint32_t *d_pos, const uint64_t *d_out_offsets, uint64_t n_pos_max,
+                                                  uint64_t *d_values) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    return values_text_batch_counts_async_impl(ws, d_text, text_bytes, max_chars, max_records, d_starts, d_counts, encoding,
+                                               len, canonical, d_pos, d_out_offsets, n_pos_max, d_values, true);
+}
+
+// What the counts kernels make of {counts, bounds}, by the function they call (mm_text_counts.h): no device.
+int mm_debug_text_counts_view(uint32_t k, uint32_t w, uint64_t max_chars, uint64_t max_records, uint64_t n_chars,
+                              uint64_t n_records, uint64_t out[4]) {
+    if (!out) return MM_ERR_NULL;
+    if (w == 0) return MM_ERR_W_ZERO;
+    if (max_chars >= (1ull << 32) || max_records >= (1ull << 31)) return MM_ERR_LEN_TOO_LARGE;  // (the entry points' rule)
+    const mm::TextCountsView v = mm::text_counts_view(k + w - 1, max_chars, max_records, n_chars, n_records);
+    out[0] = v.tiles;
+    out[1] = mm::text_counts_tiles(max_chars);
+    out[2] = v.win_end;
+    out[3] = v.refused;
+    return MM_OK;
 }
 
 int mm_values_u64_text_batch_host(mm_workspace_t *ws, const uint8_t *text, uint64_t n_records, const uint64_t *starts,

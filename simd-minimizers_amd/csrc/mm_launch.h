@@ -234,6 +234,9 @@ struct TextRunArgs {
     uint64_t n_records = 0;
     unsigned long long *tile_rec = nullptr;
     unsigned long long *offsets = nullptr;
+    // batch, or null: the true {characters, records} in device memory, read by the kernels; n and n_records are then
+    // upper bounds that size the launch (mm_text_counts.h), win_end is not looked at
+    const uint64_t *counts = nullptr;
 };
 int launch_generic_text(const TextRunArgs &a, hipStream_t stream);
 // ---- the fused text kernel (mm_text_walk.hip): one launch, w <= 128 and k <= 1024 (prebuilt W: 5, 11, 19)

@@ -43,7 +43,7 @@ int text_prebuilt_windows(uint32_t *out, int capacity) {
 }
 
 uint64_t text_walk_tiles(uint64_t windows) { return (windows + kTextTile - 1) / kTextTile; }
-uint64_t text_batch_tiles(uint64_t n_chars) { return text_walk_tiles(n_chars + 1); }
+uint64_t text_batch_tiles(uint64_t n_chars) { return text_counts_tiles(n_chars); }
 
 namespace {
 TextWalkFn pick_window(uint32_t w, bool canon, bool hash_rc, uint32_t mode, bool batch) {
@@ -86,7 +86,10 @@ int launch_text_walk(const TextRunArgs &a, hipStream_t stream) {
     p.n_records = a.n_records;
     p.tile_rec = a.tile_rec;
     p.offsets = a.offsets;
-    // (a batch: windows 0 .. n inclusive, so that the records that start in the last l - 1 bytes get their offsets)
+    p.counts = a.batch ? a.counts : nullptr;
+    // (a batch: windows 0 .. n inclusive, so that the records that start in the last l - 1 bytes get their offsets; with
+    // a.counts, n and n_records are upper bounds: the grid, the status words and tile_rec are sized for the bound, the
+    // kernels find the real tiles themselves)
     const uint64_t tiles = a.batch ? text_batch_tiles(a.n) : text_walk_tiles(a.win_end - a.win_begin);
     // (untagged look-back words and the ticket, cleared per launch as the generic family does)
     if (hipMemsetAsync(a.out.status, 0, sizeof(unsigned long long) * tiles, stream) != hipSuccess) return -1;
@@ -94,7 +97,7 @@ int launch_text_walk(const TextRunArgs &a, hipStream_t stream) {
     if (a.timing_start) hipEventRecord(a.timing_start, stream);
     if (a.batch)
         hipLaunchKernelGGL(text_batch_tiles_kernel, dim3((uint32_t)((tiles + 255) / 256)), dim3(256), 0, stream, a.starts,
-                           a.n_records, a.k + a.w - 1, tiles, a.tile_rec);
+                           a.n_records, a.k + a.w - 1, tiles, a.tile_rec, p.counts, a.n);
     hipLaunchKernelGGL(fn, dim3((uint32_t)tiles), dim3(kTextThreads), 0, stream, p);
     if (a.timing_stop) hipEventRecord(a.timing_stop, stream);
     return hipGetLastError() == hipSuccess ? 0 : -1;

@@ -25,8 +25,15 @@
 // (up to kTextBnd of them; a tile with more reads them from global memory instead); every thread finds its first
 // window's record by a search in that list and steps forward.  The thread whose windows hold g == starts[r] writes
 // offsets[r]; the grid spans windows 0 .. n_chars, so records that start in the last l - 1 bytes get theirs too.
+//
+// BATCH with p.counts (mm_run_text_batch_counts_*): the two counts are device words that an earlier call on the stream
+// writes (mm_fasta_text_device_async), p.n and p.n_records are only their upper bounds and the grid is sized from them.
+// Every workgroup reads the counts right behind its ticket (text_counts_view, mm_text_counts.h): a ticket at or past the
+// real tile count leaves before it touches anything, "the last tile" is the last REAL tile, and counts beyond the bounds
+// are refused by the workgroup that holds ticket 0 (count 0, offsets[0] = 0, error word 6).
 #pragma once
 #include "mm_common.h"
+#include "mm_text_counts.h"
 
 namespace mm {
 
@@ -43,6 +50,7 @@ constexpr uint32_t kTextBytes = (kTextHashRun * kTextThreads + kTextMaxK + 32 + 
 constexpr uint32_t kTextSelStride = kTextPerThread / 2 + 1;       // dwords per thread's 32 offsets (+1: no conflicts)
 static_assert(kTextHashRun % 2 == 1, "odd runs keep the key stores of a wave on distinct banks");
 static_assert(kTextThreads == 256, "one table entry per thread");
+static_assert(kTextTile == kTextCountsTile, "text_counts_view counts tiles of kTextTile windows");
 constexpr uint32_t kTextBnd = 2048;                               // BATCH: record starts of a tile held in LDS (4 KB)
 static_assert(kTextTile + 1 + kTextMaxW + kTextMaxK < 0xffffu, "tile-local byte offsets fit 16 bits");
 
@@ -60,14 +68,26 @@ struct TextWalkParams {
     uint64_t n_records;
     const unsigned long long *tile_rec;
     unsigned long long *offsets;  // [n_records + 1]
+    // BATCH, or null: {characters, records} in device memory, read when the kernel runs; n and n_records are then their
+    // upper bounds and win_end is not looked at
+    const uint64_t *counts;
 };
 
 // One thread per tile of a BATCH launch: the range of record starts that tile t's collect stage needs (upper bounds of
 // its front window t * kTextTile - 1 and of the last byte it reaches, in starts[0 .. n_records]).  Records in any order
 // give some range inside [0, n_records + 1]: the walk never indexes outside it.
+// counts (or null): the batch's true {characters, records}; n_chars and n_records are then their bounds, tiles the launched
+// tiles, and only the real tiles get their range (a refused or record-less batch has none: the walk reads no range then).
 __global__ __launch_bounds__(256) void text_batch_tiles_kernel(const uint64_t *starts, uint64_t n_records, uint32_t l,
-                                                               uint64_t tiles, unsigned long long *tile_rec) {
+                                                               uint64_t tiles, unsigned long long *tile_rec,
+                                                               const uint64_t *counts, uint64_t n_chars) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (counts) {
+        const TextCountsView v = text_counts_view(l, n_chars, n_records, counts[0], counts[1]);
+        if (!v.walk) return;
+        if (v.tiles < tiles) tiles = v.tiles;
+        n_records = v.n_records;
+    }
     if (t >= tiles) return;
     auto upper = [&](long long x) -> uint64_t {  // first i in [0, n_records + 1) with starts[i] > x
         uint64_t lo = 0, hi = n_records + 1;
@@ -103,6 +123,30 @@ __global__ __launch_bounds__(kTextThreads) void text_walk_kernel(TextWalkParams 
     const uint32_t w = W > 0 ? (uint32_t)W : p.w;
     const uint32_t k = p.k;
     if (tid == 0) s_bid = atomicAdd(p.out.ticket, 1u);
+    // the batch's size: kernel arguments, or (BATCH with p.counts) the device's own counts within those bounds
+    uint64_t n = p.n, n_records = p.n_records, win_end = p.win_end;
+    uint32_t last_bid = gridDim.x - 1;
+    if constexpr (BATCH) {
+        if (p.counts) {
+            __syncthreads();
+            const uint32_t b = s_bid;
+            const TextCountsView v = text_counts_view(k + w - 1, p.n, p.n_records, p.counts[0], p.counts[1]);
+            if (b >= v.tiles) return;  // (a surplus workgroup: no status word, no table, no output)
+            if (!v.walk) {
+                // counts beyond the bounds, or no record: ticket 0 alone, and nobody reads the starts
+                if (tid == 0 && b == 0) {
+                    *p.out.total = 0ull;
+                    p.offsets[0] = 0ull;
+                    if (v.refused) flag_error(p.out.error, 6u);
+                }
+                return;
+            }
+            n = v.n;
+            n_records = v.n_records;
+            win_end = v.win_end;
+            last_bid = (uint32_t)v.tiles - 1u;
+        }
+    }
     s_in[tid] = p.tables[tid];
     s_out[tid] = p.tables[256 + tid];
 
@@ -119,7 +163,7 @@ __global__ __launch_bounds__(kTextThreads) void text_walk_kernel(TextWalkParams 
     const uint64_t tbase = a0a >= 0 ? (uint64_t)a0a : 0u;
     // the tile's own descriptor (offsets stay small for any n < 2^32), whole dwords up to the end of the text: the text's
     // last dword may hold bytes behind it - same dword, same page - that only k-mers past the last window see
-    const uint64_t rem = ((p.n + sh + 3u) & ~3ull) - tbase;
+    const uint64_t rem = ((n + sh + 3u) & ~3ull) - tbase;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
         reinterpret_cast<void *>(addr - sh + tbase), 0, (int)(uint32_t)(rem < 0xfffffff0ull ? rem : 0xfffffff0ull), 0x00020000);
     const uint32_t span = kTextTile + 1 + w + k;       // bytes the tile reads (+1 spare)
@@ -214,7 +258,7 @@ __global__ __launch_bounds__(kTextThreads) void text_walk_kernel(TextWalkParams 
     };
     uint32_t prev = 0;
     bool have_prev = false;
-    if (w0 + u_prev >= 1 && w0 + u_prev - 1 < p.win_end) {  // (window w0 + u_prev - 1 exists)
+    if (w0 + u_prev >= 1 && w0 + u_prev - 1 < win_end) {  // (window w0 + u_prev - 1 exists)
         // (window u_prev: the spare slot for u_prev = 0, else the last offset of the previous thread)
         const uint16_t *q = u_prev == 0 ? reinterpret_cast<const uint16_t *>(s_sel + kTextThreads * kTextSelStride - 1)
                                         : reinterpret_cast<const uint16_t *>(s_sel + (tid - 1) * kTextSelStride) +
@@ -262,11 +306,11 @@ __global__ __launch_bounds__(kTextThreads) void text_walk_kernel(TextWalkParams 
                 nxt = (uint32_t)(ri + 1) < nb ? bnd((uint32_t)(ri + 1)) : ~0u;
             }
             const int r = (int)rb + ri;
-            in_rec = r >= 0 && (uint32_t)r < (uint32_t)p.n_records && u + l <= nxt;
+            in_rec = r >= 0 && (uint32_t)r < (uint32_t)n_records && u + l <= nxt;
             first_of_rec = u == cur;
             smask |= (uint32_t)first_of_rec << j;
         }
-        if (g < p.win_end && in_rec) {
+        if (g < win_end && in_rec) {
             if (MODE == 0) f = first_of_rec || pp != prev;
             else if (MODE == 1) f = (pp == (uint32_t)g) || (pp == (uint32_t)g + w - 1);
             else f = (pp == (uint32_t)g + w / 2);
@@ -314,9 +358,9 @@ __global__ __launch_bounds__(kTextThreads) void text_walk_kernel(TextWalkParams 
             ++dst;
         }
     }
-    if (tid == 0 && bid == gridDim.x - 1) {
+    if (tid == 0 && bid == last_bid) {
         *p.out.total = s_excl + block_total;
-        if (BATCH) p.offsets[p.n_records] = s_excl + block_total;
+        if (BATCH) p.offsets[n_records] = s_excl + block_total;
     }
 }
 

@@ -129,6 +129,10 @@ struct ValuesTextArgs {
     const unsigned long long *offsets;         // batch: [n_records + 1]; offsets[n_records] = the true count
     unsigned long long n_pos_max;              // what pos / out hold: the grid's size (single text: the count)
     unsigned long long *out;                   // u64: one word per value; u128: {lo, hi}
+    // batch, or null: the true {characters, records} in device memory (mm_values_*_text_batch_counts_*); n_records and
+    // max_chars are then their bounds - counts beyond them, or no record, and the kernel writes nothing
+    const unsigned long long *counts = nullptr;
+    unsigned long long max_chars = 0;
 };
 // 0, -1 (HIP failure), -3 (grid too large)
 int launch_values_text(const ValuesTextArgs &a, int encoding, bool u128, bool batch, hipStream_t stream);

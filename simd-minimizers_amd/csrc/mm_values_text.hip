@@ -40,8 +40,14 @@ __global__ __launch_bounds__(kBlockThreads) void values_text_kernel(ValuesTextAr
     constexpr uint32_t kOutBytes = U128 ? 16u : 8u;
 
     unsigned long long total = a.n_pos_max;
+    unsigned long long n_records = a.n_records;
     if constexpr (BATCH) {
-        const unsigned long long total0 = a.offsets[a.n_records];
+        if (a.counts) {  // (uniform: the device's own counts, within the caller's bounds or nothing is written)
+            const unsigned long long c_chars = a.counts[0], c_records = a.counts[1];
+            if (c_chars > a.max_chars || c_records > n_records || c_records == 0ull) return;
+            n_records = c_records;
+        }
+        const unsigned long long total0 = a.offsets[n_records];
         if (total0 < total) total = total0;  // (never past what the buffers hold)
     }
     const unsigned long long i0 = (unsigned long long)blockIdx.x * kPerBlock;  // first value of the workgroup
@@ -75,8 +81,8 @@ __global__ __launch_bounds__(kBlockThreads) void values_text_kernel(ValuesTextAr
         // one search per workgroup: the records of its first and last value (uniform: scalar loads).  A value's record is
         // at most n_records - 1 (i < offsets[n_records]); searching no further keeps offsets[r + 1] and starts[r] inside
         // their arrays whatever the offsets hold.
-        const unsigned long long r_first = values_read_of(offsets, 0ull, a.n_records - 1ull, i0);
-        const unsigned long long r_last = values_read_of(offsets, r_first, a.n_records - 1ull, i0 + here - 1u);
+        const unsigned long long r_first = values_read_of(offsets, 0ull, n_records - 1ull, i0);
+        const unsigned long long r_last = values_read_of(offsets, r_first, n_records - 1ull, i0 + here - 1u);
         const unsigned long long span = r_last - r_first + 2ull;  // offsets[r_first .. r_last + 1]
         const bool staged = span <= (unsigned long long)kValuesTextStage;
         if (staged) {
