@@ -143,7 +143,9 @@ int mm_workspace_sync(mm_workspace_t *ws);
  *                 runs issued since the last check gives the right result;
  *   MM_ERR_CAPACITY  mm_run_text_batch_counts_device_async found d_counts beyond max_chars / max_records (an asynchronous
  *                 loader that overflowed its tables): that run wrote count 0 and offsets[0] = 0, nothing else, and its
- *                 values call wrote nothing; mm_last_error() names the call;
+ *                 values call wrote nothing; mm_last_error() names the call.  Likewise
+ *                 mm_run_packed_reads_counts_device_async found d_counts beyond max_bases / max_records: that run wrote
+ *                 count 0 and offsets of 0, no position;
  *   MM_ERR_HIP    a kernel refused to run (mm_last_error() says why).
  * The synchronous entry points check (and repeat the run) themselves. */
 int mm_workspace_check(mm_workspace_t *ws);
@@ -885,6 +887,81 @@ int mm_run_packed_reads_skip_ambiguous_host(const mm_plan_t *plan, mm_workspace_
                                             const uint64_t *read_starts /* [n_reads + 1] */, uint32_t max_read_len,
                                             uint32_t *out_pos, uint64_t capacity,
                                             uint64_t *out_offsets /* [n_reads + 1] */, uint64_t *out_count);
+/* The packed reads run with its two counts taken from the DEVICE: d_counts has the packers' layout (d_counts[0] = bases,
+ * d_counts[1] = records, as mm_fastq_pack_device_async / mm_fasta_pack_device_async leave it) and is read when the kernels
+ * run, so a packer, this call and mm_values_*_reads_device_async (with n_reads = max_records) queue on one stream and the
+ * caller waits once (mm_workspace_check) - FASTQ / FASTA in device memory -> records -> positions -> values with no host
+ * wait in between.  It replaces reading the packer's counts back before mm_run_packed_reads_device_async.  The reference
+ * has no counterpart: its loader and Builder::run are synchronous host code (bench/src/lib.rs:51-82, src/lib.rs:378).
+ *  max_bases / max_records  upper bounds of the two counts, all the host knows: they size the lane table, the walk's grid
+ *                         and the workspace buffers.  Behind a packer: 4 * packed_capacity_bytes (or the text length) and
+ *                         the packer's max_records
+ *  d_read_starts          [max_records + 1]; with (n_bases, n_records) = d_counts[0..1] at kernel time, entries past
+ *                         [n_records] are never used to form an address or a length, and starts are cut to n_bases
+ *  d_out_pos / d_out_sk / d_out_offsets[0 .. n_records] / d_count
+ *                         bit for bit what mm_run_packed_reads_device_async writes given n_records, n_bases and
+ *                         max_read_len = 0xffffffff as host arguments
+ *  d_out_offsets[n_records .. max_records]
+ *                         all hold the total: the tail is FILLED (reads past n_records are empty), so
+ *                         mm_values_u64/u128_reads_device_async follows on the same stream with n_reads = max_records
+ * The run ALWAYS takes the lane table (mm_lanes.hip): one lane per read needs max_read_len and n_reads inside the walk.  For
+ * short reads of one length a caller who knows its counts keeps mm_run_packed_reads_device / mm_run_reads_device.
+ * No read (n_records == 0) or no read of l = k + w - 1 bases: count 0 and every offset 0, written by the kernels.  Counts
+ * BEYOND a bound (d_counts[0] > max_bases or d_counts[1] > max_records: a packer whose buffer or table was too small): the
+ * run behaves as an empty batch - count 0, every offset 0, d_out_pos untouched - and mm_workspace_check returns
+ * MM_ERR_CAPACITY (kernel error 7; mm_last_error() names this call).  No byte outside [d_packed, d_packed + packed_bytes)
+ * is loaded whatever d_counts and d_read_starts hold.
+ * Refusals before anything is queued, in this order, the same in both forms: NULL plan (MM_ERR_NULL); a text plan
+ * (MM_ERR_BAD_MODE); max_bases >= 2^32 or max_records >= 2^31 (MM_ERR_LEN_TOO_LARGE); d_out_sk with syncmers
+ * (MM_ERR_BAD_MODE); a forward plan in the skip-ambiguous form (MM_ERR_HASHER_NOT_CANONICAL); d_packed, d_read_starts,
+ * d_counts, d_out_offsets (or d_amb) NULL (MM_ERR_NULL); base_offset + max_bases beyond 4 * packed_bytes, or amb_offset +
+ * max_bases beyond 8 * amb_bytes (MM_ERR_CAPACITY); a plan without a lane-table launch - mm_workspace_force_generic, w >
+ * 128, no reads-mode kernel with MM_JIT=0, MM_LANE_TABLE=0, no lane length that fits - MM_ERR_BAD_MODE, and
+ * mm_last_error() points to mm_run_packed_reads_device; a NULL workspace last (MM_ERR_NULL).
+ * Kernels: the four table kernels in their counts instantiation (two for max_records <= 2048), the reads-mode walk with a
+ * grid for max_records + max_bases / S + 1 lanes, and an epilogue that fills the offsets' tail. */
+int mm_run_packed_reads_counts_device_async(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
+                                            uint64_t packed_bytes, uint64_t base_offset, uint64_t max_bases,
+                                            uint64_t max_records, const uint64_t *d_read_starts /* [max_records + 1] */,
+                                            const uint64_t *d_counts /* [2]: bases, records */, uint32_t *d_out_pos,
+                                            uint32_t *d_out_sk /* or NULL */, uint64_t capacity,
+                                            uint64_t *d_out_offsets /* [max_records + 1] */, uint64_t *d_count);
+/* Same, then waits ONCE and returns out[0] = positions, out[1] = n_bases, out[2] = n_records (a look-back time-out repeats
+ * the run, as in every synchronous form; the asynchronous form reports it as MM_ERR_ORDER from mm_workspace_check).
+ * MM_ERR_CAPACITY when the positions exceeded `capacity` (out[0]: the need) or the counts exceeded the bounds (out[0] = 0,
+ * out[1..2]: the true counts). */
+int mm_run_packed_reads_counts_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed, uint64_t packed_bytes,
+                                      uint64_t base_offset, uint64_t max_bases, uint64_t max_records,
+                                      const uint64_t *d_read_starts, const uint64_t *d_counts, uint32_t *d_out_pos,
+                                      uint32_t *d_out_sk, uint64_t capacity, uint64_t *d_out_offsets,
+                                      uint64_t *out /* [3]: positions, n_bases, n_records */);
+/* Builder::run_skip_ambiguous_windows per record (src/lib.rs:451-496) with the counts on the device: the counts form of
+ * mm_run_packed_reads_skip_ambiguous_device_async, behind mm_fastq_pack_n_device_async / mm_fasta_pack_n_device_async on one
+ * stream.  The window ambiguity is prepared over the bound span max_bases (the packers clear d_amb; a lane only reads window
+ * bits inside its record).  Canonical plans, no super-k-mer indices; everything else as above. */
+int mm_run_packed_reads_skip_ambiguous_counts_device_async(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
+                                                           uint64_t packed_bytes, uint64_t base_offset, const void *d_amb,
+                                                           uint64_t amb_bytes, uint64_t amb_offset, uint64_t max_bases,
+                                                           uint64_t max_records,
+                                                           const uint64_t *d_read_starts /* [max_records + 1] */,
+                                                           const uint64_t *d_counts /* [2]: bases, records */,
+                                                           uint32_t *d_out_pos, uint64_t capacity,
+                                                           uint64_t *d_out_offsets /* [max_records + 1] */,
+                                                           uint64_t *d_count);
+int mm_run_packed_reads_skip_ambiguous_counts_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
+                                                     uint64_t packed_bytes, uint64_t base_offset, const void *d_amb,
+                                                     uint64_t amb_bytes, uint64_t amb_offset, uint64_t max_bases,
+                                                     uint64_t max_records, const uint64_t *d_read_starts,
+                                                     const uint64_t *d_counts, uint32_t *d_out_pos, uint64_t capacity,
+                                                     uint64_t *d_out_offsets,
+                                                     uint64_t *out /* [3]: positions, n_bases, n_records */);
+/* What the table kernels of the calls above make of counts and bounds, by the function they call themselves (no device; for
+ * tests): out[0] = reads the table is built for (n_records; 0 when refused), out[1] = 1 when a count exceeds its bound
+ * (refused), out[2] = the lane bound at one window per lane, max_records + max_bases + 1 (the grid of a run is sized from
+ * max_records + max_bases / S + 1 at S windows per lane, never more).  The entry points' rule for the bounds:
+ * MM_ERR_LEN_TOO_LARGE for max_bases >= 2^32 or max_records >= 2^31; MM_ERR_NULL. */
+int mm_debug_lane_counts_view(uint64_t max_bases, uint64_t max_records, uint64_t n_bases, uint64_t n_records,
+                              uint64_t out[3]);
 /* ------------------------------------------------------------------ several devices from one call
  * The reference's parallel driver is host code: rayon over the contigs, one Builder::run each
  * (bench/src/bin/paper.rs:442-459).  A device group holds one workspace (stream, scratch) per listed device; a

@@ -101,6 +101,8 @@ class Workspace {
     Workspace(const Workspace &) = delete;
     Workspace &operator=(const Workspace &) = delete;
     mm_workspace_t *get() const { return ws_; }
+    // the completion half of the asynchronous calls (mm_workspace_check): waits for the stream, throws what they raised
+    void check_async() { check(mm_workspace_check(ws_)); }
     static Workspace &thread_default() {  // the reference's thread_local CACHE (src/lib.rs:217-219)
         thread_local Workspace w;
         return w;
@@ -340,6 +342,28 @@ class Builder {  // src/lib.rs:225-230
         check(r);
         pos.resize(n);
         if (sk_) sk_->assign(sk.begin(), sk.begin() + n);
+    }
+
+    // run_many over reads that a device packer left (mm_fastq_pack_device_async / mm_fasta_pack_device_async), their two
+    // counts still in DEVICE memory (mm_run_packed_reads_counts_device_async): queued on the workspace's stream behind the
+    // packer, nothing waits - Workspace::check_async() (mm_workspace_check) is the one wait, and reports counts beyond the bounds
+    // as MM_ERR_CAPACITY.  Device pointers throughout: d_packed / d_read_starts [max_records + 1] / d_counts {bases, records}
+    // as the packer wrote them, max_bases / max_records their upper bounds (the text length, the packer's max_records);
+    // d_out_offsets [max_records + 1] is written whole (reads past the real count are empty), so
+    // mm_values_u64_reads_device_async follows with n_reads = max_records.  With .super_kmers(..) configured pass d_out_sk.
+    // The reference has no counterpart: its loader and Builder::run are synchronous (bench/src/lib.rs:51-82, src/lib.rs:378).
+    void run_many_counts_device(const void *d_packed, uint64_t packed_bytes, uint64_t max_bases, uint64_t max_records,
+                                const uint64_t *d_read_starts, const uint64_t *d_counts, uint32_t *d_out_pos,
+                                uint64_t capacity, uint64_t *d_out_offsets, uint64_t *d_count = nullptr,
+                                uint32_t *d_out_sk = nullptr) const {
+        Workspace &ws = ws_ ? *ws_ : Workspace::thread_default();
+        mm_plan_t *plan = nullptr;
+        check(mm_plan_create(&plan, k_, w_, CANONICAL, (mm_mode_t)SYNCMER, has_hasher_ ? &hasher_ : nullptr));
+        const int r = mm_run_packed_reads_counts_device_async(plan, ws.get(), d_packed, packed_bytes, 0, max_bases, max_records,
+                                                              d_read_starts, d_counts, d_out_pos, d_out_sk, capacity,
+                                                              d_out_offsets, d_count);
+        mm_plan_destroy(plan);
+        check(r);
     }
 
     // Output::values_u64 / values_u128 (src/lib.rs:584-629) of EVERY read of run_many in ONE call (mm_values_u64_reads_host /

@@ -327,6 +327,15 @@ def _load_lib():
             L.mm_values_u128_text_batch_counts_device_async.argtypes = values_counts_args
             L.mm_debug_text_counts_view.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
                                                     u64p]
+        if hasattr(L, "mm_run_packed_reads_counts_device"):  # (packed reads run with its counts on the device)
+            rc_args = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, vp, vp, vp, vp, C.c_uint64, vp]
+            L.mm_run_packed_reads_counts_device_async.argtypes = rc_args + [vp]
+            L.mm_run_packed_reads_counts_device.argtypes = rc_args + [u64p]
+            rc_skip_args = [vp, vp, vp, C.c_uint64, C.c_uint64, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, vp, vp, vp,
+                            C.c_uint64, vp]
+            L.mm_run_packed_reads_skip_ambiguous_counts_device_async.argtypes = rc_skip_args + [vp]
+            L.mm_run_packed_reads_skip_ambiguous_counts_device.argtypes = rc_skip_args + [u64p]
+            L.mm_debug_lane_counts_view.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, u64p]
         _lib = L
     return _lib
 
@@ -374,6 +383,9 @@ EXPORTED_SYMBOLS = [
     "mm_run_text_batch_counts_device_async", "mm_run_text_batch_counts_device",
     "mm_values_u64_text_batch_counts_device_async", "mm_values_u128_text_batch_counts_device_async",
     "mm_debug_text_counts_view",
+    "mm_run_packed_reads_counts_device_async", "mm_run_packed_reads_counts_device",
+    "mm_run_packed_reads_skip_ambiguous_counts_device_async", "mm_run_packed_reads_skip_ambiguous_counts_device",
+    "mm_debug_lane_counts_view",
 ]
 
 
@@ -1663,6 +1675,148 @@ def fasta_text_pipeline_device(builder: "Builder", text, max_records: int, encod
         values_text_batch_counts_device(builder, seq_n, starts, counts, pos, offsets, pos.numel(), encoding, u128=u128,
                                         out=values, max_chars=n)
     return FastaTextPipeline(builder, ws, seq, starts, rec_pos, counts, pos, offsets, count, values, max_records)
+
+
+def lane_counts_view(max_bases: int, max_records: int, n_bases: int, n_records: int) -> dict:
+    """What the lane-table kernels of the reads counts calls make of the device's counts and the caller's bounds
+    (``mm_debug_lane_counts_view``: the function they call, on the host; no GPU)."""
+    out = (C.c_uint64 * 3)()
+    _check(lib().mm_debug_lane_counts_view(max_bases, max_records, n_bases, n_records, out))
+    return {"n_reads_eff": int(out[0]), "refused": bool(out[1]), "lane_bound": int(out[2])}
+
+
+def run_packed_reads_counts_device(builder: "Builder", d_packed, d_starts, d_counts, out_pos, out_offsets, out_sk=None,
+                                   max_bases=None, max_records=None, amb=None, sync=True, d_count=None):
+    """``run_packed_reads_device`` with the two counts taken from the DEVICE (``mm_run_packed_reads_counts_device*``):
+    ``d_packed`` / ``d_starts`` / ``d_counts`` = the packed uint8 buffer, the int64 starts (``max_records + 1``) and the
+    int64 {bases, records} as ``mm_fastq_pack_device_async`` / ``mm_fasta_pack_device_async`` write them, read when the
+    kernels run.  ``max_bases`` (default: all of ``d_packed``) and ``max_records`` (default: what ``d_starts`` holds)
+    bound them; ``out_offsets`` holds ``max_records + 1`` entries and is written whole (reads past the real count are
+    empty).  ``amb`` (uint8 CUDA tensor of a ``*_pack_n`` packer): the skip-ambiguous form.  Always a lane-table launch.
+    ``sync=True``: one wait, returns (positions, n_bases, n_records).  ``sync=False``: queued on the builder's workspace,
+    returns None; ``Workspace.check`` reports counts beyond the bounds as ``MM_ERR_CAPACITY`` (``d_count``: an optional
+    int64 CUDA tensor that receives the number of positions)."""
+    if max_records is None:
+        max_records = d_starts.numel() - 1
+    max_records = int(max_records)
+    if max_records < 0 or d_starts.numel() < max_records + 1 or out_offsets.numel() < max_records + 1:
+        raise ValueError("d_starts and out_offsets hold max_records + 1 entries each")
+    if d_counts.numel() < 2:
+        raise ValueError("d_counts holds two words: bases, records")
+    packed_bytes = int(d_packed.numel())
+    if max_bases is None:
+        max_bases = 4 * packed_bytes
+    if amb is not None and out_sk is not None:
+        raise ValueError("the skip-ambiguous form has no super-k-mer indices")
+    cap = out_pos.numel() if out_pos is not None else 0
+    head = (builder.plan().h, builder._ws().h, _ptr(d_packed), packed_bytes, 0)
+    tail = (int(max_bases), max_records, _ptr(d_starts), _ptr(d_counts), _ptr(out_pos))
+    if amb is not None:
+        args = head + (_ptr(amb), int(amb.numel()), 0) + tail + (cap, _ptr(out_offsets))
+        f_async, f_sync = (lib().mm_run_packed_reads_skip_ambiguous_counts_device_async,
+                           lib().mm_run_packed_reads_skip_ambiguous_counts_device)
+    else:
+        args = head + tail + (_ptr(out_sk), cap, _ptr(out_offsets))
+        f_async, f_sync = lib().mm_run_packed_reads_counts_device_async, lib().mm_run_packed_reads_counts_device
+    if not sync:
+        _check_counts(f_async(*args, _ptr(d_count)))
+        return None
+    out = (C.c_uint64 * 3)()
+    code = f_sync(*args, out)
+    if code == ERR["CAPACITY"]:
+        if out_pos is not None and out[0] > cap:
+            raise MinimizerError(code, f"output capacity {cap} < {out[0]}")
+        raise MinimizerError(code, f"counts ({out[1]} bases, {out[2]} records) beyond max_bases {int(max_bases)} / "
+                                   f"max_records {max_records}")
+    _check_counts(code)
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+class FastxPipeline:
+    """What ``fastx_pipeline_device`` queued: the device tensors of packer, run and values (``packed``, ``amb`` or None,
+    ``starts``, ``rec_pos``, ``counts``, ``pos``, ``offsets``, ``count``, ``values`` or None), all still being written
+    until ``finish()`` has waited."""
+
+    def __init__(self, builder, ws, packed, amb, starts, rec_pos, counts, pos, offsets, count, values, max_records):
+        self.builder, self.ws = builder, ws
+        self.packed, self.amb, self.starts, self.rec_pos, self.counts = packed, amb, starts, rec_pos, counts
+        self.pos, self.offsets, self.count, self.values = pos, offsets, count, values
+        self.max_records = max_records
+
+    def finish(self):
+        """The ONE wait of the pipeline: ``Workspace.check`` (``MinimizerError`` ``MM_ERR_CAPACITY`` when the file holds
+        more than ``max_records`` records), then the counts.  Returns (records, n_positions, positions, offsets, values):
+        the ``FastaRecords`` of ``fasta_pack_device``, the count ``run_packed_reads_device`` returns with its
+        ``out_pos[:count]`` / ``out_offsets[:n + 1]`` (CUDA tensors), and the values tensor of ``values_reads_device``
+        cut to the count (None when no values were asked for)."""
+        try:
+            self.ws.check()
+        except MinimizerError as e:
+            if e.code == ERR["CAPACITY"]:
+                raise MinimizerError(e.code, f"{e} ({lib().mm_last_error().decode()}); max_records was {self.max_records}")
+            raise
+        _, n_rec = (int(x) for x in self.counts.cpu().numpy())
+        cnt = int(self.count.item())
+        recs = FastaRecords(self.packed, self.starts[: n_rec + 1].cpu().numpy().astype(np.uint64),
+                            self.rec_pos[:n_rec].cpu().numpy().astype(np.uint64), self.amb)
+        vals = None
+        if self.values is not None:
+            per = self.values.numel() // max(1, self.pos.numel())
+            vals = self.values[: per * cnt]
+        return recs, cnt, self.pos[:cnt], self.offsets[: n_rec + 1], vals
+
+
+def fastx_pipeline_device(builder: "Builder", text, max_records: int, fmt: str, with_amb=False, values=None,
+                          u128=False) -> FastxPipeline:
+    """FASTA / FASTQ bytes -> packed records -> positions (-> values) queued on ONE stream with no synchronisation in
+    between: ``mm_fastq_pack_device_async`` / ``mm_fasta_pack_device_async`` (``with_amb``: their ``_n`` forms and the
+    skip-ambiguous run), ``mm_run_packed_reads_counts_device_async`` and, with ``values`` true (or ``u128``),
+    ``mm_values_u64/u128_reads_device_async`` with ``n_reads = max_records`` on the builder's workspace; the packer's counts
+    never visit the host.  ``text`` = the file's bytes (bytes / numpy uint8 / torch uint8 CUDA tensor on the workspace's
+    device).  ``fmt`` = ``"fasta"`` or ``"fastq"``, given by the caller: looking at the first byte would be a host wait, and
+    the asynchronous FASTQ packer wants the text to start at its first ``@``.  Returns a ``FastxPipeline``; its
+    ``finish()`` waits once."""
+    import torch
+
+    if fmt not in ("fasta", "fastq"):
+        raise ValueError('fmt is "fasta" or "fastq"')
+    ws = builder._ws()
+    dev = f"cuda:{ws.device}"
+    if isinstance(text, (bytes, bytearray)):
+        text = np.frombuffer(bytes(text), dtype=np.uint8).copy()
+    if isinstance(text, np.ndarray):
+        t = torch.from_numpy(np.ascontiguousarray(text)).to(dev) if text.size else torch.zeros(0, dtype=torch.uint8, device=dev)
+    else:
+        t = text
+    n = int(t.numel())
+    max_records = int(max_records)
+    want_values = bool(values) or u128
+    packed = torch.empty((n // 4 + 8 + 3) // 4 * 4 + 64, dtype=torch.uint8, device=dev)
+    amb = torch.empty((n // 8 + 8 + 3) // 4 * 4 + 64, dtype=torch.uint8, device=dev) if with_amb else None
+    starts = torch.zeros(max_records + 1, dtype=torch.int64, device=dev)
+    rec_pos = torch.zeros(max(max_records, 1), dtype=torch.int64, device=dev)
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    pos = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    offsets = torch.zeros(max_records + 1, dtype=torch.int64, device=dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    per = 2 if u128 else 1
+    vals = torch.zeros(per * max(n, 1), dtype=torch.int64, device=dev) if want_values else None
+    torch.cuda.synchronize(ws.device)  # (the tensors above are torch's work on its own stream: before, not between)
+    L = lib()
+    head = (ws.h, _ptr(t) if n else None, n, _ptr(packed), packed.numel() // 4 * 4)
+    tail = (_ptr(starts), _ptr(rec_pos), max_records, _ptr(counts))
+    if with_amb:
+        f = L.mm_fastq_pack_n_device_async if fmt == "fastq" else L.mm_fasta_pack_n_device_async
+        _check(f(*head, _ptr(amb), amb.numel() // 4 * 4, *tail))
+    else:
+        f = L.mm_fastq_pack_device_async if fmt == "fastq" else L.mm_fasta_pack_device_async
+        _check(f(*head, *tail))
+    run_packed_reads_counts_device(builder, packed, starts, counts, pos, offsets, max_bases=n, max_records=max_records,
+                                   amb=amb, sync=False, d_count=count)
+    if want_values and max_records:
+        values_reads_device(builder, packed, max_records, pos, offsets, read_starts=starts, n_pos_max=pos.numel(), out=vals,
+                            u128=u128)
+    return FastxPipeline(builder, ws, packed, amb, starts, rec_pos, counts, pos, offsets, count, vals, max_records)
 
 
 def run_packed_reads_device(builder: "Builder", records: FastaRecords, out_pos, out_offsets, out_sk=None, max_read_len=None):

@@ -20,6 +20,7 @@
 #include "mm_env.h"
 #include "mm_launch.h"
 #include "mm_fasta_text.h"
+#include "mm_lane_counts.h"
 #include "mm_text_counts.h"
 #include "mm_values_batch.h"
 #include "mm_values_reads.h"
@@ -408,6 +409,10 @@ int collect_timing(mm_workspace *ws) {
 const char *const kTextCountsRefused =
     "mm_run_text_batch_counts_device_async: d_counts exceed max_chars / max_records (the loader overflowed its tables?); "
     "count 0 and offsets[0] = 0 were written, nothing else";
+// (kernel error 7: the counts of a packed reads run, read on the device, lie beyond the bounds the caller gave)
+const char *const kLaneCountsRefused =
+    "mm_run_packed_reads_counts_device_async: d_counts exceed max_bases / max_records (the packer overflowed its table or "
+    "buffer?); count 0 and offsets of 0 were written, no position";
 int judge_run_error(mm_workspace *ws) {
     const uint32_t code = (uint32_t)ws->h_total[1];
     if (code == 0) return 0;
@@ -442,6 +447,10 @@ int judge_run_error(mm_workspace *ws) {
     }
     if (code == 6u) {
         g_last_error = kTextCountsRefused;
+        return MM_ERR_CAPACITY;
+    }
+    if (code == 7u) {
+        g_last_error = kLaneCountsRefused;
         return MM_ERR_CAPACITY;
     }
     char buf[128];
@@ -868,6 +877,10 @@ int mm_workspace_check(mm_workspace_t *ws) {
     }
     if (code == 6u) {
         g_last_error = kTextCountsRefused;
+        return MM_ERR_CAPACITY;
+    }
+    if (code == 7u) {
+        g_last_error = kLaneCountsRefused;
         return MM_ERR_CAPACITY;
     }
     char buf[128];
@@ -1954,6 +1967,211 @@ int mm_run_packed_reads_skip_ambiguous_device(const mm_plan_t *plan, mm_workspac
     const AmbArgs amb{d_amb, amb_bytes, amb_offset};
     return run_reads_sync(plan, ws, d_packed, packed_bytes, base_offset, n_reads, 0, max_read_len, nullptr, d_out_pos, capacity,
                           d_out_offsets, out_count, &amb, nullptr, d_read_starts, total_bases);
+}
+
+// --------------------------------------------- packed reads, counts on the device
+// mm_run_packed_reads_device_async with its counts in DEVICE memory (d_counts, the layout mm_fastq_pack_device_async and
+// mm_fasta_pack_device_async write: bases, records), read when the kernels run: packer and run queue back to back,
+// nothing waits for the host.  The host knows upper bounds only and sizes the lane table, the walk's grid and the
+// workspace buffers from them; the table kernels do the rest (mm_lane_counts.h, mm_lanes.hip).  The run ALWAYS takes the
+// lane table: one lane per read needs max_read_len and n_reads inside the walk.  The reference has no counterpart
+// (its loader and Builder::run are synchronous host code, bench/src/lib.rs:51-82, src/lib.rs:378); the results are those
+// of mm_run_packed_reads_device_async given the counts as host arguments and max_read_len = 0xffffffff.
+// The argument checks, before anything is touched, in the documented order; the workspace is looked at for
+// mm_workspace_force_generic and the lane length only, and refused last when it is NULL.
+static int packed_reads_counts_check(const mm_plan_t *plan, const mm_workspace_t *ws, const void *d_packed,
+                                     uint64_t packed_bytes, uint64_t base_offset, uint64_t max_bases, uint64_t max_records,
+                                     const uint64_t *d_read_starts, const uint64_t *d_counts, const uint32_t *d_out_sk,
+                                     const uint64_t *d_out_offsets, const AmbArgs *amb) {
+    if (!plan) return MM_ERR_NULL;
+    if (plan->text) return MM_ERR_BAD_MODE;  // (a plan of mm_plan_create_text: text entry points only)
+    if (max_bases >= (1ull << 32) || max_records >= (1ull << 31)) return MM_ERR_LEN_TOO_LARGE;
+    if (d_out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;  // src/lib.rs:339
+    if (amb && !plan->canonical_windows) return MM_ERR_HASHER_NOT_CANONICAL;  // src/lib.rs:451
+    if (!d_out_offsets || !d_counts || !d_read_starts || !d_packed || (amb && !amb->d_amb)) return MM_ERR_NULL;
+    if (base_offset > 4 * packed_bytes || max_bases > 4 * packed_bytes - base_offset) return MM_ERR_CAPACITY;
+    if (amb && (amb->bit_offset > 8 * amb->bytes || max_bases > 8 * amb->bytes - amb->bit_offset)) return MM_ERR_CAPACITY;
+    // a plan without a lane-table launch: the per-read paths need the counts on the host
+    const char *why = nullptr;
+    if (ws && ws->force_generic) why = "the generic family (mm_workspace_force_generic) runs one launch per read";
+    else if (!mm::fused_reads_supported(plan->w, plan->canonical_windows, (int)plan->ht.canonical, plan->mode, d_out_sk != nullptr))
+        why = "no reads-mode kernel for this plan (w > 128, or MM_JIT=0 and no prebuilt instance)";
+    else if (lane_table_policy() == 0) why = "MM_LANE_TABLE=0 switches the lane table off";
+    else {
+        mm::ReadsArgs a{};
+        a.w = plan->w;
+        a.k = plan->k;
+        a.mode = plan->mode;
+        a.canonical_windows = plan->canonical_windows;
+        a.n_reads = max_records ? max_records : 1;
+        a.out.sk = const_cast<uint32_t *>(d_out_sk);
+        a.wamb = amb ? reinterpret_cast<const uint32_t *>(amb->d_amb) : nullptr;  // (only "is there one" is asked)
+        mm::SegPlan sp;
+        if (mm::fused_segments_plan(a, max_bases, ws ? ws->nblk : 0u, &sp) != 0) why = "no lane length fits this plan";
+    }
+    if (why) {
+        g_last_error = std::string("mm_run_packed_reads_counts_device*: ") + why +
+                       "; read the counts back and call mm_run_packed_reads_device";
+        return MM_ERR_BAD_MODE;
+    }
+    return ws ? MM_OK : MM_ERR_NULL;
+}
+
+static int run_reads_counts_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
+                                       uint64_t packed_bytes, uint64_t base_offset, uint64_t max_bases,
+                                       uint64_t max_records, const uint64_t *d_read_starts, const uint64_t *d_counts,
+                                       uint32_t *d_out_pos, uint32_t *d_out_sk, uint64_t capacity, uint64_t *d_out_offsets,
+                                       uint64_t *d_count, const AmbArgs *amb) {
+    int r = packed_reads_counts_check(plan, ws, d_packed, packed_bytes, base_offset, max_bases, max_records, d_read_starts,
+                                      d_counts, d_out_sk, d_out_offsets, amb);
+    if (r) return r;
+    if (!d_out_pos) {
+        capacity = 0;
+        d_out_sk = nullptr;
+    }
+    MM_HIP(set_device(ws->device));
+    mm::SeqView view;
+    r = make_view(d_packed, packed_bytes, base_offset, max_bases, &view);
+    if (r) return r;
+    mm::ReadsArgs a;
+    a.seq = view;
+    a.ht = plan->ht;
+    a.k = plan->k;
+    a.w = plan->w;
+    a.mode = plan->mode;
+    a.canonical_windows = plan->canonical_windows;
+    a.n_reads = max_records ? max_records : 1;  // (what sizes the launch; the walk is given max_records itself)
+    a.read_stride = 0;
+    a.read_len = 0xffffffffu;
+    a.read_lens = nullptr;
+    a.read_starts = reinterpret_cast<const unsigned long long *>(d_read_starts);
+    a.read_offsets = reinterpret_cast<unsigned long long *>(d_out_offsets);
+    a.out.pos = d_out_pos;
+    a.out.sk = d_out_sk;
+    a.out.cap = capacity;
+    a.out.total = ws->total;
+    a.out.ticket = ws->ticket;
+    a.out.error = reinterpret_cast<uint32_t *>(ws->total + 1);
+    a.use_ticket = (ws->force_ticket || mm::mm_env("MM_FORCE_TICKET")) ? 1 : 0;
+    a.timing_start = a.timing_stop = nullptr;
+    a.wamb = nullptr;
+    a.wamb_dwords = 0;
+    MM_HIP(hipMemsetAsync(ws->total, 0, 2 * sizeof(unsigned long long), ws->stream));
+    const uint64_t l = (uint64_t)plan->k + plan->w - 1;
+    if (amb) {
+        // the window bits of the whole BOUND span (the packers clear d_amb; a lane only reads window bits inside its
+        // record).  A bound below l has no window: one cleared dword stands for the bits, so that the plan keeps its
+        // landing area
+        if (max_bases >= l) {
+            r = prepare_window_ambiguity(ws, *amb, max_bases, (uint32_t)l, 0, max_bases - l + 1, &a.wamb_dwords);
+            if (r) return r;
+        } else {
+            r = grow(ws->wamb, ws->wamb_dwords, 16, sizeof(uint32_t));
+            if (r) return r;
+            MM_HIP(hipMemsetAsync(ws->wamb, 0, 16 * sizeof(uint32_t), ws->stream));
+            a.wamb_dwords = 16;
+        }
+        a.wamb = ws->wamb;
+    }
+    mm::SegSource src{a.read_starts, nullptr, 0, 0xffffffffu};
+    src.counts = reinterpret_cast<const unsigned long long *>(d_counts);
+    src.max_bases = (uint32_t)max_bases;
+    src.max_records = (uint32_t)max_records;
+    r = run_lane_table(ws, a, src, max_bases);
+    if (r < 0) return r;
+    if (r != 0) {  // (the check above found a lane-table launch for this plan: only a kernel that failed to compile ends here)
+        g_last_error = std::string("mm_run_packed_reads_counts_device*: no reads-mode kernel (") + mm::fused_unavailable_reason() +
+                       "); read the counts back and call mm_run_packed_reads_device";
+        return MM_ERR_BAD_MODE;
+    }
+    if (d_count)
+        MM_HIP(hipMemcpyAsync(d_count, ws->total, sizeof(unsigned long long), hipMemcpyDeviceToDevice, ws->stream));
+    return MM_OK;
+}
+
+static int run_reads_counts_sync(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed, uint64_t packed_bytes,
+                                 uint64_t base_offset, uint64_t max_bases, uint64_t max_records,
+                                 const uint64_t *d_read_starts, const uint64_t *d_counts, uint32_t *d_out_pos,
+                                 uint32_t *d_out_sk, uint64_t capacity, uint64_t *d_out_offsets, uint64_t *out,
+                                 const AmbArgs *amb) {
+    const int rc = packed_reads_counts_check(plan, ws, d_packed, packed_bytes, base_offset, max_bases, max_records,
+                                             d_read_starts, d_counts, d_out_sk, d_out_offsets, amb);
+    if (rc) return rc;
+    if (out) out[0] = out[1] = out[2] = 0;
+    uint64_t count = 0;
+    // (the two counts come back with the run's words: h_total[4..5], one wait for all of them)
+    const int r = run_sync(ws, capacity, d_out_pos != nullptr, &count, [&](bool *) {
+        const int q = run_reads_counts_async_impl(plan, ws, d_packed, packed_bytes, base_offset, max_bases, max_records,
+                                                  d_read_starts, d_counts, d_out_pos, d_out_sk, capacity, d_out_offsets,
+                                                  nullptr, amb);
+        if (q) return q;
+        MM_HIP(hipMemcpyAsync(ws->h_total + 4, d_counts, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
+        return (int)MM_OK;
+    });
+    if (out && (r == MM_OK || r == MM_ERR_CAPACITY)) {
+        out[0] = count;
+        out[1] = ws->h_total[4];
+        out[2] = ws->h_total[5];
+    }
+    return r;
+}
+
+int mm_run_packed_reads_counts_device_async(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
+                                            uint64_t packed_bytes, uint64_t base_offset, uint64_t max_bases,
+                                            uint64_t max_records, const uint64_t *d_read_starts, const uint64_t *d_counts,
+                                            uint32_t *d_out_pos, uint32_t *d_out_sk, uint64_t capacity,
+                                            uint64_t *d_out_offsets, uint64_t *d_count) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (ws) ws->async_unchecked = true;
+    return run_reads_counts_async_impl(plan, ws, d_packed, packed_bytes, base_offset, max_bases, max_records, d_read_starts,
+                                       d_counts, d_out_pos, d_out_sk, capacity, d_out_offsets, d_count, nullptr);
+}
+
+int mm_run_packed_reads_counts_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed, uint64_t packed_bytes,
+                                      uint64_t base_offset, uint64_t max_bases, uint64_t max_records,
+                                      const uint64_t *d_read_starts, const uint64_t *d_counts, uint32_t *d_out_pos,
+                                      uint32_t *d_out_sk, uint64_t capacity, uint64_t *d_out_offsets, uint64_t *out) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    return run_reads_counts_sync(plan, ws, d_packed, packed_bytes, base_offset, max_bases, max_records, d_read_starts,
+                                 d_counts, d_out_pos, d_out_sk, capacity, d_out_offsets, out, nullptr);
+}
+
+// Builder::run_skip_ambiguous_windows (src/lib.rs:451-496) per record with the counts on the device: what the *_pack_n
+// packers write goes straight in, on the packer's stream.
+int mm_run_packed_reads_skip_ambiguous_counts_device_async(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
+                                                           uint64_t packed_bytes, uint64_t base_offset, const void *d_amb,
+                                                           uint64_t amb_bytes, uint64_t amb_offset, uint64_t max_bases,
+                                                           uint64_t max_records, const uint64_t *d_read_starts,
+                                                           const uint64_t *d_counts, uint32_t *d_out_pos, uint64_t capacity,
+                                                           uint64_t *d_out_offsets, uint64_t *d_count) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (ws) ws->async_unchecked = true;
+    const AmbArgs amb{d_amb, amb_bytes, amb_offset};
+    return run_reads_counts_async_impl(plan, ws, d_packed, packed_bytes, base_offset, max_bases, max_records, d_read_starts,
+                                       d_counts, d_out_pos, nullptr, capacity, d_out_offsets, d_count, &amb);
+}
+
+int mm_run_packed_reads_skip_ambiguous_counts_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
+                                                     uint64_t packed_bytes, uint64_t base_offset, const void *d_amb,
+                                                     uint64_t amb_bytes, uint64_t amb_offset, uint64_t max_bases,
+                                                     uint64_t max_records, const uint64_t *d_read_starts,
+                                                     const uint64_t *d_counts, uint32_t *d_out_pos, uint64_t capacity,
+                                                     uint64_t *d_out_offsets, uint64_t *out) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    const AmbArgs amb{d_amb, amb_bytes, amb_offset};
+    return run_reads_counts_sync(plan, ws, d_packed, packed_bytes, base_offset, max_bases, max_records, d_read_starts,
+                                 d_counts, d_out_pos, nullptr, capacity, d_out_offsets, out, &amb);
+}
+
+// What the table kernels of the counts calls make of {counts, bounds}, by the function they call (mm_lane_counts.h): no device.
+int mm_debug_lane_counts_view(uint64_t max_bases, uint64_t max_records, uint64_t n_bases, uint64_t n_records, uint64_t out[3]) {
+    if (!out) return MM_ERR_NULL;
+    if (max_bases >= (1ull << 32) || max_records >= (1ull << 31)) return MM_ERR_LEN_TOO_LARGE;  // (the entry points' rule)
+    const mm::LaneCountsView v = mm::lane_counts_view(max_bases, max_records, n_bases, n_records);
+    out[0] = v.n_reads_eff;
+    out[1] = v.refused;
+    out[2] = mm::lane_counts_bound(max_bases, max_records, 1u);
+    return MM_OK;
 }
 
 int mm_run_reads_device_async(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,

@@ -1113,7 +1113,9 @@ int launch_fused_segments(const ReadsArgs &a, const SegSource &src, const SegPla
     p.taper_per_level = 1;
     p.taper_min_nblk = 0;
     p.taper_start = 0;
-    p.n_reads = (uint32_t)a.n_reads;
+    // (counts on the device: the walk takes the bound as its number of reads - lanes behind the real ones carry no read -
+    // and leaves the total in read_offsets[max_records]; a.n_reads >= 1 sized the launch)
+    p.n_reads = src.counts ? src.max_records : (uint32_t)a.n_reads;
     p.reads_per_lane = 1;
     p.read_stride = a.read_stride;
     p.read_len = a.read_len;
@@ -1141,7 +1143,9 @@ int launch_fused_segments(const ReadsArgs &a, const SegSource &src, const SegPla
         return -1;
     if (a.use_ticket && hipMemsetAsync(a.out.ticket, 0, sizeof(uint32_t), stream) != hipSuccess) return -1;
     if (const char *pad = mm_env("MM_LDS_PAD")) g_lds_pad = (uint32_t)atoi(pad);
-    return launch_kernel(kr, (uint32_t)plan.tiles, plan.lds_bytes + p.land_bytes + g_lds_pad, stream, p, a.timing_start, a.timing_stop);
+    const int lr = launch_kernel(kr, (uint32_t)plan.tiles, plan.lds_bytes + p.land_bytes + g_lds_pad, stream, p, a.timing_start, a.timing_stop);
+    if (lr != 0 || !src.counts) return lr;
+    return launch_lane_tail(src, a.read_offsets, stream);
 }
 
 int launch_fused_reads(const ReadsArgs &a, hipStream_t stream) {

@@ -164,6 +164,10 @@ struct SegSource {  // where read r starts (bases from the first base of the spa
     const uint32_t *lens;              // null: starts[r + 1] - starts[r] when `starts` is given, max_len otherwise
     unsigned long long stride;
     uint32_t max_len;                  // longer reads are cut to it
+    // counts on the device (mm_run_packed_reads_counts_*; mm_lane_counts.h): {bases, records} as the packers leave them,
+    // read by the table kernels; `starts` is then given, and the launch's n_reads and total_bases are upper bounds
+    const unsigned long long *counts = nullptr;
+    uint32_t max_bases = 0, max_records = 0;  // what the counts may be at most (max_records may be 0: the launch is sized for 1)
 };
 struct SegPlan {
     uint32_t nblk, S, list_cap, lds_bytes;  // lane length (blocks, windows), entries and bytes of the lane lists
@@ -179,6 +183,8 @@ uint64_t lane_table_blocks(uint64_t n_reads);
 // (`error`: the run's error words, OutParams::error - code 5 when the reads need more lanes than plan.lanes_cap)
 int launch_lane_table(const SegSource &src, uint64_t n_reads, uint32_t l, const SegPlan &plan, const SegBuffers &b,
                       uint32_t *error, hipStream_t stream);
+// a counts run's epilogue behind the walk: offsets[n_records .. max_records) = offsets[max_records], the walk's total
+int launch_lane_tail(const SegSource &src, unsigned long long *offsets, hipStream_t stream);
 // lane length and grid of a lane-table launch over `n_reads` reads of `total_bases` bases in all (nblk_want: blocks per
 // lane, 0 = the default lanes of the plan).  Returns 0, -2 (no kernel) or -3 (no lane length fits).
 int fused_segments_plan(const ReadsArgs &a, uint64_t total_bases, uint32_t nblk_want, SegPlan *plan);
