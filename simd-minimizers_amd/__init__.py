@@ -43,14 +43,15 @@ class Hasher(C.Structure):
                 ("canonical", C.c_uint32), ("fw_xor", C.c_uint32), ("rc_xor", C.c_uint32), ("kind", C.c_uint32)]
 
     @staticmethod
-    def from_tables(fw, rc, rot=7, canonical=True) -> "Hasher":
+    def from_tables(fw, rc, rot=7, canonical=True, fw_xor=0, rc_xor=0) -> "Hasher":
         h = Hasher()
         for i in range(4):
             h.fw[i] = int(fw[i]) & 0xFFFFFFFF
             h.rc[i] = int(rc[i]) & 0xFFFFFFFF
         h.rot = rot
         h.canonical = 1 if canonical else 0
-        h.fw_xor = h.rc_xor = h.kind = 0
+        h.fw_xor, h.rc_xor = int(fw_xor) & 0xFFFFFFFF, int(rc_xor) & 0xFFFFFFFF
+        h.kind = 0
         return h
 
     def is_canonical(self) -> bool:
