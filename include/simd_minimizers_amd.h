@@ -962,6 +962,71 @@ int mm_run_packed_reads_skip_ambiguous_counts_device(const mm_plan_t *plan, mm_w
  * MM_ERR_LEN_TOO_LARGE for max_bases >= 2^32 or max_records >= 2^31; MM_ERR_NULL. */
 int mm_debug_lane_counts_view(uint64_t max_bases, uint64_t max_records, uint64_t n_bases, uint64_t n_records,
                               uint64_t out[3]);
+/* ------------------------------------------------------------------ a file of any size, in chunks
+ * FASTA / FASTQ text of ANY size through the device: the caller feeds host bytes in calls of any size, the stream cuts them
+ * into chunks of chunk_bytes so that no record is split, and every chunk runs packer -> counts run -> values (the calls
+ * above) on a slot with a stream of its own, several chunks in flight: the upload of one chunk, the kernels of another and
+ * the download of a third overlap.  The reference has no counterpart beyond "the loader reads any file"
+ * (needletail::parse_fastx_file, bench/src/lib.rs:51-82, record by record on the CPU, Builder::run per record,
+ * src/lib.rs:378); the results per record are those of the one-shot calls on the whole file.
+ *   The cut rule (csrc/mm_fastx_cut.h; every chunk but the last): FASTQ - behind the 4 * floor(N / 4)-th of the chunk's N
+ *   newlines; FASTA - at the last record's '>' (with no record yet: behind the last newline).  What lies behind the cut
+ *   goes in front of the next chunk, so a packer sees at most 2 * chunk_bytes bytes.
+ *   mm_fastx_stream_feed    copies into the filling slot's page-locked staging buffer and launches the slot when it holds
+ *                           chunk_bytes new bytes; *consumed < n_bytes only when no slot is free: call mm_fastx_stream_next
+ *   mm_fastx_stream_finish  no more bytes: the part-filled slot (and the last tail) is launched as the last chunk
+ *   mm_fastx_stream_next    MM_OK and the OLDEST launched batch when it is complete, when no slot is free to fill, or after
+ *                           finish (then it waits); else MM_FASTX_NEED_INPUT; MM_FASTX_END once everything is drained.  A
+ *                           batch's pointers are page-locked host memory, valid until the following call of
+ *                           mm_fastx_stream_next or mm_fastx_stream_destroy.  With the default of 3 slots one is read by the
+ *                           caller, one runs and one fills.
+ * Offsets: rec_text_pos, text_begin and text_end are ABSOLUTE (first_byte + every byte consumed before) and 64-bit - the
+ * 2^32 limit of the packers holds per chunk only; the batches' [text_begin, text_end) tile the fed bytes.  Everything else is
+ * chunk-local: rec_base and offsets start at 0 in every batch, positions are record-local.
+ * Format: MM_FASTX_AUTO decides by the first non-blank byte, as mm_fasta_pack_device does ('@' / '>', anything else:
+ * MM_ERR_FORMAT); blank bytes in front of a FASTQ are passed over and counted in the offsets.  A stream with no bytes, or
+ * blank ones only, gives MM_FASTX_END and no batch.
+ * Errors (a failing stream stays failed: every later call returns the same code, destroy works): MM_ERR_CAPACITY for a
+ * chunk that is not the last and has no cut (a record longer than chunk_bytes; FASTA chromosomes belong to mm_run_host), for
+ * more than max_records records or more than max_positions positions in a chunk - mm_last_error() names the bound and the
+ * need.  A look-back time-out of a chunk's run (MM_ERR_ORDER) repeats that run, as every synchronous form does.
+ * Refusals of mm_fastx_stream_create before any device is touched, in this order: NULL arguments (MM_ERR_NULL); a text plan
+ * (MM_ERR_BAD_MODE); chunk_bytes outside [64, 2^31) or max_records >= 2^31 (MM_ERR_LEN_TOO_LARGE); MM_FASTX_SK with syncmers
+ * or with MM_FASTX_SKIP_AMBIGUOUS (MM_ERR_BAD_MODE); a forward plan with MM_FASTX_SKIP_AMBIGUOUS
+ * (MM_ERR_HASHER_NOT_CANONICAL); both values flags (MM_ERR_BAD_MODE); a value length above 32 / 64 (MM_ERR_VALUE_LEN); a plan
+ * without a lane-table launch (MM_ERR_BAD_MODE, as mm_run_packed_reads_counts_device_async says); an unknown format, flag or
+ * slots outside 0, 2..8 (MM_ERR_BAD_MODE); no device (MM_ERR_NO_DEVICE).
+ * A stream is used by one thread at a time, like a workspace; the plan must outlive it; every entry restores the caller's
+ * current device.  Memory per slot: csrc/mm_fastx_stream.hip and DESIGN.md 4.4e. */
+typedef struct mm_fastx_stream mm_fastx_stream_t;
+enum { MM_FASTX_AUTO = 0, MM_FASTX_FASTA = 1, MM_FASTX_FASTQ = 2 };
+enum { MM_FASTX_SK = 1, MM_FASTX_SKIP_AMBIGUOUS = 2, MM_FASTX_VALUES_U64 = 4, MM_FASTX_VALUES_U128 = 8 };
+enum { MM_FASTX_NEED_INPUT = 1, MM_FASTX_END = 2 };           /* positive: not errors */
+typedef struct mm_fastx_stream_config {
+    int device; int format; uint32_t flags; uint32_t slots;    /* slots: 0 = default (3), else 2..8 */
+    uint64_t chunk_bytes;      /* new bytes per chunk; 64 <= chunk_bytes < 2^31 */
+    uint64_t max_records;      /* per chunk */
+    uint64_t max_positions;    /* per chunk; 0 = worst case (2 * chunk_bytes) */
+    uint64_t first_byte;       /* absolute offset of the first byte fed (resuming / sharding a file) */
+} mm_fastx_stream_config_t;
+typedef struct mm_fastx_batch {
+    uint64_t n_records, n_bases, n_positions;
+    uint64_t text_begin, text_end;      /* absolute byte range [begin, end) of the file this batch covers */
+    const uint64_t *rec_text_pos;       /* [n_records]  absolute offset of each record's '>' / '@' */
+    const uint64_t *rec_base;           /* [n_records + 1] record r has rec_base[r+1] - rec_base[r] bases */
+    const uint64_t *offsets;            /* [n_records + 1] into pos / sk / values, offsets[0] = 0 */
+    const uint32_t *pos, *sk;           /* record-local; sk NULL without MM_FASTX_SK */
+    const uint64_t *values;             /* NULL without a values flag; u128: two words per value */
+} mm_fastx_batch_t;
+int  mm_fastx_stream_create(mm_fastx_stream_t **out, const mm_plan_t *plan, const mm_fastx_stream_config_t *cfg);
+int  mm_fastx_stream_feed(mm_fastx_stream_t *s, const uint8_t *text, uint64_t n_bytes, uint64_t *consumed);
+int  mm_fastx_stream_finish(mm_fastx_stream_t *s);
+int  mm_fastx_stream_next(mm_fastx_stream_t *s, mm_fastx_batch_t *out);
+void mm_fastx_stream_destroy(mm_fastx_stream_t *s);
+/* The cut rule on a text in HOST memory, by the function the trim kernel calls itself (csrc/mm_fastx_cut.h; no device, like
+ * mm_debug_lane_counts_view): format MM_FASTX_FASTA / MM_FASTX_FASTQ (MM_ERR_BAD_MODE otherwise), last != 0 keeps everything;
+ * out = {cut, kept records, dropped records}. */
+int mm_debug_fastx_cut(const uint8_t *text, uint64_t n, int format, int last, uint64_t out[3]);
 /* ------------------------------------------------------------------ several devices from one call
  * The reference's parallel driver is host code: rayon over the contigs, one Builder::run each
  * (bench/src/bin/paper.rs:442-459).  A device group holds one workspace (stream, scratch) per listed device; a

@@ -366,6 +366,55 @@ class Builder {  // src/lib.rs:225-230
         check(r);
     }
 
+    // A FASTA / FASTQ source of ANY size through the device in chunks (mm_fastx_stream_*): `reader(buf, cap)` fills up to
+    // cap bytes and returns how many (0 at the end), `on_batch(const mm_fastx_batch_t &)` receives every batch - the records
+    // that lie whole inside one chunk, with absolute 64-bit text offsets; its pointers are valid until on_batch returns.
+    // `options`: device and first_byte as given; format, slots, chunk_bytes, max_records, max_positions as given; flags: the
+    // MM_FASTX_* bits (super-k-mer indices arrive in the batch, whatever .super_kmers(..) was configured with).  The
+    // reference's loader reads any file record by record on the CPU (bench/src/lib.rs:51-82); it has no other counterpart.
+    template <class Reader, class OnBatch>
+    void stream_fastx(Reader &&reader, OnBatch &&on_batch, const mm_fastx_stream_config_t &options,
+                      size_t read_bytes = size_t(1) << 22) const {
+        mm_plan_t *plan = nullptr;
+        check(mm_plan_create(&plan, k_, w_, CANONICAL, (mm_mode_t)SYNCMER, has_hasher_ ? &hasher_ : nullptr));
+        mm_fastx_stream_t *st = nullptr;
+        int r = mm_fastx_stream_create(&st, plan, &options);
+        if (r == MM_OK) {
+            std::vector<uint8_t> buf(read_bytes ? read_bytes : 1);
+            mm_fastx_batch_t batch;
+            try {
+                for (;;) {
+                    const size_t got = reader(buf.data(), buf.size());
+                    if (got == 0) break;
+                    for (uint64_t done = 0; done < got && r == MM_OK;) {
+                        uint64_t took = 0;
+                        r = mm_fastx_stream_feed(st, buf.data() + done, got - done, &took);
+                        done += took;
+                        if (r == MM_OK && done < got) {
+                            r = mm_fastx_stream_next(st, &batch);
+                            if (r == MM_OK) on_batch(static_cast<const mm_fastx_batch_t &>(batch));
+                            else if (r == MM_FASTX_NEED_INPUT) r = MM_OK;
+                        }
+                    }
+                    if (r != MM_OK) break;
+                }
+                if (r == MM_OK) r = mm_fastx_stream_finish(st);
+                while (r == MM_OK) {
+                    r = mm_fastx_stream_next(st, &batch);
+                    if (r == MM_OK) on_batch(static_cast<const mm_fastx_batch_t &>(batch));
+                }
+                if (r == MM_FASTX_END) r = MM_OK;
+            } catch (...) {
+                mm_fastx_stream_destroy(st);
+                mm_plan_destroy(plan);
+                throw;
+            }
+            mm_fastx_stream_destroy(st);
+        }
+        mm_plan_destroy(plan);
+        check(r);
+    }
+
     // Output::values_u64 / values_u128 (src/lib.rs:584-629) of EVERY read of run_many in ONE call (mm_values_u64_reads_host /
     // mm_values_u128_reads_host): `reads`, `pos` and `offsets` as run_many took and wrote them; read r's values are
     // [offsets[r] .. offsets[r + 1]) of the result, what run(reads[r], ..).values_u64() returns.

@@ -337,6 +337,14 @@ def _load_lib():
             L.mm_run_packed_reads_skip_ambiguous_counts_device_async.argtypes = rc_skip_args + [vp]
             L.mm_run_packed_reads_skip_ambiguous_counts_device.argtypes = rc_skip_args + [u64p]
             L.mm_debug_lane_counts_view.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, u64p]
+        if hasattr(L, "mm_fastx_stream_create"):  # (FASTA / FASTQ files of any size through the device in chunks)
+            L.mm_fastx_stream_create.argtypes = [C.POINTER(vp), vp, vp]
+            L.mm_fastx_stream_feed.argtypes = [vp, vp, C.c_uint64, u64p]
+            L.mm_fastx_stream_finish.argtypes = [vp]
+            L.mm_fastx_stream_next.argtypes = [vp, vp]
+            L.mm_fastx_stream_destroy.argtypes = [vp]
+            L.mm_fastx_stream_destroy.restype = None
+            L.mm_debug_fastx_cut.argtypes = [vp, C.c_uint64, C.c_int, C.c_int, u64p]
         _lib = L
     return _lib
 
@@ -387,6 +395,8 @@ EXPORTED_SYMBOLS = [
     "mm_run_packed_reads_counts_device_async", "mm_run_packed_reads_counts_device",
     "mm_run_packed_reads_skip_ambiguous_counts_device_async", "mm_run_packed_reads_skip_ambiguous_counts_device",
     "mm_debug_lane_counts_view",
+    "mm_fastx_stream_create", "mm_fastx_stream_feed", "mm_fastx_stream_finish", "mm_fastx_stream_next",
+    "mm_fastx_stream_destroy", "mm_debug_fastx_cut",
 ]
 
 
@@ -1818,6 +1828,195 @@ def fastx_pipeline_device(builder: "Builder", text, max_records: int, fmt: str, 
         values_reads_device(builder, packed, max_records, pos, offsets, read_starts=starts, n_pos_max=pos.numel(), out=vals,
                             u128=u128)
     return FastxPipeline(builder, ws, packed, amb, starts, rec_pos, counts, pos, offsets, count, vals, max_records)
+
+
+# ---- FASTA / FASTQ files of any size through the device in chunks (mm_fastx_stream_*)
+FASTX_AUTO, FASTX_FASTA, FASTX_FASTQ = 0, 1, 2
+FASTX_SK, FASTX_SKIP_AMBIGUOUS, FASTX_VALUES_U64, FASTX_VALUES_U128 = 1, 2, 4, 8
+FASTX_NEED_INPUT, FASTX_END = 1, 2
+_FASTX_FORMATS = {"auto": FASTX_AUTO, "fasta": FASTX_FASTA, "fastq": FASTX_FASTQ}
+
+
+class FastxStreamConfig(C.Structure):
+    """``mm_fastx_stream_config_t``."""
+    _fields_ = [("device", C.c_int), ("format", C.c_int), ("flags", C.c_uint32), ("slots", C.c_uint32),
+                ("chunk_bytes", C.c_uint64), ("max_records", C.c_uint64), ("max_positions", C.c_uint64),
+                ("first_byte", C.c_uint64)]
+
+
+class _FastxBatchC(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_bases", C.c_uint64), ("n_positions", C.c_uint64),
+                ("text_begin", C.c_uint64), ("text_end", C.c_uint64), ("rec_text_pos", C.c_void_p),
+                ("rec_base", C.c_void_p), ("offsets", C.c_void_p), ("pos", C.c_void_p), ("sk", C.c_void_p),
+                ("values", C.c_void_p)]
+
+
+def _view(address, n, ctype, dtype):
+    if not address or n == 0:
+        return np.zeros(0, dtype=dtype)
+    return np.ctypeslib.as_array(C.cast(address, C.POINTER(ctype)), shape=(n,))
+
+
+class FastxBatch:
+    """One batch of a ``FastxStream``: the records that lie whole inside one chunk.  ``rec_text_pos`` (absolute byte
+    offsets of the records' '>' / '@'), ``text_begin`` / ``text_end`` (the absolute byte range the batch covers) are
+    64-bit file offsets; ``rec_base`` and ``offsets`` (n_records + 1 each) start at 0 in every batch; ``pos`` (and
+    ``sk``) are record-local; ``values``: uint64, two words {lo, hi} per value for u128, or None.  The arrays are VIEWS
+    of the stream's page-locked buffers, valid until its following ``next()``; ``copy()`` detaches them."""
+
+    def __init__(self, c: _FastxBatchC, u128: bool, views=True):
+        n, p = int(c.n_records), int(c.n_positions)
+        self.n_records, self.n_bases, self.n_positions = n, int(c.n_bases), p
+        self.text_begin, self.text_end = int(c.text_begin), int(c.text_end)
+        self.rec_text_pos = _view(c.rec_text_pos, n, C.c_uint64, np.uint64)
+        self.rec_base = _view(c.rec_base, n + 1, C.c_uint64, np.uint64)
+        self.offsets = _view(c.offsets, n + 1, C.c_uint64, np.uint64)
+        self.pos = _view(c.pos, p, C.c_uint32, np.uint32)
+        self.sk = _view(c.sk, p, C.c_uint32, np.uint32) if c.sk else None
+        self.values = _view(c.values, p * (2 if u128 else 1), C.c_uint64, np.uint64) if c.values else None
+
+    def copy(self) -> "FastxBatch":
+        for name in ("rec_text_pos", "rec_base", "offsets", "pos", "sk", "values"):
+            a = getattr(self, name)
+            if a is not None:
+                setattr(self, name, np.array(a, copy=True))
+        return self
+
+
+class FastxStream:
+    """FASTA / FASTQ text of any size through the device in chunks (``mm_fastx_stream_*``): ``feed(bytes) -> consumed``
+    (fewer than given only when no slot is free: call ``next()``), ``finish()``, ``next()`` -> a ``FastxBatch``, None
+    when the stream wants input first (``MM_FASTX_NEED_INPUT``), ``StopIteration`` once everything is drained.
+    ``chunk_bytes`` new bytes per chunk, ``max_records`` / ``max_positions`` per chunk (0: the worst case,
+    2 * chunk_bytes positions), ``fmt`` "auto" / "fasta" / "fastq", ``values`` None / "u64" / "u128",
+    ``super_kmers`` / ``skip_ambiguous`` as the one-shot calls have them, ``first_byte`` the absolute offset of the
+    first byte fed, ``slots`` chunks in flight (0: the default of 3).  Iterating yields the remaining batches (after
+    ``finish()``).  A failing stream raises ``MinimizerError`` from every later call."""
+
+    def __init__(self, builder: "Builder", chunk_bytes: int, max_records: int, fmt="auto", values=None, super_kmers=False,
+                 skip_ambiguous=False, max_positions=0, first_byte=0, slots=0, device=None):
+        if fmt not in _FASTX_FORMATS:
+            raise ValueError('fmt is "auto", "fasta" or "fastq"')
+        if values not in (None, "u64", "u128"):
+            raise ValueError('values is None, "u64" or "u128"')
+        flags = (FASTX_SK if super_kmers else 0) | (FASTX_SKIP_AMBIGUOUS if skip_ambiguous else 0)
+        flags |= {None: 0, "u64": FASTX_VALUES_U64, "u128": FASTX_VALUES_U128}[values]
+        self.h = None
+        self.u128 = values == "u128"
+        self.builder = builder
+        self._plan = builder.plan()  # (the stream keeps the plan's handle: it must outlive the stream)
+        dev = builder._ws().device if device is None and builder._workspace is not None else (device or 0)
+        self.config = FastxStreamConfig(int(dev), _FASTX_FORMATS[fmt], flags, int(slots), int(chunk_bytes), int(max_records),
+                                        int(max_positions), int(first_byte))
+        h = C.c_void_p()
+        code = lib().mm_fastx_stream_create(C.byref(h), self._plan.h, C.byref(self.config))
+        if code:
+            self._raise(code)
+        self.h = h
+        self.finished = False
+
+    @staticmethod
+    def _raise(code):
+        L = lib()
+        raise MinimizerError(code, f"{L.mm_strerror(code).decode()}: {L.mm_last_error().decode()}")
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().mm_fastx_stream_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def feed(self, data) -> int:
+        buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+        took = C.c_uint64(0)
+        code = lib().mm_fastx_stream_feed(self.h, buf.ctypes.data if buf.size else None, buf.size, C.byref(took))
+        if code:
+            self._raise(code)
+        return int(took.value)
+
+    def finish(self):
+        code = lib().mm_fastx_stream_finish(self.h)
+        if code:
+            self._raise(code)
+        self.finished = True
+
+    def next(self):
+        c = _FastxBatchC()
+        code = lib().mm_fastx_stream_next(self.h, C.byref(c))
+        if code == FASTX_NEED_INPUT:
+            return None
+        if code == FASTX_END:
+            raise StopIteration
+        if code:
+            self._raise(code)
+        return FastxBatch(c, self.u128)
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        b = self.next()
+        if b is None:
+            raise RuntimeError("the stream wants input: feed() more bytes or finish() before iterating")
+        return b
+
+
+def fastx_cut(text: bytes, fmt: str, last: bool = False) -> dict:
+    """The stream's cut rule on a host text (``mm_debug_fastx_cut``: the function the trim kernel calls, no GPU)."""
+    buf = np.frombuffer(text, dtype=np.uint8)
+    out = (C.c_uint64 * 3)()
+    _check(lib().mm_debug_fastx_cut(buf.ctypes.data if buf.size else None, buf.size, _FASTX_FORMATS[fmt], int(last), out))
+    return {"cut": int(out[0]), "kept": int(out[1]), "dropped": int(out[2])}
+
+
+def stream_fastx(builder: "Builder", source, chunk_bytes: int = 64 << 20, max_records: int = 1 << 20, read_bytes: int = 8 << 20,
+                 **options):
+    """Generator over the batches (``FastxBatch``, numpy COPIES) of a FASTA / FASTQ ``source``: a path, a binary file
+    object or an iterable of bytes, of any size.  ``options`` as ``FastxStream`` takes them; ``read_bytes``: how much a
+    path or file object is read at a time."""
+    import os
+
+    def pieces():
+        if isinstance(source, (str, os.PathLike)):
+            with open(source, "rb") as f:
+                while True:
+                    b = f.read(read_bytes)
+                    if not b:
+                        return
+                    yield b
+        elif hasattr(source, "read"):
+            while True:
+                b = source.read(read_bytes)
+                if not b:
+                    return
+                yield b
+        else:
+            yield from source
+
+    with FastxStream(builder, chunk_bytes, max_records, **options) as st:
+        for piece in pieces():
+            view = memoryview(piece)
+            done = 0
+            while done < len(view):
+                done += st.feed(view[done:])
+                if done < len(view):
+                    b = st.next()
+                    if b is not None:
+                        yield b.copy()
+        st.finish()
+        for b in st:
+            yield b.copy()
 
 
 def run_packed_reads_device(builder: "Builder", records: FastaRecords, out_pos, out_offsets, out_sk=None, max_read_len=None):

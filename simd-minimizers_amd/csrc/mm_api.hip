@@ -5303,3 +5303,29 @@ int mm_run_batch_sharded_host(const mm_plan_t *plan, mm_device_group_t *g, uint6
 }
 
 }  // extern "C"
+
+// What the FASTA / FASTQ stream (mm_fastx_stream.hip) asks of the file that owns plans and workspaces (mm_fastx_stream.h).
+#include "mm_fastx_stream.h"
+namespace mm {
+ApiPlanInfo api_plan_info(const mm_plan_t *plan) {
+    ApiPlanInfo i;
+    i.k = plan->k;
+    i.w = plan->w;
+    i.mode = plan->mode;
+    i.canonical_windows = plan->canonical_windows;
+    i.canonical_hasher = plan->text ? (int)plan->tt.canonical : (int)plan->hasher.canonical;
+    i.text = plan->text ? 1 : 0;
+    return i;
+}
+int api_reads_counts_refusal(const mm_plan_t *plan, uint64_t max_bases, uint64_t max_records, int want_sk, int want_amb) {
+    // (the check reads no pointer: any non-null value stands for the buffers, and for a workspace with no knob set)
+    static const uint64_t some = 0;
+    const AmbArgs amb{&some, ~0ull >> 3, 0};
+    const int r = packed_reads_counts_check(plan, nullptr, &some, ~0ull >> 2, 0, max_bases, max_records, &some, &some,
+                                            want_sk ? reinterpret_cast<const uint32_t *>(&some) : nullptr, &some,
+                                            want_amb ? &amb : nullptr);
+    return r == MM_ERR_NULL && plan ? (int)MM_OK : r;  // (MM_ERR_NULL with a plan: the missing workspace, refused last)
+}
+hipStream_t api_workspace_stream(mm_workspace_t *ws) { return ws->stream; }
+void api_set_last_error(const char *text) { g_last_error = text; }
+}  // namespace mm

@@ -1,0 +1,33 @@
+// mm_fastx_stream.h - what the FASTA / FASTQ stream (mm_fastx_stream.hip) shares with the kernel file of its trim step
+// (mm_fastx_cut.hip) and asks of the host file that owns plans and workspaces (mm_api.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/simd_minimizers_amd.h"
+
+namespace mm {
+
+// The trim step behind a packer, on `stream` (mm_fastx_cut.hip): d_counts {bases, records} rewritten in place to the kept
+// ones, d_cut[0] = cut, d_cut[1] = 1 when records > max_records kept the rule from being applied.  d_newlines: one word of
+// scratch.  The text may have any alignment; no byte outside [d_text, d_text + n_bytes) rounded to whole dwords is loaded.
+// Returns 0, or -1 when a launch failed.
+int launch_fastx_trim(const uint8_t *d_text, uint64_t n_bytes, int format, int last, const unsigned long long *d_rec_base,
+                      const unsigned long long *d_rec_text_pos, uint64_t max_records, unsigned long long *d_counts,
+                      unsigned long long *d_cut, unsigned long long *d_newlines, hipStream_t stream);
+
+// ---- from mm_api.hip
+struct ApiPlanInfo {
+    uint32_t k, w, mode;
+    int canonical_windows;  // the strand-vote tie-break (what the skip-ambiguous run asks for)
+    int canonical_hasher;   // what the values calls take as `canonical`
+    int text;               // a plan of mm_plan_create_text
+};
+ApiPlanInfo api_plan_info(const mm_plan_t *plan);
+// What mm_run_packed_reads_counts_device_async would say to this plan and these bounds before it touches a device, pointers
+// and workspace aside: MM_OK or its refusal (mm_last_error() set as that call sets it).
+int api_reads_counts_refusal(const mm_plan_t *plan, uint64_t max_bases, uint64_t max_records, int want_sk, int want_amb);
+hipStream_t api_workspace_stream(mm_workspace_t *ws);
+void api_set_last_error(const char *text);
+
+}  // namespace mm

@@ -1,0 +1,539 @@
+// mm_fastx_stream.hip - FASTA / FASTQ files of ANY size through the device in chunks (mm_fastx_stream_*, host code).
+//
+// The reference's loader reads a file of any size record by record on the CPU (needletail::parse_fastx_file,
+// bench/src/lib.rs:51-82) and runs the builder per record (src/lib.rs:378); beyond that it has no counterpart.  Here the
+// caller feeds bytes, the stream cuts them into chunks of chunk_bytes, and every chunk goes through the calls that exist
+// for a whole file - packer, counts run, values - on a slot of its own:
+//   slot = a workspace (its own stream), a page-locked staging buffer for chunk_bytes of text, device buffers for a text
+//          of 2 * chunk_bytes (the carry area in front of the new bytes) and the outputs, page-locked landing buffers.
+//   launch(chunk i + 1): upload of the new bytes - queued BEFORE the host looks at chunk i's cut; wait for the 32 bytes
+//          {B', R', cut, overflow} of chunk i (they arrive behind its packer and trim step, ahead of its run); device copy
+//          of chunk i's tail text[cut, n) directly in front of the new bytes; packer; trim (mm_fastx_cut.hip); the counts
+//          run; values; the run's count to the host.
+//   collect(chunk): once the count is on the host, the downloads of exactly the filled parts are queued; the batch is
+//          complete when they are done.  feed() and next() both move chunks along, neither waits unless it must.
+// A tail always lies inside its chunk's NEW bytes (a chunk whose cut is 0 is an error), so it is at most chunk_bytes long.
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "mm_fastx_cut.h"
+#include "mm_fastx_stream.h"
+
+namespace {
+
+enum SlotState { kFree = 0, kFilling, kRunning, kDownloading, kDelivered };
+
+struct Slot {
+    mm_workspace_t *ws = nullptr;
+    hipStream_t stream = nullptr;
+    // device
+    uint8_t *d_text = nullptr;  // [2 * chunk_bytes + 64]: carry area, then the new bytes
+    uint8_t *d_packed = nullptr, *d_amb = nullptr;
+    uint64_t *d_rec_base = nullptr, *d_rec_pos = nullptr, *d_offsets = nullptr;
+    unsigned long long *d_meta = nullptr;  // [0..1] bases, records  [2..3] cut, overflow  [4] positions  [5] newlines
+    uint32_t *d_pos = nullptr, *d_sk = nullptr;
+    uint64_t *d_values = nullptr;
+    // page-locked host
+    uint8_t *h_text = nullptr;
+    unsigned long long *h_meta = nullptr;
+    uint64_t *h_rec_pos = nullptr, *h_rec_base = nullptr, *h_offsets = nullptr, *h_values = nullptr;
+    uint32_t *h_pos = nullptr, *h_sk = nullptr;
+    hipEvent_t ev_cut = nullptr, ev_run = nullptr, ev_done = nullptr, ev_tail = nullptr;
+    bool tail_pending = false;  // the chunk behind this slot's copies its tail out of d_text: ev_tail says when it has
+    // the chunk in the slot
+    SlotState state = kFree;
+    uint64_t n_new = 0, n_text = 0, text_off = 0, abs_begin = 0, report_begin = 0;
+    int last = 0, retries = 0;
+};
+
+struct DeviceGuard {  // every entry restores the caller's current device
+    int saved = -1;
+    DeviceGuard() {
+        if (hipGetDevice(&saved) != hipSuccess) {
+            (void)hipGetLastError();
+            saved = -1;
+        }
+    }
+    ~DeviceGuard() {
+        if (saved >= 0) (void)hipSetDevice(saved);
+    }
+};
+
+}  // namespace
+
+struct mm_fastx_stream {
+    const mm_plan_t *plan = nullptr;
+    mm::ApiPlanInfo info{};
+    mm_fastx_stream_config_t cfg{};
+    uint32_t value_len = 0;
+    uint64_t C = 0, max_records = 0, max_positions = 0, packed_cap = 0, amb_cap = 0;
+    int n_slots = 0;
+    Slot slots[8];
+    int fill = 0;      // the slot that takes the bytes fed next
+    int oldest = 0;    // the oldest launched slot that next() has not delivered yet
+    int in_flight = 0; // launched, not delivered
+    int prev = -1;     // the slot of the chunk launched last (its tail goes in front of the next one)
+    int delivered = -1;
+    int format = 0;    // MM_FASTX_FASTA / MM_FASTX_FASTQ once it is known
+    std::string line_blanks;  // MM_FASTX_AUTO, before the first non-blank byte: the blank bytes of the line it stands in
+    uint64_t skipped = 0;     // blank bytes in front of the text that were not handed to a packer
+    bool any_launched = false, finished = false, final_done = false;
+    int failed = 0;
+    std::string fail_text;
+};
+
+namespace {
+
+int fail(mm_fastx_stream *s, int code, const std::string &text) {
+    s->failed = code;
+    s->fail_text = text;
+    mm::api_set_last_error(s->fail_text.c_str());
+    return code;
+}
+int fail_hip(mm_fastx_stream *s, hipError_t e, const char *what) {
+    return fail(s, MM_ERR_HIP, std::string("mm_fastx_stream: ") + what + ": " + hipGetErrorString(e));
+}
+// (a failed call of the library: its own text stands in mm_last_error())
+int fail_call(mm_fastx_stream *s, int code) { return fail(s, code, std::string("mm_fastx_stream: ") + mm_last_error()); }
+int again(mm_fastx_stream *s) {
+    mm::api_set_last_error(s->fail_text.c_str());
+    return s->failed;
+}
+#define FX_HIP(call)                                         \
+    do {                                                     \
+        hipError_t e_ = (call);                              \
+        if (e_ != hipSuccess) return fail_hip(s, e_, #call); \
+    } while (0)
+
+bool is_blank(uint8_t c) { return c == ' ' || c == '\t' || c == '\r' || c == '\n'; }
+bool can_fill(const Slot &sl) { return sl.state == kFree || sl.state == kFilling; }
+
+// steps 5-7 of a launched slot: the counts run, the values, the run's count to the host (queued again after a look-back
+// time-out: the packed records and the trimmed counts are still where the run reads them)
+int queue_run(mm_fastx_stream *s, Slot &sl) {
+    const uint32_t flags = s->cfg.flags;
+    uint64_t *const d_counts = reinterpret_cast<uint64_t *>(sl.d_meta), *const d_count = reinterpret_cast<uint64_t *>(sl.d_meta + 4);
+    int r;
+    if (flags & MM_FASTX_SKIP_AMBIGUOUS)
+        r = mm_run_packed_reads_skip_ambiguous_counts_device_async(s->plan, sl.ws, sl.d_packed, s->packed_cap, 0, sl.d_amb, s->amb_cap, 0,
+                                                                   sl.n_text, s->max_records, sl.d_rec_base, d_counts, sl.d_pos,
+                                                                   s->max_positions, sl.d_offsets, d_count);
+    else
+        r = mm_run_packed_reads_counts_device_async(s->plan, sl.ws, sl.d_packed, s->packed_cap, 0, sl.n_text, s->max_records,
+                                                    sl.d_rec_base, d_counts, sl.d_pos, sl.d_sk, s->max_positions, sl.d_offsets, d_count);
+    if (r) return fail_call(s, r);
+    if (sl.d_values && s->max_records) {
+        r = (flags & MM_FASTX_VALUES_U128 ? mm_values_u128_reads_device_async : mm_values_u64_reads_device_async)(
+            sl.ws, sl.d_packed, s->packed_cap, 0, s->max_records, sl.d_rec_base, 0, s->value_len, s->info.canonical_windows, sl.d_pos,
+            sl.d_offsets, s->max_positions, sl.d_values);
+        if (r) return fail_call(s, r);
+    }
+    FX_HIP(hipSetDevice(s->cfg.device));
+    FX_HIP(hipMemcpyAsync(sl.h_meta + 4, sl.d_meta + 4, sizeof(unsigned long long), hipMemcpyDeviceToHost, sl.stream));
+    FX_HIP(hipEventRecord(sl.ev_run, sl.stream));
+    return MM_OK;
+}
+
+// Launches the chunk in the filling slot (steps 1-7).  `last`: nothing follows.  A last chunk without a byte - no new one,
+// no tail - is not launched.
+int launch(mm_fastx_stream *s, int last) {
+    Slot &sl = s->slots[s->fill];
+    FX_HIP(hipSetDevice(s->cfg.device));
+    // (this slot's previous chunk: the chunk behind it may still be copying its tail out of d_text)
+    if (sl.tail_pending) {
+        FX_HIP(hipStreamWaitEvent(sl.stream, sl.ev_tail, 0));
+        sl.tail_pending = false;
+    }
+    if (sl.n_new) FX_HIP(hipMemcpyAsync(sl.d_text + s->C, sl.h_text, sl.n_new, hipMemcpyHostToDevice, sl.stream));
+    uint64_t tail = 0;
+    if (s->prev >= 0) {
+        Slot &p = s->slots[s->prev];
+        FX_HIP(hipEventSynchronize(p.ev_cut));
+        const uint64_t cut = p.h_meta[2];
+        // (a chunk that cannot be cut: its own collect step names the reason; nothing can follow it)
+        if (p.h_meta[3] || cut == 0 || cut > p.n_text) {
+            if (p.h_meta[3])
+                return fail(s, MM_ERR_CAPACITY, "mm_fastx_stream: more than max_records = " + std::to_string(s->max_records) +
+                                                    " records in a chunk: " + std::to_string(p.h_meta[1]) + " needed");
+            return fail(s, MM_ERR_CAPACITY, "mm_fastx_stream: a record longer than chunk_bytes = " + std::to_string(s->C) +
+                                                " (no cut in a chunk of " + std::to_string(p.n_text) + " bytes)");
+        }
+        tail = p.n_text - cut;
+        if (tail > s->C) return fail(s, MM_ERR_CAPACITY, "mm_fastx_stream: a tail longer than chunk_bytes");
+        if (tail) {
+            FX_HIP(hipMemcpyAsync(sl.d_text + s->C - tail, p.d_text + p.text_off + cut, tail, hipMemcpyDeviceToDevice, sl.stream));
+            FX_HIP(hipEventRecord(p.ev_tail, sl.stream));
+            p.tail_pending = true;
+        }
+        sl.abs_begin = p.abs_begin + cut;
+        sl.report_begin = sl.abs_begin;
+    } else {
+        sl.abs_begin = s->cfg.first_byte + s->skipped;
+        sl.report_begin = s->cfg.first_byte;
+    }
+    sl.n_text = tail + sl.n_new;
+    sl.text_off = s->C - tail;
+    sl.last = last;
+    sl.retries = 0;
+    if (sl.n_text == 0) {  // (only a last chunk comes here without a byte)
+        sl.state = kFree;
+        sl.n_new = 0;
+        return MM_OK;
+    }
+    const uint8_t *text = sl.d_text + sl.text_off;
+    uint64_t *const d_counts = reinterpret_cast<uint64_t *>(sl.d_meta);
+    int r;
+    if (s->cfg.flags & MM_FASTX_SKIP_AMBIGUOUS)
+        r = (s->format == MM_FASTX_FASTQ ? mm_fastq_pack_n_device_async : mm_fasta_pack_n_device_async)(
+            sl.ws, text, sl.n_text, sl.d_packed, s->packed_cap, sl.d_amb, s->amb_cap, sl.d_rec_base, sl.d_rec_pos, s->max_records, d_counts);
+    else
+        r = (s->format == MM_FASTX_FASTQ ? mm_fastq_pack_device_async : mm_fasta_pack_device_async)(
+            sl.ws, text, sl.n_text, sl.d_packed, s->packed_cap, sl.d_rec_base, sl.d_rec_pos, s->max_records, d_counts);
+    if (r) return fail_call(s, r);
+    FX_HIP(hipSetDevice(s->cfg.device));
+    if (mm::launch_fastx_trim(text, sl.n_text, s->format, last, reinterpret_cast<unsigned long long *>(sl.d_rec_base),
+                              reinterpret_cast<unsigned long long *>(sl.d_rec_pos), s->max_records, sl.d_meta, sl.d_meta + 2,
+                              sl.d_meta + 5, sl.stream))
+        return fail_hip(s, hipGetLastError(), "the trim step");
+    FX_HIP(hipMemcpyAsync(sl.h_meta, sl.d_meta, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, sl.stream));
+    FX_HIP(hipEventRecord(sl.ev_cut, sl.stream));
+    r = queue_run(s, sl);
+    if (r) return r;
+    sl.state = kRunning;
+    s->prev = s->fill;
+    s->any_launched = true;
+    if (s->in_flight == 0) s->oldest = s->fill;
+    ++s->in_flight;
+    s->fill = (s->fill + 1) % s->n_slots;
+    return MM_OK;
+}
+
+// A running slot whose count has arrived (or, with `block`, once it has): judge the run, queue the downloads.
+int collect(mm_fastx_stream *s, Slot &sl, bool block) {
+    while (sl.state == kRunning) {
+        if (!block) {
+            const hipError_t q = hipEventQuery(sl.ev_run);
+            if (q == hipErrorNotReady) {
+                (void)hipGetLastError();  // (not an error: the launchers ask for the last one)
+                return MM_OK;
+            }
+            if (q != hipSuccess) return fail_hip(s, q, "hipEventQuery");
+        }
+        FX_HIP(hipEventSynchronize(sl.ev_run));
+        const int r = mm_workspace_check(sl.ws);
+        if (r == MM_ERR_ORDER && sl.retries < 2) {
+            // a look-back timed out: this chunk's run again (the workspace takes its tile ids from a ticket from now on)
+            ++sl.retries;
+            const int q = queue_run(s, sl);
+            if (q) return q;
+            continue;
+        }
+        const uint64_t n_bases = sl.h_meta[0], n_records = sl.h_meta[1], cut = sl.h_meta[2], n_pos = sl.h_meta[4];
+        if (sl.h_meta[3])
+            return fail(s, MM_ERR_CAPACITY, "mm_fastx_stream: more than max_records = " + std::to_string(s->max_records) +
+                                                " records in a chunk: " + std::to_string(n_records) + " needed");
+        if (r) return fail_call(s, r);
+        if (!sl.last && cut == 0)
+            return fail(s, MM_ERR_CAPACITY, "mm_fastx_stream: a record longer than chunk_bytes = " + std::to_string(s->C) +
+                                                " (no cut in a chunk of " + std::to_string(sl.n_text) + " bytes)");
+        if (n_pos > s->max_positions)
+            return fail(s, MM_ERR_CAPACITY, "mm_fastx_stream: more than max_positions = " + std::to_string(s->max_positions) +
+                                                " positions in a chunk: " + std::to_string(n_pos) + " needed");
+        if (n_records > s->max_records || n_bases > sl.n_text || cut > sl.n_text)
+            return fail(s, MM_ERR_HIP, "mm_fastx_stream: the trim step left counts beyond their bounds");
+        FX_HIP(hipSetDevice(s->cfg.device));
+        if (n_records) FX_HIP(hipMemcpyAsync(sl.h_rec_pos, sl.d_rec_pos, n_records * 8, hipMemcpyDeviceToHost, sl.stream));
+        FX_HIP(hipMemcpyAsync(sl.h_rec_base, sl.d_rec_base, (n_records + 1) * 8, hipMemcpyDeviceToHost, sl.stream));
+        FX_HIP(hipMemcpyAsync(sl.h_offsets, sl.d_offsets, (n_records + 1) * 8, hipMemcpyDeviceToHost, sl.stream));
+        if (n_pos) {
+            FX_HIP(hipMemcpyAsync(sl.h_pos, sl.d_pos, n_pos * 4, hipMemcpyDeviceToHost, sl.stream));
+            if (sl.d_sk) FX_HIP(hipMemcpyAsync(sl.h_sk, sl.d_sk, n_pos * 4, hipMemcpyDeviceToHost, sl.stream));
+            if (sl.d_values)
+                FX_HIP(hipMemcpyAsync(sl.h_values, sl.d_values, n_pos * (s->cfg.flags & MM_FASTX_VALUES_U128 ? 16 : 8),
+                                      hipMemcpyDeviceToHost, sl.stream));
+        }
+        FX_HIP(hipEventRecord(sl.ev_done, sl.stream));
+        sl.state = kDownloading;
+    }
+    return MM_OK;
+}
+
+int collect_all(mm_fastx_stream *s) {
+    for (int i = 0, at = s->oldest; i < s->in_flight; ++i, at = (at + 1) % s->n_slots) {
+        const int r = collect(s, s->slots[at], false);
+        if (r) return r;
+    }
+    return MM_OK;
+}
+
+// after mm_fastx_stream_finish: the last chunk (the part-filled slot and the tail in front of it), as soon as a slot is free
+int launch_final(mm_fastx_stream *s) {
+    if (!s->finished || s->final_done || s->format == 0) return MM_OK;
+    if (!can_fill(s->slots[s->fill])) return MM_OK;
+    s->final_done = true;
+    return launch(s, 1);
+}
+
+template <class T>
+hipError_t dev_alloc(T *&p, uint64_t bytes) {
+    return hipMalloc(reinterpret_cast<void **>(&p), bytes ? bytes : 8);
+}
+template <class T>
+hipError_t host_alloc(T *&p, uint64_t bytes) {
+    return hipHostMalloc(reinterpret_cast<void **>(&p), bytes ? bytes : 8, hipHostMallocDefault);
+}
+
+void destroy_slots(mm_fastx_stream *s) {
+    for (int i = 0; i < s->n_slots; ++i) {
+        Slot &sl = s->slots[i];
+        if (sl.stream) (void)hipStreamSynchronize(sl.stream);
+    }
+    for (int i = 0; i < s->n_slots; ++i) {
+        Slot &sl = s->slots[i];
+        void *dev[] = {sl.d_text, sl.d_packed, sl.d_amb, sl.d_rec_base, sl.d_rec_pos, sl.d_offsets, sl.d_meta, sl.d_pos, sl.d_sk, sl.d_values};
+        for (void *p : dev)
+            if (p) (void)hipFree(p);
+        void *host[] = {sl.h_text, sl.h_meta, sl.h_rec_pos, sl.h_rec_base, sl.h_offsets, sl.h_values, sl.h_pos, sl.h_sk};
+        for (void *p : host)
+            if (p) (void)hipHostFree(p);
+        hipEvent_t ev[] = {sl.ev_cut, sl.ev_run, sl.ev_done, sl.ev_tail};
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        if (sl.ws) mm_workspace_destroy(sl.ws);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int mm_debug_fastx_cut(const uint8_t *text, uint64_t n, int format, int last, uint64_t out[3]) {
+    if (!out || (!text && n)) return MM_ERR_NULL;
+    if (format != MM_FASTX_FASTA && format != MM_FASTX_FASTQ) return MM_ERR_BAD_MODE;
+    mm::fastx_cut_host(text, n, format, last ? 1 : 0, out);
+    return MM_OK;
+}
+
+int mm_fastx_stream_create(mm_fastx_stream_t **out, const mm_plan_t *plan, const mm_fastx_stream_config_t *cfg) {
+    if (out) *out = nullptr;
+    if (!out || !plan || !cfg) return MM_ERR_NULL;
+    const mm::ApiPlanInfo info = mm::api_plan_info(plan);
+    if (info.text) return MM_ERR_BAD_MODE;
+    if (cfg->chunk_bytes < 64 || cfg->chunk_bytes >= (1ull << 31) || cfg->max_records >= (1ull << 31)) return MM_ERR_LEN_TOO_LARGE;
+    const uint32_t flags = cfg->flags;
+    if ((flags & MM_FASTX_SK) && (info.mode != MM_MINIMIZERS || (flags & MM_FASTX_SKIP_AMBIGUOUS))) return MM_ERR_BAD_MODE;
+    if ((flags & MM_FASTX_SKIP_AMBIGUOUS) && !info.canonical_windows) return MM_ERR_HASHER_NOT_CANONICAL;
+    if ((flags & MM_FASTX_VALUES_U64) && (flags & MM_FASTX_VALUES_U128)) return MM_ERR_BAD_MODE;
+    const uint32_t value_len = mm_plan_value_len(plan);
+    if (((flags & MM_FASTX_VALUES_U64) && value_len > 32) || ((flags & MM_FASTX_VALUES_U128) && value_len > 64)) return MM_ERR_VALUE_LEN;
+    const int refusal = mm::api_reads_counts_refusal(plan, 2 * cfg->chunk_bytes, cfg->max_records, (flags & MM_FASTX_SK) != 0,
+                                                     (flags & MM_FASTX_SKIP_AMBIGUOUS) != 0);
+    if (refusal) return refusal;
+    if (cfg->format < MM_FASTX_AUTO || cfg->format > MM_FASTX_FASTQ || (cfg->slots != 0 && (cfg->slots < 2 || cfg->slots > 8)) ||
+        (flags & ~15u)) {
+        mm::api_set_last_error("mm_fastx_stream_create: format is MM_FASTX_AUTO / _FASTA / _FASTQ, slots 0 or 2..8, flags MM_FASTX_*");
+        return MM_ERR_BAD_MODE;
+    }
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
+        (void)hipGetLastError();
+        mm::api_set_last_error("no HIP device visible");
+        return MM_ERR_NO_DEVICE;
+    }
+    if (cfg->device < 0 || cfg->device >= n_dev) return MM_ERR_NO_DEVICE;
+    DeviceGuard guard;
+    mm_fastx_stream *s = new (std::nothrow) mm_fastx_stream;
+    if (!s) return MM_ERR_ALLOC;
+    s->plan = plan;
+    s->info = info;
+    s->cfg = *cfg;
+    s->value_len = value_len;
+    s->C = cfg->chunk_bytes;
+    s->max_records = cfg->max_records;
+    s->max_positions = (cfg->max_positions == 0 || cfg->max_positions > 2 * s->C) ? 2 * s->C : cfg->max_positions;
+    s->packed_cap = ((2 * s->C / 4 + 8 + 3) & ~3ull) + 64;
+    s->amb_cap = ((2 * s->C / 8 + 8 + 3) & ~3ull) + 64;
+    s->n_slots = cfg->slots ? (int)cfg->slots : 3;
+    s->format = cfg->format;  // (MM_FASTX_AUTO = 0: not known yet)
+    const uint64_t R = s->max_records, P = s->max_positions;
+    const uint64_t per_value = flags & MM_FASTX_VALUES_U128 ? 16 : 8;
+    const bool want_values = (flags & (MM_FASTX_VALUES_U64 | MM_FASTX_VALUES_U128)) != 0;
+    int rc = MM_OK;
+    hipError_t e = hipSetDevice(cfg->device);
+    for (int i = 0; i < s->n_slots && e == hipSuccess && rc == MM_OK; ++i) {
+        Slot &sl = s->slots[i];
+        rc = mm_workspace_create(&sl.ws, cfg->device, nullptr);
+        if (rc) break;
+        sl.stream = mm::api_workspace_stream(sl.ws);
+        e = hipSetDevice(cfg->device);
+        if (e == hipSuccess) e = dev_alloc(sl.d_text, 2 * s->C + 64);
+        if (e == hipSuccess) e = dev_alloc(sl.d_packed, s->packed_cap);
+        if (e == hipSuccess && (flags & MM_FASTX_SKIP_AMBIGUOUS)) e = dev_alloc(sl.d_amb, s->amb_cap);
+        if (e == hipSuccess) e = dev_alloc(sl.d_rec_base, (R + 1) * 8);
+        if (e == hipSuccess) e = dev_alloc(sl.d_rec_pos, (R + 1) * 8);
+        if (e == hipSuccess) e = dev_alloc(sl.d_offsets, (R + 1) * 8);
+        if (e == hipSuccess) e = dev_alloc(sl.d_meta, 64);
+        if (e == hipSuccess) e = hipMemset(sl.d_meta, 0, 64);
+        if (e == hipSuccess) e = dev_alloc(sl.d_pos, P * 4);
+        if (e == hipSuccess && (flags & MM_FASTX_SK)) e = dev_alloc(sl.d_sk, P * 4);
+        if (e == hipSuccess && want_values) e = dev_alloc(sl.d_values, P * per_value);
+        if (e == hipSuccess) e = host_alloc(sl.h_text, s->C);
+        if (e == hipSuccess) e = host_alloc(sl.h_meta, 64);
+        if (e == hipSuccess) e = host_alloc(sl.h_rec_pos, (R + 1) * 8);
+        if (e == hipSuccess) e = host_alloc(sl.h_rec_base, (R + 1) * 8);
+        if (e == hipSuccess) e = host_alloc(sl.h_offsets, (R + 1) * 8);
+        if (e == hipSuccess) e = host_alloc(sl.h_pos, P * 4);
+        if (e == hipSuccess && (flags & MM_FASTX_SK)) e = host_alloc(sl.h_sk, P * 4);
+        if (e == hipSuccess && want_values) e = host_alloc(sl.h_values, P * per_value);
+        hipEvent_t *ev[] = {&sl.ev_cut, &sl.ev_run, &sl.ev_done, &sl.ev_tail};
+        for (hipEvent_t *p : ev)
+            if (e == hipSuccess) e = hipEventCreateWithFlags(p, hipEventDisableTiming);
+        if (e == hipSuccess) memset(sl.h_meta, 0, 64);
+    }
+    if (rc == MM_OK && e != hipSuccess) {
+        mm::api_set_last_error((std::string("mm_fastx_stream_create: ") + hipGetErrorString(e)).c_str());
+        (void)hipGetLastError();
+        rc = (e == hipErrorOutOfMemory) ? MM_ERR_ALLOC : MM_ERR_HIP;
+    }
+    if (rc) {
+        destroy_slots(s);
+        delete s;
+        return rc;
+    }
+    *out = s;
+    return MM_OK;
+}
+
+void mm_fastx_stream_destroy(mm_fastx_stream_t *s) {
+    if (!s) return;
+    DeviceGuard guard;
+    (void)hipSetDevice(s->cfg.device);
+    destroy_slots(s);
+    delete s;
+}
+
+int mm_fastx_stream_feed(mm_fastx_stream_t *s, const uint8_t *text, uint64_t n_bytes, uint64_t *consumed) {
+    if (consumed) *consumed = 0;
+    if (!s || !consumed || (!text && n_bytes)) return MM_ERR_NULL;
+    if (s->failed) return again(s);
+    if (s->finished) return fail(s, MM_ERR_BAD_MODE, "mm_fastx_stream_feed: called after mm_fastx_stream_finish");
+    DeviceGuard guard;
+    FX_HIP(hipSetDevice(s->cfg.device));
+    uint64_t taken = 0;
+    // in front of the text: FASTQ has to start with its first '@' (a line's role is the number of newlines in front of it),
+    // so blank bytes are passed over and counted; FASTA keeps every byte (what stands in front of a '>' decides about it)
+    while (taken < n_bytes && (s->format == 0 || (s->format == MM_FASTX_FASTQ && !s->any_launched && s->slots[s->fill].n_new == 0))) {
+        const uint8_t c = text[taken];
+        if (is_blank(c)) {
+            ++taken, ++s->skipped;
+            if (s->format == 0) {
+                if (c == '\n') s->line_blanks.clear();
+                else if (s->line_blanks.size() < 64) s->line_blanks.push_back((char)c);
+            }
+            continue;
+        }
+        if (s->format != 0) break;
+        if (c == '@') {
+            s->format = MM_FASTX_FASTQ;
+        } else if (c == '>') {
+            // (blank lines in front are gone; blank bytes on the header's own line stay, they make it no header)
+            s->format = MM_FASTX_FASTA;
+            Slot &sl = s->slots[s->fill];
+            memcpy(sl.h_text, s->line_blanks.data(), s->line_blanks.size());
+            sl.n_new = s->line_blanks.size();
+            sl.state = kFilling;
+            s->skipped -= s->line_blanks.size();
+        } else {
+            *consumed = taken;
+            return fail(s, MM_ERR_FORMAT, "mm_fastx_stream_feed: the first non-blank byte is neither '@' (FASTQ) nor '>' (FASTA)");
+        }
+        break;
+    }
+    while (taken < n_bytes && s->format != 0) {
+        Slot &sl = s->slots[s->fill];
+        if (!can_fill(sl)) break;
+        sl.state = kFilling;
+        const uint64_t room = s->C - sl.n_new, m = room < n_bytes - taken ? room : n_bytes - taken;
+        memcpy(sl.h_text + sl.n_new, text + taken, m);
+        sl.n_new += m;
+        taken += m;
+        if (sl.n_new == s->C) {
+            const int r = launch(s, 0);
+            if (r) {
+                *consumed = taken;
+                return r;
+            }
+        }
+    }
+    *consumed = taken;
+    return s->in_flight ? collect_all(s) : (int)MM_OK;
+}
+
+int mm_fastx_stream_finish(mm_fastx_stream_t *s) {
+    if (!s) return MM_ERR_NULL;
+    if (s->failed) return again(s);
+    DeviceGuard guard;
+    FX_HIP(hipSetDevice(s->cfg.device));
+    s->finished = true;
+    return launch_final(s);
+}
+
+int mm_fastx_stream_next(mm_fastx_stream_t *s, mm_fastx_batch_t *out) {
+    if (!s || !out) return MM_ERR_NULL;
+    memset(out, 0, sizeof *out);
+    if (s->failed) return again(s);
+    DeviceGuard guard;
+    FX_HIP(hipSetDevice(s->cfg.device));
+    if (s->delivered >= 0) {  // the batch handed out by the last call: its slot is free again
+        Slot &d = s->slots[s->delivered];
+        d.state = kFree;
+        d.n_new = 0;
+        s->delivered = -1;
+    }
+    int r = launch_final(s);
+    if (r) return r;
+    if (s->in_flight == 0) return s->finished && (s->final_done || s->format == 0) ? (int)MM_FASTX_END : (int)MM_FASTX_NEED_INPUT;
+    r = collect_all(s);
+    if (r) return r;
+    Slot &sl = s->slots[s->oldest];
+    const bool must = s->finished || !can_fill(s->slots[s->fill]);
+    if (sl.state == kRunning) {
+        if (!must) return MM_FASTX_NEED_INPUT;
+        r = collect(s, sl, true);
+        if (r) return r;
+    }
+    if (!must) {
+        const hipError_t q = hipEventQuery(sl.ev_done);
+        if (q == hipErrorNotReady) {
+            (void)hipGetLastError();
+            return MM_FASTX_NEED_INPUT;
+        }
+        if (q != hipSuccess) return fail_hip(s, q, "hipEventQuery");
+    }
+    FX_HIP(hipEventSynchronize(sl.ev_done));
+    const uint64_t n_records = sl.h_meta[1];
+    for (uint64_t i = 0; i < n_records; ++i) sl.h_rec_pos[i] += sl.abs_begin;
+    out->n_records = n_records;
+    out->n_bases = sl.h_meta[0];
+    out->n_positions = sl.h_meta[4];
+    out->text_begin = sl.report_begin;
+    out->text_end = sl.abs_begin + (sl.last ? sl.n_text : sl.h_meta[2]);
+    out->rec_text_pos = sl.h_rec_pos;
+    out->rec_base = sl.h_rec_base;
+    out->offsets = sl.h_offsets;
+    out->pos = sl.h_pos;
+    out->sk = sl.h_sk;
+    out->values = sl.h_values;
+    sl.state = kDelivered;
+    s->delivered = s->oldest;
+    s->oldest = (s->oldest + 1) % s->n_slots;
+    --s->in_flight;
+    return MM_OK;
+}
+
+}  // extern "C"
