@@ -987,7 +987,7 @@ int mm_debug_lane_counts_view(uint64_t max_bases, uint64_t max_records, uint64_t
  * MM_ERR_FORMAT); blank bytes in front of a FASTQ are passed over and counted in the offsets.  A stream with no bytes, or
  * blank ones only, gives MM_FASTX_END and no batch.
  * Errors (a failing stream stays failed: every later call returns the same code, destroy works): MM_ERR_CAPACITY for a
- * chunk that is not the last and has no cut (a record longer than chunk_bytes; FASTA chromosomes belong to mm_run_host), for
+ * chunk that is not the last and has no cut (a record longer than chunk_bytes; FASTA chromosomes: MM_FASTX_LONG_RECORDS), for
  * more than max_records records or more than max_positions positions in a chunk - mm_last_error() names the bound and the
  * need.  A look-back time-out of a chunk's run (MM_ERR_ORDER) repeats that run, as every synchronous form does.
  * Refusals of mm_fastx_stream_create before any device is touched, in this order: NULL arguments (MM_ERR_NULL); a text plan
@@ -995,12 +995,14 @@ int mm_debug_lane_counts_view(uint64_t max_bases, uint64_t max_records, uint64_t
  * or with MM_FASTX_SKIP_AMBIGUOUS (MM_ERR_BAD_MODE); a forward plan with MM_FASTX_SKIP_AMBIGUOUS
  * (MM_ERR_HASHER_NOT_CANONICAL); both values flags (MM_ERR_BAD_MODE); a value length above 32 / 64 (MM_ERR_VALUE_LEN); a plan
  * without a lane-table launch (MM_ERR_BAD_MODE, as mm_run_packed_reads_counts_device_async says); an unknown format, flag or
- * slots outside 0, 2..8 (MM_ERR_BAD_MODE); no device (MM_ERR_NO_DEVICE).
+ * slots outside 0, 2..8 (MM_ERR_BAD_MODE); MM_FASTX_LONG_RECORDS with chunk_bytes < 4 * (k + w - 1) (MM_ERR_CAPACITY); no
+ * device (MM_ERR_NO_DEVICE).
  * A stream is used by one thread at a time, like a workspace; the plan must outlive it; every entry restores the caller's
  * current device.  Memory per slot: csrc/mm_fastx_stream.hip and DESIGN.md 4.4e. */
 typedef struct mm_fastx_stream mm_fastx_stream_t;
 enum { MM_FASTX_AUTO = 0, MM_FASTX_FASTA = 1, MM_FASTX_FASTQ = 2 };
-enum { MM_FASTX_SK = 1, MM_FASTX_SKIP_AMBIGUOUS = 2, MM_FASTX_VALUES_U64 = 4, MM_FASTX_VALUES_U128 = 8 };
+enum { MM_FASTX_SK = 1, MM_FASTX_SKIP_AMBIGUOUS = 2, MM_FASTX_VALUES_U64 = 4, MM_FASTX_VALUES_U128 = 8,
+       MM_FASTX_LONG_RECORDS = 16 };
 enum { MM_FASTX_NEED_INPUT = 1, MM_FASTX_END = 2 };           /* positive: not errors */
 typedef struct mm_fastx_stream_config {
     int device; int format; uint32_t flags; uint32_t slots;    /* slots: 0 = default (3), else 2..8 */
@@ -1027,6 +1029,50 @@ void mm_fastx_stream_destroy(mm_fastx_stream_t *s);
  * mm_debug_lane_counts_view): format MM_FASTX_FASTA / MM_FASTX_FASTQ (MM_ERR_BAD_MODE otherwise), last != 0 keeps everything;
  * out = {cut, kept records, dropped records}. */
 int mm_debug_fastx_cut(const uint8_t *text, uint64_t n, int format, int last, uint64_t out[3]);
+/* ---- FASTA records longer than a chunk: MM_FASTX_LONG_RECORDS (genome FASTA: chromosomes of any length below 2^32 bases)
+ * Opt-in; without the flag every batch and every error is as described above, and the flag acts on FASTA text only (a FASTQ
+ * stream, explicit or found by MM_FASTX_AUTO, behaves as without it).  With it, a chunk in which the FASTA rule finds no
+ * cut is no longer an error when the chunk is ONE record from its first byte on and that record's header line is complete:
+ * the whole chunk is delivered as a PIECE of an OPEN record, and the next chunk's device text begins with a synthetic header
+ * line ">\n" followed by the piece's last l - 1 sequence bytes (l = k + w - 1; text[T, n), T from the trim step) - the
+ * packers, the run and the values calls see an ordinary FASTA whose record 0 begins with the l - 1 overlap bases.  A seam
+ * epilogue makes the result exact: record 0's positions (and super-k-mer indices, which are window indices) get
+ * first_base added on the device, behind the values; for minimizers the piece's first position is dropped, with its
+ * index and value, when it equals the last position the record emitted before (a lane's first window always emits; the
+ * rule by which the reference joins lanes, src/collect.rs:265-271, and mm_run_device_async joins window ranges) - so
+ *   positions, indices and values of one record are the concatenation of its pieces' slices, in order, and equal what
+ *   the one-shot calls give for the whole record.
+ * What a batch says about pieces (valid for the batch last returned by mm_fastx_stream_next; all zeros without the flag,
+ * for FASTQ, and for batches without a piece):
+ *   first_continues  record 0 continues the previous batch's last record: rec_text_pos[0] is the absolute offset of the
+ *                    record's real '>' (the same in every piece); rec_base counts what the packer wrote, the first_overlap
+ *                    repeated bases included; pos / sk of record 0 are record-global (piece-local + first_base)
+ *   last_open        the last record goes on in the next batch (such a batch holds that one record only)
+ *   first_base       the record-global index of record 0's first packed base: the record's bases delivered before, minus
+ *                    first_overlap
+ *   first_overlap    how many of record 0's bases repeat the end of the previous piece: l - 1, or all it had
+ * so a record has sum(piece bases) - sum(first_overlap) bases.  text_begin / text_end still tile the fed bytes (a piece
+ * covers exactly its chunk's new bytes), offsets still start at 0 and n_positions counts what is delivered.
+ * Errors with the flag, the stream stays failed: MM_ERR_CAPACITY for a chunk that begins with a header line that does not
+ * end inside it ("a record longer than chunk_bytes", as without the flag), for a piece that brings no new base of its record
+ * ("cannot advance": a chunk of line ends), for an overlap text longer than chunk_bytes; MM_ERR_LEN_TOO_LARGE for a record
+ * that reaches 2^32 bases.  Still out: FASTQ records longer than a chunk, records of 2^32 bases or more, several devices,
+ * gzip.  A sequence line that begins with '>' is a header line, as everywhere; a '>' inside a sequence line is a base the
+ * packers map like any other letter, but must not be the first of the l - 1 overlap bytes' line (it would read as a header).
+ * Memory: the carry area grows by 16 bytes (2 are used); a packer sees at most 2 * chunk_bytes + 2 bytes. */
+typedef struct mm_fastx_pieces {
+    uint32_t first_continues;  /* record 0 continues the previous batch's last record */
+    uint32_t last_open;        /* the last record goes on in the next batch */
+    uint64_t first_base;       /* record-global index of record 0's first packed base (0 if !first_continues) */
+    uint64_t first_overlap;    /* how many of record 0's bases repeat the previous piece (l-1 or fewer; else 0) */
+} mm_fastx_pieces_t;
+int mm_fastx_stream_pieces(const mm_fastx_stream_t *s, mm_fastx_pieces_t *out);
+/* The split rule on a FASTA text in HOST memory (csrc/mm_fastx_cut.h, the function the trim kernel calls; no device):
+ * l = k + w - 1; out = {cut, T, open, overlap} - open = 1: the chunk is a piece (cut = n), T the offset of its (l - 1)-th
+ * sequence byte from the end ('\n' and '\r' are no sequence bytes), never inside the header line (fewer than l - 1: the
+ * first sequence byte, n when there is none), overlap the sequence bytes in text[T, n); open = 0: cut is
+ * mm_debug_fastx_cut's and T = overlap = 0. */
+int mm_debug_fastx_split(const uint8_t *text, uint64_t n, uint32_t l, int last, uint64_t out[4]);
 /* ------------------------------------------------------------------ several devices from one call
  * The reference's parallel driver is host code: rayon over the contigs, one Builder::run each
  * (bench/src/bin/paper.rs:442-459).  A device group holds one workspace (stream, scratch) per listed device; a

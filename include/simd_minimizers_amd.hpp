@@ -15,6 +15,7 @@
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -372,6 +373,9 @@ class Builder {  // src/lib.rs:225-230
     // `options`: device and first_byte as given; format, slots, chunk_bytes, max_records, max_positions as given; flags: the
     // MM_FASTX_* bits (super-k-mer indices arrive in the batch, whatever .super_kmers(..) was configured with).  The
     // reference's loader reads any file record by record on the CPU (bench/src/lib.rs:51-82); it has no other counterpart.
+    // With MM_FASTX_LONG_RECORDS among the flags a FASTA record longer than a chunk arrives in pieces: an `on_batch` that
+    // takes (const mm_fastx_batch_t &, const mm_fastx_pieces_t &) receives mm_fastx_stream_pieces() of every batch with it
+    // (fastx_pieces() below for a stream driven by hand).
     template <class Reader, class OnBatch>
     void stream_fastx(Reader &&reader, OnBatch &&on_batch, const mm_fastx_stream_config_t &options,
                       size_t read_bytes = size_t(1) << 22) const {
@@ -382,6 +386,12 @@ class Builder {  // src/lib.rs:225-230
         if (r == MM_OK) {
             std::vector<uint8_t> buf(read_bytes ? read_bytes : 1);
             mm_fastx_batch_t batch;
+            auto deliver = [&](const mm_fastx_batch_t &b) {
+                if constexpr (std::is_invocable_v<OnBatch &, const mm_fastx_batch_t &, const mm_fastx_pieces_t &>)
+                    on_batch(b, fastx_pieces(st));
+                else
+                    on_batch(b);
+            };
             try {
                 for (;;) {
                     const size_t got = reader(buf.data(), buf.size());
@@ -392,7 +402,7 @@ class Builder {  // src/lib.rs:225-230
                         done += took;
                         if (r == MM_OK && done < got) {
                             r = mm_fastx_stream_next(st, &batch);
-                            if (r == MM_OK) on_batch(static_cast<const mm_fastx_batch_t &>(batch));
+                            if (r == MM_OK) deliver(batch);
                             else if (r == MM_FASTX_NEED_INPUT) r = MM_OK;
                         }
                     }
@@ -401,7 +411,7 @@ class Builder {  // src/lib.rs:225-230
                 if (r == MM_OK) r = mm_fastx_stream_finish(st);
                 while (r == MM_OK) {
                     r = mm_fastx_stream_next(st, &batch);
-                    if (r == MM_OK) on_batch(static_cast<const mm_fastx_batch_t &>(batch));
+                    if (r == MM_OK) deliver(batch);
                 }
                 if (r == MM_FASTX_END) r = MM_OK;
             } catch (...) {
@@ -413,6 +423,14 @@ class Builder {  // src/lib.rs:225-230
         }
         mm_plan_destroy(plan);
         check(r);
+    }
+
+    // What the batch last returned by mm_fastx_stream_next says about pieces (mm_fastx_stream_pieces; zeros without
+    // MM_FASTX_LONG_RECORDS).
+    static mm_fastx_pieces_t fastx_pieces(const mm_fastx_stream_t *st) {
+        mm_fastx_pieces_t p;
+        check(mm_fastx_stream_pieces(st, &p));
+        return p;
     }
 
     // Output::values_u64 / values_u128 (src/lib.rs:584-629) of EVERY read of run_many in ONE call (mm_values_u64_reads_host /

@@ -345,6 +345,9 @@ def _load_lib():
             L.mm_fastx_stream_destroy.argtypes = [vp]
             L.mm_fastx_stream_destroy.restype = None
             L.mm_debug_fastx_cut.argtypes = [vp, C.c_uint64, C.c_int, C.c_int, u64p]
+        if hasattr(L, "mm_fastx_stream_pieces"):  # (FASTA records longer than a chunk: MM_FASTX_LONG_RECORDS)
+            L.mm_fastx_stream_pieces.argtypes = [vp, vp]
+            L.mm_debug_fastx_split.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_int, u64p]
         _lib = L
     return _lib
 
@@ -396,7 +399,7 @@ EXPORTED_SYMBOLS = [
     "mm_run_packed_reads_skip_ambiguous_counts_device_async", "mm_run_packed_reads_skip_ambiguous_counts_device",
     "mm_debug_lane_counts_view",
     "mm_fastx_stream_create", "mm_fastx_stream_feed", "mm_fastx_stream_finish", "mm_fastx_stream_next",
-    "mm_fastx_stream_destroy", "mm_debug_fastx_cut",
+    "mm_fastx_stream_destroy", "mm_debug_fastx_cut", "mm_fastx_stream_pieces", "mm_debug_fastx_split",
 ]
 
 
@@ -1832,7 +1835,7 @@ def fastx_pipeline_device(builder: "Builder", text, max_records: int, fmt: str, 
 
 # ---- FASTA / FASTQ files of any size through the device in chunks (mm_fastx_stream_*)
 FASTX_AUTO, FASTX_FASTA, FASTX_FASTQ = 0, 1, 2
-FASTX_SK, FASTX_SKIP_AMBIGUOUS, FASTX_VALUES_U64, FASTX_VALUES_U128 = 1, 2, 4, 8
+FASTX_SK, FASTX_SKIP_AMBIGUOUS, FASTX_VALUES_U64, FASTX_VALUES_U128, FASTX_LONG_RECORDS = 1, 2, 4, 8, 16
 FASTX_NEED_INPUT, FASTX_END = 1, 2
 _FASTX_FORMATS = {"auto": FASTX_AUTO, "fasta": FASTX_FASTA, "fastq": FASTX_FASTQ}
 
@@ -1851,6 +1854,11 @@ class _FastxBatchC(C.Structure):
                 ("values", C.c_void_p)]
 
 
+class _FastxPiecesC(C.Structure):
+    _fields_ = [("first_continues", C.c_uint32), ("last_open", C.c_uint32), ("first_base", C.c_uint64),
+                ("first_overlap", C.c_uint64)]
+
+
 def _view(address, n, ctype, dtype):
     if not address or n == 0:
         return np.zeros(0, dtype=dtype)
@@ -1862,10 +1870,19 @@ class FastxBatch:
     offsets of the records' '>' / '@'), ``text_begin`` / ``text_end`` (the absolute byte range the batch covers) are
     64-bit file offsets; ``rec_base`` and ``offsets`` (n_records + 1 each) start at 0 in every batch; ``pos`` (and
     ``sk``) are record-local; ``values``: uint64, two words {lo, hi} per value for u128, or None.  The arrays are VIEWS
-    of the stream's page-locked buffers, valid until its following ``next()``; ``copy()`` detaches them."""
+    of the stream's page-locked buffers, valid until its following ``next()``; ``copy()`` detaches them.
+    With ``long_records`` (``mm_fastx_pieces_t``): ``first_continues`` - record 0 continues the previous batch's last
+    record (its ``pos`` / ``sk`` are record-global, its ``rec_text_pos`` the record's real '>', its first
+    ``first_overlap`` bases repeat the previous piece and ``first_base`` is the record-global index of its first base);
+    ``last_open`` - the last record goes on in the next batch.  ``fastx_join`` puts the pieces together."""
 
-    def __init__(self, c: _FastxBatchC, u128: bool, views=True):
+    def __init__(self, c: _FastxBatchC, u128: bool, views=True, pieces: "_FastxPiecesC" = None):
         n, p = int(c.n_records), int(c.n_positions)
+        self.u128 = u128
+        self.first_continues = bool(pieces.first_continues) if pieces is not None else False
+        self.last_open = bool(pieces.last_open) if pieces is not None else False
+        self.first_base = int(pieces.first_base) if pieces is not None else 0
+        self.first_overlap = int(pieces.first_overlap) if pieces is not None else 0
         self.n_records, self.n_bases, self.n_positions = n, int(c.n_bases), p
         self.text_begin, self.text_end = int(c.text_begin), int(c.text_end)
         self.rec_text_pos = _view(c.rec_text_pos, n, C.c_uint64, np.uint64)
@@ -1890,18 +1907,21 @@ class FastxStream:
     ``chunk_bytes`` new bytes per chunk, ``max_records`` / ``max_positions`` per chunk (0: the worst case,
     2 * chunk_bytes positions), ``fmt`` "auto" / "fasta" / "fastq", ``values`` None / "u64" / "u128",
     ``super_kmers`` / ``skip_ambiguous`` as the one-shot calls have them, ``first_byte`` the absolute offset of the
-    first byte fed, ``slots`` chunks in flight (0: the default of 3).  Iterating yields the remaining batches (after
+    first byte fed, ``slots`` chunks in flight (0: the default of 3), ``long_records`` FASTA records longer than a chunk
+    come in pieces (``MM_FASTX_LONG_RECORDS``; see ``FastxBatch`` and ``fastx_join``).  Iterating yields the remaining batches (after
     ``finish()``).  A failing stream raises ``MinimizerError`` from every later call."""
 
     def __init__(self, builder: "Builder", chunk_bytes: int, max_records: int, fmt="auto", values=None, super_kmers=False,
-                 skip_ambiguous=False, max_positions=0, first_byte=0, slots=0, device=None):
+                 skip_ambiguous=False, max_positions=0, first_byte=0, slots=0, device=None, long_records=False):
         if fmt not in _FASTX_FORMATS:
             raise ValueError('fmt is "auto", "fasta" or "fastq"')
         if values not in (None, "u64", "u128"):
             raise ValueError('values is None, "u64" or "u128"')
         flags = (FASTX_SK if super_kmers else 0) | (FASTX_SKIP_AMBIGUOUS if skip_ambiguous else 0)
         flags |= {None: 0, "u64": FASTX_VALUES_U64, "u128": FASTX_VALUES_U128}[values]
+        flags |= FASTX_LONG_RECORDS if long_records else 0
         self.h = None
+        self.long_records = bool(long_records)
         self.u128 = values == "u128"
         self.builder = builder
         self._plan = builder.plan()  # (the stream keeps the plan's handle: it must outlive the stream)
@@ -1960,7 +1980,11 @@ class FastxStream:
             raise StopIteration
         if code:
             self._raise(code)
-        return FastxBatch(c, self.u128)
+        pieces = None
+        if self.long_records:
+            pieces = _FastxPiecesC()
+            _check(lib().mm_fastx_stream_pieces(self.h, C.byref(pieces)))
+        return FastxBatch(c, self.u128, pieces=pieces)
 
     def __iter__(self):
         return self
@@ -1978,6 +2002,53 @@ def fastx_cut(text: bytes, fmt: str, last: bool = False) -> dict:
     out = (C.c_uint64 * 3)()
     _check(lib().mm_debug_fastx_cut(buf.ctypes.data if buf.size else None, buf.size, _FASTX_FORMATS[fmt], int(last), out))
     return {"cut": int(out[0]), "kept": int(out[1]), "dropped": int(out[2])}
+
+
+def fastx_split(text: bytes, l: int, last: bool = False) -> dict:
+    """The stream's split rule for FASTA records longer than a chunk, on a host text (``mm_debug_fastx_split``, no GPU):
+    ``l`` = k + w - 1."""
+    buf = np.frombuffer(text, dtype=np.uint8)
+    out = (C.c_uint64 * 4)()
+    _check(lib().mm_debug_fastx_split(buf.ctypes.data if buf.size else None, buf.size, int(l), int(last), out))
+    return {"cut": int(out[0]), "T": int(out[1]), "open": int(out[2]), "overlap": int(out[3])}
+
+
+def fastx_join(batches):
+    """Generator over the RECORDS of a ``long_records`` stream's batches, pieces joined: per record
+    ``(rec_text_pos, n_bases, pos, sk, values)`` - ``pos`` (uint32, record-global), ``sk`` and ``values`` (None when the
+    stream has none; u128 values keep two words per value) are the concatenation of the pieces' slices."""
+    cat = lambda xs, t: np.concatenate(xs) if xs else np.zeros(0, t)  # noqa: E731
+    held = None  # [rec_text_pos, n_bases, [pos], [sk] or None, [values] or None]
+
+    def done(h):
+        return (h[0], h[1], cat(h[2], np.uint32), None if h[3] is None else cat(h[3], np.uint32),
+                None if h[4] is None else cat(h[4], np.uint64))
+
+    for b in batches:
+        per = 2 if b.u128 else 1
+        for r in range(b.n_records):
+            o0, o1 = int(b.offsets[r]), int(b.offsets[r + 1])
+            n = int(b.rec_base[r + 1]) - int(b.rec_base[r])
+            part = (np.array(b.pos[o0:o1], copy=True), None if b.sk is None else np.array(b.sk[o0:o1], copy=True),
+                    None if b.values is None else np.array(b.values[o0 * per:o1 * per], copy=True))
+            if r == 0 and b.first_continues:
+                if held is None or held[0] != int(b.rec_text_pos[0]):
+                    raise ValueError("fastx_join: a continuing piece without the piece before it")
+                held[1] += n - b.first_overlap
+            else:
+                if held is not None:
+                    yield done(held)
+                held = [int(b.rec_text_pos[r]), n, [], None if part[1] is None else [], None if part[2] is None else []]
+            held[2].append(part[0])
+            if part[1] is not None:
+                held[3].append(part[1])
+            if part[2] is not None:
+                held[4].append(part[2])
+            if not (r == b.n_records - 1 and b.last_open):
+                yield done(held)
+                held = None
+    if held is not None:
+        yield done(held)
 
 
 def stream_fastx(builder: "Builder", source, chunk_bytes: int = 64 << 20, max_records: int = 1 << 20, read_bytes: int = 8 << 20,

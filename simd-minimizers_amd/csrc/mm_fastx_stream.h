@@ -11,10 +11,15 @@ namespace mm {
 // The trim step behind a packer, on `stream` (mm_fastx_cut.hip): d_counts {bases, records} rewritten in place to the kept
 // ones, d_cut[0] = cut, d_cut[1] = 1 when records > max_records kept the rule from being applied.  d_newlines: one word of
 // scratch.  The text may have any alignment; no byte outside [d_text, d_text + n_bytes) rounded to whole dwords is loaded.
-// Returns 0, or -1 when a launch failed.
-int launch_fastx_trim(const uint8_t *d_text, uint64_t n_bytes, int format, int last, const unsigned long long *d_rec_base,
-                      const unsigned long long *d_rec_text_pos, uint64_t max_records, unsigned long long *d_counts,
-                      unsigned long long *d_cut, unsigned long long *d_newlines, hipStream_t stream);
+// long_records (MM_FASTX_LONG_RECORDS on FASTA text) and l = k + w - 1: the split rule, d_cut[2..4] = {T, open, overlap}
+// (zeros without it; d_cut has five words).  Returns 0, or -1 when a launch failed.
+int launch_fastx_trim(const uint8_t *d_text, uint64_t n_bytes, int format, int last, int long_records, uint32_t l,
+                      const unsigned long long *d_rec_base, const unsigned long long *d_rec_text_pos, uint64_t max_records,
+                      unsigned long long *d_counts, unsigned long long *d_cut, unsigned long long *d_newlines, hipStream_t stream);
+// The seam epilogue's device part, behind the run and the values on `stream`: pos[j] (and sk[j] when d_sk is not null)
+// += bias for j < min(d_offsets[1], max_positions), record 0's slice; nothing when d_counts[1] is 0 or above max_records.
+int launch_fastx_bias(const unsigned long long *d_counts, const unsigned long long *d_offsets, uint64_t max_records,
+                      uint64_t max_positions, uint32_t bias, uint32_t *d_pos, uint32_t *d_sk, hipStream_t stream);
 
 // ---- from mm_api.hip
 struct ApiPlanInfo {

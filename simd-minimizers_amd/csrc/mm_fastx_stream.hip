@@ -13,6 +13,14 @@
 //   collect(chunk): once the count is on the host, the downloads of exactly the filled parts are queued; the batch is
 //          complete when they are done.  feed() and next() both move chunks along, neither waits unless it must.
 // A tail always lies inside its chunk's NEW bytes (a chunk whose cut is 0 is an error), so it is at most chunk_bytes long.
+//
+// MM_FASTX_LONG_RECORDS (FASTA text): a chunk that is one record from its first byte on and has no cut is a PIECE of an open
+// record (the split rule of mm_fastx_cut.h).  The chunk behind it starts with ">\n" and the piece's last l - 1 sequence
+// bytes text[T, n) in place of a tail, so packer, run and values work on it unchanged; behind the values the seam
+// epilogue's kernel adds first_base to record 0's positions (queue_run), and mm_fastx_stream_next, which hands the batches
+// out in text order, drops a minimizer piece's first position when the record emitted it last (the reference's rule for
+// joining lanes, src/collect.rs:265-271).  Nothing crosses from slot to slot on the device, so a repeated run repeats
+// nothing but its own slot's work.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -32,15 +40,15 @@ struct Slot {
     mm_workspace_t *ws = nullptr;
     hipStream_t stream = nullptr;
     // device
-    uint8_t *d_text = nullptr;  // [2 * chunk_bytes + 64]: carry area, then the new bytes
+    uint8_t *d_text = nullptr;  // [A + chunk_bytes + 64]: carry area (A bytes), then the new bytes
     uint8_t *d_packed = nullptr, *d_amb = nullptr;
     uint64_t *d_rec_base = nullptr, *d_rec_pos = nullptr, *d_offsets = nullptr;
-    unsigned long long *d_meta = nullptr;  // [0..1] bases, records  [2..3] cut, overflow  [4] positions  [5] newlines
+    unsigned long long *d_meta = nullptr;  // [0..1] bases, records  [2..6] cut, overflow, T, open, overlap  [7] positions  [8] newlines
     uint32_t *d_pos = nullptr, *d_sk = nullptr;
     uint64_t *d_values = nullptr;
     // page-locked host
     uint8_t *h_text = nullptr;
-    unsigned long long *h_meta = nullptr;
+    unsigned long long *h_meta = nullptr;  // words 0..7 of d_meta; bytes 120..121: the synthetic header line ">\n"
     uint64_t *h_rec_pos = nullptr, *h_rec_base = nullptr, *h_offsets = nullptr, *h_values = nullptr;
     uint32_t *h_pos = nullptr, *h_sk = nullptr;
     hipEvent_t ev_cut = nullptr, ev_run = nullptr, ev_done = nullptr, ev_tail = nullptr;
@@ -49,6 +57,9 @@ struct Slot {
     SlotState state = kFree;
     uint64_t n_new = 0, n_text = 0, text_off = 0, abs_begin = 0, report_begin = 0;
     int last = 0, retries = 0;
+    // MM_FASTX_LONG_RECORDS: record 0 continues the open record of the chunk before
+    bool continues = false;
+    uint64_t first_base = 0, first_overlap = 0, rec0_pos = 0;  // rec0_pos: the absolute offset of the record's real '>'
 };
 
 struct DeviceGuard {  // every entry restores the caller's current device
@@ -72,6 +83,11 @@ struct mm_fastx_stream {
     mm_fastx_stream_config_t cfg{};
     uint32_t value_len = 0;
     uint64_t C = 0, max_records = 0, max_positions = 0, packed_cap = 0, amb_cap = 0;
+    uint64_t A = 0;  // the carry area in front of the new bytes: C, with MM_FASTX_LONG_RECORDS C + 16 (2 bytes of it are used)
+    // MM_FASTX_LONG_RECORDS, in the order of delivery: the last position the open record has emitted
+    bool have_last = false;
+    uint32_t last_emitted = 0;
+    mm_fastx_pieces_t pieces{};  // of the batch handed out last
     int n_slots = 0;
     Slot slots[8];
     int fill = 0;      // the slot that takes the bytes fed next
@@ -112,19 +128,22 @@ int again(mm_fastx_stream *s) {
 
 bool is_blank(uint8_t c) { return c == ' ' || c == '\t' || c == '\r' || c == '\n'; }
 bool can_fill(const Slot &sl) { return sl.state == kFree || sl.state == kFilling; }
+// the split rule is in force: the flag, on FASTA text (a FASTQ stream behaves as without it)
+bool long_fasta(const mm_fastx_stream *s) { return (s->cfg.flags & MM_FASTX_LONG_RECORDS) && s->format == MM_FASTX_FASTA; }
 
 // steps 5-7 of a launched slot: the counts run, the values, the run's count to the host (queued again after a look-back
 // time-out: the packed records and the trimmed counts are still where the run reads them)
 int queue_run(mm_fastx_stream *s, Slot &sl) {
     const uint32_t flags = s->cfg.flags;
-    uint64_t *const d_counts = reinterpret_cast<uint64_t *>(sl.d_meta), *const d_count = reinterpret_cast<uint64_t *>(sl.d_meta + 4);
+    uint64_t *const d_counts = reinterpret_cast<uint64_t *>(sl.d_meta), *const d_count = reinterpret_cast<uint64_t *>(sl.d_meta + 7);
+    const uint64_t max_bases = sl.n_text - (sl.continues ? 2 : 0);  // (the synthetic header line holds no base)
     int r;
     if (flags & MM_FASTX_SKIP_AMBIGUOUS)
         r = mm_run_packed_reads_skip_ambiguous_counts_device_async(s->plan, sl.ws, sl.d_packed, s->packed_cap, 0, sl.d_amb, s->amb_cap, 0,
-                                                                   sl.n_text, s->max_records, sl.d_rec_base, d_counts, sl.d_pos,
+                                                                   max_bases, s->max_records, sl.d_rec_base, d_counts, sl.d_pos,
                                                                    s->max_positions, sl.d_offsets, d_count);
     else
-        r = mm_run_packed_reads_counts_device_async(s->plan, sl.ws, sl.d_packed, s->packed_cap, 0, sl.n_text, s->max_records,
+        r = mm_run_packed_reads_counts_device_async(s->plan, sl.ws, sl.d_packed, s->packed_cap, 0, max_bases, s->max_records,
                                                     sl.d_rec_base, d_counts, sl.d_pos, sl.d_sk, s->max_positions, sl.d_offsets, d_count);
     if (r) return fail_call(s, r);
     if (sl.d_values && s->max_records) {
@@ -134,7 +153,12 @@ int queue_run(mm_fastx_stream *s, Slot &sl) {
         if (r) return fail_call(s, r);
     }
     FX_HIP(hipSetDevice(s->cfg.device));
-    FX_HIP(hipMemcpyAsync(sl.h_meta + 4, sl.d_meta + 4, sizeof(unsigned long long), hipMemcpyDeviceToHost, sl.stream));
+    // the seam epilogue's device part, behind the values (they read k-mers at piece-local positions): record 0's positions
+    // and window indices become record-global.  A repeated run writes the slice anew, so the bias is never added twice.
+    if (sl.continues && mm::launch_fastx_bias(sl.d_meta, reinterpret_cast<unsigned long long *>(sl.d_offsets), s->max_records,
+                                              s->max_positions, (uint32_t)sl.first_base, sl.d_pos, sl.d_sk, sl.stream))
+        return fail_hip(s, hipGetLastError(), "the seam epilogue");
+    FX_HIP(hipMemcpyAsync(sl.h_meta + 7, sl.d_meta + 7, sizeof(unsigned long long), hipMemcpyDeviceToHost, sl.stream));
     FX_HIP(hipEventRecord(sl.ev_run, sl.stream));
     return MM_OK;
 }
@@ -149,11 +173,39 @@ int launch(mm_fastx_stream *s, int last) {
         FX_HIP(hipStreamWaitEvent(sl.stream, sl.ev_tail, 0));
         sl.tail_pending = false;
     }
-    if (sl.n_new) FX_HIP(hipMemcpyAsync(sl.d_text + s->C, sl.h_text, sl.n_new, hipMemcpyHostToDevice, sl.stream));
+    if (sl.n_new) FX_HIP(hipMemcpyAsync(sl.d_text + s->A, sl.h_text, sl.n_new, hipMemcpyHostToDevice, sl.stream));
     uint64_t tail = 0;
-    if (s->prev >= 0) {
+    sl.continues = false;
+    sl.first_base = sl.first_overlap = sl.rec0_pos = 0;
+    if (s->prev >= 0) FX_HIP(hipEventSynchronize(s->slots[s->prev].ev_cut));
+    if (s->prev >= 0 && long_fasta(s) && s->slots[s->prev].h_meta[5] && !s->slots[s->prev].h_meta[3]) {
+        // the chunk before is a piece of an open record: ">\n", its last l - 1 sequence bytes text[T, n), the new bytes
         Slot &p = s->slots[s->prev];
-        FX_HIP(hipEventSynchronize(p.ev_cut));
+        const uint64_t T = p.h_meta[4], overlap = p.h_meta[6], bases = p.h_meta[0];
+        if (T > p.n_text || p.h_meta[2] != p.n_text || overlap > bases)
+            return fail(s, MM_ERR_HIP, "mm_fastx_stream: the trim step left counts beyond their bounds");
+        if (bases <= p.first_overlap)
+            return fail(s, MM_ERR_CAPACITY, "mm_fastx_stream: a piece of " + std::to_string(p.n_text) +
+                                                " bytes brings no new base of its record (cannot advance)");
+        if (p.first_base + bases >= (1ull << 32))
+            return fail(s, MM_ERR_LEN_TOO_LARGE, "mm_fastx_stream: a record of 2^32 bases or more");
+        tail = p.n_text - T;
+        if (tail > s->C)  // (with the header line a packer sees 2 * chunk_bytes + 2 bytes at most, 2 * chunk_bytes bases)
+            return fail(s, MM_ERR_CAPACITY, "mm_fastx_stream: the overlap of a split record is longer than chunk_bytes");
+        uint8_t *const dst = sl.d_text + s->A - tail - 2;
+        FX_HIP(hipMemcpyAsync(dst, reinterpret_cast<const uint8_t *>(sl.h_meta) + 120, 2, hipMemcpyHostToDevice, sl.stream));
+        if (tail) FX_HIP(hipMemcpyAsync(dst + 2, p.d_text + p.text_off + T, tail, hipMemcpyDeviceToDevice, sl.stream));
+        FX_HIP(hipEventRecord(p.ev_tail, sl.stream));
+        p.tail_pending = true;
+        sl.continues = true;
+        sl.first_base = p.first_base + bases - overlap;
+        sl.first_overlap = overlap;
+        sl.rec0_pos = p.continues ? p.rec0_pos : p.abs_begin;  // (an open chunk's record starts at its first byte)
+        sl.abs_begin = p.abs_begin + T - 2;  // (the header line has two bytes at least, so T >= 2)
+        sl.report_begin = p.abs_begin + p.n_text;
+        tail += 2;
+    } else if (s->prev >= 0) {
+        Slot &p = s->slots[s->prev];
         const uint64_t cut = p.h_meta[2];
         // (a chunk that cannot be cut: its own collect step names the reason; nothing can follow it)
         if (p.h_meta[3] || cut == 0 || cut > p.n_text) {
@@ -166,7 +218,7 @@ int launch(mm_fastx_stream *s, int last) {
         tail = p.n_text - cut;
         if (tail > s->C) return fail(s, MM_ERR_CAPACITY, "mm_fastx_stream: a tail longer than chunk_bytes");
         if (tail) {
-            FX_HIP(hipMemcpyAsync(sl.d_text + s->C - tail, p.d_text + p.text_off + cut, tail, hipMemcpyDeviceToDevice, sl.stream));
+            FX_HIP(hipMemcpyAsync(sl.d_text + s->A - tail, p.d_text + p.text_off + cut, tail, hipMemcpyDeviceToDevice, sl.stream));
             FX_HIP(hipEventRecord(p.ev_tail, sl.stream));
             p.tail_pending = true;
         }
@@ -177,7 +229,7 @@ int launch(mm_fastx_stream *s, int last) {
         sl.report_begin = s->cfg.first_byte;
     }
     sl.n_text = tail + sl.n_new;
-    sl.text_off = s->C - tail;
+    sl.text_off = s->A - tail;
     sl.last = last;
     sl.retries = 0;
     if (sl.n_text == 0) {  // (only a last chunk comes here without a byte)
@@ -196,11 +248,11 @@ int launch(mm_fastx_stream *s, int last) {
             sl.ws, text, sl.n_text, sl.d_packed, s->packed_cap, sl.d_rec_base, sl.d_rec_pos, s->max_records, d_counts);
     if (r) return fail_call(s, r);
     FX_HIP(hipSetDevice(s->cfg.device));
-    if (mm::launch_fastx_trim(text, sl.n_text, s->format, last, reinterpret_cast<unsigned long long *>(sl.d_rec_base),
-                              reinterpret_cast<unsigned long long *>(sl.d_rec_pos), s->max_records, sl.d_meta, sl.d_meta + 2,
-                              sl.d_meta + 5, sl.stream))
+    if (mm::launch_fastx_trim(text, sl.n_text, s->format, last, long_fasta(s) ? 1 : 0, s->info.k + s->info.w - 1,
+                              reinterpret_cast<unsigned long long *>(sl.d_rec_base), reinterpret_cast<unsigned long long *>(sl.d_rec_pos),
+                              s->max_records, sl.d_meta, sl.d_meta + 2, sl.d_meta + 8, sl.stream))
         return fail_hip(s, hipGetLastError(), "the trim step");
-    FX_HIP(hipMemcpyAsync(sl.h_meta, sl.d_meta, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, sl.stream));
+    FX_HIP(hipMemcpyAsync(sl.h_meta, sl.d_meta, 7 * sizeof(unsigned long long), hipMemcpyDeviceToHost, sl.stream));
     FX_HIP(hipEventRecord(sl.ev_cut, sl.stream));
     r = queue_run(s, sl);
     if (r) return r;
@@ -233,7 +285,7 @@ int collect(mm_fastx_stream *s, Slot &sl, bool block) {
             if (q) return q;
             continue;
         }
-        const uint64_t n_bases = sl.h_meta[0], n_records = sl.h_meta[1], cut = sl.h_meta[2], n_pos = sl.h_meta[4];
+        const uint64_t n_bases = sl.h_meta[0], n_records = sl.h_meta[1], cut = sl.h_meta[2], n_pos = sl.h_meta[7];
         if (sl.h_meta[3])
             return fail(s, MM_ERR_CAPACITY, "mm_fastx_stream: more than max_records = " + std::to_string(s->max_records) +
                                                 " records in a chunk: " + std::to_string(n_records) + " needed");
@@ -319,6 +371,19 @@ int mm_debug_fastx_cut(const uint8_t *text, uint64_t n, int format, int last, ui
     return MM_OK;
 }
 
+int mm_debug_fastx_split(const uint8_t *text, uint64_t n, uint32_t l, int last, uint64_t out[4]) {
+    if (!out || (!text && n)) return MM_ERR_NULL;
+    mm::fastx_split_host(text, n, l, last ? 1 : 0, out);
+    return MM_OK;
+}
+
+int mm_fastx_stream_pieces(const mm_fastx_stream_t *s, mm_fastx_pieces_t *out) {
+    if (!s || !out) return MM_ERR_NULL;
+    if (s->delivered >= 0) *out = s->pieces;
+    else memset(out, 0, sizeof *out);
+    return MM_OK;
+}
+
 int mm_fastx_stream_create(mm_fastx_stream_t **out, const mm_plan_t *plan, const mm_fastx_stream_config_t *cfg) {
     if (out) *out = nullptr;
     if (!out || !plan || !cfg) return MM_ERR_NULL;
@@ -335,9 +400,16 @@ int mm_fastx_stream_create(mm_fastx_stream_t **out, const mm_plan_t *plan, const
                                                      (flags & MM_FASTX_SKIP_AMBIGUOUS) != 0);
     if (refusal) return refusal;
     if (cfg->format < MM_FASTX_AUTO || cfg->format > MM_FASTX_FASTQ || (cfg->slots != 0 && (cfg->slots < 2 || cfg->slots > 8)) ||
-        (flags & ~15u)) {
+        (flags & ~31u)) {
         mm::api_set_last_error("mm_fastx_stream_create: format is MM_FASTX_AUTO / _FASTA / _FASTQ, slots 0 or 2..8, flags MM_FASTX_*");
         return MM_ERR_BAD_MODE;
+    }
+    // (a piece must be able to move past its own overlap: l - 1 bases, up to three bytes each with "\r\n" behind every base)
+    if ((flags & MM_FASTX_LONG_RECORDS) && cfg->chunk_bytes < 4ull * (info.k + info.w - 1)) {
+        mm::api_set_last_error(("mm_fastx_stream_create: MM_FASTX_LONG_RECORDS needs chunk_bytes >= 4 * (k + w - 1) = " +
+                                std::to_string(4ull * (info.k + info.w - 1)))
+                                   .c_str());
+        return MM_ERR_CAPACITY;
     }
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
@@ -354,6 +426,7 @@ int mm_fastx_stream_create(mm_fastx_stream_t **out, const mm_plan_t *plan, const
     s->cfg = *cfg;
     s->value_len = value_len;
     s->C = cfg->chunk_bytes;
+    s->A = s->C + ((flags & MM_FASTX_LONG_RECORDS) ? 16 : 0);
     s->max_records = cfg->max_records;
     s->max_positions = (cfg->max_positions == 0 || cfg->max_positions > 2 * s->C) ? 2 * s->C : cfg->max_positions;
     s->packed_cap = ((2 * s->C / 4 + 8 + 3) & ~3ull) + 64;
@@ -371,19 +444,19 @@ int mm_fastx_stream_create(mm_fastx_stream_t **out, const mm_plan_t *plan, const
         if (rc) break;
         sl.stream = mm::api_workspace_stream(sl.ws);
         e = hipSetDevice(cfg->device);
-        if (e == hipSuccess) e = dev_alloc(sl.d_text, 2 * s->C + 64);
+        if (e == hipSuccess) e = dev_alloc(sl.d_text, s->A + s->C + 64);
         if (e == hipSuccess) e = dev_alloc(sl.d_packed, s->packed_cap);
         if (e == hipSuccess && (flags & MM_FASTX_SKIP_AMBIGUOUS)) e = dev_alloc(sl.d_amb, s->amb_cap);
         if (e == hipSuccess) e = dev_alloc(sl.d_rec_base, (R + 1) * 8);
         if (e == hipSuccess) e = dev_alloc(sl.d_rec_pos, (R + 1) * 8);
         if (e == hipSuccess) e = dev_alloc(sl.d_offsets, (R + 1) * 8);
-        if (e == hipSuccess) e = dev_alloc(sl.d_meta, 64);
-        if (e == hipSuccess) e = hipMemset(sl.d_meta, 0, 64);
+        if (e == hipSuccess) e = dev_alloc(sl.d_meta, 128);
+        if (e == hipSuccess) e = hipMemset(sl.d_meta, 0, 128);
         if (e == hipSuccess) e = dev_alloc(sl.d_pos, P * 4);
         if (e == hipSuccess && (flags & MM_FASTX_SK)) e = dev_alloc(sl.d_sk, P * 4);
         if (e == hipSuccess && want_values) e = dev_alloc(sl.d_values, P * per_value);
         if (e == hipSuccess) e = host_alloc(sl.h_text, s->C);
-        if (e == hipSuccess) e = host_alloc(sl.h_meta, 64);
+        if (e == hipSuccess) e = host_alloc(sl.h_meta, 128);
         if (e == hipSuccess) e = host_alloc(sl.h_rec_pos, (R + 1) * 8);
         if (e == hipSuccess) e = host_alloc(sl.h_rec_base, (R + 1) * 8);
         if (e == hipSuccess) e = host_alloc(sl.h_offsets, (R + 1) * 8);
@@ -393,7 +466,10 @@ int mm_fastx_stream_create(mm_fastx_stream_t **out, const mm_plan_t *plan, const
         hipEvent_t *ev[] = {&sl.ev_cut, &sl.ev_run, &sl.ev_done, &sl.ev_tail};
         for (hipEvent_t *p : ev)
             if (e == hipSuccess) e = hipEventCreateWithFlags(p, hipEventDisableTiming);
-        if (e == hipSuccess) memset(sl.h_meta, 0, 64);
+        if (e == hipSuccess) {
+            memset(sl.h_meta, 0, 128);
+            memcpy(reinterpret_cast<uint8_t *>(sl.h_meta) + 120, ">\n", 2);
+        }
     }
     if (rc == MM_OK && e != hipSuccess) {
         mm::api_set_last_error((std::string("mm_fastx_stream_create: ") + hipGetErrorString(e)).c_str());
@@ -518,17 +594,44 @@ int mm_fastx_stream_next(mm_fastx_stream_t *s, mm_fastx_batch_t *out) {
     FX_HIP(hipEventSynchronize(sl.ev_done));
     const uint64_t n_records = sl.h_meta[1];
     for (uint64_t i = 0; i < n_records; ++i) sl.h_rec_pos[i] += sl.abs_begin;
+    // The seam (MM_FASTX_LONG_RECORDS), decided here because batches are handed out in the order of the text: a piece's
+    // first window always emits its minimizer, so when that is the position the record emitted last (the window before
+    // the seam chose it too) the piece's first element is dropped - the batch starts at element 1 and the offsets behind
+    // record 0 move down by one.  Syncmers have no such rule: with l - 1 bases repeated no window occurs twice.
+    uint64_t drop = 0;
+    const bool last_open = long_fasta(s) && !sl.last && sl.h_meta[5];
+    memset(&s->pieces, 0, sizeof s->pieces);
+    if (!sl.continues) s->have_last = false;
+    if ((sl.continues || last_open) && n_records) {
+        const uint64_t n0 = sl.h_offsets[1];
+        if (sl.continues) {
+            if (sl.first_base + (sl.h_rec_base[1] - sl.h_rec_base[0]) >= (1ull << 32))
+                return fail(s, MM_ERR_LEN_TOO_LARGE, "mm_fastx_stream: a record of 2^32 bases or more");
+            sl.h_rec_pos[0] = sl.rec0_pos;
+            if (s->info.mode == MM_MINIMIZERS && n0 && s->have_last && sl.h_pos[0] == s->last_emitted) drop = 1;
+            s->pieces.first_continues = 1;
+            s->pieces.first_base = sl.first_base;
+            s->pieces.first_overlap = sl.first_overlap;
+        }
+        if (n0) {
+            s->have_last = true;
+            s->last_emitted = sl.h_pos[n0 - 1];
+        }
+        if (drop)
+            for (uint64_t i = 1; i <= n_records; ++i) --sl.h_offsets[i];
+    }
+    s->pieces.last_open = last_open ? 1 : 0;
     out->n_records = n_records;
     out->n_bases = sl.h_meta[0];
-    out->n_positions = sl.h_meta[4];
+    out->n_positions = sl.h_meta[7] - drop;
     out->text_begin = sl.report_begin;
     out->text_end = sl.abs_begin + (sl.last ? sl.n_text : sl.h_meta[2]);
     out->rec_text_pos = sl.h_rec_pos;
     out->rec_base = sl.h_rec_base;
     out->offsets = sl.h_offsets;
-    out->pos = sl.h_pos;
-    out->sk = sl.h_sk;
-    out->values = sl.h_values;
+    out->pos = sl.h_pos + drop;
+    out->sk = sl.h_sk ? sl.h_sk + drop : nullptr;
+    out->values = sl.h_values ? sl.h_values + drop * (s->cfg.flags & MM_FASTX_VALUES_U128 ? 2 : 1) : nullptr;
     sl.state = kDelivered;
     s->delivered = s->oldest;
     s->oldest = (s->oldest + 1) % s->n_slots;
