@@ -202,9 +202,11 @@ int mm_prebuilt_flavour_window_sizes(int canonical_windows, int reads_mode, mm_m
  *                          syncmer plan, as the runs themselves reject d_out_sk there (src/lib.rs:339)
  * A text plan (mm_plan_create_text) has its fused text kernels - or the generic family's - loaded; none is compiled.
  * report (may be NULL): `kernels` = kernels looked at; of them `compiled` were compiled by hiprtc in this call,
- * `from_disk` were loaded from MM_JIT_CACHE_DIR, `unavailable` cannot be had (MM_JIT=0, w > 128, a compile failure) -
+ * `from_disk` were loaded from MM_JIT_CACHE_DIR, `unavailable` cannot be had (MM_JIT=0, a compile failure) -
  * the rest were prebuilt or already loaded.  Runs of a plan with unavailable kernels take the generic family, as they
  * do without prepare: the call still returns MM_OK, loads that family, and mm_last_error() carries the reason.
+ * A plan with w > 128 has no fused kernel by design: the prebuilt generic family is its only path, is what gets loaded,
+ * and nothing counts as unavailable.
  * After MM_OK with unavailable == 0, no run of this plan in the prepared families on this device compiles anything.
  * what == 0, or MM_PREPARE_SUPERKMERS alone (no family named) on a minimizer plan: MM_OK and a zero report; the
  * syncmer-plan check comes first, so MM_PREPARE_SUPERKMERS alone on a syncmer plan is still MM_ERR_BAD_MODE.  Bits of

@@ -1103,7 +1103,8 @@ int mm_plan_prepare(const mm_plan_t *plan, mm_workspace_t *ws, uint32_t what, mm
             MM_HIP(mm::text_walk_prepare(plan->w, plan->canonical_windows != 0, plan->tt.canonical != 0, plan->mode, &c.kernels));
         else
             MM_HIP(mm::generic_prepare(true, &c.kernels));
-    } else if (ws->force_generic) {
+    } else if (ws->force_generic || plan->w > mm::kJitMaxW) {
+        // (w > kJitMaxW: no fused kernel exists for any plan, the prebuilt generic family is the only path - nothing is missing)
         MM_HIP(mm::generic_prepare(false, &c.kernels));
     } else {
         MM_HIP(mm::fused_prepare(plan->k, plan->w, plan->canonical_windows, (int)plan->ht.canonical, plan->mode, sequence, reads,
@@ -1396,6 +1397,7 @@ static int batch_issue(const mm_plan_t *plan, mm_workspace_t *ws, uint64_t n_seq
                        uint32_t *d_out_pos, uint32_t *d_out_sk, uint64_t capacity, BatchIssue *bi) {
     bi->n_seqs = n_seqs;
     bi->launched = false;
+    ws->last_lane_table = false;  // (also when the batch falls back to one launch per sequence)
     if (ws->force_generic || n_seqs == 0 || n_seqs >= (1ull << 32) ||
         !mm::fused_supported(plan->k, plan->w, plan->canonical_windows, (int)plan->ht.canonical))
         return MM_BATCH_FALLBACK;
@@ -1451,7 +1453,6 @@ static int batch_issue(const mm_plan_t *plan, mm_workspace_t *ws, uint64_t n_seq
     // lanes are any 256 consecutive segments of the batch, where the tile table below gives every sequence tiles of its
     // own (a 10 kbp contig fills 33 of 256 lanes).  Needs all sequences inside ONE ALLOCATION and one span of < 2^32 bases from the lowest
     // pointer (one allocation, the FASTA packer's buffer); long contigs keep their tiles (tapered tail, sequence kernel).
-    ws->last_lane_table = false;
     if (nonempty && lane_table_policy() != 0) {
         mm::RunArgs probe = a;
         probe.work_windows = 0;
@@ -1766,6 +1767,7 @@ static int run_reads_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, const
 
     bool fast = !ws->force_generic && mm::fused_reads_supported(plan->w, plan->canonical_windows, (int)plan->ht.canonical,
                                                                 plan->mode, d_out_sk != nullptr);
+    ws->last_lane_table = false;  // (also when no reads-mode kernel serves the plan: one launch per read below)
     if (fast) {
         mm::ReadsArgs a;
         a.seq = view;
@@ -1799,7 +1801,6 @@ static int run_reads_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, const
         // One lane per read (rounds 2-5) while the longest read fits a default lane; the lane table (round 6) for
         // longer ones - a lane per read then needs lists that leave a CU one or two workgroups, and above about 1.5 kbp
         // none at all (the per-read loop below, 33 us per read, was what a HiFi / ONT batch got).
-        ws->last_lane_table = false;
         const int policy = lane_table_policy();
         bool lanes = policy == 1;
         if (policy == -1) {
