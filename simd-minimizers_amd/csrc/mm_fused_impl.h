@@ -1614,18 +1614,38 @@ __device__ __forceinline__ unsigned long long lookback_overlapped(unsigned long 
 // 1.85 / 1.35 and 1.723 against 1.698: both wait for the same event, and the chain waits with ONE lane polling ONE
 // word.  Removed in round 4; DESIGN.md appendix A.)
 
+// (round 8) The part of a wave's copy-out that needs neither the tile's first output slot nor the other waves' totals:
+// lane c reads entry c of each of the wave's 64 lists (16-bit entries, two lists per register).  The lists were written
+// by this wave's own lanes, so the reads need no workgroup barrier and run in front of it (wave 0: in front of its
+// look-back), where a wave that has finished its walk would only wait; copy_out_wave<PRE> then stores from these
+// registers.  Entries past a list's end are read as whatever the row holds and never stored.
+// (The values - vbt + first window of the list's lane + entry - are made behind the barrier, one add per list as before:
+// kept packed, the entries hold 32 registers across the look-back and the barrier instead of 64.)
+constexpr int kPreWords = kWave / 2;
+__device__ __forceinline__ void copy_out_preload(const uint8_t *smem, const int wave, const int lane,
+                                                 uint32_t (&pre)[kPreWords]) {
+    const uint8_t *rd = smem + (uint32_t)lane * kListStride + 2u * (uint32_t)wave * kWave;
+    __builtin_amdgcn_wave_barrier();  // (no instruction: the lanes' list stores stay in front of the reads of other lanes' entries)
+#pragma unroll
+    for (int i = 0; i < kPreWords; ++i) pre[i] = *reinterpret_cast<const uint32_t *>(rd + 4 * i);
+}
+
 // Phase 2, the copy-out of one wave: the 64 lists of its lanes (LDS, entry c of lane t at c * stride + eb * t)
 // go to the output in lane order (= window order) from slot run0 on.  `vbt` = value of list entry 0 of the
 // tile's lane 0 (first window of the tile, minus one for minimizer positions; 0 in reads mode), `S` = windows
 // per lane, `kSh` = kSkShift of the window size (super-k-mer entries), `my_count` / `excl` = length of the
 // lane's list and its first slot relative to run0, `wave_total` = sum of the wave's lengths.  Shared by the
 // fused kernel and by the expander of the split path (mm_split.hip).
-template <bool E8, bool SK, bool READS>
+// PRE: `pre` holds the first 64 entries of the wave's lists, read by copy_out_preload in front of the workgroup barrier;
+// the fast path takes them from there instead of reading the lists (every other path reads the lists itself).
+template <bool E8, bool SK, bool READS, bool PRE = false>
 __device__ __forceinline__ void copy_out_wave(const uint8_t *smem, const OutParams &out, const uint32_t debug,
                                               const int wave, const int lane, const uint32_t vbt, const uint32_t S,
                                               const uint32_t kSh, const unsigned long long run0,
                                               const uint32_t wave_total, const uint32_t my_count,
-                                              const uint32_t excl, const uint32_t lane_vb = 0u) {
+                                              const uint32_t excl, const uint32_t lane_vb = 0u,
+                                              uint32_t *pre = nullptr) {
+    static_assert(!PRE || (!SK && !READS && !E8), "preloaded entries: 16-bit positions of sequence mode only");
     // lane_vb (READS): what the entries of THIS lane's list are relative to on top of vbt - the lane's first window
     // inside its read in lane-table launches (LaneSeg::win0), 0 otherwise
     constexpr uint32_t kStride = list_stride(E8), kEB = E8 ? 1u : 2u;
@@ -1709,13 +1729,21 @@ __device__ __forceinline__ void copy_out_wave(const uint8_t *smem, const OutPara
                 uint32_t ent[kBatch];
 #pragma unroll
                 for (int u = 0; u < kBatch; ++u) ent[u] = entry(L0 + u);
+                // (PRE: the batch's registers are taken up here as they are - no instruction; the values of a batch are
+                // made behind the stores of the batch before it, as when the entries came from the lists, and not all 64
+                // at once, which cost registers of the walk)
+                if (PRE) {
+#pragma unroll
+                    for (int u = 0; u < kBatch; u += 2) asm volatile("" : "+v"(pre[(L0 + u) / 2]) : : "memory");
+                }
 #pragma unroll
                 for (int u = 0; u < kBatch; ++u) {
                     const uint32_t pkl = __builtin_amdgcn_readlane(pk, L0 + u);
                     const uint32_t n = pkl & 511u, off = pkl >> 9;
                     const uint32_t vbl = READS ? vb0 + __builtin_amdgcn_readlane(lane_vb, L0 + u) : vb0 + (uint32_t)(L0 + u) * S;
                     const uint32_t iw = ent[u] >> kSh;
-                    const uint32_t val = SK ? vbl + iw + (ent[u] & kRelMask) : vbl + ent[u];
+                    const uint32_t pe = PRE ? (((L0 + u) & 1) ? pre[(L0 + u) / 2] >> 16 : pre[(L0 + u) / 2] & 0xffffu) : 0u;
+                    const uint32_t val = PRE ? vbl + pe : (SK ? vbl + iw + (ent[u] & kRelMask) : vbl + ent[u]);
                     // (round 2 experiment: storing every list as one or two full, aligned 128-byte lines
                     // instead changed the forward kernel by -1.5 % / +3 % - the stores cost by their bytes,
                     // not by their partial lines, so staging them into aligned runs would not pay)
@@ -2170,6 +2198,11 @@ __global__ __launch_bounds__(kFusedThreads, MM_MIN_BLOCKS) void fused_kernel(con
             publish_aggregate(p.out.status, bid, tot, etag);
         }
     }
+    // (round 8) the fixed-k walk of sequence mode: the list reads of the copy-out are issued here, in front of the
+    // look-back and the barrier (copy_out_preload); the registers of the walk are free
+    constexpr bool kPreCopy = !READS && !SK && !kE8 && MODE == 0 && kc_rule(W, KC);
+    uint32_t pre_ent[kPreWords];
+    if constexpr (kPreCopy) copy_out_preload(lists, wave, lane, pre_ent);
     if (wave == 0) {
         // Wave 0 runs the look-back (non-blocking, see lookback_overlapped) as soon as its own lanes
         // are done; the wave that finishes last has published the tile's aggregate.
@@ -2210,7 +2243,25 @@ __global__ __launch_bounds__(kFusedThreads, MM_MIN_BLOCKS) void fused_kernel(con
     }
     if (batch && tid == 0 && local_tile == 0 && !redo) p.batch_offsets[batch_s] = s_excl;
 
-    if (!overflow) {
+    if constexpr (kPreCopy) {
+        if (!overflow)
+            copy_out_wave<kE8, SK, READS, true>(lists, p.out, MM_DBG(p), wave, lane, (uint32_t)bw0 - 1u, S,
+                                                (uint32_t)kSkShift<W>, run0, wave_total, my_count, excl, 0u, pre_ent);
+        // The redo walk as a statement of its own BEHIND the copy-out, its condition opaque to the compiler: as the other
+        // side of the copy-out's branch it is laid out in front of the copy-out with a common exit, and the preloaded
+        // entries stay allocated across the walk, which needs every register (4 registers spilled, one of them at the
+        // start of every walk).
+        uint32_t again = (uint32_t)__builtin_amdgcn_readfirstlane(overflow ? 1u : 0u);
+        asm volatile("" : "+s"(again));
+        if (again != 0u && lane_active) {
+            // some list overflowed: walk the tile again, now storing straight to the output
+            ctx.dst = run0 + excl;
+            bool over;
+            if (kAmbi && p.wamb) lane_walk<W, CANON, HASH_RC, MODE, SK, true, true, kAmbi, kE8>(p, ctx, over);
+            else if (partial) lane_walk<W, CANON, HASH_RC, MODE, SK, true, true, false, kE8, KC>(p, ctx, over);
+            else lane_walk<W, CANON, HASH_RC, MODE, SK, true, false, false, kE8, KC>(p, ctx, over);
+        }
+    } else if (!overflow) {
         copy_out_wave<kE8, SK, READS>(lists, p.out, MM_DBG(p), wave, lane,
                                       (READS ? 0u : (uint32_t)bw0) - (MODE == 0 ? 1u : 0u), S, (uint32_t)kSkShift<W>,
                                       run0, wave_total, my_count, excl, lane_vb);
