@@ -541,7 +541,8 @@ uint32_t mm_values_reads_lds_stage(void);
  * bytes zero-extended past packed_bytes[s], and otherwise whatever the bytes hold.  A sequence without values is never
  * dereferenced: its pointer may be NULL and its packed_bytes 0.
  * The kernel is queued on the workspace's stream and the call does not wait for it; the host arrays are the caller's again
- * on return (the tables are staged through page-locked memory of the workspace's own).
+ * on return (the tables are staged through two page-locked areas of the workspace's own, used in turn: a call waits only to
+ * reuse an area whose upload, two calls back, is still queued).
  * Refused before anything is touched: MM_ERR_NULL for a NULL workspace, for NULL arrays when there is work and for a NULL
  * d_packed[s] of a sequence that has values; MM_ERR_VALUE_LEN for len == 0, len > 32 (u64) or len > 64 (u128);
  * MM_ERR_UNSORTED for offsets that decrease; MM_ERR_CAPACITY for a sequence with values whose (base_offset + n_bases + 3) / 4
