@@ -502,8 +502,8 @@ int stage_outputs(mm_workspace_t *ws, uint64_t cap, bool want_sk) {
 
 // ... and their way back: `n_offsets` offsets from d_vals (batches), `count` positions (and indices) if they were asked
 // for, and one wait when anything was queued.
-int download_positions(mm_workspace_t *ws, uint32_t *out_pos, uint32_t *out_sk, uint64_t count,
-                       uint64_t *out_offsets = nullptr, uint64_t n_offsets = 0) {
+int download_positions(mm_workspace_t *ws, uint32_t *out_pos, uint32_t *out_sk, uint64_t count, uint64_t *out_offsets,
+                       uint64_t n_offsets) {
     if (out_offsets)
         MM_HIP(hipMemcpyAsync(out_offsets, ws->d_vals, n_offsets * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
     if (out_pos && count) {
@@ -512,6 +512,128 @@ int download_positions(mm_workspace_t *ws, uint32_t *out_pos, uint32_t *out_sk, 
     }
     if (out_offsets || (out_pos && count)) MM_HIP(hipStreamSynchronize(ws->stream));
     return MM_OK;
+}
+
+// ---- launch arguments.  mm::RunArgs / ReadsArgs / TextRunArgs are value-initialised where they are filled (`a{}`): a
+// field that a site does not name is null / 0.  What they take from the plan and the workspace is written here, once.
+template <class Args>
+void set_plan(Args &a, const mm_plan_t *plan) {
+    a.k = plan->k;
+    a.w = plan->w;
+    a.mode = plan->mode;
+    a.canonical_windows = plan->canonical_windows;
+}
+// (packed plans: the hasher's tables travel in the arguments; byte text keeps its tables on the device, set_text_tables)
+template <class Args>
+void set_packed_plan(Args &a, const mm_plan_t *plan) {
+    set_plan(a, plan);
+    a.ht = plan->ht;
+}
+// The per-run error word (OutParams::error; judge_run_error reads its host copy).
+uint32_t *error_word(mm_workspace_t *ws) { return reinterpret_cast<uint32_t *>(ws->total + 1); }
+// The outputs of a run on this workspace: the caller's positions / indices / capacity, the workspace's total, ticket and
+// error words.  (status, count_out and total_host are the launch's own business.)
+mm::OutParams out_params(mm_workspace_t *ws, uint32_t *pos, uint32_t *sk, uint64_t cap) {
+    mm::OutParams o{};
+    o.pos = pos;
+    o.sk = sk;
+    o.cap = cap;
+    o.total = ws->total;
+    o.ticket = ws->ticket;
+    o.error = error_word(ws);
+    return o;
+}
+int use_ticket(const mm_workspace_t *ws) { return (ws->force_ticket || mm::mm_env("MM_FORCE_TICKET")) ? 1 : 0; }
+// Positions per window that a plan's mode gives on random sequence (sizes of lists and of first result buffers).
+double expected_density(const mm_plan_t *plan) {
+    return plan->mode == MM_OPEN_SYNCMERS ? 1.0 / plan->w : (plan->mode == MM_CLOSED_SYNCMERS ? 2.0 / plan->w : 2.0 / (plan->w + 1.0));
+}
+// The stand-in for a plan that the mm_debug_* planners fill their arguments from (no hasher, no device).  `mode` 3:
+// minimizers WITH super-k-mer indices - their 16-bit list entries bound the lanes; 4: minimizers over a PackedNSeq - the
+// skip-ambiguous walk's landing area and lane rules.
+mm_plan_t debug_plan(uint32_t k, uint32_t w, int canonical_windows, int mode) {
+    mm_plan_t p{};
+    p.k = k;
+    p.w = w;
+    p.canonical_windows = canonical_windows;
+    p.mode = (mode == 3 || mode == 4) ? 0u : (uint32_t)mode;
+    return p;
+}
+
+// ---- the timed launch.  arm() creates an event pair when the workspace times its launches (mm_workspace_enable_timing)
+// and hands it to the launch's arguments; done() - the launch is queued - gives the pair to ws->events, where
+// collect_timing finds and destroys it, and notes the path that ran.  Every other way out of the scope destroys what was
+// created: a second hipEventCreate that failed, a launcher that has no kernel for the plan, a refused launch, an
+// allocation that failed in between.  ws->events therefore only holds pairs that were recorded.
+class TimedLaunch {
+  public:
+    explicit TimedLaunch(mm_workspace_t *ws) : ws_(ws) {}
+    TimedLaunch(const TimedLaunch &) = delete;
+    TimedLaunch &operator=(const TimedLaunch &) = delete;
+    ~TimedLaunch() { drop(); }
+    template <class Args>
+    int arm(Args &a) {
+        a.timing_start = a.timing_stop = nullptr;
+        if (!ws_->timing) return MM_OK;
+        MM_HIP(hipEventCreate(&e0_));
+        MM_HIP(hipEventCreate(&e1_));
+        a.timing_start = e0_;
+        a.timing_stop = e1_;
+        return MM_OK;
+    }
+    void done(int path) {
+        if (e0_) ws_->events.emplace_back(e0_, e1_);
+        e0_ = e1_ = nullptr;
+        ws_->last_path = path;
+    }
+    void drop() {
+        if (e0_) hipEventDestroy(e0_);
+        if (e1_) hipEventDestroy(e1_);
+        e0_ = e1_ = nullptr;
+    }
+
+  private:
+    mm_workspace_t *ws_;
+    hipEvent_t e0_ = nullptr, e1_ = nullptr;
+};
+// (call it while the TimedLaunch is alive: the runtime's last error is the launch's, not an event's)
+int launch_failed() {
+    g_last_error = std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError());
+    return MM_ERR_HIP;
+}
+
+// The page-locked landing buffer of a batch's offsets (a pageable one would make the copy block).
+int grow_h_batch(mm_workspace_t *ws, uint64_t n) {
+    if (ws->h_batch_n >= n) return MM_OK;
+    if (ws->h_batch) hipHostFree(ws->h_batch);
+    ws->h_batch = nullptr;
+    ws->h_batch_n = 0;
+    const uint64_t want = n * 2;
+    MM_HIP(hipHostMalloc(reinterpret_cast<void **>(&ws->h_batch), want * sizeof(unsigned long long), hipHostMallocDefault));
+    ws->h_batch_n = want;
+    return MM_OK;
+}
+
+// The epilogue of the synchronous counts runs (packed reads, text batch): `issue` queues the run; the two counts come
+// back with the run's words (h_total[4..5]: one wait for all of them).  out[0] = positions, out[1..2] = the counts, on
+// MM_OK and on MM_ERR_CAPACITY (the need, or the true counts beyond their bounds); zeros otherwise.
+template <class Issue>
+int run_counts_sync(mm_workspace_t *ws, const uint64_t *d_counts, uint64_t capacity, bool wants_positions, uint64_t *out,
+                    Issue issue) {
+    if (out) out[0] = out[1] = out[2] = 0;
+    uint64_t count = 0;
+    const int r = run_sync(ws, capacity, wants_positions, &count, [&](bool *) {
+        const int q = issue();
+        if (q) return q;
+        MM_HIP(hipMemcpyAsync(ws->h_total + 4, d_counts, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
+        return (int)MM_OK;
+    });
+    if (out && (r == MM_OK || r == MM_ERR_CAPACITY)) {
+        out[0] = count;
+        out[1] = ws->h_total[4];
+        out[2] = ws->h_total[5];
+    }
+    return r;
 }
 
 }  // namespace
@@ -939,34 +1061,16 @@ int mm_workspace_last_lane_table(const mm_workspace_t *ws) { return ws && ws->la
 // the planner's view of a run: everything but the sizes is a placeholder (no device is touched)
 static mm::RunArgs debug_plan_args(uint32_t w, int canonical_windows, int mode, uint64_t n_seqs, uint64_t n_windows0) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
-    mm::RunArgs a;
-    memset(&a.seq, 0, sizeof a.seq);
-    memset(&a.ht, 0, sizeof a.ht);
+    const mm_plan_t plan = debug_plan(21, w, canonical_windows, mode);
+    mm::RunArgs a{};
+    set_packed_plan(a, &plan);
     a.ht.canonical = canonical_windows ? 1u : 0u;
-    a.k = 21;
-    a.w = w;
-    a.canonical_windows = canonical_windows;
-    // (3: minimizers WITH super-k-mer indices - their 16-bit list entries bound the lanes; 4: minimizers over a PackedNSeq -
-    // the skip-ambiguous walk's landing area and lane rules)
-    a.mode = (mode == 3 || mode == 4) ? 0u : (uint32_t)mode;
-    a.win_begin = 0;
     a.win_end = n_windows0;
-    memset(&a.out, 0, sizeof a.out);
     static uint32_t sk_marker, amb_marker;
     if (mode == 3) a.out.sk = &sk_marker;  // (only its being non-null matters to the planner)
-    a.wamb = mode == 4 ? &amb_marker : nullptr;
-    a.wamb_dwords = 0;
-    a.batch_seqs = nullptr;
-    a.batch_tile_seq = nullptr;
-    a.batch_offsets = nullptr;
+    if (mode == 4) a.wamb = &amb_marker;
     a.batch_n = (uint32_t)n_seqs;
-    a.batch_tiles = 0;
-    a.nblk = 0;
     a.work_windows = n_windows0;
-    a.use_ticket = 0;
-    a.scratch = nullptr;
-    a.generic_round_windows = 0;
-    a.timing_start = a.timing_stop = nullptr;
     return a;
 }
 
@@ -1016,24 +1120,13 @@ int mm_debug_launch_plan(uint32_t w, int canonical_windows, int mode, uint64_t n
 int mm_debug_lane_plan(uint32_t k, uint32_t w, int canonical_windows, int mode, uint64_t n_reads, uint64_t total_bases,
                        uint32_t blocks_per_lane, uint64_t *out6) {
     if (!out6 || w == 0 || k == 0) return MM_ERR_NULL;
-    mm::ReadsArgs a;
-    memset(&a.seq, 0, sizeof a.seq);
-    memset(&a.ht, 0, sizeof a.ht);
-    memset(&a.out, 0, sizeof a.out);
-    a.k = k;
-    a.w = w;
-    a.mode = (mode == 3 || mode == 4) ? 0u : (uint32_t)mode;
-    a.canonical_windows = canonical_windows;
+    const mm_plan_t stand_in = debug_plan(k, w, canonical_windows, mode);
+    mm::ReadsArgs a{};
+    set_packed_plan(a, &stand_in);
     a.n_reads = n_reads;
-    a.read_stride = a.read_len = 0;
-    a.read_lens = nullptr;
-    a.read_offsets = nullptr;
     static uint32_t sk_marker, amb_marker;  // (only their being non-null matters to the planner)
     if (mode == 3) a.out.sk = &sk_marker;
-    a.wamb = mode == 4 ? &amb_marker : nullptr;
-    a.wamb_dwords = 0;
-    a.use_ticket = 0;
-    a.timing_start = a.timing_stop = nullptr;
+    if (mode == 4) a.wamb = &amb_marker;
     mm::SegPlan plan;
     const int r = mm::fused_segments_plan(a, total_bases, blocks_per_lane, &plan);
     if (r) return MM_ERR_LEN_TOO_LARGE;
@@ -1126,6 +1219,79 @@ struct AmbArgs {
     uint64_t bit_offset;
 };
 
+// ---- What the caller of a run passed: one plain struct per family.  The exported wrappers fill one by field name, the
+// checks, *_async_impl and *_sync functions take (plan, ws, call).  Fields that a wrapper does not name are null / 0.
+struct SeqCall {  // one sequence: mm_run_device*, mm_run_skip_ambiguous_device*, and every loop over reads or sequences
+    const void *d_packed;
+    uint64_t packed_bytes, base_offset, n_bases, win_begin, win_end;
+    uint32_t *d_out_pos, *d_out_sk;
+    uint64_t capacity;
+    uint64_t *d_count;
+    // keep the running total of the previous launch, so that consecutive runs write their outputs back to back (the
+    // kernels take the total as the carry-in of their first tile)
+    bool append;
+    const AmbArgs *amb;  // null: a plain PackedSeq
+    // synchronous callers: *host_total_written is set when the kernel stores the total into a page-locked host word
+    // itself - ws->h_total[0], or host_word_dev (as the device addresses it: the pipelined host path gives every chunk
+    // its own)
+    bool *host_total_written;
+    unsigned long long *host_word_dev;
+};
+struct ReadsCall {  // reads of one packed buffer at a fixed stride, or (d_read_starts) back to back
+    const void *d_packed;
+    uint64_t packed_bytes, base_offset, n_reads;
+    uint32_t read_stride, read_len;  // (back to back: read_len is the longest read to expect, read_stride is not used)
+    const uint32_t *d_read_lens;
+    // reads packed back to back (round 4): read r = bases [starts[r], starts[r + 1]) of the buffer, n_reads + 1 device
+    // entries; total_bases = starts[n_reads], which the caller knows from the packer's counts
+    const uint64_t *d_read_starts;
+    uint64_t total_bases;
+    uint32_t *d_out_pos, *d_out_sk;
+    uint64_t capacity;
+    uint64_t *d_out_offsets, *d_count;
+    const AmbArgs *amb;
+};
+struct ReadsCountsCall {  // reads back to back with {bases, records} in device memory (d_counts)
+    const void *d_packed;
+    uint64_t packed_bytes, base_offset, max_bases, max_records;
+    const uint64_t *d_read_starts, *d_counts;
+    uint32_t *d_out_pos, *d_out_sk;
+    uint64_t capacity;
+    uint64_t *d_out_offsets, *d_count;
+    const AmbArgs *amb;
+};
+struct BatchCall {  // separately allocated sequences (host arrays of n_seqs entries; base_offsets may be null)
+    uint64_t n_seqs;
+    const void *const *d_packed;
+    const uint64_t *packed_bytes, *base_offsets, *n_bases;
+    uint32_t *d_out_pos, *d_out_sk;
+    uint64_t capacity;
+};
+struct TextCall {  // one byte text
+    const void *d_text;
+    uint64_t text_bytes, n, win_begin, win_end;
+    uint32_t *d_out_pos, *d_out_sk;
+    uint64_t capacity;
+    uint64_t *d_count;
+};
+struct TextBatchCall {  // records of one byte text
+    const void *d_text;
+    uint64_t text_bytes, n_records;
+    const uint64_t *d_starts;
+    uint64_t n_chars;
+    uint32_t *d_out_pos, *d_out_sk;
+    uint64_t capacity;
+    uint64_t *d_out_offsets, *d_count;
+};
+struct TextBatchCountsCall {  // the same with {characters, records} in device memory (d_counts)
+    const void *d_text;
+    uint64_t text_bytes, max_chars, max_records;
+    const uint64_t *d_starts, *d_counts;
+    uint32_t *d_out_pos, *d_out_sk;
+    uint64_t capacity;
+    uint64_t *d_out_offsets, *d_count;
+};
+
 // Fills ws->wamb with the window ambiguity bits of windows [win_begin - 1, win_end) of a
 // sequence / buffer span of `span_bases` bases whose windows are l bases long.
 static int prepare_window_ambiguity(mm_workspace_t *ws, const AmbArgs &amb, uint64_t span_bases,
@@ -1152,91 +1318,59 @@ static int prepare_window_ambiguity(mm_workspace_t *ws, const AmbArgs &amb, uint
     return MM_OK;
 }
 
-// `append`: keep the running total of the previous launch, so that consecutive runs write their
-// outputs back to back (the kernels take the total as the carry-in of their first tile).
-static int run_device_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
-                                 uint64_t packed_bytes, uint64_t base_offset, uint64_t n_bases,
-                                 uint64_t win_begin, uint64_t win_end, uint32_t *d_out_pos,
-                                 uint32_t *d_out_sk, uint64_t capacity, uint64_t *d_count,
-                                 bool append, const AmbArgs *amb = nullptr, bool *host_total_written = nullptr,
-                                 unsigned long long *host_word_dev = nullptr) {
-    // (host_word_dev: another page-locked word - as the device addresses it - to receive the total instead of
-    // ws->h_total[0]: the pipelined host path gives every chunk its own)
+static int run_device_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, const SeqCall &c) {
+    uint64_t win_end = c.win_end, capacity = c.capacity;
     // Stream operations of one run (round 4): the fused kernel alone.  Its look-back words are epoch-tagged (no
     // clear), a run that does not append ignores the old total (no clear), and its last tile stores the total to
     // d_count and - for the synchronous entry points, host_total_written != null - to the page-locked host word
     // ws->h_total[0] as well (no copies).  The split path, the generic family and empty runs keep the cleared
     // total + copy protocol of rounds 1-3.  The per-run error word total[1] is NOT cleared here any more: the entry
     // points that read it clear it themselves.
-    if (host_total_written) *host_total_written = false;
+    if (c.host_total_written) *c.host_total_written = false;
     if (!plan || !ws) return MM_ERR_NULL;
-    if (n_bases >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
-    if (d_out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;  // src/lib.rs:339
-    if (amb) {
+    if (c.n_bases >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
+    if (c.d_out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;  // src/lib.rs:339
+    if (c.amb) {
         // run_skip_ambiguous_windows exists on canonical builders only and has no super-k-mer
         // flavour (src/lib.rs:451-496; assert src/minimizers.rs:176)
         if (!plan->canonical_windows) return MM_ERR_HASHER_NOT_CANONICAL;
-        if (d_out_sk) return MM_ERR_BAD_MODE;
+        if (c.d_out_sk) return MM_ERR_BAD_MODE;
     }
-    if (!d_out_pos) capacity = 0;
+    if (!c.d_out_pos) capacity = 0;
     MM_HIP(set_device(ws->device));
     const uint64_t l = (uint64_t)plan->k + plan->w - 1;
-    const uint64_t n_w = n_bases >= l ? n_bases - l + 1 : 0;
+    const uint64_t n_w = c.n_bases >= l ? c.n_bases - l + 1 : 0;
     if (win_end > n_w) win_end = n_w;
     bool total_cleared = false, count_stored = false;
     auto clear_total = [&]() -> int {  // (families that take *total as their carry-in; with it the per-run error word)
-        if (!append && !total_cleared) MM_HIP(hipMemsetAsync(ws->total, 0, 2 * sizeof(unsigned long long), ws->stream));
+        if (!c.append && !total_cleared) MM_HIP(hipMemsetAsync(ws->total, 0, 2 * sizeof(unsigned long long), ws->stream));
         total_cleared = true;
         return MM_OK;
     };
-    if (win_begin < win_end) {
-        if (!d_packed) return MM_ERR_NULL;
-        mm::RunArgs a;
-        int r = make_view(d_packed, packed_bytes, base_offset, n_bases, &a.seq);
+    if (c.win_begin < win_end) {
+        if (!c.d_packed) return MM_ERR_NULL;
+        mm::RunArgs a{};
+        int r = make_view(c.d_packed, c.packed_bytes, c.base_offset, c.n_bases, &a.seq);
         if (r) return r;
-        a.ht = plan->ht;
-        a.k = plan->k;
-        a.w = plan->w;
-        a.canonical_windows = plan->canonical_windows;
-        a.mode = plan->mode;
-        a.win_begin = win_begin;
+        set_packed_plan(a, plan);
+        a.win_begin = c.win_begin;
         a.win_end = win_end;
-        a.out.pos = d_out_pos;
-        a.out.sk = d_out_sk;
-        a.out.cap = capacity;
-        a.out.total = ws->total;
-        a.out.ticket = ws->ticket;
-        a.out.error = reinterpret_cast<uint32_t *>(ws->total + 1);
+        a.out = out_params(ws, c.d_out_pos, c.d_out_sk, capacity);
         a.nblk = ws->nblk;
-        a.use_ticket = (ws->force_ticket || mm::mm_env("MM_FORCE_TICKET")) ? 1 : 0;
-        a.scratch = nullptr;
-        a.generic_round_windows = 0;
-        a.timing_start = a.timing_stop = nullptr;
-        a.wamb = nullptr;
-        a.wamb_dwords = 0;
-        a.batch_seqs = nullptr;
-        a.batch_tile_seq = nullptr;
-        a.batch_offsets = nullptr;
-        a.batch_n = 0;
-        a.batch_tiles = 0;
-        a.work_windows = win_end - win_begin;
-        a.append = append;
-        if (amb) {
-            r = prepare_window_ambiguity(ws, *amb, n_bases, (uint32_t)l, win_begin, win_end, &a.wamb_dwords);
+        a.use_ticket = use_ticket(ws);
+        a.work_windows = win_end - c.win_begin;
+        a.append = c.append;
+        if (c.amb) {
+            r = prepare_window_ambiguity(ws, *c.amb, c.n_bases, (uint32_t)l, c.win_begin, win_end, &a.wamb_dwords);
             if (r) return r;
             a.wamb = ws->wamb;
         }
         bool fused = !ws->force_generic &&
                      mm::fused_supported(plan->k, plan->w, plan->canonical_windows,
                                          (int)plan->ht.canonical);
-        if (ws->timing) {
-            hipEvent_t e0, e1;
-            MM_HIP(hipEventCreate(&e0));
-            MM_HIP(hipEventCreate(&e1));
-            ws->events.emplace_back(e0, e1);
-            a.timing_start = e0;
-            a.timing_stop = e1;
-        }
+        TimedLaunch timed(ws);  // (one pair for whichever launch finally runs: split, fused, or generic after lr == -2)
+        r = timed.arm(a);
+        if (r) return r;
         int lr = 0;
         bool split = false;
 #ifdef MM_EXPERIMENTS
@@ -1263,12 +1397,12 @@ static int run_device_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, cons
             a.status_avail = ws->status_words;
             r = next_status_epoch(ws, &a.status_epoch);
             if (r) return r;
-            a.out.count_out = reinterpret_cast<unsigned long long *>(d_count);
-            a.out.total_host = host_total_written ? (host_word_dev ? host_word_dev : ws->h_total_dev) : nullptr;
+            a.out.count_out = reinterpret_cast<unsigned long long *>(c.d_count);
+            a.out.total_host = c.host_total_written ? (c.host_word_dev ? c.host_word_dev : ws->h_total_dev) : nullptr;
             lr = mm::launch_fused(a, ws->stream);
             if (lr == 0) {
-                count_stored = d_count != nullptr;
-                if (host_total_written && a.out.total_host) *host_total_written = true;
+                count_stored = c.d_count != nullptr;
+                if (c.host_total_written && a.out.total_host) *c.host_total_written = true;
             }
             a.out.count_out = a.out.total_host = nullptr;
             if (lr == -2) {
@@ -1279,7 +1413,7 @@ static int run_device_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, cons
             }
         }
         if (!fused) {
-            const uint64_t nwin = win_end - win_begin;
+            const uint64_t nwin = win_end - c.win_begin;
             a.generic_round_windows = nwin < (1ull << 24) ? nwin : (1ull << 24);
             r = grow_bytes(ws->scratch, ws->scratch_bytes, mm::generic_scratch_bytes(a.generic_round_windows, plan->w));
             if (r) return r;
@@ -1292,17 +1426,14 @@ static int run_device_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, cons
             ws->status_dirty = true;  // (the generic family clears and writes untagged words)
             lr = mm::launch_generic(a, ws->stream);
         }
-        if (lr != 0) {
-            g_last_error = std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError());
-            return MM_ERR_HIP;
-        }
-        ws->last_path = fused ? (split ? MM_PATH_SPLIT : MM_PATH_FUSED) : MM_PATH_GENERIC;
+        if (lr != 0) return launch_failed();
+        timed.done(fused ? (split ? MM_PATH_SPLIT : MM_PATH_FUSED) : MM_PATH_GENERIC);
     } else {
         const int r = clear_total();  // an empty run: the total is what it was (append) or 0
         if (r) return r;
     }
-    if (d_count && !count_stored)
-        MM_HIP(hipMemcpyAsync(d_count, ws->total, sizeof(unsigned long long), hipMemcpyDeviceToDevice,
+    if (c.d_count && !count_stored)
+        MM_HIP(hipMemcpyAsync(c.d_count, ws->total, sizeof(unsigned long long), hipMemcpyDeviceToDevice,
                               ws->stream));
     return MM_OK;
 }
@@ -1314,8 +1445,10 @@ int mm_run_device_async(const mm_plan_t *plan, mm_workspace_t *ws, const void *d
     ApiScope api_scope;  // (restores the calling thread's current device on return)
     if (const int bad = dna_plan_only(plan)) return bad;
     if (ws) ws->async_unchecked = true;
-    return run_device_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_bases, win_begin,
-                                 win_end, d_out_pos, d_out_sk, capacity, d_count, false);
+    return run_device_async_impl(plan, ws, {.d_packed = d_packed, .packed_bytes = packed_bytes, .base_offset = base_offset,
+                                            .n_bases = n_bases, .win_begin = win_begin, .win_end = win_end,
+                                            .d_out_pos = d_out_pos, .d_out_sk = d_out_sk, .capacity = capacity,
+                                            .d_count = d_count});
 }
 
 // Lane-table launch (round 6; mm_lanes.hip): reads / sequences of ANY lengths in ONE launch of the reads-mode kernel at
@@ -1346,26 +1479,13 @@ static int run_lane_table(mm_workspace_t *ws, mm::ReadsArgs &a, const mm::SegSou
     r = next_status_epoch(ws, &a.status_epoch);
     if (r) return r;
     mm::SegBuffers b{ws->seg_table, ws->seg_origin, ws->seg_first, ws->seg_blk};
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    a.timing_start = a.timing_stop = nullptr;
-    if (ws->timing) {
-        MM_HIP(hipEventCreate(&e0));
-        MM_HIP(hipEventCreate(&e1));
-        a.timing_start = e0;
-        a.timing_stop = e1;
-    }
+    TimedLaunch timed(ws);
+    r = timed.arm(a);
+    if (r) return r;
     const int lr = mm::launch_fused_segments(a, src, plan, b, ws->stream);
-    if (lr != 0) {
-        if (e0) hipEventDestroy(e0);
-        if (e1) hipEventDestroy(e1);
-        if (lr == -1) {
-            g_last_error = std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError());
-            return MM_ERR_HIP;
-        }
-        return 1;
-    }
-    if (ws->timing) ws->events.emplace_back(e0, e1);
-    ws->last_path = MM_PATH_FUSED;
+    if (lr == -1) return launch_failed();
+    if (lr != 0) return 1;
+    timed.done(MM_PATH_FUSED);
     ws->last_lane_table = true;
     ws->last_lanes = plan.lanes_cap;
     return MM_OK;
@@ -1391,50 +1511,28 @@ struct BatchIssue {
     bool launched = false;                 // false: nothing was queued (no tile at all): every offset is 0
 };
 
-static int batch_issue(const mm_plan_t *plan, mm_workspace_t *ws, uint64_t n_seqs,
-                       const void *const *d_packed, const uint64_t *packed_bytes,
-                       const uint64_t *base_offsets, const uint64_t *n_bases,
-                       uint32_t *d_out_pos, uint32_t *d_out_sk, uint64_t capacity, BatchIssue *bi) {
-    bi->n_seqs = n_seqs;
+static int batch_issue(const mm_plan_t *plan, mm_workspace_t *ws, const BatchCall &c, BatchIssue *bi) {
+    uint64_t capacity = c.capacity;
+    bi->n_seqs = c.n_seqs;
     bi->launched = false;
     ws->last_lane_table = false;  // (also when the batch falls back to one launch per sequence)
-    if (ws->force_generic || n_seqs == 0 || n_seqs >= (1ull << 32) ||
+    if (ws->force_generic || c.n_seqs == 0 || c.n_seqs >= (1ull << 32) ||
         !mm::fused_supported(plan->k, plan->w, plan->canonical_windows, (int)plan->ht.canonical))
         return MM_BATCH_FALLBACK;
-    if (d_out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;
-    if (!d_out_pos) capacity = 0;
-    mm::RunArgs a;
-    a.ht = plan->ht;
-    a.k = plan->k;
-    a.w = plan->w;
-    a.canonical_windows = plan->canonical_windows;
-    a.mode = plan->mode;
-    a.win_begin = a.win_end = 0;
-    a.out.pos = d_out_pos;
-    a.out.sk = d_out_sk;
-    a.out.cap = capacity;
-    a.out.total = ws->total;
-    a.out.ticket = ws->ticket;
-    a.out.error = reinterpret_cast<uint32_t *>(ws->total + 1);
+    if (c.d_out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;
+    if (!c.d_out_pos) capacity = 0;
+    mm::RunArgs a{};
+    set_packed_plan(a, plan);
+    a.out = out_params(ws, c.d_out_pos, c.d_out_sk, capacity);
     a.nblk = ws->nblk;
-    a.scratch = nullptr;
-    a.generic_round_windows = 0;
-    a.wamb = nullptr;
-    a.wamb_dwords = 0;
-    a.seq = mm::SeqView{nullptr, 0, 0, 0};
-    a.batch_seqs = nullptr;
-    a.batch_tile_seq = nullptr;
-    a.batch_offsets = nullptr;
-    a.batch_n = (uint32_t)n_seqs;
-    a.batch_tiles = 0;
+    a.batch_n = (uint32_t)c.n_seqs;
     const uint64_t l = (uint64_t)plan->k + plan->w - 1;
     // lane length: a tile should not be much larger than a typical sequence of the batch (every
     // sequence starts a tile of its own), nor the batch too short to fill the chip
-    a.work_windows = 0;
     uint64_t nonempty = 0;
-    for (uint64_t s = 0; s < n_seqs; ++s) {
-        a.work_windows += n_bases[s] >= l ? n_bases[s] - l + 1 : 0;
-        nonempty += n_bases[s] >= l ? 1 : 0;
+    for (uint64_t s = 0; s < c.n_seqs; ++s) {
+        a.work_windows += c.n_bases[s] >= l ? c.n_bases[s] - l + 1 : 0;
+        nonempty += c.n_bases[s] >= l ? 1 : 0;
     }
     if (nonempty) {
         const uint64_t per_seq = a.work_windows / nonempty * 1024ull;
@@ -1442,12 +1540,12 @@ static int batch_issue(const mm_plan_t *plan, mm_workspace_t *ws, uint64_t n_seq
     }
     std::vector<mm::BatchSeq> &seqs = bi->seqs;
     std::vector<mm::BatchTile> &tile_seq = bi->tile_seq;
-    seqs.assign(n_seqs, mm::BatchSeq{nullptr, 0, 0, 0, 0, {0, 0}});
+    seqs.assign(c.n_seqs, mm::BatchSeq{nullptr, 0, 0, 0, 0, {0, 0}});
     tile_seq.clear();
-    std::vector<uint64_t> nws(n_seqs);
-    for (uint64_t s = 0; s < n_seqs; ++s) {
-        if (n_bases[s] >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
-        nws[s] = n_bases[s] >= l ? n_bases[s] - l + 1 : 0;
+    std::vector<uint64_t> nws(c.n_seqs);
+    for (uint64_t s = 0; s < c.n_seqs; ++s) {
+        if (c.n_bases[s] >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
+        nws[s] = c.n_bases[s] >= l ? c.n_bases[s] - l + 1 : 0;
     }
     // Round 6: batches of SHORT sequences take a lane-table launch of the reads-mode kernel (mm_lanes.hip) - a tile's 256
     // lanes are any 256 consecutive segments of the batch, where the tile table below gives every sequence tiles of its
@@ -1458,24 +1556,24 @@ static int batch_issue(const mm_plan_t *plan, mm_workspace_t *ws, uint64_t n_seq
         probe.work_windows = 0;
         const uint64_t tile_w = mm::fused_tile_windows(probe);  // windows of a default tile
         uint64_t total_w = 0;
-        for (uint64_t s = 0; s < n_seqs; ++s) total_w += nws[s];
+        for (uint64_t s = 0; s < c.n_seqs; ++s) total_w += nws[s];
         // (the crossover, measured on 1 Gbp of equal contigs - tools/gpu_batch_crossover.py, profiles/r06_batch_crossover.txt: the
         // lane table wins up to 500 kbp per contig and the per-sequence tiles from 1 Mbp on, at w = 11 - 6 and 13 tiles per
         // contig - as at w = 51 - 1.4 and 2.8: eight tiles or 750 k windows, whichever is less)
         const uint64_t per_seq_limit = 8 * tile_w < 750000ull ? 8 * tile_w : 750000ull;
         const bool short_seqs = total_w / nonempty < per_seq_limit;
         if ((short_seqs || lane_table_policy() == 1) &&
-            mm::fused_reads_supported(plan->w, plan->canonical_windows, (int)plan->ht.canonical, plan->mode, d_out_sk != nullptr)) {
+            mm::fused_reads_supported(plan->w, plan->canonical_windows, (int)plan->ht.canonical, plan->mode, c.d_out_sk != nullptr)) {
             uintptr_t lo = ~(uintptr_t)0, hi = 0;
             uint32_t max_len = 0;
-            for (uint64_t s = 0; s < n_seqs; ++s) {
+            for (uint64_t s = 0; s < c.n_seqs; ++s) {
                 if (nws[s] == 0) continue;
-                if (!d_packed[s]) return MM_ERR_NULL;
-                const uintptr_t p0 = reinterpret_cast<uintptr_t>(d_packed[s]);
-                if ((((base_offsets ? base_offsets[s] : 0) + n_bases[s] + 3) / 4) > packed_bytes[s]) return MM_ERR_CAPACITY;
+                if (!c.d_packed[s]) return MM_ERR_NULL;
+                const uintptr_t p0 = reinterpret_cast<uintptr_t>(c.d_packed[s]);
+                if ((((c.base_offsets ? c.base_offsets[s] : 0) + c.n_bases[s] + 3) / 4) > c.packed_bytes[s]) return MM_ERR_CAPACITY;
                 lo = p0 < lo ? p0 : lo;
-                hi = p0 + packed_bytes[s] > hi ? p0 + packed_bytes[s] : hi;
-                if (n_bases[s] > max_len) max_len = (uint32_t)n_bases[s];
+                hi = p0 + c.packed_bytes[s] > hi ? p0 + c.packed_bytes[s] : hi;
+                if (c.n_bases[s] > max_len) max_len = (uint32_t)c.n_bases[s];
             }
             const uint64_t span_bytes = hi - lo;
             // ONE descriptor covers the span from the lowest sequence to the end of the highest, and a lane's loads run a few
@@ -1494,57 +1592,41 @@ static int batch_issue(const mm_plan_t *plan, mm_workspace_t *ws, uint64_t n_seq
                 }
             }
             if (one_allocation && span_bytes < (1ull << 30) - 64) {
-                bi->starts.assign(n_seqs + 1, 0);
-                bi->lens.assign(n_seqs, 0);
+                bi->starts.assign(c.n_seqs + 1, 0);
+                bi->lens.assign(c.n_seqs, 0);
                 uint64_t total_bases = 0;
-                for (uint64_t s = 0; s < n_seqs; ++s) {
+                for (uint64_t s = 0; s < c.n_seqs; ++s) {
                     if (nws[s] == 0) continue;  // (no window: an empty lane; its start is never read from)
-                    bi->starts[s] = (reinterpret_cast<uintptr_t>(d_packed[s]) - lo) * 4ull + (base_offsets ? base_offsets[s] : 0);
-                    bi->lens[s] = (uint32_t)n_bases[s];
-                    total_bases += n_bases[s];
+                    bi->starts[s] = (reinterpret_cast<uintptr_t>(c.d_packed[s]) - lo) * 4ull + (c.base_offsets ? c.base_offsets[s] : 0);
+                    bi->lens[s] = (uint32_t)c.n_bases[s];
+                    total_bases += c.n_bases[s];
                 }
-                mm::ReadsArgs ra;
+                mm::ReadsArgs ra{};
                 int r = make_view(reinterpret_cast<const void *>(lo), span_bytes, 0, span_bytes * 4ull, &ra.seq);
                 if (r == MM_OK) {
-                    r = grow(ws->seg_starts, ws->seg_starts_n, n_seqs + 1, sizeof(unsigned long long));
+                    r = grow(ws->seg_starts, ws->seg_starts_n, c.n_seqs + 1, sizeof(unsigned long long));
                     if (r) return r;
-                    r = grow(ws->seg_lens, ws->seg_lens_n, n_seqs, sizeof(uint32_t));
+                    r = grow(ws->seg_lens, ws->seg_lens_n, c.n_seqs, sizeof(uint32_t));
                     if (r) return r;
-                    r = grow(ws->batch_offsets, ws->batch_offsets_n, n_seqs + 1, sizeof(unsigned long long));
+                    r = grow(ws->batch_offsets, ws->batch_offsets_n, c.n_seqs + 1, sizeof(unsigned long long));
                     if (r) return r;
-                    if (ws->h_batch_n < n_seqs + 1) {
-                        if (ws->h_batch) hipHostFree(ws->h_batch);
-                        ws->h_batch = nullptr;
-                        ws->h_batch_n = 0;
-                        const uint64_t want = (n_seqs + 1) * 2;
-                        MM_HIP(hipHostMalloc(reinterpret_cast<void **>(&ws->h_batch), want * sizeof(unsigned long long), hipHostMallocDefault));
-                        ws->h_batch_n = want;
-                    }
-                    MM_HIP(hipMemcpyAsync(ws->seg_starts, bi->starts.data(), (n_seqs + 1) * sizeof(unsigned long long),
+                    r = grow_h_batch(ws, c.n_seqs + 1);
+                    if (r) return r;
+                    MM_HIP(hipMemcpyAsync(ws->seg_starts, bi->starts.data(), (c.n_seqs + 1) * sizeof(unsigned long long),
                                           hipMemcpyHostToDevice, ws->stream));
-                    MM_HIP(hipMemcpyAsync(ws->seg_lens, bi->lens.data(), n_seqs * sizeof(uint32_t), hipMemcpyHostToDevice, ws->stream));
-                    ra.ht = plan->ht;
-                    ra.k = plan->k;
-                    ra.w = plan->w;
-                    ra.mode = plan->mode;
-                    ra.canonical_windows = plan->canonical_windows;
-                    ra.n_reads = n_seqs;
-                    ra.read_stride = 0;
+                    MM_HIP(hipMemcpyAsync(ws->seg_lens, bi->lens.data(), c.n_seqs * sizeof(uint32_t), hipMemcpyHostToDevice, ws->stream));
+                    set_packed_plan(ra, plan);
+                    ra.n_reads = c.n_seqs;
                     ra.read_len = max_len;
-                    ra.read_lens = nullptr;
-                    ra.read_starts = nullptr;
                     ra.read_offsets = ws->batch_offsets;
-                    ra.wamb = nullptr;
-                    ra.wamb_dwords = 0;
                     ra.out = a.out;
-                    ra.use_ticket = (ws->force_ticket || mm::mm_env("MM_FORCE_TICKET")) ? 1 : 0;
-                    ra.timing_start = ra.timing_stop = nullptr;
+                    ra.use_ticket = use_ticket(ws);
                     MM_HIP(hipMemsetAsync(ws->total, 0, 2 * sizeof(unsigned long long), ws->stream));
                     const mm::SegSource src{ws->seg_starts, ws->seg_lens, 0, max_len};
                     r = run_lane_table(ws, ra, src, total_bases);
                     if (r < 0) return r;
                     if (r == 0) {
-                        MM_HIP(hipMemcpyAsync(ws->h_batch, ws->batch_offsets, (n_seqs + 1) * sizeof(unsigned long long),
+                        MM_HIP(hipMemcpyAsync(ws->h_batch, ws->batch_offsets, (c.n_seqs + 1) * sizeof(unsigned long long),
                                               hipMemcpyDeviceToHost, ws->stream));
                         MM_HIP(hipMemcpyAsync(ws->h_total, ws->total, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ws->stream));
                         bi->launched = true;
@@ -1558,16 +1640,16 @@ static int batch_issue(const mm_plan_t *plan, mm_workspace_t *ws, uint64_t n_seq
         // the tile table (mm_fused.hip): whole tiles per sequence, lanes sized for whole rounds of resident
         // workgroups or - long batches - default lanes and a tapered last round
         uint32_t nb = 0;
-        if (!mm::fused_batch_tiles(a, nws.data(), n_seqs, tile_seq, &nb)) return MM_BATCH_FALLBACK;
+        if (!mm::fused_batch_tiles(a, nws.data(), c.n_seqs, tile_seq, &nb)) return MM_BATCH_FALLBACK;
         a.nblk = nb;
     }
-    for (uint64_t s = 0; s < n_seqs; ++s) {
+    for (uint64_t s = 0; s < c.n_seqs; ++s) {
         const uint64_t nw = nws[s];
         mm::BatchSeq &b = seqs[s];
         if (nw == 0) continue;
-        if (!d_packed[s]) return MM_ERR_NULL;
+        if (!c.d_packed[s]) return MM_ERR_NULL;
         mm::SeqView v;
-        int r = make_view(d_packed[s], packed_bytes[s], base_offsets ? base_offsets[s] : 0, n_bases[s], &v);
+        int r = make_view(c.d_packed[s], c.packed_bytes[s], c.base_offsets ? c.base_offsets[s] : 0, c.n_bases[s], &v);
         if (r) return r;
         b.d = v.d;
         b.n_dwords = v.n_dwords;
@@ -1576,21 +1658,15 @@ static int batch_issue(const mm_plan_t *plan, mm_workspace_t *ws, uint64_t n_seq
     }
     const uint64_t n_tiles = tile_seq.size();
     if (n_tiles == 0) return MM_OK;  // (launched stays false: every offset is 0)
-    int r = grow(ws->batch_seqs, ws->batch_seqs_n, n_seqs, sizeof(mm::BatchSeq));
+    int r = grow(ws->batch_seqs, ws->batch_seqs_n, c.n_seqs, sizeof(mm::BatchSeq));
     if (r) return r;
     r = grow(ws->batch_tiles, ws->batch_tiles_n, n_tiles, sizeof(mm::BatchTile));
     if (r) return r;
-    r = grow(ws->batch_offsets, ws->batch_offsets_n, n_seqs + 1, sizeof(unsigned long long));
+    r = grow(ws->batch_offsets, ws->batch_offsets_n, c.n_seqs + 1, sizeof(unsigned long long));
     if (r) return r;
-    if (ws->h_batch_n < n_seqs + 1) {  // page-locked landing buffer of the offsets (a pageable one would make the copy block)
-        if (ws->h_batch) hipHostFree(ws->h_batch);
-        ws->h_batch = nullptr;
-        ws->h_batch_n = 0;
-        const uint64_t want = (n_seqs + 1) * 2;
-        MM_HIP(hipHostMalloc(reinterpret_cast<void **>(&ws->h_batch), want * sizeof(unsigned long long), hipHostMallocDefault));
-        ws->h_batch_n = want;
-    }
-    MM_HIP(hipMemcpyAsync(ws->batch_seqs, seqs.data(), n_seqs * sizeof(mm::BatchSeq), hipMemcpyHostToDevice,
+    r = grow_h_batch(ws, c.n_seqs + 1);
+    if (r) return r;
+    MM_HIP(hipMemcpyAsync(ws->batch_seqs, seqs.data(), c.n_seqs * sizeof(mm::BatchSeq), hipMemcpyHostToDevice,
                           ws->stream));
     MM_HIP(hipMemcpyAsync(ws->batch_tiles, tile_seq.data(), n_tiles * sizeof(mm::BatchTile), hipMemcpyHostToDevice,
                           ws->stream));
@@ -1602,30 +1678,19 @@ static int batch_issue(const mm_plan_t *plan, mm_workspace_t *ws, uint64_t n_seq
     if (r) return r;
     a.out.status = ws->status;
     a.status_avail = ws->status_words;
-    a.use_ticket = (ws->force_ticket || mm::mm_env("MM_FORCE_TICKET")) ? 1 : 0;
-    a.timing_start = a.timing_stop = nullptr;
+    a.use_ticket = use_ticket(ws);
     r = next_status_epoch(ws, &a.status_epoch);
     if (r) return r;
     MM_HIP(hipMemsetAsync(ws->total, 0, 2 * sizeof(unsigned long long), ws->stream));
-    MM_HIP(hipMemsetAsync(ws->batch_offsets, 0xFF, (n_seqs + 1) * sizeof(unsigned long long), ws->stream));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (ws->timing) {
-        MM_HIP(hipEventCreate(&e0));
-        MM_HIP(hipEventCreate(&e1));
-        a.timing_start = e0;
-        a.timing_stop = e1;
-    }
+    MM_HIP(hipMemsetAsync(ws->batch_offsets, 0xFF, (c.n_seqs + 1) * sizeof(unsigned long long), ws->stream));
+    TimedLaunch timed(ws);
+    r = timed.arm(a);
+    if (r) return r;
     const int lr = mm::launch_fused(a, ws->stream);
-    if (lr != 0) {
-        if (e0) hipEventDestroy(e0);
-        if (e1) hipEventDestroy(e1);
-        if (lr == -2) return MM_BATCH_FALLBACK;
-        g_last_error = std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError());
-        return MM_ERR_HIP;
-    }
-    if (ws->timing) ws->events.emplace_back(e0, e1);
-    ws->last_path = MM_PATH_FUSED;
-    MM_HIP(hipMemcpyAsync(ws->h_batch, ws->batch_offsets, (n_seqs + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+    if (lr == -2) return MM_BATCH_FALLBACK;
+    if (lr != 0) return launch_failed();
+    timed.done(MM_PATH_FUSED);
+    MM_HIP(hipMemcpyAsync(ws->h_batch, ws->batch_offsets, (c.n_seqs + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost,
                           ws->stream));
     MM_HIP(hipMemcpyAsync(ws->h_total, ws->total, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ws->stream));
     bi->launched = true;
@@ -1658,16 +1723,12 @@ static int batch_finish(mm_workspace_t *ws, BatchIssue *bi, bool has_pos, uint64
     return MM_OK;
 }
 
-static int run_batch_one_launch(const mm_plan_t *plan, mm_workspace_t *ws, uint64_t n_seqs,
-                                const void *const *d_packed, const uint64_t *packed_bytes,
-                                const uint64_t *base_offsets, const uint64_t *n_bases,
-                                uint32_t *d_out_pos, uint32_t *d_out_sk, uint64_t capacity,
-                                uint64_t *out_offsets) {
+static int run_batch_one_launch(const mm_plan_t *plan, mm_workspace_t *ws, const BatchCall &c, uint64_t *out_offsets) {
     BatchIssue bi;
     for (int attempt = 0; attempt < 2; ++attempt) {
-        int r = batch_issue(plan, ws, n_seqs, d_packed, packed_bytes, base_offsets, n_bases, d_out_pos, d_out_sk, capacity, &bi);
+        int r = batch_issue(plan, ws, c, &bi);
         if (r) return r;
-        r = batch_finish(ws, &bi, d_out_pos != nullptr, capacity, out_offsets);
+        r = batch_finish(ws, &bi, c.d_out_pos != nullptr, c.capacity, out_offsets);
         if (r != MM_BATCH_REDO) return r;
     }
     g_last_error = "look-back scan timed out in ticket mode";
@@ -1685,8 +1746,9 @@ int mm_run_batch_device(const mm_plan_t *plan, mm_workspace_t *ws, uint64_t n_se
     if (n_seqs && (!d_packed || !packed_bytes || !n_bases)) return MM_ERR_NULL;
     MM_HIP(set_device(ws->device));
     {
-        int r = run_batch_one_launch(plan, ws, n_seqs, d_packed, packed_bytes, base_offsets, n_bases,
-                                     d_out_pos, d_out_sk, capacity, out_offsets);
+        int r = run_batch_one_launch(plan, ws, {.n_seqs = n_seqs, .d_packed = d_packed, .packed_bytes = packed_bytes,
+                                                .base_offsets = base_offsets, .n_bases = n_bases, .d_out_pos = d_out_pos,
+                                                .d_out_sk = d_out_sk, .capacity = capacity}, out_offsets);
         if (r != MM_BATCH_FALLBACK) return r;
     }
     for (int attempt = 0; attempt < 2; ++attempt) {
@@ -1698,9 +1760,10 @@ int mm_run_batch_device(const mm_plan_t *plan, mm_workspace_t *ws, uint64_t n_se
         // (the runs below do not clear the per-run error word themselves)
         if (hipMemsetAsync(ws->total, 0, 2 * sizeof(unsigned long long), ws->stream) != hipSuccess) r = MM_ERR_HIP;
         for (uint64_t s = 0; s < n_seqs && r == MM_OK; ++s) {
-            r = run_device_async_impl(plan, ws, d_packed[s], packed_bytes[s],
-                                      base_offsets ? base_offsets[s] : 0, n_bases[s], 0, UINT64_MAX,
-                                      d_out_pos, d_out_sk, capacity, nullptr, s != 0);
+            r = run_device_async_impl(plan, ws, {.d_packed = d_packed[s], .packed_bytes = packed_bytes[s],
+                                                 .base_offset = base_offsets ? base_offsets[s] : 0, .n_bases = n_bases[s],
+                                                 .win_end = UINT64_MAX, .d_out_pos = d_out_pos, .d_out_sk = d_out_sk,
+                                                 .capacity = capacity, .append = s != 0});
             if (r == MM_OK &&
                 hipMemcpyAsync(&h[s + 1], ws->total, sizeof(unsigned long long), hipMemcpyDeviceToHost,
                                ws->stream) != hipSuccess)
@@ -1728,73 +1791,55 @@ int mm_run_batch_device(const mm_plan_t *plan, mm_workspace_t *ws, uint64_t n_se
 // Fast path: the reads-mode fused kernel (one lane per read, one launch; prebuilt for minimizers,
 // specialised at first use for the syncmer modes and other w).  Anything it cannot take (w > 128,
 // reads too long for the LDS lists) runs one launch per read on the same stream: slower, same results.
-static int run_reads_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
-                                uint64_t packed_bytes, uint64_t base_offset, uint64_t n_reads,
-                                uint32_t read_stride, uint32_t read_len, const uint32_t *d_read_lens,
-                                uint32_t *d_out_pos, uint64_t capacity, uint64_t *d_out_offsets,
-                                uint64_t *d_count, const AmbArgs *amb = nullptr, uint32_t *d_out_sk = nullptr,
-                                const uint64_t *d_read_starts = nullptr, uint64_t total_bases = 0) {
-    // d_read_starts (round 4): reads packed back to back, read r = bases [starts[r], starts[r + 1]) of the buffer
-    // (n_reads + 1 device entries; total_bases = starts[n_reads], which the caller knows from the packer's counts);
-    // read_len is then the longest read to expect (longer ones are cut to it), read_stride is not used.
-    if (!plan || !ws || !d_out_offsets) return MM_ERR_NULL;
-    if (n_reads >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
+static int run_reads_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, const ReadsCall &c) {
+    uint32_t *d_out_sk = c.d_out_sk;
+    uint64_t capacity = c.capacity;
+    if (!plan || !ws || !c.d_out_offsets) return MM_ERR_NULL;
+    if (c.n_reads >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
     // (back-to-back reads WITH ambiguity bits: mm_run_packed_reads_skip_ambiguous_* - bit j of the span belongs to base j)
-    if (d_read_starts && d_read_lens) return MM_ERR_BAD_MODE;
-    if (amb && !plan->canonical_windows) return MM_ERR_HASHER_NOT_CANONICAL;
+    if (c.d_read_starts && c.d_read_lens) return MM_ERR_BAD_MODE;
+    if (c.amb && !plan->canonical_windows) return MM_ERR_HASHER_NOT_CANONICAL;
     if (d_out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;  // src/lib.rs:339
-    if (d_out_sk && amb) return MM_ERR_BAD_MODE;  // the reference has no skip-ambiguous super-k-mer run
-    if (!d_out_pos) {
+    if (d_out_sk && c.amb) return MM_ERR_BAD_MODE;  // the reference has no skip-ambiguous super-k-mer run
+    if (!c.d_out_pos) {
         capacity = 0;
         d_out_sk = nullptr;
     }
     MM_HIP(set_device(ws->device));
     MM_HIP(hipMemsetAsync(ws->total, 0, 2 * sizeof(unsigned long long), ws->stream));
-    if (n_reads == 0 || read_len == 0) {
-        MM_HIP(hipMemsetAsync(d_out_offsets, 0, (n_reads + 1) * sizeof(uint64_t), ws->stream));
-        if (d_count) MM_HIP(hipMemsetAsync(d_count, 0, sizeof(uint64_t), ws->stream));
+    if (c.n_reads == 0 || c.read_len == 0) {
+        MM_HIP(hipMemsetAsync(c.d_out_offsets, 0, (c.n_reads + 1) * sizeof(uint64_t), ws->stream));
+        if (c.d_count) MM_HIP(hipMemsetAsync(c.d_count, 0, sizeof(uint64_t), ws->stream));
         return MM_OK;
     }
-    if (!d_packed) return MM_ERR_NULL;
-    const uint64_t span = d_read_starts ? total_bases : (n_reads - 1) * (uint64_t)read_stride + read_len;
+    if (!c.d_packed) return MM_ERR_NULL;
+    const uint64_t span = c.d_read_starts ? c.total_bases : (c.n_reads - 1) * (uint64_t)c.read_stride + c.read_len;
     if (span >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
     // bases of all reads together, which bound a lane table's lanes: reads back to back cover their span once, fixed-stride
     // reads may OVERLAP (read_len > read_stride: 5 kbp windows every 1 kbp) and then cover it several times
-    const uint64_t read_bases = d_read_starts ? span : (span > n_reads * (uint64_t)read_len ? span : n_reads * (uint64_t)read_len);
+    const uint64_t read_bases = c.d_read_starts ? span : (span > c.n_reads * (uint64_t)c.read_len ? span : c.n_reads * (uint64_t)c.read_len);
     mm::SeqView view;
-    int r = make_view(d_packed, packed_bytes, base_offset, span, &view);
+    int r = make_view(c.d_packed, c.packed_bytes, c.base_offset, span, &view);
     if (r) return r;
 
     bool fast = !ws->force_generic && mm::fused_reads_supported(plan->w, plan->canonical_windows, (int)plan->ht.canonical,
                                                                 plan->mode, d_out_sk != nullptr);
     ws->last_lane_table = false;  // (also when no reads-mode kernel serves the plan: one launch per read below)
     if (fast) {
-        mm::ReadsArgs a;
+        mm::ReadsArgs a{};
         a.seq = view;
-        a.ht = plan->ht;
-        a.k = plan->k;
-        a.w = plan->w;
-        a.mode = plan->mode;
-        a.canonical_windows = plan->canonical_windows;
-        a.n_reads = n_reads;
-        a.read_stride = read_stride;
-        a.read_len = read_len;
-        a.read_lens = d_read_lens;
-        a.read_starts = reinterpret_cast<const unsigned long long *>(d_read_starts);
-        a.read_offsets = reinterpret_cast<unsigned long long *>(d_out_offsets);
-        a.out.pos = d_out_pos;
-        a.out.sk = d_out_sk;
-        a.out.cap = capacity;
-        a.out.total = ws->total;
-        a.out.ticket = ws->ticket;
-        a.out.error = reinterpret_cast<uint32_t *>(ws->total + 1);
-        a.use_ticket = (ws->force_ticket || mm::mm_env("MM_FORCE_TICKET")) ? 1 : 0;
-        a.timing_start = a.timing_stop = nullptr;
-        a.wamb = nullptr;
-        a.wamb_dwords = 0;
+        set_packed_plan(a, plan);
+        a.n_reads = c.n_reads;
+        a.read_stride = c.read_stride;
+        a.read_len = c.read_len;
+        a.read_lens = c.d_read_lens;
+        a.read_starts = reinterpret_cast<const unsigned long long *>(c.d_read_starts);
+        a.read_offsets = reinterpret_cast<unsigned long long *>(c.d_out_offsets);
+        a.out = out_params(ws, c.d_out_pos, d_out_sk, capacity);
+        a.use_ticket = use_ticket(ws);
         const uint64_t l = (uint64_t)plan->k + plan->w - 1;
-        if (amb && span >= l) {
-            r = prepare_window_ambiguity(ws, *amb, span, (uint32_t)l, 0, span - l + 1, &a.wamb_dwords);
+        if (c.amb && span >= l) {
+            r = prepare_window_ambiguity(ws, *c.amb, span, (uint32_t)l, 0, span - l + 1, &a.wamb_dwords);
             if (r) return r;
             a.wamb = ws->wamb;
         }
@@ -1809,14 +1854,14 @@ static int run_reads_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, const
             // tools/gpu_reads_crossover.py, profiles/r06_reads_crossover.txt: reads of up to 353 windows 0.68 / 0.87 ms one lane
             // each against 0.79 / 1.00 through the table (forward / canonical); up to 481 windows 0.92 / 1.18 against 0.74 / 0.95)
             mm::SegPlan sp;
-            const uint64_t max_nw = read_len >= l ? read_len - l + 1 : 0;
-            const double dens = plan->mode == MM_OPEN_SYNCMERS ? 1.0 / plan->w : (plan->mode == MM_CLOSED_SYNCMERS ? 2.0 / plan->w : 2.0 / (plan->w + 1.0));
+            const uint64_t max_nw = c.read_len >= l ? c.read_len - l + 1 : 0;
+            const double dens = expected_density(plan);
             const uint64_t one_lane = (uint64_t)((48.0 * 1024.0 / 516.0 - 8.0) / (1.3 * dens));
             lanes = mm::fused_segments_plan(a, read_bases, ws->nblk, &sp) == 0 && max_nw > (sp.S > one_lane ? sp.S : one_lane);
         }
         int lr = -3;
         if (lanes) {
-            const mm::SegSource src{a.read_starts, a.read_starts ? nullptr : d_read_lens, read_stride, read_len};
+            const mm::SegSource src{a.read_starts, a.read_starts ? nullptr : c.d_read_lens, c.read_stride, c.read_len};
             r = run_lane_table(ws, a, src, read_bases);
             if (r < 0) return r;
             lr = r == 0 ? 0 : -3;
@@ -1827,28 +1872,18 @@ static int run_reads_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, const
             a.out.status = ws->status;
             r = next_status_epoch(ws, &a.status_epoch);
             if (r) return r;
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            a.timing_start = a.timing_stop = nullptr;
-            if (ws->timing) {
-                MM_HIP(hipEventCreate(&e0));
-                MM_HIP(hipEventCreate(&e1));
-                a.timing_start = e0;
-                a.timing_stop = e1;
-            }
+            TimedLaunch timed(ws);
+            r = timed.arm(a);
+            if (r) return r;
             lr = mm::launch_fused_reads(a, ws->stream);
             if (lr == 0) {
-                if (ws->timing) ws->events.emplace_back(e0, e1);
-                ws->last_path = MM_PATH_FUSED;
+                timed.done(MM_PATH_FUSED);
             } else {
-                if (e0) hipEventDestroy(e0);
-                if (e1) hipEventDestroy(e1);
-                if (lr == -1) {
-                    g_last_error = std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError());
-                    return MM_ERR_HIP;
-                }
+                if (lr == -1) return launch_failed();
+                timed.drop();  // (a lane-table launch below times itself)
                 // (reads too long for one lane each and no lane-table launch either - switched off, or no kernel)
                 if (lr == -3 && !lanes && policy != 0) {
-                    const mm::SegSource src{a.read_starts, a.read_starts ? nullptr : d_read_lens, read_stride, read_len};
+                    const mm::SegSource src{a.read_starts, a.read_starts ? nullptr : c.d_read_lens, c.read_stride, c.read_len};
                     r = run_lane_table(ws, a, src, read_bases);
                     if (r < 0) return r;
                     if (r == 0) lr = 0;
@@ -1860,51 +1895,44 @@ static int run_reads_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, const
     if (!fast) {
         std::vector<uint32_t> lens;
         std::vector<uint64_t> starts;
-        if (d_read_starts) {
-            starts.resize(n_reads + 1);
-            MM_HIP(hipMemcpyAsync(starts.data(), d_read_starts, (n_reads + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost,
+        if (c.d_read_starts) {
+            starts.resize(c.n_reads + 1);
+            MM_HIP(hipMemcpyAsync(starts.data(), c.d_read_starts, (c.n_reads + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost,
                                   ws->stream));
             MM_HIP(hipStreamSynchronize(ws->stream));
         }
-        if (d_read_lens) {
-            lens.resize(n_reads);
-            MM_HIP(hipMemcpyAsync(lens.data(), d_read_lens, n_reads * sizeof(uint32_t),
+        if (c.d_read_lens) {
+            lens.resize(c.n_reads);
+            MM_HIP(hipMemcpyAsync(lens.data(), c.d_read_lens, c.n_reads * sizeof(uint32_t),
                                   hipMemcpyDeviceToHost, ws->stream));
             MM_HIP(hipStreamSynchronize(ws->stream));
         }
-        MM_HIP(hipMemsetAsync(d_out_offsets, 0, sizeof(uint64_t), ws->stream));
-        const uint8_t *bytes = static_cast<const uint8_t *>(d_packed);
-        for (uint64_t i = 0; i < n_reads; ++i) {
-            const uint64_t first = base_offset + (d_read_starts ? starts[i] : i * (uint64_t)read_stride);
-            uint64_t len = d_read_lens ? (lens[i] < read_len ? lens[i] : read_len) : read_len;
-            if (d_read_starts) len = starts[i + 1] - starts[i] < read_len ? starts[i + 1] - starts[i] : read_len;
+        MM_HIP(hipMemsetAsync(c.d_out_offsets, 0, sizeof(uint64_t), ws->stream));
+        const uint8_t *bytes = static_cast<const uint8_t *>(c.d_packed);
+        for (uint64_t i = 0; i < c.n_reads; ++i) {
+            const uint64_t first = c.base_offset + (c.d_read_starts ? starts[i] : i * (uint64_t)c.read_stride);
+            uint64_t len = c.d_read_lens ? (lens[i] < c.read_len ? lens[i] : c.read_len) : c.read_len;
+            if (c.d_read_starts) len = starts[i + 1] - starts[i] < c.read_len ? starts[i + 1] - starts[i] : c.read_len;
             AmbArgs ra;
-            if (amb) ra = AmbArgs{amb->d_amb, amb->bytes, amb->bit_offset + (d_read_starts ? starts[i] : i * (uint64_t)read_stride)};
-            r = run_device_async_impl(plan, ws, bytes + first / 4, packed_bytes - first / 4, first % 4, len,
-                                      0, UINT64_MAX, d_out_pos, d_out_sk, capacity, nullptr, i != 0,
-                                      amb ? &ra : nullptr);
+            if (c.amb) ra = AmbArgs{c.amb->d_amb, c.amb->bytes, c.amb->bit_offset + (c.d_read_starts ? starts[i] : i * (uint64_t)c.read_stride)};
+            r = run_device_async_impl(plan, ws, {.d_packed = bytes + first / 4, .packed_bytes = c.packed_bytes - first / 4,
+                                                 .base_offset = first % 4, .n_bases = len, .win_end = UINT64_MAX,
+                                                 .d_out_pos = c.d_out_pos, .d_out_sk = d_out_sk, .capacity = capacity,
+                                                 .append = i != 0, .amb = c.amb ? &ra : nullptr});
             if (r) return r;
-            MM_HIP(hipMemcpyAsync(d_out_offsets + i + 1, ws->total, sizeof(uint64_t),
+            MM_HIP(hipMemcpyAsync(c.d_out_offsets + i + 1, ws->total, sizeof(uint64_t),
                                   hipMemcpyDeviceToDevice, ws->stream));
         }
     }
-    if (d_count)
-        MM_HIP(hipMemcpyAsync(d_count, ws->total, sizeof(unsigned long long), hipMemcpyDeviceToDevice,
+    if (c.d_count)
+        MM_HIP(hipMemcpyAsync(c.d_count, ws->total, sizeof(unsigned long long), hipMemcpyDeviceToDevice,
                               ws->stream));
     return MM_OK;
 }
 
-static int run_reads_sync(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
-                          uint64_t packed_bytes, uint64_t base_offset, uint64_t n_reads,
-                          uint32_t read_stride, uint32_t read_len, const uint32_t *d_read_lens,
-                          uint32_t *d_out_pos, uint64_t capacity, uint64_t *d_out_offsets,
-                          uint64_t *out_count, const AmbArgs *amb, uint32_t *d_out_sk = nullptr,
-                          const uint64_t *d_read_starts = nullptr, uint64_t total_bases = 0) {
-    return run_sync(ws, capacity, d_out_pos != nullptr, out_count, [&](bool *) {
-        return run_reads_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_reads, read_stride, read_len,
-                                    d_read_lens, d_out_pos, capacity, d_out_offsets, nullptr, amb, d_out_sk,
-                                    d_read_starts, total_bases);
-    });
+// (the call's d_count stays null: the count comes back through the workspace's host words)
+static int run_reads_sync(const mm_plan_t *plan, mm_workspace_t *ws, const ReadsCall &c, uint64_t *out_count) {
+    return run_sync(ws, c.capacity, c.d_out_pos != nullptr, out_count, [&](bool *) { return run_reads_async_impl(plan, ws, c); });
 }
 
 // Reads packed back to back (the FASTQ / FASTA packers' layout): read r = bases [d_read_starts[r], d_read_starts[r + 1]).
@@ -1917,8 +1945,10 @@ int mm_run_packed_reads_device_async(const mm_plan_t *plan, mm_workspace_t *ws, 
     if (const int bad = dna_plan_only(plan)) return bad;
     if (!d_read_starts && n_reads) return MM_ERR_NULL;
     if (ws) ws->async_unchecked = true;
-    return run_reads_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_reads, 0, max_read_len, nullptr, d_out_pos,
-                                capacity, d_out_offsets, d_count, nullptr, d_out_sk, d_read_starts, total_bases);
+    return run_reads_async_impl(plan, ws, {.d_packed = d_packed, .packed_bytes = packed_bytes, .base_offset = base_offset,
+                                           .n_reads = n_reads, .read_len = max_read_len, .d_read_starts = d_read_starts,
+                                           .total_bases = total_bases, .d_out_pos = d_out_pos, .d_out_sk = d_out_sk,
+                                           .capacity = capacity, .d_out_offsets = d_out_offsets, .d_count = d_count});
 }
 
 int mm_run_packed_reads_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed, uint64_t packed_bytes,
@@ -1928,8 +1958,10 @@ int mm_run_packed_reads_device(const mm_plan_t *plan, mm_workspace_t *ws, const 
     ApiScope api_scope;  // (restores the calling thread's current device on return)
     if (const int bad = dna_plan_only(plan)) return bad;
     if (!ws || (!d_read_starts && n_reads)) return MM_ERR_NULL;
-    return run_reads_sync(plan, ws, d_packed, packed_bytes, base_offset, n_reads, 0, max_read_len, nullptr, d_out_pos, capacity,
-                          d_out_offsets, out_count, nullptr, d_out_sk, d_read_starts, total_bases);
+    return run_reads_sync(plan, ws, {.d_packed = d_packed, .packed_bytes = packed_bytes, .base_offset = base_offset,
+                                     .n_reads = n_reads, .read_len = max_read_len, .d_read_starts = d_read_starts,
+                                     .total_bases = total_bases, .d_out_pos = d_out_pos, .d_out_sk = d_out_sk,
+                                     .capacity = capacity, .d_out_offsets = d_out_offsets}, out_count);
 }
 
 // Builder::run_skip_ambiguous_windows (src/lib.rs:451-496) per record of a back-to-back buffer: what the *_pack_n packers
@@ -1952,8 +1984,10 @@ int mm_run_packed_reads_skip_ambiguous_device_async(const mm_plan_t *plan, mm_wo
     if (c) return c;
     if (ws) ws->async_unchecked = true;
     const AmbArgs amb{d_amb, amb_bytes, amb_offset};
-    return run_reads_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_reads, 0, max_read_len, nullptr, d_out_pos,
-                                capacity, d_out_offsets, d_count, &amb, nullptr, d_read_starts, total_bases);
+    return run_reads_async_impl(plan, ws, {.d_packed = d_packed, .packed_bytes = packed_bytes, .base_offset = base_offset,
+                                           .n_reads = n_reads, .read_len = max_read_len, .d_read_starts = d_read_starts,
+                                           .total_bases = total_bases, .d_out_pos = d_out_pos, .capacity = capacity,
+                                           .d_out_offsets = d_out_offsets, .d_count = d_count, .amb = &amb});
 }
 
 int mm_run_packed_reads_skip_ambiguous_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
@@ -1966,8 +2000,10 @@ int mm_run_packed_reads_skip_ambiguous_device(const mm_plan_t *plan, mm_workspac
     const int c = packed_reads_skip_check(plan, d_amb, n_reads, d_read_starts);
     if (c) return c;
     const AmbArgs amb{d_amb, amb_bytes, amb_offset};
-    return run_reads_sync(plan, ws, d_packed, packed_bytes, base_offset, n_reads, 0, max_read_len, nullptr, d_out_pos, capacity,
-                          d_out_offsets, out_count, &amb, nullptr, d_read_starts, total_bases);
+    return run_reads_sync(plan, ws, {.d_packed = d_packed, .packed_bytes = packed_bytes, .base_offset = base_offset,
+                                     .n_reads = n_reads, .read_len = max_read_len, .d_read_starts = d_read_starts,
+                                     .total_bases = total_bases, .d_out_pos = d_out_pos, .capacity = capacity,
+                                     .d_out_offsets = d_out_offsets, .amb = &amb}, out_count);
 }
 
 // --------------------------------------------- packed reads, counts on the device
@@ -1980,35 +2016,29 @@ int mm_run_packed_reads_skip_ambiguous_device(const mm_plan_t *plan, mm_workspac
 // of mm_run_packed_reads_device_async given the counts as host arguments and max_read_len = 0xffffffff.
 // The argument checks, before anything is touched, in the documented order; the workspace is looked at for
 // mm_workspace_force_generic and the lane length only, and refused last when it is NULL.
-static int packed_reads_counts_check(const mm_plan_t *plan, const mm_workspace_t *ws, const void *d_packed,
-                                     uint64_t packed_bytes, uint64_t base_offset, uint64_t max_bases, uint64_t max_records,
-                                     const uint64_t *d_read_starts, const uint64_t *d_counts, const uint32_t *d_out_sk,
-                                     const uint64_t *d_out_offsets, const AmbArgs *amb) {
+static int packed_reads_counts_check(const mm_plan_t *plan, const mm_workspace_t *ws, const ReadsCountsCall &c) {
     if (!plan) return MM_ERR_NULL;
     if (plan->text) return MM_ERR_BAD_MODE;  // (a plan of mm_plan_create_text: text entry points only)
-    if (max_bases >= (1ull << 32) || max_records >= (1ull << 31)) return MM_ERR_LEN_TOO_LARGE;
-    if (d_out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;  // src/lib.rs:339
-    if (amb && !plan->canonical_windows) return MM_ERR_HASHER_NOT_CANONICAL;  // src/lib.rs:451
-    if (!d_out_offsets || !d_counts || !d_read_starts || !d_packed || (amb && !amb->d_amb)) return MM_ERR_NULL;
-    if (base_offset > 4 * packed_bytes || max_bases > 4 * packed_bytes - base_offset) return MM_ERR_CAPACITY;
-    if (amb && (amb->bit_offset > 8 * amb->bytes || max_bases > 8 * amb->bytes - amb->bit_offset)) return MM_ERR_CAPACITY;
+    if (c.max_bases >= (1ull << 32) || c.max_records >= (1ull << 31)) return MM_ERR_LEN_TOO_LARGE;
+    if (c.d_out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;  // src/lib.rs:339
+    if (c.amb && !plan->canonical_windows) return MM_ERR_HASHER_NOT_CANONICAL;  // src/lib.rs:451
+    if (!c.d_out_offsets || !c.d_counts || !c.d_read_starts || !c.d_packed || (c.amb && !c.amb->d_amb)) return MM_ERR_NULL;
+    if (c.base_offset > 4 * c.packed_bytes || c.max_bases > 4 * c.packed_bytes - c.base_offset) return MM_ERR_CAPACITY;
+    if (c.amb && (c.amb->bit_offset > 8 * c.amb->bytes || c.max_bases > 8 * c.amb->bytes - c.amb->bit_offset)) return MM_ERR_CAPACITY;
     // a plan without a lane-table launch: the per-read paths need the counts on the host
     const char *why = nullptr;
     if (ws && ws->force_generic) why = "the generic family (mm_workspace_force_generic) runs one launch per read";
-    else if (!mm::fused_reads_supported(plan->w, plan->canonical_windows, (int)plan->ht.canonical, plan->mode, d_out_sk != nullptr))
+    else if (!mm::fused_reads_supported(plan->w, plan->canonical_windows, (int)plan->ht.canonical, plan->mode, c.d_out_sk != nullptr))
         why = "no reads-mode kernel for this plan (w > 128, or MM_JIT=0 and no prebuilt instance)";
     else if (lane_table_policy() == 0) why = "MM_LANE_TABLE=0 switches the lane table off";
     else {
         mm::ReadsArgs a{};
-        a.w = plan->w;
-        a.k = plan->k;
-        a.mode = plan->mode;
-        a.canonical_windows = plan->canonical_windows;
-        a.n_reads = max_records ? max_records : 1;
-        a.out.sk = const_cast<uint32_t *>(d_out_sk);
-        a.wamb = amb ? reinterpret_cast<const uint32_t *>(amb->d_amb) : nullptr;  // (only "is there one" is asked)
+        set_plan(a, plan);  // (the planner asks for sizes only: no tables)
+        a.n_reads = c.max_records ? c.max_records : 1;
+        a.out.sk = const_cast<uint32_t *>(c.d_out_sk);
+        a.wamb = c.amb ? reinterpret_cast<const uint32_t *>(c.amb->d_amb) : nullptr;  // (only "is there one" is asked)
         mm::SegPlan sp;
-        if (mm::fused_segments_plan(a, max_bases, ws ? ws->nblk : 0u, &sp) != 0) why = "no lane length fits this plan";
+        if (mm::fused_segments_plan(a, c.max_bases, ws ? ws->nblk : 0u, &sp) != 0) why = "no lane length fits this plan";
     }
     if (why) {
         g_last_error = std::string("mm_run_packed_reads_counts_device*: ") + why +
@@ -2018,45 +2048,24 @@ static int packed_reads_counts_check(const mm_plan_t *plan, const mm_workspace_t
     return ws ? MM_OK : MM_ERR_NULL;
 }
 
-static int run_reads_counts_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
-                                       uint64_t packed_bytes, uint64_t base_offset, uint64_t max_bases,
-                                       uint64_t max_records, const uint64_t *d_read_starts, const uint64_t *d_counts,
-                                       uint32_t *d_out_pos, uint32_t *d_out_sk, uint64_t capacity, uint64_t *d_out_offsets,
-                                       uint64_t *d_count, const AmbArgs *amb) {
-    int r = packed_reads_counts_check(plan, ws, d_packed, packed_bytes, base_offset, max_bases, max_records, d_read_starts,
-                                      d_counts, d_out_sk, d_out_offsets, amb);
+static int run_reads_counts_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, const ReadsCountsCall &c) {
+    int r = packed_reads_counts_check(plan, ws, c);
     if (r) return r;
-    if (!d_out_pos) {
-        capacity = 0;
-        d_out_sk = nullptr;
-    }
+    const uint64_t max_bases = c.max_bases, max_records = c.max_records;
+    const AmbArgs *const amb = c.amb;
+    uint64_t *const d_count = c.d_count;
     MM_HIP(set_device(ws->device));
-    mm::SeqView view;
-    r = make_view(d_packed, packed_bytes, base_offset, max_bases, &view);
+    mm::ReadsArgs a{};
+    r = make_view(c.d_packed, c.packed_bytes, c.base_offset, max_bases, &a.seq);
     if (r) return r;
-    mm::ReadsArgs a;
-    a.seq = view;
-    a.ht = plan->ht;
-    a.k = plan->k;
-    a.w = plan->w;
-    a.mode = plan->mode;
-    a.canonical_windows = plan->canonical_windows;
+    set_packed_plan(a, plan);
     a.n_reads = max_records ? max_records : 1;  // (what sizes the launch; the walk is given max_records itself)
-    a.read_stride = 0;
     a.read_len = 0xffffffffu;
-    a.read_lens = nullptr;
-    a.read_starts = reinterpret_cast<const unsigned long long *>(d_read_starts);
-    a.read_offsets = reinterpret_cast<unsigned long long *>(d_out_offsets);
-    a.out.pos = d_out_pos;
-    a.out.sk = d_out_sk;
-    a.out.cap = capacity;
-    a.out.total = ws->total;
-    a.out.ticket = ws->ticket;
-    a.out.error = reinterpret_cast<uint32_t *>(ws->total + 1);
-    a.use_ticket = (ws->force_ticket || mm::mm_env("MM_FORCE_TICKET")) ? 1 : 0;
-    a.timing_start = a.timing_stop = nullptr;
-    a.wamb = nullptr;
-    a.wamb_dwords = 0;
+    a.read_starts = reinterpret_cast<const unsigned long long *>(c.d_read_starts);
+    a.read_offsets = reinterpret_cast<unsigned long long *>(c.d_out_offsets);
+    // (no positions asked for: no capacity, no indices)
+    a.out = out_params(ws, c.d_out_pos, c.d_out_pos ? c.d_out_sk : nullptr, c.d_out_pos ? c.capacity : 0);
+    a.use_ticket = use_ticket(ws);
     MM_HIP(hipMemsetAsync(ws->total, 0, 2 * sizeof(unsigned long long), ws->stream));
     const uint64_t l = (uint64_t)plan->k + plan->w - 1;
     if (amb) {
@@ -2075,7 +2084,7 @@ static int run_reads_counts_async_impl(const mm_plan_t *plan, mm_workspace_t *ws
         a.wamb = ws->wamb;
     }
     mm::SegSource src{a.read_starts, nullptr, 0, 0xffffffffu};
-    src.counts = reinterpret_cast<const unsigned long long *>(d_counts);
+    src.counts = reinterpret_cast<const unsigned long long *>(c.d_counts);
     src.max_bases = (uint32_t)max_bases;
     src.max_records = (uint32_t)max_records;
     r = run_lane_table(ws, a, src, max_bases);
@@ -2090,31 +2099,11 @@ static int run_reads_counts_async_impl(const mm_plan_t *plan, mm_workspace_t *ws
     return MM_OK;
 }
 
-static int run_reads_counts_sync(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed, uint64_t packed_bytes,
-                                 uint64_t base_offset, uint64_t max_bases, uint64_t max_records,
-                                 const uint64_t *d_read_starts, const uint64_t *d_counts, uint32_t *d_out_pos,
-                                 uint32_t *d_out_sk, uint64_t capacity, uint64_t *d_out_offsets, uint64_t *out,
-                                 const AmbArgs *amb) {
-    const int rc = packed_reads_counts_check(plan, ws, d_packed, packed_bytes, base_offset, max_bases, max_records,
-                                             d_read_starts, d_counts, d_out_sk, d_out_offsets, amb);
+static int run_reads_counts_sync(const mm_plan_t *plan, mm_workspace_t *ws, const ReadsCountsCall &c, uint64_t *out) {
+    const int rc = packed_reads_counts_check(plan, ws, c);
     if (rc) return rc;
-    if (out) out[0] = out[1] = out[2] = 0;
-    uint64_t count = 0;
-    // (the two counts come back with the run's words: h_total[4..5], one wait for all of them)
-    const int r = run_sync(ws, capacity, d_out_pos != nullptr, &count, [&](bool *) {
-        const int q = run_reads_counts_async_impl(plan, ws, d_packed, packed_bytes, base_offset, max_bases, max_records,
-                                                  d_read_starts, d_counts, d_out_pos, d_out_sk, capacity, d_out_offsets,
-                                                  nullptr, amb);
-        if (q) return q;
-        MM_HIP(hipMemcpyAsync(ws->h_total + 4, d_counts, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
-        return (int)MM_OK;
-    });
-    if (out && (r == MM_OK || r == MM_ERR_CAPACITY)) {
-        out[0] = count;
-        out[1] = ws->h_total[4];
-        out[2] = ws->h_total[5];
-    }
-    return r;
+    return run_counts_sync(ws, c.d_counts, c.capacity, c.d_out_pos != nullptr, out,
+                           [&]() { return run_reads_counts_async_impl(plan, ws, c); });
 }
 
 int mm_run_packed_reads_counts_device_async(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
@@ -2124,8 +2113,11 @@ int mm_run_packed_reads_counts_device_async(const mm_plan_t *plan, mm_workspace_
                                             uint64_t *d_out_offsets, uint64_t *d_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
     if (ws) ws->async_unchecked = true;
-    return run_reads_counts_async_impl(plan, ws, d_packed, packed_bytes, base_offset, max_bases, max_records, d_read_starts,
-                                       d_counts, d_out_pos, d_out_sk, capacity, d_out_offsets, d_count, nullptr);
+    return run_reads_counts_async_impl(plan, ws, {.d_packed = d_packed, .packed_bytes = packed_bytes, .base_offset = base_offset,
+                                                  .max_bases = max_bases, .max_records = max_records,
+                                                  .d_read_starts = d_read_starts, .d_counts = d_counts, .d_out_pos = d_out_pos,
+                                                  .d_out_sk = d_out_sk, .capacity = capacity, .d_out_offsets = d_out_offsets,
+                                                  .d_count = d_count});
 }
 
 int mm_run_packed_reads_counts_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed, uint64_t packed_bytes,
@@ -2133,8 +2125,10 @@ int mm_run_packed_reads_counts_device(const mm_plan_t *plan, mm_workspace_t *ws,
                                       const uint64_t *d_read_starts, const uint64_t *d_counts, uint32_t *d_out_pos,
                                       uint32_t *d_out_sk, uint64_t capacity, uint64_t *d_out_offsets, uint64_t *out) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
-    return run_reads_counts_sync(plan, ws, d_packed, packed_bytes, base_offset, max_bases, max_records, d_read_starts,
-                                 d_counts, d_out_pos, d_out_sk, capacity, d_out_offsets, out, nullptr);
+    return run_reads_counts_sync(plan, ws, {.d_packed = d_packed, .packed_bytes = packed_bytes, .base_offset = base_offset,
+                                            .max_bases = max_bases, .max_records = max_records, .d_read_starts = d_read_starts,
+                                            .d_counts = d_counts, .d_out_pos = d_out_pos, .d_out_sk = d_out_sk,
+                                            .capacity = capacity, .d_out_offsets = d_out_offsets}, out);
 }
 
 // Builder::run_skip_ambiguous_windows (src/lib.rs:451-496) per record with the counts on the device: what the *_pack_n
@@ -2148,8 +2142,11 @@ int mm_run_packed_reads_skip_ambiguous_counts_device_async(const mm_plan_t *plan
     ApiScope api_scope;  // (restores the calling thread's current device on return)
     if (ws) ws->async_unchecked = true;
     const AmbArgs amb{d_amb, amb_bytes, amb_offset};
-    return run_reads_counts_async_impl(plan, ws, d_packed, packed_bytes, base_offset, max_bases, max_records, d_read_starts,
-                                       d_counts, d_out_pos, nullptr, capacity, d_out_offsets, d_count, &amb);
+    return run_reads_counts_async_impl(plan, ws, {.d_packed = d_packed, .packed_bytes = packed_bytes, .base_offset = base_offset,
+                                                  .max_bases = max_bases, .max_records = max_records,
+                                                  .d_read_starts = d_read_starts, .d_counts = d_counts, .d_out_pos = d_out_pos,
+                                                  .capacity = capacity, .d_out_offsets = d_out_offsets, .d_count = d_count,
+                                                  .amb = &amb});
 }
 
 int mm_run_packed_reads_skip_ambiguous_counts_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
@@ -2160,8 +2157,10 @@ int mm_run_packed_reads_skip_ambiguous_counts_device(const mm_plan_t *plan, mm_w
                                                      uint64_t *d_out_offsets, uint64_t *out) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
     const AmbArgs amb{d_amb, amb_bytes, amb_offset};
-    return run_reads_counts_sync(plan, ws, d_packed, packed_bytes, base_offset, max_bases, max_records, d_read_starts,
-                                 d_counts, d_out_pos, nullptr, capacity, d_out_offsets, out, &amb);
+    return run_reads_counts_sync(plan, ws, {.d_packed = d_packed, .packed_bytes = packed_bytes, .base_offset = base_offset,
+                                            .max_bases = max_bases, .max_records = max_records, .d_read_starts = d_read_starts,
+                                            .d_counts = d_counts, .d_out_pos = d_out_pos, .capacity = capacity,
+                                            .d_out_offsets = d_out_offsets, .amb = &amb}, out);
 }
 
 // What the table kernels of the counts calls make of {counts, bounds}, by the function they call (mm_lane_counts.h): no device.
@@ -2183,8 +2182,10 @@ int mm_run_reads_device_async(const mm_plan_t *plan, mm_workspace_t *ws, const v
     ApiScope api_scope;  // (restores the calling thread's current device on return)
     if (const int bad = dna_plan_only(plan)) return bad;
     if (ws) ws->async_unchecked = true;
-    return run_reads_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_reads, read_stride,
-                                read_len, d_read_lens, d_out_pos, capacity, d_out_offsets, d_count);
+    return run_reads_async_impl(plan, ws, {.d_packed = d_packed, .packed_bytes = packed_bytes, .base_offset = base_offset,
+                                           .n_reads = n_reads, .read_stride = read_stride, .read_len = read_len,
+                                           .d_read_lens = d_read_lens, .d_out_pos = d_out_pos, .capacity = capacity,
+                                           .d_out_offsets = d_out_offsets, .d_count = d_count});
 }
 
 int mm_run_reads_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
@@ -2194,8 +2195,10 @@ int mm_run_reads_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d
                         uint64_t *out_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
     if (const int bad = dna_plan_only(plan)) return bad;
-    return run_reads_sync(plan, ws, d_packed, packed_bytes, base_offset, n_reads, read_stride, read_len,
-                          d_read_lens, d_out_pos, capacity, d_out_offsets, out_count, nullptr);
+    return run_reads_sync(plan, ws, {.d_packed = d_packed, .packed_bytes = packed_bytes, .base_offset = base_offset,
+                                     .n_reads = n_reads, .read_stride = read_stride, .read_len = read_len,
+                                     .d_read_lens = d_read_lens, .d_out_pos = d_out_pos, .capacity = capacity,
+                                     .d_out_offsets = d_out_offsets}, out_count);
 }
 
 int mm_run_reads_superkmers_device_async(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
@@ -2207,9 +2210,10 @@ int mm_run_reads_superkmers_device_async(const mm_plan_t *plan, mm_workspace_t *
     if (const int bad = dna_plan_only(plan)) return bad;
     if (ws) ws->async_unchecked = true;
     if (!d_out_sk) return MM_ERR_NULL;
-    return run_reads_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_reads, read_stride,
-                                read_len, d_read_lens, d_out_pos, capacity, d_out_offsets, d_count, nullptr,
-                                d_out_sk);
+    return run_reads_async_impl(plan, ws, {.d_packed = d_packed, .packed_bytes = packed_bytes, .base_offset = base_offset,
+                                           .n_reads = n_reads, .read_stride = read_stride, .read_len = read_len,
+                                           .d_read_lens = d_read_lens, .d_out_pos = d_out_pos, .d_out_sk = d_out_sk,
+                                           .capacity = capacity, .d_out_offsets = d_out_offsets, .d_count = d_count});
 }
 
 int mm_run_reads_superkmers_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
@@ -2220,8 +2224,10 @@ int mm_run_reads_superkmers_device(const mm_plan_t *plan, mm_workspace_t *ws, co
     ApiScope api_scope;  // (restores the calling thread's current device on return)
     if (const int bad = dna_plan_only(plan)) return bad;
     if (!d_out_sk) return MM_ERR_NULL;
-    return run_reads_sync(plan, ws, d_packed, packed_bytes, base_offset, n_reads, read_stride, read_len,
-                          d_read_lens, d_out_pos, capacity, d_out_offsets, out_count, nullptr, d_out_sk);
+    return run_reads_sync(plan, ws, {.d_packed = d_packed, .packed_bytes = packed_bytes, .base_offset = base_offset,
+                                     .n_reads = n_reads, .read_stride = read_stride, .read_len = read_len,
+                                     .d_read_lens = d_read_lens, .d_out_pos = d_out_pos, .d_out_sk = d_out_sk,
+                                     .capacity = capacity, .d_out_offsets = d_out_offsets}, out_count);
 }
 
 int mm_run_reads_skip_ambiguous_device_async(const mm_plan_t *plan, mm_workspace_t *ws,
@@ -2235,8 +2241,10 @@ int mm_run_reads_skip_ambiguous_device_async(const mm_plan_t *plan, mm_workspace
     if (const int bad = dna_plan_only(plan)) return bad;
     if (ws) ws->async_unchecked = true;
     const AmbArgs amb{d_amb, amb_bytes, amb_offset};
-    return run_reads_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_reads, read_stride,
-                                read_len, d_read_lens, d_out_pos, capacity, d_out_offsets, d_count, &amb);
+    return run_reads_async_impl(plan, ws, {.d_packed = d_packed, .packed_bytes = packed_bytes, .base_offset = base_offset,
+                                           .n_reads = n_reads, .read_stride = read_stride, .read_len = read_len,
+                                           .d_read_lens = d_read_lens, .d_out_pos = d_out_pos, .capacity = capacity,
+                                           .d_out_offsets = d_out_offsets, .d_count = d_count, .amb = &amb});
 }
 
 int mm_run_reads_skip_ambiguous_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
@@ -2248,8 +2256,10 @@ int mm_run_reads_skip_ambiguous_device(const mm_plan_t *plan, mm_workspace_t *ws
     ApiScope api_scope;  // (restores the calling thread's current device on return)
     if (const int bad = dna_plan_only(plan)) return bad;
     const AmbArgs amb{d_amb, amb_bytes, amb_offset};
-    return run_reads_sync(plan, ws, d_packed, packed_bytes, base_offset, n_reads, read_stride, read_len,
-                          d_read_lens, d_out_pos, capacity, d_out_offsets, out_count, &amb);
+    return run_reads_sync(plan, ws, {.d_packed = d_packed, .packed_bytes = packed_bytes, .base_offset = base_offset,
+                                     .n_reads = n_reads, .read_stride = read_stride, .read_len = read_len,
+                                     .d_read_lens = d_read_lens, .d_out_pos = d_out_pos, .capacity = capacity,
+                                     .d_out_offsets = d_out_offsets, .amb = &amb}, out_count);
 }
 
 // ---- PackedNSeq: Builder::run_skip_ambiguous_windows (src/lib.rs:451-496)
@@ -2262,26 +2272,26 @@ int mm_run_skip_ambiguous_device_async(const mm_plan_t *plan, mm_workspace_t *ws
     if (const int bad = dna_plan_only(plan)) return bad;
     if (ws) ws->async_unchecked = true;
     const AmbArgs amb{d_amb, amb_bytes, amb_offset};
-    return run_device_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_bases, win_begin,
-                                 win_end, d_out_pos, nullptr, capacity, d_count, false, &amb);
+    return run_device_async_impl(plan, ws, {.d_packed = d_packed, .packed_bytes = packed_bytes, .base_offset = base_offset,
+                                            .n_bases = n_bases, .win_begin = win_begin, .win_end = win_end,
+                                            .d_out_pos = d_out_pos, .capacity = capacity, .d_count = d_count, .amb = &amb});
 }
 
-static int run_device_sync(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
-                           uint64_t packed_bytes, uint64_t base_offset, uint64_t n_bases,
-                           uint64_t win_begin, uint64_t win_end, uint32_t *d_out_pos, uint32_t *d_out_sk,
-                           uint64_t capacity, uint64_t *out_count, const AmbArgs *amb) {
+// (the call's d_count, append and host words are not the caller's to set here)
+static int run_device_sync(const mm_plan_t *plan, mm_workspace_t *ws, const SeqCall &c, uint64_t *out_count) {
     // One stream operation per call when the fused kernel runs: its last tile stores the total straight into the
     // page-locked word h_total[0] and a tile that raises an error stores the code into h_total[1] (flag_error),
     // so the host only waits for the stream.  (Rounds 1-3: two clears, the kernel, a copy - about 33 us a call.)
     // The split path, the generic family and empty runs leave host_written false: the device words, cleared by the
     // run itself, are copied.
-    return run_sync(ws, capacity, d_out_pos != nullptr, out_count, [&](bool *host_written) -> int {
+    return run_sync(ws, c.capacity, c.d_out_pos != nullptr, out_count, [&](bool *host_written) -> int {
         ws->h_total[0] = 0;
         ws->h_total[1] = 0;
         // (no mapped host words on this runtime: the device's error word is read back, so clear it first)
         if (!ws->h_total_dev) MM_HIP(hipMemsetAsync(ws->total + 1, 0, sizeof(unsigned long long), ws->stream));
-        return run_device_async_impl(plan, ws, d_packed, packed_bytes, base_offset, n_bases, win_begin, win_end,
-                                     d_out_pos, d_out_sk, capacity, nullptr, false, amb, host_written);
+        SeqCall run = c;
+        run.host_total_written = host_written;
+        return run_device_async_impl(plan, ws, run);
     });
 }
 
@@ -2293,8 +2303,9 @@ int mm_run_skip_ambiguous_device(const mm_plan_t *plan, mm_workspace_t *ws, cons
     ApiScope api_scope;  // (restores the calling thread's current device on return)
     if (const int bad = dna_plan_only(plan)) return bad;
     const AmbArgs amb{d_amb, amb_bytes, amb_offset};
-    return run_device_sync(plan, ws, d_packed, packed_bytes, base_offset, n_bases, win_begin, win_end,
-                           d_out_pos, nullptr, capacity, out_count, &amb);
+    return run_device_sync(plan, ws, {.d_packed = d_packed, .packed_bytes = packed_bytes, .base_offset = base_offset,
+                                      .n_bases = n_bases, .win_begin = win_begin, .win_end = win_end, .d_out_pos = d_out_pos,
+                                      .capacity = capacity, .amb = &amb}, out_count);
 }
 
 int mm_run_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
@@ -2303,25 +2314,35 @@ int mm_run_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packe
                   uint64_t capacity, uint64_t *out_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
     if (const int bad = dna_plan_only(plan)) return bad;
-    return run_device_sync(plan, ws, d_packed, packed_bytes, base_offset, n_bases, win_begin, win_end,
-                           d_out_pos, d_out_sk, capacity, out_count, nullptr);
+    return run_device_sync(plan, ws, {.d_packed = d_packed, .packed_bytes = packed_bytes, .base_offset = base_offset,
+                                      .n_bases = n_bases, .win_begin = win_begin, .win_end = win_end, .d_out_pos = d_out_pos,
+                                      .d_out_sk = d_out_sk, .capacity = capacity}, out_count);
 }
 
-static int run_host_common(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed,
-                           uint64_t packed_bytes, uint64_t base_offset, uint64_t n_bases,
-                           uint32_t *out_pos, uint32_t *out_sk, uint64_t capacity,
-                           uint64_t *out_count, const AmbArgs *amb = nullptr) {
+// What a host entry point asks for: the sequence (packed bytes on the host, or already staged on the device) and the
+// caller's HOST buffers for positions, indices and the count.
+struct HostCall {
+    const void *packed;
+    uint64_t packed_bytes, base_offset, n_bases;
+    uint32_t *out_pos, *out_sk;
+    uint64_t capacity;
+    uint64_t *out_count;
+};
+
+// (c.packed: the staged bytes on the device)
+static int run_host_common(const mm_plan_t *plan, mm_workspace_t *ws, const HostCall &c, const AmbArgs *amb) {
     const uint64_t l = (uint64_t)plan->k + plan->w - 1;
-    const uint64_t n_w = n_bases >= l ? n_bases - l + 1 : 0;
-    const uint64_t cap = capped(out_pos, capacity, n_w);
-    int r = stage_outputs(ws, cap, out_sk != nullptr);
+    const uint64_t n_w = c.n_bases >= l ? c.n_bases - l + 1 : 0;
+    const uint64_t cap = capped(c.out_pos, c.capacity, n_w);
+    int r = stage_outputs(ws, cap, c.out_sk != nullptr);
     if (r) return r;
     uint64_t count = 0;
-    r = run_device_sync(plan, ws, d_packed, packed_bytes, base_offset, n_bases, 0, UINT64_MAX,
-                        cap ? ws->d_out : nullptr, (out_sk && cap) ? ws->d_sk : nullptr, cap, &count, amb);
-    if (out_count) *out_count = count;
+    r = run_device_sync(plan, ws, {.d_packed = c.packed, .packed_bytes = c.packed_bytes, .base_offset = c.base_offset,
+                                   .n_bases = c.n_bases, .win_end = UINT64_MAX, .d_out_pos = cap ? ws->d_out : nullptr,
+                                   .d_out_sk = (c.out_sk && cap) ? ws->d_sk : nullptr, .capacity = cap, .amb = amb}, &count);
+    if (c.out_count) *c.out_count = count;
     if (r) return r;
-    return download_positions(ws, out_pos, out_sk, count);
+    return download_positions(ws, c.out_pos, c.out_sk, count, nullptr, 0);
 }
 
 // Host entry point for long sequences, pipelined: the window range is cut into chunks; while chunk c is computed,
@@ -2360,9 +2381,11 @@ static void *device_alias_of_host(const void *p) {
     return at.devicePointer;
 }
 
-static int run_host_pipelined(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *packed,
-                              uint64_t base_offset, uint64_t n_bases, uint32_t *out_pos, uint32_t *out_sk,
-                              uint64_t capacity, uint64_t *out_count) {
+static int run_host_pipelined(const mm_plan_t *plan, mm_workspace_t *ws, const HostCall &call) {
+    const uint8_t *const packed = static_cast<const uint8_t *>(call.packed);
+    const uint64_t base_offset = call.base_offset, n_bases = call.n_bases, capacity = call.capacity;
+    uint32_t *const out_pos = call.out_pos, *const out_sk = call.out_sk;
+    uint64_t *const out_count = call.out_count;
     const uint64_t l = (uint64_t)plan->k + plan->w - 1;
     const uint64_t n_w = n_bases >= l ? n_bases - l + 1 : 0;
     if (!out_pos || n_w < kPipeMinWindows || mm::mm_env("MM_NO_PIPELINE") || !ws->h_total_dev) return MM_PIPE_FALLBACK;
@@ -2469,9 +2492,11 @@ static int run_host_pipelined(const mm_plan_t *plan, mm_workspace_t *ws, const u
         MM_HIP(hipEventRecord(ws->ev_in[c], ws->copy_in));
         MM_HIP(hipStreamWaitEvent(ws->stream, ws->ev_in[c], 0));
         bool hw = false;
-        const int rr = run_device_async_impl(plan, ws, ws->d_in, bytes + 16, base_offset, n_bases, wb, we, k_pos, k_sk, cap,
-                                             out_mode == 1 ? reinterpret_cast<uint64_t *>(ws->d_pipe + c + 1) : nullptr, c != 0,
-                                             nullptr, &hw, ws->h_pipe_dev + c);
+        const int rr = run_device_async_impl(
+            plan, ws, {.d_packed = ws->d_in, .packed_bytes = bytes + 16, .base_offset = base_offset, .n_bases = n_bases,
+                       .win_begin = wb, .win_end = we, .d_out_pos = k_pos, .d_out_sk = k_sk, .capacity = cap,
+                       .d_count = out_mode == 1 ? reinterpret_cast<uint64_t *>(ws->d_pipe + c + 1) : nullptr, .append = c != 0,
+                       .host_total_written = &hw, .host_word_dev = ws->h_pipe_dev + c});
         if (rr) return rr;
         // (families whose kernels do not store the total themselves: the device word, copied)
         if (!hw)
@@ -2634,8 +2659,11 @@ static const int MM_SMALL_NOT_TAKEN = 1;  // (run_host_small's answer to a call 
 static const uint64_t kSmallBases = 64ull << 10;
 static const uint64_t kSmallInBytes = (kSmallBases + 3) / 4 + 64;                 // bytes in, with room for a base offset
 static const uint64_t kSmallOutElems = kSmallBases;                               // at most one position per window
-static int run_host_small(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *packed, uint64_t base_offset,
-                          uint64_t n_bases, uint32_t *out_pos, uint32_t *out_sk, uint64_t capacity, uint64_t *out_count) {
+static int run_host_small(const mm_plan_t *plan, mm_workspace_t *ws, const HostCall &c) {
+    const uint8_t *const packed = static_cast<const uint8_t *>(c.packed);
+    const uint64_t base_offset = c.base_offset, n_bases = c.n_bases, capacity = c.capacity;
+    uint32_t *const out_pos = c.out_pos, *const out_sk = c.out_sk;
+    uint64_t *const out_count = c.out_count;
     const uint64_t bytes = (base_offset + n_bases + 3) / 4;
     if (!ws->h_total_dev || n_bases > kSmallBases || bytes + 16 > kSmallInBytes || mm::mm_env("MM_NO_SMALL_HOST")) return MM_SMALL_NOT_TAKEN;
     const uint64_t in_room = (kSmallInBytes + 255) & ~255ull;
@@ -2660,8 +2688,9 @@ static int run_host_small(const mm_plan_t *plan, mm_workspace_t *ws, const uint8
     uint32_t *h_pos = reinterpret_cast<uint32_t *>(ws->h_small + in_room), *h_sk = h_pos + kSmallOutElems;
     uint32_t *d_pos = reinterpret_cast<uint32_t *>(ws->h_small_dev + in_room), *d_sk = d_pos + kSmallOutElems;
     uint64_t count = 0;
-    const int r = run_device_sync(plan, ws, ws->h_small_dev, bytes + 16, base_offset, n_bases, 0, UINT64_MAX, cap ? d_pos : nullptr,
-                                  (out_sk && cap) ? d_sk : nullptr, cap, &count, nullptr);
+    const int r = run_device_sync(plan, ws, {.d_packed = ws->h_small_dev, .packed_bytes = bytes + 16, .base_offset = base_offset,
+                                             .n_bases = n_bases, .win_end = UINT64_MAX, .d_out_pos = cap ? d_pos : nullptr,
+                                             .d_out_sk = (out_sk && cap) ? d_sk : nullptr, .capacity = cap}, &count);
     if (out_count) *out_count = count;
     if (r) return r;
     if (out_pos && count) {
@@ -2682,27 +2711,42 @@ int mm_run_host(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *packed
     MM_HIP(set_device(ws->device));
     const uint64_t bytes = (base_offset + n_bases + 3) / 4;
     if (bytes && !packed) return MM_ERR_NULL;
+    HostCall c{.packed = packed, .packed_bytes = bytes, .base_offset = base_offset, .n_bases = n_bases, .out_pos = out_pos,
+               .out_sk = out_sk, .capacity = capacity, .out_count = out_count};
     {
-        const int rs = run_host_small(plan, ws, packed, base_offset, n_bases, out_pos, out_sk, capacity, out_count);
+        const int rs = run_host_small(plan, ws, c);
         if (rs != MM_SMALL_NOT_TAKEN) return rs;
     }
     int r = grow_bytes(ws->d_in, ws->d_in_bytes, bytes + 16);
     if (r) return r;
     if (bytes) {
         if (!packed) return MM_ERR_NULL;
-        r = run_host_pipelined(plan, ws, packed, base_offset, n_bases, out_pos, out_sk, capacity, out_count);
+        r = run_host_pipelined(plan, ws, c);
         if (r != MM_PIPE_FALLBACK) return r;
         MM_HIP(hipMemcpyAsync(ws->d_in, packed, bytes, hipMemcpyHostToDevice, ws->stream));
     }
-    return run_host_common(plan, ws, ws->d_in, bytes + 16, base_offset, n_bases, out_pos, out_sk,
-                           capacity, out_count);
+    c.packed = ws->d_in;  // (staged, with the slack the kernels may touch)
+    c.packed_bytes = bytes + 16;
+    return run_host_common(plan, ws, c, nullptr);
 }
 
 // The staging of both packed-reads host entry points, behind their own argument checks: [packed bytes + slack | starts] in
 // d_in, the ambiguity bits (amb != null: PackedNSeq reads) in d_amb, positions (and indices) in d_out / d_sk, offsets in d_vals.
-static int packed_reads_host_impl(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *packed, const uint8_t *amb,
-                                  uint64_t n_reads, const uint64_t *read_starts, uint32_t max_read_len, uint32_t *out_pos,
-                                  uint32_t *out_sk, uint64_t capacity, uint64_t *out_offsets, uint64_t *out_count) {
+struct PackedReadsHostCall {
+    const uint8_t *packed, *amb;
+    uint64_t n_reads;
+    const uint64_t *read_starts;
+    uint32_t max_read_len;
+    uint32_t *out_pos, *out_sk;
+    uint64_t capacity;
+    uint64_t *out_offsets, *out_count;
+};
+static int packed_reads_host_impl(const mm_plan_t *plan, mm_workspace_t *ws, const PackedReadsHostCall &c) {
+    const uint8_t *const packed = c.packed, *const amb = c.amb;
+    const uint64_t n_reads = c.n_reads;
+    const uint64_t *const read_starts = c.read_starts;
+    uint32_t *const out_pos = c.out_pos, *const out_sk = c.out_sk;
+    uint64_t *const out_count = c.out_count;
     if (out_count) *out_count = 0;
     MM_HIP(set_device(ws->device));
     const uint64_t total_bases = n_reads ? read_starts[n_reads] : 0;
@@ -2714,7 +2758,7 @@ static int packed_reads_host_impl(const mm_plan_t *plan, mm_workspace_t *ws, con
     int r = grow_bytes(ws->d_in, ws->d_in_bytes, starts_at + (n_reads + 1) * sizeof(uint64_t));
     if (r == MM_OK && amb) r = grow_bytes(ws->d_amb, ws->d_amb_bytes, abytes + 16);
     if (r) return r;
-    const uint64_t cap = capped(out_pos, capacity, total_bases);
+    const uint64_t cap = capped(out_pos, c.capacity, total_bases);
     r = stage_outputs(ws, cap, out_sk != nullptr);
     if (r == MM_OK) r = grow(ws->d_vals, ws->d_vals_elems, n_reads + 1, sizeof(unsigned long long));
     if (r) return r;
@@ -2728,12 +2772,14 @@ static int packed_reads_host_impl(const mm_plan_t *plan, mm_workspace_t *ws, con
     if (n_reads) MM_HIP(hipMemcpyAsync(din + starts_at, read_starts, (n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ws->stream));
     const AmbArgs a{damb, abytes + 16, 0};
     uint64_t count = 0;
-    r = run_reads_sync(plan, ws, din, starts_at, 0, n_reads, 0, max_read_len, nullptr, cap ? ws->d_out : nullptr, cap,
-                       reinterpret_cast<uint64_t *>(ws->d_vals), &count, amb ? &a : nullptr, (out_sk && cap) ? ws->d_sk : nullptr,
-                       reinterpret_cast<const uint64_t *>(din + starts_at), total_bases);
+    r = run_reads_sync(plan, ws, {.d_packed = din, .packed_bytes = starts_at, .n_reads = n_reads, .read_len = c.max_read_len,
+                                  .d_read_starts = reinterpret_cast<const uint64_t *>(din + starts_at), .total_bases = total_bases,
+                                  .d_out_pos = cap ? ws->d_out : nullptr, .d_out_sk = (out_sk && cap) ? ws->d_sk : nullptr,
+                                  .capacity = cap, .d_out_offsets = reinterpret_cast<uint64_t *>(ws->d_vals),
+                                  .amb = amb ? &a : nullptr}, &count);
     if (out_count) *out_count = count;
     if (r) return r;
-    return download_positions(ws, out_pos, out_sk, count, out_offsets, n_reads + 1);
+    return download_positions(ws, out_pos, out_sk, count, c.out_offsets, n_reads + 1);
 }
 
 // Many short sequences from HOST memory in one call (round 4): what a caller that looped Builder::run over its reads
@@ -2747,8 +2793,9 @@ int mm_run_packed_reads_host(const mm_plan_t *plan, mm_workspace_t *ws, const ui
     if (!plan || !ws || !out_offsets) return MM_ERR_NULL;
     if (n_reads && (!read_starts || !packed)) return MM_ERR_NULL;
     if (out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;
-    return packed_reads_host_impl(plan, ws, packed, nullptr, n_reads, read_starts, max_read_len, out_pos, out_sk, capacity,
-                                  out_offsets, out_count);
+    return packed_reads_host_impl(plan, ws, {.packed = packed, .n_reads = n_reads, .read_starts = read_starts,
+                                             .max_read_len = max_read_len, .out_pos = out_pos, .out_sk = out_sk,
+                                             .capacity = capacity, .out_offsets = out_offsets, .out_count = out_count});
 }
 
 // The same with ambiguity bits (PackedNSeq reads from host memory).
@@ -2762,16 +2809,22 @@ int mm_run_packed_reads_skip_ambiguous_host(const mm_plan_t *plan, mm_workspace_
     if (!plan || !ws || !out_offsets || (n_reads && !packed)) return MM_ERR_NULL;
     // (no reads: the bits are not looked at, like the device entry point's - but the launch still takes the skip path)
     static const uint8_t no_bits = 0;
-    return packed_reads_host_impl(plan, ws, packed, amb ? amb : &no_bits, n_reads, read_starts, max_read_len, out_pos, nullptr,
-                                  capacity, out_offsets, out_count);
+    return packed_reads_host_impl(plan, ws, {.packed = packed, .amb = amb ? amb : &no_bits, .n_reads = n_reads,
+                                             .read_starts = read_starts, .max_read_len = max_read_len, .out_pos = out_pos,
+                                             .capacity = capacity, .out_offsets = out_offsets, .out_count = out_count});
 }
 
 // The staging of the sequence host entry points other than mm_run_host, behind their own argument checks: `src` is packed
 // bytes or (ascii) one byte per base, packed on the device; `skip` runs the skip-ambiguous windows over the bits of `amb`
 // (packed source) or over the bits the ASCII packer writes.
-static int run_host_staged(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *src, bool ascii, uint64_t base_offset,
-                           bool skip, const uint8_t *amb, uint64_t amb_offset, uint64_t n_bases, uint32_t *out_pos,
-                           uint32_t *out_sk, uint64_t capacity, uint64_t *out_count) {
+// (c.packed: the HOST source; skip != null runs the skip-ambiguous windows, over skip->amb for a packed source)
+struct HostAmb {
+    const uint8_t *amb;
+    uint64_t amb_offset;
+};
+static int run_host_staged(const mm_plan_t *plan, mm_workspace_t *ws, const HostCall &c, bool ascii, const HostAmb *skip) {
+    const uint8_t *const src = static_cast<const uint8_t *>(c.packed), *const amb = skip ? skip->amb : nullptr;
+    const uint64_t base_offset = c.base_offset, n_bases = c.n_bases, amb_offset = skip ? skip->amb_offset : 0;
     MM_HIP(set_device(ws->device));
     const uint64_t bytes = (base_offset + n_bases + 3) / 4, abytes = (amb_offset + n_bases + 7) / 8;
     int r = grow_bytes(ws->d_in, ws->d_in_bytes, bytes + 16);
@@ -2792,8 +2845,10 @@ static int run_host_staged(const mm_plan_t *plan, mm_workspace_t *ws, const uint
         }
     }
     const AmbArgs a{ws->d_amb, abytes + 16, amb_offset};
-    return run_host_common(plan, ws, ws->d_in, bytes + 16, base_offset, n_bases, out_pos, out_sk, capacity, out_count,
-                           skip ? &a : nullptr);
+    HostCall staged = c;
+    staged.packed = ws->d_in;
+    staged.packed_bytes = bytes + 16;
+    return run_host_common(plan, ws, staged, skip ? &a : nullptr);
 }
 
 int mm_run_host_ascii(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *ascii,
@@ -2804,7 +2859,8 @@ int mm_run_host_ascii(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *
     if (!plan || !ws) return MM_ERR_NULL;
     if (n_bases >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
     if (out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;
-    return run_host_staged(plan, ws, ascii, true, 0, false, nullptr, 0, n_bases, out_pos, out_sk, capacity, out_count);
+    return run_host_staged(plan, ws, {.packed = ascii, .n_bases = n_bases, .out_pos = out_pos, .out_sk = out_sk,
+                                      .capacity = capacity, .out_count = out_count}, true, nullptr);
 }
 
 // ------------------------------------------------------------------- text
@@ -2835,49 +2891,42 @@ static int text_tables_on_device(mm_workspace_t *ws, const mm::TextTables &tt, c
     return MM_OK;
 }
 
-static int run_text_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_text, uint64_t text_bytes,
-                               uint64_t n, uint64_t win_begin, uint64_t win_end, uint32_t *d_out_pos,
-                               uint32_t *d_out_sk, uint64_t capacity, uint64_t *d_count) {
+// What every text launch takes from its plan: the sizes, the hasher's scalars, its tables on the device.
+static int set_text_plan(mm::TextRunArgs &a, const mm_plan_t *plan, mm_workspace_t *ws) {
+    set_plan(a, plan);
+    a.hash_rc = plan->tt.canonical != 0;
+    a.fw0 = plan->tt.fw0;
+    a.rc0 = plan->tt.rc0;
+    a.rot = plan->tt.rot;
+    return text_tables_on_device(ws, plan->tt, &a.tables);
+}
+
+static int run_text_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, const TextCall &c) {
+    uint64_t win_end = c.win_end, capacity = c.capacity;
     if (!plan || !ws) return MM_ERR_NULL;
     if (!plan->text) return MM_ERR_BAD_MODE;  // (a plan of mm_plan_create: packed entry points only)
-    if (n >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
-    if (d_out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;  // src/lib.rs:339
-    if (!d_out_pos) capacity = 0;
+    if (c.n >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
+    if (c.d_out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;  // src/lib.rs:339
+    if (!c.d_out_pos) capacity = 0;
     const uint64_t l = (uint64_t)plan->k + plan->w - 1;
-    const uint64_t n_w = n >= l ? n - l + 1 : 0;
+    const uint64_t n_w = c.n >= l ? c.n - l + 1 : 0;
     if (win_end > n_w) win_end = n_w;
-    if (win_begin < win_end) {  // (every check before the first stream operation)
-        if (!d_text) return MM_ERR_NULL;
-        if (text_bytes < n) return MM_ERR_CAPACITY;
+    if (c.win_begin < win_end) {  // (every check before the first stream operation)
+        if (!c.d_text) return MM_ERR_NULL;
+        if (c.text_bytes < c.n) return MM_ERR_CAPACITY;
     }
     MM_HIP(set_device(ws->device));
     MM_HIP(hipMemsetAsync(ws->total, 0, 2 * sizeof(unsigned long long), ws->stream));
-    if (win_begin < win_end) {
-        mm::TextRunArgs a;
-        int r = text_tables_on_device(ws, plan->tt, &a.tables);
+    if (c.win_begin < win_end) {
+        mm::TextRunArgs a{};
+        int r = set_text_plan(a, plan, ws);
         if (r) return r;
-        a.text = static_cast<const uint8_t *>(d_text);
-        a.n = n;
-        a.k = plan->k;
-        a.w = plan->w;
-        a.canonical_windows = plan->canonical_windows;
-        a.mode = plan->mode;
-        a.win_begin = win_begin;
+        a.text = static_cast<const uint8_t *>(c.d_text);
+        a.n = c.n;
+        a.win_begin = c.win_begin;
         a.win_end = win_end;
-        a.out.pos = d_out_pos;
-        a.out.sk = d_out_sk;
-        a.out.cap = capacity;
-        a.out.total = ws->total;
-        a.out.ticket = ws->ticket;
-        a.out.error = reinterpret_cast<uint32_t *>(ws->total + 1);
-        a.timing_start = a.timing_stop = nullptr;
-        a.hash_rc = plan->tt.canonical != 0;
-        a.fw0 = plan->tt.fw0;
-        a.rc0 = plan->tt.rc0;
-        a.rot = plan->tt.rot;
-        a.scratch = nullptr;
-        a.generic_round_windows = 0;
-        const uint64_t nwin = win_end - win_begin;
+        a.out = out_params(ws, c.d_out_pos, c.d_out_sk, capacity);
+        const uint64_t nwin = win_end - c.win_begin;
         const bool fused = !ws->force_generic && mm::text_walk_supported(plan->k, plan->w);
         if (fused) {
             r = grow_status(ws, mm::text_walk_tiles(nwin) + 1);
@@ -2892,22 +2941,14 @@ static int run_text_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, const 
         }
         a.out.status = ws->status;
         ws->status_dirty = true;  // (both text families clear and write untagged words)
-        if (ws->timing) {
-            hipEvent_t e0, e1;
-            MM_HIP(hipEventCreate(&e0));
-            MM_HIP(hipEventCreate(&e1));
-            ws->events.emplace_back(e0, e1);
-            a.timing_start = e0;
-            a.timing_stop = e1;
-        }
-        if ((fused ? mm::launch_text_walk(a, ws->stream) : mm::launch_generic_text(a, ws->stream)) != 0) {
-            g_last_error = std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError());
-            return MM_ERR_HIP;
-        }
-        ws->last_path = fused ? MM_PATH_FUSED : MM_PATH_GENERIC;
+        TimedLaunch timed(ws);
+        r = timed.arm(a);
+        if (r) return r;
+        if ((fused ? mm::launch_text_walk(a, ws->stream) : mm::launch_generic_text(a, ws->stream)) != 0) return launch_failed();
+        timed.done(fused ? MM_PATH_FUSED : MM_PATH_GENERIC);
     }
-    if (d_count)
-        MM_HIP(hipMemcpyAsync(d_count, ws->total, sizeof(unsigned long long), hipMemcpyDeviceToDevice, ws->stream));
+    if (c.d_count)
+        MM_HIP(hipMemcpyAsync(c.d_count, ws->total, sizeof(unsigned long long), hipMemcpyDeviceToDevice, ws->stream));
     return MM_OK;
 }
 
@@ -2916,23 +2957,21 @@ int mm_run_text_device_async(const mm_plan_t *plan, mm_workspace_t *ws, const vo
                              uint32_t *d_out_sk, uint64_t capacity, uint64_t *d_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
     if (ws) ws->async_unchecked = true;
-    return run_text_async_impl(plan, ws, d_text, text_bytes, n, win_begin, win_end, d_out_pos, d_out_sk, capacity,
-                               d_count);
+    return run_text_async_impl(plan, ws, {.d_text = d_text, .text_bytes = text_bytes, .n = n, .win_begin = win_begin,
+                                          .win_end = win_end, .d_out_pos = d_out_pos, .d_out_sk = d_out_sk,
+                                          .capacity = capacity, .d_count = d_count});
 }
 
-static int run_text_sync(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_text, uint64_t text_bytes,
-                         uint64_t n, uint64_t win_begin, uint64_t win_end, uint32_t *d_out_pos, uint32_t *d_out_sk,
-                         uint64_t capacity, uint64_t *out_count) {
-    return run_sync(ws, capacity, d_out_pos != nullptr, out_count, [&](bool *) {
-        return run_text_async_impl(plan, ws, d_text, text_bytes, n, win_begin, win_end, d_out_pos, d_out_sk, capacity, nullptr);
-    });
+static int run_text_sync(const mm_plan_t *plan, mm_workspace_t *ws, const TextCall &c, uint64_t *out_count) {
+    return run_sync(ws, c.capacity, c.d_out_pos != nullptr, out_count, [&](bool *) { return run_text_async_impl(plan, ws, c); });
 }
 
 int mm_run_text_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_text, uint64_t text_bytes,
                        uint64_t n, uint64_t win_begin, uint64_t win_end, uint32_t *d_out_pos, uint32_t *d_out_sk,
                        uint64_t capacity, uint64_t *out_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
-    return run_text_sync(plan, ws, d_text, text_bytes, n, win_begin, win_end, d_out_pos, d_out_sk, capacity,
+    return run_text_sync(plan, ws, {.d_text = d_text, .text_bytes = text_bytes, .n = n, .win_begin = win_begin,
+                                    .win_end = win_end, .d_out_pos = d_out_pos, .d_out_sk = d_out_sk, .capacity = capacity},
                          out_count);
 }
 
@@ -2953,11 +2992,12 @@ int mm_run_text_host(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *t
     if (r) return r;
     if (n) MM_HIP(hipMemcpyAsync(ws->d_ascii, text, n, hipMemcpyHostToDevice, ws->stream));
     uint64_t count = 0;
-    r = run_text_sync(plan, ws, ws->d_ascii, n, n, 0, UINT64_MAX, cap ? ws->d_out : nullptr, (out_sk && cap) ? ws->d_sk : nullptr,
-                      cap, &count);
+    r = run_text_sync(plan, ws, {.d_text = ws->d_ascii, .text_bytes = n, .n = n, .win_end = UINT64_MAX,
+                                 .d_out_pos = cap ? ws->d_out : nullptr, .d_out_sk = (out_sk && cap) ? ws->d_sk : nullptr,
+                                 .capacity = cap}, &count);
     if (out_count) *out_count = count;
     if (r) return r;
-    return download_positions(ws, out_pos, out_sk, count);
+    return download_positions(ws, out_pos, out_sk, count, nullptr, 0);
 }
 
 // ------------------------------------------------------------- text batch
@@ -2966,92 +3006,64 @@ int mm_run_text_host(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *t
 // whole batch in ONE launch (BATCH instances, mm_text_walk_impl.h); plans it does not take run one generic-family launch
 // per record in stream order (slow: the starts come back to the host first), each appending to the same output and total.
 // The argument checks of the batch entry points, before anything is touched (no workspace needed).
-static int text_batch_check(const mm_plan_t *plan, const void *d_text, uint64_t text_bytes, uint64_t n_records,
-                            const uint64_t *d_starts, uint64_t n_chars, const uint32_t *d_out_sk,
-                            const uint64_t *d_out_offsets) {
+static int text_batch_check(const mm_plan_t *plan, const TextBatchCall &c) {
     if (!plan) return MM_ERR_NULL;
     if (!plan->text) return MM_ERR_BAD_MODE;  // (a plan of mm_plan_create: packed entry points only)
-    if (n_chars >= (1ull << 32) || n_records >= (1ull << 31)) return MM_ERR_LEN_TOO_LARGE;
-    if (d_out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;  // src/lib.rs:339
-    if (!d_out_offsets || (n_records && !d_starts)) return MM_ERR_NULL;
-    if (n_chars > text_bytes) return MM_ERR_CAPACITY;
-    if (n_chars && !d_text) return MM_ERR_NULL;
+    if (c.n_chars >= (1ull << 32) || c.n_records >= (1ull << 31)) return MM_ERR_LEN_TOO_LARGE;
+    if (c.d_out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;  // src/lib.rs:339
+    if (!c.d_out_offsets || (c.n_records && !c.d_starts)) return MM_ERR_NULL;
+    if (c.n_chars > c.text_bytes) return MM_ERR_CAPACITY;
+    if (c.n_chars && !c.d_text) return MM_ERR_NULL;
     return MM_OK;
 }
 
-static int run_text_batch_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_text, uint64_t text_bytes,
-                                     uint64_t n_records, const uint64_t *d_starts, uint64_t n_chars, uint32_t *d_out_pos,
-                                     uint32_t *d_out_sk, uint64_t capacity, uint64_t *d_out_offsets, uint64_t *d_count) {
-    int r = text_batch_check(plan, d_text, text_bytes, n_records, d_starts, n_chars, d_out_sk, d_out_offsets);
+static int run_text_batch_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, const TextBatchCall &c) {
+    int r = text_batch_check(plan, c);
     if (r) return r;
     if (!ws) return MM_ERR_NULL;
-    if (!d_out_pos) capacity = 0;
+    const uint64_t capacity = c.d_out_pos ? c.capacity : 0;
     MM_HIP(set_device(ws->device));
     MM_HIP(hipMemsetAsync(ws->total, 0, 2 * sizeof(unsigned long long), ws->stream));
     const uint64_t l = (uint64_t)plan->k + plan->w - 1;
-    if (n_records == 0 || n_chars < l) {  // (no window anywhere: every record's slice is empty)
-        MM_HIP(hipMemsetAsync(d_out_offsets, 0, (n_records + 1) * sizeof(uint64_t), ws->stream));
+    if (c.n_records == 0 || c.n_chars < l) {  // (no window anywhere: every record's slice is empty)
+        MM_HIP(hipMemsetAsync(c.d_out_offsets, 0, (c.n_records + 1) * sizeof(uint64_t), ws->stream));
     } else {
-        mm::TextRunArgs a;
-        r = text_tables_on_device(ws, plan->tt, &a.tables);
+        mm::TextRunArgs a{};
+        r = set_text_plan(a, plan, ws);
         if (r) return r;
-        a.text = static_cast<const uint8_t *>(d_text);
-        a.k = plan->k;
-        a.w = plan->w;
-        a.canonical_windows = plan->canonical_windows;
-        a.mode = plan->mode;
-        a.out.pos = d_out_pos;
-        a.out.sk = d_out_sk;
-        a.out.cap = capacity;
-        a.out.total = ws->total;
-        a.out.ticket = ws->ticket;
-        a.out.error = reinterpret_cast<uint32_t *>(ws->total + 1);
-        a.timing_start = a.timing_stop = nullptr;
-        a.hash_rc = plan->tt.canonical != 0;
-        a.fw0 = plan->tt.fw0;
-        a.rc0 = plan->tt.rc0;
-        a.rot = plan->tt.rot;
-        a.scratch = nullptr;
-        a.generic_round_windows = 0;
+        a.text = static_cast<const uint8_t *>(c.d_text);
+        a.out = out_params(ws, c.d_out_pos, c.d_out_sk, capacity);
         const bool fused = !ws->force_generic && mm::text_walk_supported(plan->k, plan->w);
         if (fused) {
-            const uint64_t tiles = mm::text_batch_tiles(n_chars);
+            const uint64_t tiles = mm::text_batch_tiles(c.n_chars);
             r = grow_status(ws, tiles + 1);
             if (r == MM_OK) r = grow(ws->d_text_tiles, ws->d_text_tiles_elems, 2 * tiles, sizeof(unsigned long long));
             if (r) return r;
             a.out.status = ws->status;
             ws->status_dirty = true;  // (the text kernels clear and write untagged words)
-            a.n = n_chars;
-            a.win_begin = 0;
-            a.win_end = n_chars - l + 1;
+            a.n = c.n_chars;
+            a.win_end = c.n_chars - l + 1;
             a.batch = true;
-            a.starts = d_starts;
-            a.n_records = n_records;
+            a.starts = c.d_starts;
+            a.n_records = c.n_records;
             a.tile_rec = ws->d_text_tiles;
-            a.offsets = reinterpret_cast<unsigned long long *>(d_out_offsets);
-            if (ws->timing) {
-                hipEvent_t e0, e1;
-                MM_HIP(hipEventCreate(&e0));
-                MM_HIP(hipEventCreate(&e1));
-                ws->events.emplace_back(e0, e1);
-                a.timing_start = e0;
-                a.timing_stop = e1;
-            }
-            if (mm::launch_text_walk(a, ws->stream) != 0) {
-                g_last_error = std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError());
-                return MM_ERR_HIP;
-            }
+            a.offsets = reinterpret_cast<unsigned long long *>(c.d_out_offsets);
+            TimedLaunch timed(ws);
+            r = timed.arm(a);
+            if (r) return r;
+            if (mm::launch_text_walk(a, ws->stream) != 0) return launch_failed();
+            timed.done(MM_PATH_FUSED);
         } else {
             // one generic launch per record: the look-back adds the running total to each launch's first tile, so the
             // launches append; record r's offset is that total just before its launch (a device-to-device copy)
-            std::vector<uint64_t> hs(n_records + 1);
-            MM_HIP(hipMemcpyAsync(hs.data(), d_starts, (n_records + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost,
+            std::vector<uint64_t> hs(c.n_records + 1);
+            MM_HIP(hipMemcpyAsync(hs.data(), c.d_starts, (c.n_records + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost,
                                   ws->stream));
             MM_HIP(hipStreamSynchronize(ws->stream));
             uint64_t longest = 0;  // (records clamped into [0, n_chars], whatever the starts hold)
-            for (uint64_t q = 0; q < n_records; ++q) {
-                const uint64_t b = hs[q] < n_chars ? hs[q] : n_chars;
-                const uint64_t e = hs[q + 1] < b ? b : (hs[q + 1] < n_chars ? hs[q + 1] : n_chars);
+            for (uint64_t q = 0; q < c.n_records; ++q) {
+                const uint64_t b = hs[q] < c.n_chars ? hs[q] : c.n_chars;
+                const uint64_t e = hs[q + 1] < b ? b : (hs[q + 1] < c.n_chars ? hs[q + 1] : c.n_chars);
                 if (e - b > longest) longest = e - b;
             }
             const uint64_t max_windows = longest >= l ? longest - l + 1 : 0;
@@ -3063,29 +3075,26 @@ static int run_text_batch_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, 
             }
             a.out.status = ws->status;
             ws->status_dirty = true;
-            for (uint64_t q = 0; q < n_records; ++q) {
-                MM_HIP(hipMemcpyAsync(d_out_offsets + q, ws->total, sizeof(uint64_t), hipMemcpyDeviceToDevice, ws->stream));
-                const uint64_t b = hs[q] < n_chars ? hs[q] : n_chars;
-                const uint64_t e = hs[q + 1] < b ? b : (hs[q + 1] < n_chars ? hs[q + 1] : n_chars);
+            for (uint64_t q = 0; q < c.n_records; ++q) {
+                MM_HIP(hipMemcpyAsync(c.d_out_offsets + q, ws->total, sizeof(uint64_t), hipMemcpyDeviceToDevice, ws->stream));
+                const uint64_t b = hs[q] < c.n_chars ? hs[q] : c.n_chars;
+                const uint64_t e = hs[q + 1] < b ? b : (hs[q + 1] < c.n_chars ? hs[q + 1] : c.n_chars);
                 if (e - b < l) continue;
-                a.text = static_cast<const uint8_t *>(d_text) + b;
+                a.text = static_cast<const uint8_t *>(c.d_text) + b;
                 a.n = e - b;
                 a.win_begin = 0;
                 a.win_end = e - b - l + 1;
                 a.generic_round_windows = a.win_end < round ? a.win_end : round;
                 a.scratch = ws->scratch;
-                if (mm::launch_generic_text(a, ws->stream) != 0) {
-                    g_last_error = std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError());
-                    return MM_ERR_HIP;
-                }
+                if (mm::launch_generic_text(a, ws->stream) != 0) return launch_failed();  // (these launches are not timed)
             }
-            MM_HIP(hipMemcpyAsync(d_out_offsets + n_records, ws->total, sizeof(uint64_t), hipMemcpyDeviceToDevice,
+            MM_HIP(hipMemcpyAsync(c.d_out_offsets + c.n_records, ws->total, sizeof(uint64_t), hipMemcpyDeviceToDevice,
                                   ws->stream));
+            ws->last_path = MM_PATH_GENERIC;
         }
-        ws->last_path = fused ? MM_PATH_FUSED : MM_PATH_GENERIC;
     }
-    if (d_count)
-        MM_HIP(hipMemcpyAsync(d_count, ws->total, sizeof(unsigned long long), hipMemcpyDeviceToDevice, ws->stream));
+    if (c.d_count)
+        MM_HIP(hipMemcpyAsync(c.d_count, ws->total, sizeof(unsigned long long), hipMemcpyDeviceToDevice, ws->stream));
     return MM_OK;
 }
 
@@ -3094,20 +3103,27 @@ int mm_run_text_batch_device_async(const mm_plan_t *plan, mm_workspace_t *ws, co
                                    uint32_t *d_out_sk, uint64_t capacity, uint64_t *d_out_offsets, uint64_t *d_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
     if (ws) ws->async_unchecked = true;
-    return run_text_batch_async_impl(plan, ws, d_text, text_bytes, n_records, d_starts, n_chars, d_out_pos, d_out_sk,
-                                     capacity, d_out_offsets, d_count);
+    return run_text_batch_async_impl(plan, ws, {.d_text = d_text, .text_bytes = text_bytes, .n_records = n_records,
+                                                .d_starts = d_starts, .n_chars = n_chars, .d_out_pos = d_out_pos,
+                                                .d_out_sk = d_out_sk, .capacity = capacity, .d_out_offsets = d_out_offsets,
+                                                .d_count = d_count});
+}
+
+static int run_text_batch_sync(const mm_plan_t *plan, mm_workspace_t *ws, const TextBatchCall &c, uint64_t *out_count) {
+    const int rc = text_batch_check(plan, c);
+    if (rc) return rc;
+    return run_sync(ws, c.capacity, c.d_out_pos != nullptr, out_count,
+                    [&](bool *) { return run_text_batch_async_impl(plan, ws, c); });
 }
 
 int mm_run_text_batch_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_text, uint64_t text_bytes,
                              uint64_t n_records, const uint64_t *d_starts, uint64_t n_chars, uint32_t *d_out_pos,
                              uint32_t *d_out_sk, uint64_t capacity, uint64_t *d_out_offsets, uint64_t *out_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
-    const int rc = text_batch_check(plan, d_text, text_bytes, n_records, d_starts, n_chars, d_out_sk, d_out_offsets);
-    if (rc) return rc;
-    return run_sync(ws, capacity, d_out_pos != nullptr, out_count, [&](bool *) {
-        return run_text_batch_async_impl(plan, ws, d_text, text_bytes, n_records, d_starts, n_chars, d_out_pos, d_out_sk,
-                                         capacity, d_out_offsets, nullptr);
-    });
+    return run_text_batch_sync(plan, ws, {.d_text = d_text, .text_bytes = text_bytes, .n_records = n_records,
+                                          .d_starts = d_starts, .n_chars = n_chars, .d_out_pos = d_out_pos,
+                                          .d_out_sk = d_out_sk, .capacity = capacity, .d_out_offsets = d_out_offsets},
+                               out_count);
 }
 
 // --------------------------------------------- text batch, counts on the device
@@ -3117,16 +3133,14 @@ int mm_run_text_batch_device(const mm_plan_t *plan, mm_workspace_t *ws, const vo
 // reference has no counterpart (Builder::run is synchronous host code, src/lib.rs:378); the results are those of
 // mm_run_text_batch_device_async given the counts as host arguments.
 // The argument checks, before anything is touched (no workspace needed), in the order of text_batch_check.
-static int text_batch_counts_check(const mm_plan_t *plan, const void *d_text, uint64_t text_bytes, uint64_t max_chars,
-                                   uint64_t max_records, const uint64_t *d_starts, const uint64_t *d_counts,
-                                   const uint32_t *d_out_sk, const uint64_t *d_out_offsets) {
+static int text_batch_counts_check(const mm_plan_t *plan, const TextBatchCountsCall &c) {
     if (!plan) return MM_ERR_NULL;
     if (!plan->text) return MM_ERR_BAD_MODE;  // (a plan of mm_plan_create: packed entry points only)
-    if (max_chars >= (1ull << 32) || max_records >= (1ull << 31)) return MM_ERR_LEN_TOO_LARGE;
-    if (d_out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;  // src/lib.rs:339
-    if (!d_out_offsets || !d_counts || (max_records && !d_starts)) return MM_ERR_NULL;
-    if (max_chars > text_bytes) return MM_ERR_CAPACITY;
-    if (max_chars && !d_text) return MM_ERR_NULL;
+    if (c.max_chars >= (1ull << 32) || c.max_records >= (1ull << 31)) return MM_ERR_LEN_TOO_LARGE;
+    if (c.d_out_sk && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;  // src/lib.rs:339
+    if (!c.d_out_offsets || !c.d_counts || (c.max_records && !c.d_starts)) return MM_ERR_NULL;
+    if (c.max_chars > c.text_bytes) return MM_ERR_CAPACITY;
+    if (c.max_chars && !c.d_text) return MM_ERR_NULL;
     if (!mm::text_walk_supported(plan->k, plan->w)) {
         // (the generic family runs one launch per record: it needs the starts on the host)
         g_last_error = "mm_run_text_batch_counts_device*: w > 128 or k > 1024 has no fused text kernel; read the counts back "
@@ -3136,13 +3150,8 @@ static int text_batch_counts_check(const mm_plan_t *plan, const void *d_text, ui
     return MM_OK;
 }
 
-static int run_text_batch_counts_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_text,
-                                            uint64_t text_bytes, uint64_t max_chars, uint64_t max_records,
-                                            const uint64_t *d_starts, const uint64_t *d_counts, uint32_t *d_out_pos,
-                                            uint32_t *d_out_sk, uint64_t capacity, uint64_t *d_out_offsets,
-                                            uint64_t *d_count) {
-    int r = text_batch_counts_check(plan, d_text, text_bytes, max_chars, max_records, d_starts, d_counts, d_out_sk,
-                                    d_out_offsets);
+static int run_text_batch_counts_async_impl(const mm_plan_t *plan, mm_workspace_t *ws, const TextBatchCountsCall &c) {
+    int r = text_batch_counts_check(plan, c);
     if (r) return r;
     if (!ws) return MM_ERR_NULL;
     if (ws->force_generic) {
@@ -3150,62 +3159,35 @@ static int run_text_batch_counts_async_impl(const mm_plan_t *plan, mm_workspace_
                        "the host; read the counts back and call mm_run_text_batch_device";
         return MM_ERR_BAD_MODE;
     }
-    if (!d_out_pos) capacity = 0;
     MM_HIP(set_device(ws->device));
-    mm::TextRunArgs a;
-    r = text_tables_on_device(ws, plan->tt, &a.tables);
+    mm::TextRunArgs a{};
+    r = set_text_plan(a, plan, ws);
     if (r) return r;
     // (grid, look-back words and the tiles' record ranges for the bound: max_chars == 0 is still one tile, which writes
     // offsets[0] and the count)
-    const uint64_t tiles = mm::text_batch_tiles(max_chars);
+    const uint64_t tiles = mm::text_batch_tiles(c.max_chars);
     r = grow_status(ws, tiles + 1);
     if (r == MM_OK) r = grow(ws->d_text_tiles, ws->d_text_tiles_elems, 2 * tiles, sizeof(unsigned long long));
     if (r) return r;
     MM_HIP(hipMemsetAsync(ws->total, 0, 2 * sizeof(unsigned long long), ws->stream));
-    a.text = static_cast<const uint8_t *>(d_text);
-    a.k = plan->k;
-    a.w = plan->w;
-    a.canonical_windows = plan->canonical_windows;
-    a.mode = plan->mode;
-    a.out.pos = d_out_pos;
-    a.out.sk = d_out_sk;
-    a.out.cap = capacity;
-    a.out.total = ws->total;
-    a.out.ticket = ws->ticket;
-    a.out.error = reinterpret_cast<uint32_t *>(ws->total + 1);
+    a.text = static_cast<const uint8_t *>(c.d_text);
+    a.out = out_params(ws, c.d_out_pos, c.d_out_sk, c.d_out_pos ? c.capacity : 0);
     a.out.status = ws->status;
     ws->status_dirty = true;  // (the text kernels clear and write untagged words)
-    a.timing_start = a.timing_stop = nullptr;
-    a.hash_rc = plan->tt.canonical != 0;
-    a.fw0 = plan->tt.fw0;
-    a.rc0 = plan->tt.rc0;
-    a.rot = plan->tt.rot;
-    a.scratch = nullptr;
-    a.generic_round_windows = 0;
-    a.n = max_chars;
-    a.win_begin = 0;
-    a.win_end = 0;  // (from the counts, on the device)
+    a.n = c.max_chars;        // (win_end stays 0: it comes from the counts, on the device)
     a.batch = true;
-    a.starts = d_starts;
-    a.n_records = max_records;
+    a.starts = c.d_starts;
+    a.n_records = c.max_records;
     a.tile_rec = ws->d_text_tiles;
-    a.offsets = reinterpret_cast<unsigned long long *>(d_out_offsets);
-    a.counts = d_counts;
-    if (ws->timing) {
-        hipEvent_t e0, e1;
-        MM_HIP(hipEventCreate(&e0));
-        MM_HIP(hipEventCreate(&e1));
-        ws->events.emplace_back(e0, e1);
-        a.timing_start = e0;
-        a.timing_stop = e1;
-    }
-    if (mm::launch_text_walk(a, ws->stream) != 0) {
-        g_last_error = std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError());
-        return MM_ERR_HIP;
-    }
-    ws->last_path = MM_PATH_FUSED;
-    if (d_count)
-        MM_HIP(hipMemcpyAsync(d_count, ws->total, sizeof(unsigned long long), hipMemcpyDeviceToDevice, ws->stream));
+    a.offsets = reinterpret_cast<unsigned long long *>(c.d_out_offsets);
+    a.counts = c.d_counts;
+    TimedLaunch timed(ws);
+    r = timed.arm(a);
+    if (r) return r;
+    if (mm::launch_text_walk(a, ws->stream) != 0) return launch_failed();
+    timed.done(MM_PATH_FUSED);
+    if (c.d_count)
+        MM_HIP(hipMemcpyAsync(c.d_count, ws->total, sizeof(unsigned long long), hipMemcpyDeviceToDevice, ws->stream));
     return MM_OK;
 }
 
@@ -3216,8 +3198,10 @@ int mm_run_text_batch_counts_device_async(const mm_plan_t *plan, mm_workspace_t 
                                           uint64_t *d_count) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
     if (ws) ws->async_unchecked = true;
-    return run_text_batch_counts_async_impl(plan, ws, d_text, text_bytes, max_chars, max_records, d_starts, d_counts,
-                                            d_out_pos, d_out_sk, capacity, d_out_offsets, d_count);
+    return run_text_batch_counts_async_impl(plan, ws, {.d_text = d_text, .text_bytes = text_bytes, .max_chars = max_chars,
+                                                       .max_records = max_records, .d_starts = d_starts, .d_counts = d_counts,
+                                                       .d_out_pos = d_out_pos, .d_out_sk = d_out_sk, .capacity = capacity,
+                                                       .d_out_offsets = d_out_offsets, .d_count = d_count});
 }
 
 int mm_run_text_batch_counts_device(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_text, uint64_t text_bytes,
@@ -3225,26 +3209,14 @@ int mm_run_text_batch_counts_device(const mm_plan_t *plan, mm_workspace_t *ws, c
                                     const uint64_t *d_counts, uint32_t *d_out_pos, uint32_t *d_out_sk, uint64_t capacity,
                                     uint64_t *d_out_offsets, uint64_t *out) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
-    const int rc = text_batch_counts_check(plan, d_text, text_bytes, max_chars, max_records, d_starts, d_counts, d_out_sk,
-                                           d_out_offsets);
+    const TextBatchCountsCall c{.d_text = d_text, .text_bytes = text_bytes, .max_chars = max_chars, .max_records = max_records,
+                                .d_starts = d_starts, .d_counts = d_counts, .d_out_pos = d_out_pos, .d_out_sk = d_out_sk,
+                                .capacity = capacity, .d_out_offsets = d_out_offsets};
+    const int rc = text_batch_counts_check(plan, c);
     if (rc) return rc;
     if (!ws) return MM_ERR_NULL;
-    if (out) out[0] = out[1] = out[2] = 0;
-    uint64_t count = 0;
-    // (the two counts come back with the run's words: h_total[4..5], one wait for all of them)
-    const int r = run_sync(ws, capacity, d_out_pos != nullptr, &count, [&](bool *) {
-        const int q = run_text_batch_counts_async_impl(plan, ws, d_text, text_bytes, max_chars, max_records, d_starts,
-                                                       d_counts, d_out_pos, d_out_sk, capacity, d_out_offsets, nullptr);
-        if (q) return q;
-        MM_HIP(hipMemcpyAsync(ws->h_total + 4, d_counts, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
-        return (int)MM_OK;
-    });
-    if (out && (r == MM_OK || r == MM_ERR_CAPACITY)) {
-        out[0] = count;
-        out[1] = ws->h_total[4];
-        out[2] = ws->h_total[5];
-    }
-    return r;
+    return run_counts_sync(ws, d_counts, capacity, d_out_pos != nullptr, out,
+                           [&]() { return run_text_batch_counts_async_impl(plan, ws, c); });
 }
 
 int mm_run_text_batch_host(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *text, uint64_t n_records,
@@ -3295,8 +3267,9 @@ int mm_run_skip_ambiguous_host(const mm_plan_t *plan, mm_workspace_t *ws, const 
     if (!plan || !ws) return MM_ERR_NULL;
     if (n_bases >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
     if (!plan->canonical_windows) return MM_ERR_HASHER_NOT_CANONICAL;
-    return run_host_staged(plan, ws, packed, false, base_offset, true, amb, amb_offset, n_bases, out_pos, nullptr, capacity,
-                           out_count);
+    const HostAmb skip{amb, amb_offset};
+    return run_host_staged(plan, ws, {.packed = packed, .base_offset = base_offset, .n_bases = n_bases, .out_pos = out_pos,
+                                      .capacity = capacity, .out_count = out_count}, false, &skip);
 }
 
 int mm_run_skip_ambiguous_host_ascii(const mm_plan_t *plan, mm_workspace_t *ws, const uint8_t *ascii,
@@ -3307,7 +3280,9 @@ int mm_run_skip_ambiguous_host_ascii(const mm_plan_t *plan, mm_workspace_t *ws, 
     if (!plan || !ws) return MM_ERR_NULL;
     if (n_bases >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
     if (!plan->canonical_windows) return MM_ERR_HASHER_NOT_CANONICAL;
-    return run_host_staged(plan, ws, ascii, true, 0, true, nullptr, 0, n_bases, out_pos, nullptr, capacity, out_count);
+    const HostAmb skip{nullptr, 0};  // (the bits the ASCII packer writes)
+    return run_host_staged(plan, ws, {.packed = ascii, .n_bases = n_bases, .out_pos = out_pos, .capacity = capacity,
+                                      .out_count = out_count}, true, &skip);
 }
 
 int mm_pack_ascii_n_device_async(mm_workspace_t *ws, const uint8_t *d_ascii, uint64_t n_bases,
@@ -4034,7 +4009,7 @@ static int fasta_pack_async(mm_workspace_t *ws, const uint8_t *d_text, uint64_t 
                               reinterpret_cast<unsigned long long *>(d_rec_base),
                               reinterpret_cast<unsigned long long *>(d_rec_text_pos), max_records,
                               reinterpret_cast<unsigned long long *>(d_counts), ws->scratch, ws->stream, one_pass,
-                              reinterpret_cast<uint32_t *>(ws->total + 1)))
+                              error_word(ws)))
         return hip_fail(hipGetLastError(), "fasta_pack");
     return MM_OK;
 #endif
@@ -4064,8 +4039,8 @@ int mm_fasta_pack_n_device_async(mm_workspace_t *ws, const uint8_t *d_text, uint
 // record's '@': `pos_bias` is what a caller that cut blank bytes off the front adds back to the records' text positions.
 static int fastq_pack_async(mm_workspace_t *ws, const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_packed,
                             uint64_t packed_capacity_bytes, uint64_t *d_rec_base, uint64_t *d_rec_text_pos,
-                            uint64_t max_records, uint64_t *d_counts, uint64_t pos_bias, uint8_t *d_amb = nullptr,
-                            uint64_t amb_capacity_bytes = 0) {
+                            uint64_t max_records, uint64_t *d_counts, uint64_t pos_bias, uint8_t *d_amb,
+                            uint64_t amb_capacity_bytes) {
     const int p = pack_prologue(ws, d_text, n_bytes, d_packed, packed_capacity_bytes, d_rec_base, d_counts, d_amb, amb_capacity_bytes);
     if (p != MM_PACK_GO_ON) return p;
     const int r = grow_bytes(ws->scratch, ws->scratch_bytes, mm::fastq_scratch_bytes(n_bytes));
@@ -4084,7 +4059,7 @@ int mm_fastq_pack_device_async(mm_workspace_t *ws, const uint8_t *d_text, uint64
                                uint64_t max_records, uint64_t *d_counts) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
     return fastq_pack_async(ws, d_text, n_bytes, d_packed, packed_capacity_bytes, d_rec_base, d_rec_text_pos, max_records,
-                            d_counts, 0);
+                            d_counts, 0, nullptr, 0);
 }
 
 int mm_fastq_pack_n_device_async(mm_workspace_t *ws, const uint8_t *d_text, uint64_t n_bytes, uint8_t *d_packed,
@@ -4654,8 +4629,10 @@ int mm_run_sharded_host(const mm_plan_t *plan, mm_device_group_t *g, const uint8
         if (rc == MM_OK && out_sk) rc = grow(ws->d_sk, ws->d_sk_elems, cap ? cap : 1, sizeof(uint32_t));
         if (rc) return fail(rc);
         uint64_t count = 0;
-        rc = run_device_sync(plan, ws, ws->d_in, bytes + 16, base_offset, n_bases, a, e, out_pos ? ws->d_out : nullptr,
-                             (out_sk && out_pos) ? ws->d_sk : nullptr, out_pos ? cap : 0, &count, nullptr);
+        rc = run_device_sync(plan, ws, {.d_packed = ws->d_in, .packed_bytes = bytes + 16, .base_offset = base_offset,
+                                        .n_bases = n_bases, .win_begin = a, .win_end = e, .d_out_pos = out_pos ? ws->d_out : nullptr,
+                                        .d_out_sk = (out_sk && out_pos) ? ws->d_sk : nullptr, .capacity = out_pos ? cap : 0},
+                             &count);
         r.count = count;
         if (rc && rc != MM_ERR_CAPACITY) return fail(rc);
         if (rc == MM_ERR_CAPACITY) r.rc = rc;
@@ -4730,8 +4707,7 @@ int mm_run_sharded_device(const mm_plan_t *plan, mm_device_group_t *g, uint64_t 
     g->batch_ran = false;  // (the result buffers are shared between the two resident modes: ADVICE r4)
     g->batch_vals_words = 0;
     // expected positions per window (+ 15 % and a constant): a shard that needs more is run again with what it needs
-    const double dens = plan->mode == MM_OPEN_SYNCMERS ? 1.0 / plan->w
-                        : plan->mode == MM_CLOSED_SYNCMERS ? 2.0 / plan->w : 2.0 / (plan->w + 1.0);
+    const double dens = expected_density(plan);
     std::vector<char> host_written(N, 0), pending(N, 0);
     auto grow_shard = [&](uint64_t i, uint64_t need) -> int {
         mm_device_group::Shard &s = g->shard[i];
@@ -4748,9 +4724,11 @@ int mm_run_sharded_device(const mm_plan_t *plan, mm_device_group_t *g, uint64_t 
         ws->h_total[1] = 0;
         if (!ws->h_total_dev) MM_HIP(hipMemsetAsync(ws->total + 1, 0, sizeof(unsigned long long), ws->stream));
         const uint64_t cap = want_superkmers ? (s.cap_pos < s.cap_sk ? s.cap_pos : s.cap_sk) : s.cap_pos;
-        int r = run_device_async_impl(plan, ws, g->d_seq[i], g->seq_bytes + (g->own_seq[i] ? 64 : 0), base_offset, n_bases,
-                                      s.win_begin, s.win_end, s.d_pos, want_superkmers ? s.d_sk : nullptr, cap, nullptr,
-                                      false, nullptr, &hw);
+        int r = run_device_async_impl(plan, ws, {.d_packed = g->d_seq[i], .packed_bytes = g->seq_bytes + (g->own_seq[i] ? 64 : 0),
+                                                 .base_offset = base_offset, .n_bases = n_bases, .win_begin = s.win_begin,
+                                                 .win_end = s.win_end, .d_out_pos = s.d_pos,
+                                                 .d_out_sk = want_superkmers ? s.d_sk : nullptr, .capacity = cap,
+                                                 .host_total_written = &hw});
         if (r) return r;
         if (!hw)
             MM_HIP(hipMemcpyAsync(ws->h_total, ws->total, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost,
@@ -4934,8 +4912,7 @@ int mm_run_batch_sharded_device(const mm_plan_t *plan, mm_device_group_t *g, con
     if (want_superkmers && plan->mode != MM_MINIMIZERS) return MM_ERR_BAD_MODE;
     const uint64_t N = g->ws.size(), n_seqs = g->seq_entry.size();
     const uint64_t l = (uint64_t)plan->k + plan->w - 1;
-    const double dens = plan->mode == MM_OPEN_SYNCMERS ? 1.0 / plan->w
-                        : plan->mode == MM_CLOSED_SYNCMERS ? 2.0 / plan->w : 2.0 / (plan->w + 1.0);
+    const double dens = expected_density(plan);
     // One batch launch per entry, ISSUED from this thread one after the other (nothing waits), then waited for in
     // turn - the model of mm_run_sharded_device (round 4 ran a host thread per entry here because a batch launch read
     // its offsets back synchronously; round 5 split it into batch_issue / batch_finish).  An entry whose plan has no
@@ -5006,8 +4983,9 @@ int mm_run_batch_sharded_device(const mm_plan_t *plan, mm_device_group_t *g, con
         if (e.want > windows) e.want = windows;
         int rc = grow_entry(i, e.want);
         if (rc) return rc;
-        rc = batch_issue(plan, g->ws[i], m, e.dptr.data(), e.dbytes.data(), e.offs.data(), e.lens.data(), sh.d_pos,
-                         want_superkmers ? sh.d_sk : nullptr, cap_of(i), &e.bi);
+        rc = batch_issue(plan, g->ws[i], {.n_seqs = m, .d_packed = e.dptr.data(), .packed_bytes = e.dbytes.data(),
+                                          .base_offsets = e.offs.data(), .n_bases = e.lens.data(), .d_out_pos = sh.d_pos,
+                                          .d_out_sk = want_superkmers ? sh.d_sk : nullptr, .capacity = cap_of(i)}, &e.bi);
         if (rc == MM_BATCH_FALLBACK) e.sync_path = true;  // (no fused kernel for this plan: the per-sequence loop, below)
         else if (rc) return rc;
         else e.issued = true;
@@ -5320,11 +5298,12 @@ ApiPlanInfo api_plan_info(const mm_plan_t *plan) {
 }
 int api_reads_counts_refusal(const mm_plan_t *plan, uint64_t max_bases, uint64_t max_records, int want_sk, int want_amb) {
     // (the check reads no pointer: any non-null value stands for the buffers, and for a workspace with no knob set)
-    static const uint64_t some = 0;
+    static uint64_t some = 0;
     const AmbArgs amb{&some, ~0ull >> 3, 0};
-    const int r = packed_reads_counts_check(plan, nullptr, &some, ~0ull >> 2, 0, max_bases, max_records, &some, &some,
-                                            want_sk ? reinterpret_cast<const uint32_t *>(&some) : nullptr, &some,
-                                            want_amb ? &amb : nullptr);
+    const int r = packed_reads_counts_check(
+        plan, nullptr, {.d_packed = &some, .packed_bytes = ~0ull >> 2, .max_bases = max_bases, .max_records = max_records,
+                        .d_read_starts = &some, .d_counts = &some, .d_out_sk = want_sk ? reinterpret_cast<uint32_t *>(&some) : nullptr,
+                        .d_out_offsets = &some, .amb = want_amb ? &amb : nullptr});
     return r == MM_ERR_NULL && plan ? (int)MM_OK : r;  // (MM_ERR_NULL with a plan: the missing workspace, refused last)
 }
 hipStream_t api_workspace_stream(mm_workspace_t *ws) { return ws->stream; }

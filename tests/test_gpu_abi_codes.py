@@ -47,6 +47,25 @@ _VALUES_HOST = "ws:p packed:p base_offset:q n_bases:q len:u canonical:i pos:p n_
 _PACK = "ws:p d_text:p n_bytes:q d_packed:p packed_capacity_bytes:q d_rec_base:p d_rec_text_pos:p max_records:q d_counts:p"
 _PACK_N = ("ws:p d_text:p n_bytes:q d_packed:p packed_capacity_bytes:q d_amb:p amb_capacity_bytes:q d_rec_base:p "
            "d_rec_text_pos:p max_records:q d_counts:p")
+_PCOUNTS = ("plan:p ws:p d_packed:p packed_bytes:q base_offset:q max_bases:q max_records:q d_read_starts:p d_counts:p d_out_pos:p "
+            "d_out_sk:p capacity:q d_out_offsets:p")
+_PCOUNTS_SKIP = ("plan:p ws:p d_packed:p packed_bytes:q base_offset:q d_amb:p amb_bytes:q amb_offset:q max_bases:q max_records:q "
+                 "d_read_starts:p d_counts:p d_out_pos:p capacity:q d_out_offsets:p")
+_TCOUNTS = ("plan:p ws:p d_text:p text_bytes:q max_chars:q max_records:q d_starts:p d_counts:p d_out_pos:p d_out_sk:p capacity:q "
+            "d_out_offsets:p")
+_VREADS_DEV = ("ws:p d_packed:p packed_bytes:q base_offset:q n_reads:q d_read_starts:p read_stride:u len:u canonical:i d_pos:p "
+               "d_out_offsets:p n_pos_max:q d_values:p")
+_VREADS_HOST = ("ws:p packed:p packed_bytes:q base_offset:q n_reads:q read_starts:p read_stride:u len:u canonical:i pos:p "
+                "offsets:p values:p")
+_VBATCH = "ws:p n_seqs:q d_packed:p packed_bytes:p base_offsets:p n_bases:p len:u canonical:i d_pos:p offsets:p d_values:p"
+_VTEXT_DEV = "ws:p d_text:p text_bytes:q n:q encoding:i len:u canonical:i d_pos:p n_pos:q d_values:p"
+_VTEXT_HOST = "ws:p text:p n:q encoding:i len:u canonical:i pos:p n_pos:q values:p"
+_VTBATCH_DEV = ("ws:p d_text:p text_bytes:q n_records:q d_starts:p n_chars:q encoding:i len:u canonical:i d_pos:p d_out_offsets:p "
+                "n_pos_max:q d_values:p")
+_VTCOUNTS = ("ws:p d_text:p text_bytes:q max_chars:q max_records:q d_starts:p d_counts:p encoding:i len:u canonical:i d_pos:p "
+             "d_out_offsets:p n_pos_max:q d_values:p")
+_VTBATCH_HOST = "ws:p text:p n_records:q starts:p encoding:i len:u canonical:i pos:p offsets:p values:p"
+_FTEXT = "ws:p d_text:p n_bytes:q d_seq:p seq_capacity_bytes:q d_rec_start:p d_rec_text_pos:p max_records:q d_counts:p"
 SIG = {
     "mm_run_device_async": _RUN, "mm_run_device": _RUN,
     "mm_run_skip_ambiguous_device_async": _SKIP, "mm_run_skip_ambiguous_device": _SKIP,
@@ -79,6 +98,22 @@ SIG = {
     "mm_run_batch_sharded_device": "plan:p group:p base_offsets:p n_bases:p want_superkmers:i out_counts:p total:p",
     "mm_run_batch_sharded_host": "plan:p group:p n_seqs:q packed:p base_offsets:p n_bases:p out_pos:p out_sk:p capacity:q "
                                  "out_offsets:p",
+    # ---- the families added after the first recording
+    "mm_run_packed_reads_counts_device_async": _PCOUNTS + " d_count:p", "mm_run_packed_reads_counts_device": _PCOUNTS + " out:p",
+    "mm_run_packed_reads_skip_ambiguous_counts_device_async": _PCOUNTS_SKIP + " d_count:p",
+    "mm_run_packed_reads_skip_ambiguous_counts_device": _PCOUNTS_SKIP + " out:p",
+    "mm_run_text_batch_counts_device_async": _TCOUNTS + " d_count:p", "mm_run_text_batch_counts_device": _TCOUNTS + " out:p",
+    "mm_values_u64_reads_device_async": _VREADS_DEV, "mm_values_u128_reads_device_async": _VREADS_DEV,
+    "mm_values_u64_reads_host": _VREADS_HOST, "mm_values_u128_reads_host": _VREADS_HOST,
+    "mm_values_u64_batch_device_async": _VBATCH, "mm_values_u128_batch_device_async": _VBATCH,
+    "mm_values_u64_text_device_async": _VTEXT_DEV, "mm_values_u128_text_device_async": _VTEXT_DEV,
+    "mm_values_u64_text_host": _VTEXT_HOST, "mm_values_u128_text_host": _VTEXT_HOST,
+    "mm_values_u64_text_batch_device_async": _VTBATCH_DEV, "mm_values_u128_text_batch_device_async": _VTBATCH_DEV,
+    "mm_values_u64_text_batch_counts_device_async": _VTCOUNTS, "mm_values_u128_text_batch_counts_device_async": _VTCOUNTS,
+    "mm_values_u64_text_batch_host": _VTBATCH_HOST, "mm_values_u128_text_batch_host": _VTBATCH_HOST,
+    "mm_fasta_text_device_async": _FTEXT, "mm_fasta_text_device": _FTEXT + " out_counts:p",
+    "mm_pack_ascii_device_async": "ws:p d_ascii:p n_bases:q d_packed:p",
+    "mm_pack_ascii_n_device_async": "ws:p d_ascii:p n_bases:q d_packed:p d_amb:p",
 }
 _KIND = {"p": C.c_void_p, "q": C.c_uint64, "u": C.c_uint32, "i": C.c_int}
 
@@ -125,6 +160,32 @@ _pack_ok = dict(ws="ws", d_text="d_fasta", n_bytes=len(FASTA), d_packed="d_packe
                 d_rec_base="d_rec_base", d_rec_text_pos="d_rec_pos", max_records=16, d_counts="d_counts")
 _pack_n_ok = dict(_pack_ok, d_amb="d_ambout", amb_capacity_bytes=4096)
 _fastq = dict(d_text="d_fastq", n_bytes=len(FASTQ))
+
+# ---- the families added after the first recording: the reads' and the text's {bases / characters, records} are the 2-word
+# buffers d_rcounts / d_tcounts; values are asked at the read-local positions *_rpos, delimited by *_voffs
+_pcounts_ok = dict(plan="canon", ws="ws", d_packed="d_seq", packed_bytes=4096, base_offset=0, max_bases=60, max_records=3,
+                   d_read_starts="d_starts", d_counts="d_rcounts", d_out_pos="d_out", d_out_sk=None, capacity=256, d_out_offsets="d_offs")
+_pcounts_skip_ok = dict({k: v for k, v in _pcounts_ok.items() if k != "d_out_sk"}, d_amb="d_amb", amb_bytes=4096, amb_offset=0)
+_tcounts_ok = dict(plan="text", ws="ws", d_text="d_text", text_bytes=40, max_chars=40, max_records=3, d_starts="d_tstarts",
+                   d_counts="d_tcounts", d_out_pos="d_out", d_out_sk=None, capacity=256, d_out_offsets="d_offs")
+_vreads_dev_ok = dict(ws="ws", d_packed="d_seq", packed_bytes=4096, base_offset=0, n_reads=3, d_read_starts="d_starts", read_stride=0,
+                      len=5, canonical=1, d_pos="d_rpos", d_out_offsets="d_voffs", n_pos_max=4, d_values="d_vals")
+_vreads_host_ok = dict(ws="ws", packed="h_seq", packed_bytes=4096, base_offset=0, n_reads=3, read_starts="h_starts", read_stride=0,
+                       len=5, canonical=1, pos="h_rpos", offsets="h_voffs", values="h_vals")
+_vbatch_ok = dict(ws="ws", n_seqs=3, d_packed="h_bptrs", packed_bytes="h_bbytes", base_offsets=None, n_bases="h_bbases", len=5,
+                  canonical=1, d_pos="d_rpos", offsets="h_voffs", d_values="d_vals")
+_vtext_dev_ok = dict(ws="ws", d_text="d_text", text_bytes=40, n=40, encoding=0, len=5, canonical=0, d_pos="d_vpos", n_pos=4,
+                     d_values="d_vals")
+_vtext_host_ok = dict(ws="ws", text="h_text", n=40, encoding=0, len=5, canonical=0, pos="h_vpos", n_pos=4, values="h_vals")
+_vtbatch_dev_ok = dict(ws="ws", d_text="d_text", text_bytes=40, n_records=3, d_starts="d_tstarts", n_chars=40, encoding=0, len=5,
+                       canonical=0, d_pos="d_rpos", d_out_offsets="d_voffs", n_pos_max=4, d_values="d_vals")
+_vtcounts_ok = dict(ws="ws", d_text="d_text", text_bytes=40, max_chars=40, max_records=3, d_starts="d_tstarts", d_counts="d_tcounts",
+                    encoding=0, len=5, canonical=0, d_pos="d_rpos", d_out_offsets="d_voffs", n_pos_max=4, d_values="d_vals")
+_vtbatch_host_ok = dict(ws="ws", text="h_text", n_records=3, starts="h_tstarts", encoding=0, len=5, canonical=0, pos="h_rpos",
+                        offsets="h_voffs", values="h_vals")
+_ftext_ok = dict(ws="ws", d_text="d_fasta", n_bytes=len(FASTA), d_seq="d_packed", seq_capacity_bytes=4096, d_rec_start="d_rec_base",
+                 d_rec_text_pos="d_rec_pos", max_records=16, d_counts="d_counts")
+_ascii_pack_ok = dict(ws="ws", d_ascii="d_ascii", n_bases=64, d_packed="d_packed")
 
 
 def _variants(fn, ok, wrong_plan, overrides):
@@ -256,6 +317,83 @@ def cases():
     t += pack_cases("mm_fastq_pack_n_device_async", dict(_pack_n_ok, **_fastq), False)
     t += pack_cases("mm_fasta_pack_device", dict(_pack_ok, out_counts="h_counts"), True)
     t += pack_cases("mm_fasta_pack_n_device", dict(_pack_n_ok, out_counts="h_counts"), True)
+    # ---- the families added after the first recording (appended: the rows above keep their places in the fixture)
+    def counts_cases(fn, ok, wrong_plan, overrides):
+        return (_variants(fn, dict(ok, out="h_counts"), wrong_plan, overrides) +
+                _variants(fn + "_async", dict(ok, d_count="d_count"), wrong_plan, overrides))
+    bounds = [dict(max_bases=BIG), dict(max_bases=BIG, plan=None), dict(max_bases=BIG, plan="text"), dict(max_records=1 << 31),
+              dict(max_records=1 << 31, d_counts=None), dict(max_bases=BIG, ws=None)]
+    pc_more = bounds + small + [dict(d_counts=None), dict(d_counts=None, ws=None), dict(d_read_starts=None), dict(d_out_offsets=None),
+                                dict(plan="text", d_out_offsets=None), dict(d_packed=None), dict(packed_bytes=8),
+                                dict(packed_bytes=8, ws=None), dict(packed_bytes=8, d_counts=None)]
+    t += counts_cases("mm_run_packed_reads_counts_device", _pcounts_ok, "text", pc_more + [
+        dict(plan="sync", d_out_sk="d_sk"), dict(plan="sync", d_out_sk="d_sk", d_counts=None), dict(plan="sync", d_out_sk="d_sk", max_bases=BIG),
+        dict(d_out_sk="d_sk"), dict(plan="fwd"), dict(plan="sync")])
+    t += counts_cases("mm_run_packed_reads_skip_ambiguous_counts_device", _pcounts_skip_ok, "text", pc_more + [
+        dict(plan="fwd"), dict(plan="fwd", d_amb=None), dict(plan="fwd", max_bases=BIG), dict(plan="fwd", ws=None), dict(d_amb=None),
+        dict(d_amb=None, ws=None), dict(packed_bytes=8, d_amb=None), dict(amb_bytes=4), dict(amb_bytes=4, ws=None),
+        dict(plan="text", d_amb=None)])
+    t += counts_cases("mm_run_text_batch_counts_device", _tcounts_ok, "canon", small + [
+        dict(max_chars=BIG), dict(max_chars=BIG, plan=None), dict(max_chars=BIG, ws=None), dict(max_records=1 << 31), dict(max_chars=41),
+        dict(max_chars=41, d_counts=None), dict(max_chars=41, ws=None), dict(plan="text_sync", d_out_sk="d_sk"),
+        dict(plan="text_sync", d_out_sk="d_sk", d_counts=None), dict(d_out_sk="d_sk"), dict(d_counts=None), dict(d_counts=None, ws=None),
+        dict(d_out_offsets=None), dict(plan="canon", d_out_offsets=None), dict(d_starts=None), dict(d_text=None), dict(max_chars=0)])
+    for words in (1, 2):
+        name = "mm_values_u%d" % (64 * words)
+        dna_long, byte_long = 32 * words + 1, 8 * words + 1
+        common = [{}, dict(ws=None), dict(len=0), dict(len=0, ws=None), dict(canonical=0)]
+        for fn, ok, pk, ps, os_, vs, st in (
+                (name + "_reads_device_async", _vreads_dev_ok, "d_packed", "d_pos", "d_out_offsets", "d_values", "d_read_starts"),
+                (name + "_reads_host", _vreads_host_ok, "packed", "pos", "offsets", "values", "read_starts")):
+            rows = common + [dict(len=dna_long), dict(len=dna_long, ws=None), {"len": dna_long, pk: None}, dict(n_reads=0),
+                             {"n_reads": 0, pk: None}, {pk: None}, {ps: None}, {os_: None}, {vs: None}, {"len": 0, pk: None},
+                             {st: None, "read_stride": 20}, {st: None, "read_stride": 20, "packed_bytes": 8}, dict(base_offset=BIG),
+                             dict(base_offset=BIG, ws=None)]
+            rows += ([dict(n_pos_max=0), {"n_pos_max": 0, pk: None}] if fn.endswith("_async") else
+                     [{st: "h_starts_dec"}, {st: "h_starts_dec", "ws": None}, {st: "h_starts_dec", "len": 0}, dict(offsets="h_voffs_dec"),
+                      {st: "h_starts_big"}])
+            t += [(fn, dict(ok, **o)) for o in rows]
+        t += [(name + "_batch_device_async", dict(_vbatch_ok, **o)) for o in common + [
+            dict(len=dna_long), dict(len=dna_long, ws=None), dict(len=dna_long, offsets="h_voffs_dec"), dict(n_seqs=0),
+            dict(n_seqs=0, d_packed=None), dict(d_packed=None), dict(packed_bytes=None), dict(n_bases=None), dict(d_pos=None),
+            dict(offsets=None), dict(d_values=None), dict(offsets="h_voffs_dec"), dict(offsets="h_voffs_dec", ws=None),
+            dict(packed_bytes="h_bbytes_small"), dict(packed_bytes="h_bbytes_small", offsets="h_voffs_dec"), dict(d_packed="h_bptrs_null"),
+            dict(n_seqs=BIG), dict(n_seqs=BIG, ws=None), dict(base_offsets="h_bbases")]]
+        text_rows = common + [dict(len=byte_long), dict(len=byte_long, ws=None), dict(canonical=1), dict(canonical=1, len=byte_long),
+                              dict(encoding=1), dict(encoding=1, canonical=1), dict(encoding=1, len=dna_long), dict(encoding=2),
+                              dict(encoding=2, len=0), dict(encoding=2, ws=None)]
+        t += [(name + "_text_device_async", dict(_vtext_dev_ok, **o)) for o in text_rows + [
+            dict(n=BIG), dict(n=BIG, ws=None), dict(n=BIG, encoding=2), dict(n=41), dict(n=41, d_text=None), dict(text_bytes=39),
+            dict(n_pos=0), dict(n_pos=0, d_text=None), dict(d_text=None), dict(d_pos=None), dict(d_values=None)]]
+        t += [(name + "_text_host", dict(_vtext_host_ok, **o)) for o in text_rows + [
+            dict(n=BIG, text=None), dict(n_pos=0), dict(n_pos=0, text=None), dict(text=None), dict(pos=None), dict(values=None)]]
+        t += [(name + "_text_batch_device_async", dict(_vtbatch_dev_ok, **o)) for o in text_rows + [
+            dict(n_chars=BIG), dict(n_chars=BIG, ws=None), dict(n_records=1 << 31), dict(n_chars=41), dict(text_bytes=39),
+            dict(text_bytes=39, d_starts=None), dict(n_records=0), dict(n_pos_max=0), dict(n_pos_max=0, d_text=None), dict(d_text=None),
+            dict(d_starts=None), dict(d_pos=None), dict(d_out_offsets=None), dict(d_values=None)]]
+        t += [(name + "_text_batch_counts_device_async", dict(_vtcounts_ok, **o)) for o in text_rows + [
+            dict(max_chars=BIG), dict(max_chars=BIG, ws=None), dict(max_records=1 << 31), dict(max_chars=41), dict(max_chars=41, d_counts=None),
+            dict(max_records=0), dict(max_records=0, d_counts=None), dict(n_pos_max=0), dict(d_text=None), dict(d_starts=None),
+            dict(d_counts=None), dict(d_counts=None, ws=None), dict(d_pos=None), dict(d_out_offsets=None), dict(d_values=None)]]
+        t += [(name + "_text_batch_host", dict(_vtbatch_host_ok, **o)) for o in text_rows + [
+            dict(starts="h_tstarts_dec"), dict(starts="h_tstarts_dec", ws=None), dict(starts="h_tstarts_dec", len=0),
+            dict(offsets="h_voffs_dec"), dict(starts="h_starts_big"), dict(n_records=1 << 31), dict(n_records=0),
+            dict(n_records=0, text=None, starts=None), dict(text=None), dict(starts=None), dict(pos=None), dict(offsets=None),
+            dict(values=None)]]
+    ftext_rows = [{}, dict(ws=None), dict(d_counts=None), dict(d_rec_start=None), dict(d_rec_text_pos=None), dict(n_bytes=BIG),
+                  dict(n_bytes=BIG, ws=None), dict(d_seq="d_packed+1"), dict(d_seq="d_packed+1", n_bytes=BIG), dict(d_seq="d_packed+1", ws=None),
+                  dict(n_bytes=0), dict(n_bytes=0, d_text=None), dict(d_text=None), dict(d_seq=None), dict(n_bytes=0, d_counts=None)]
+    t += [("mm_fasta_text_device_async", dict(_ftext_ok, **o)) for o in ftext_rows]
+    ftext_sync_ok = dict(_ftext_ok, out_counts="h_counts")
+    t += [("mm_fasta_text_device", dict(ftext_sync_ok, **o)) for o in ftext_rows]
+    t += [("mm_fasta_text_device", dict(ftext_sync_ok, **o)) for o in (
+        _fastq, dict(_fastq, ws=None), dict(out_counts=None), dict(out_counts=None, ws=None), dict(out_counts=None, n_bytes=BIG),
+        dict(seq_capacity_bytes=4), dict(max_records=1), dict(_fastq, seq_capacity_bytes=4))]
+    ascii_rows = [{}, dict(ws=None), dict(n_bases=0), dict(n_bases=0, d_ascii=None), dict(n_bases=0, ws=None), dict(d_ascii=None),
+                  dict(d_packed=None), dict(d_ascii=None, ws=None), dict(n_bases=63)]
+    t += [("mm_pack_ascii_device_async", dict(_ascii_pack_ok, **o)) for o in ascii_rows]
+    t += [("mm_pack_ascii_n_device_async", dict(dict(_ascii_pack_ok, d_amb="d_ambout"), **o)) for o in ascii_rows + [
+        dict(d_amb=None), dict(d_amb=None, ws=None), dict(d_amb=None, n_bases=0), dict(d_amb=None, d_packed=None)]]
     names = {fn: [a.split(":")[0] for a in sig.split()] for fn, sig in SIG.items()}
     for fn, args in t:
         assert sorted(names[fn]) == sorted(args), (fn, sorted(args))
@@ -290,6 +428,11 @@ class Env:
             "h_tstarts": np.array([0, 10, 25, 40], dtype=np.uint64), "h_tstarts_dec": np.array([0, 25, 10, 40], dtype=np.uint64),
             "h_lens": np.array([20, 20, 20], dtype=np.uint32), "h_vpos": np.array([0, 3, 10, 27], dtype=np.uint32),
             "h_fasta": np.frombuffer(FASTA, dtype=np.uint8), "h_fastq": np.frombuffer(FASTQ, dtype=np.uint8),
+            "h_rcounts": np.array([60, 3], dtype=np.uint64), "h_tcounts": np.array([40, 3], dtype=np.uint64),
+            "h_rpos": np.array([0, 3, 10, 2], dtype=np.uint32), "h_voffs": np.array([0, 2, 3, 4], dtype=np.uint64),
+            "h_voffs_dec": np.array([0, 3, 2, 4], dtype=np.uint64),
+            "h_bbytes": np.array([10, 10, 10], dtype=np.uint64), "h_bbytes_small": np.array([10, 9, 10], dtype=np.uint64),
+            "h_bbases": np.array([40, 40, 40], dtype=np.uint64),
         }
         size = 1 << 16  # (every buffer is far larger than any size a case states)
         self.buf = {}
@@ -302,6 +445,11 @@ class Env:
             self.buf["h_" + name] = np.zeros(size, dtype=np.uint8)
         for name in ("out", "sk", "offs", "count", "counts", "vals", "packed", "rec_base", "rec_pos", "ambout"):
             self.buf["d_" + name] = torch.zeros(size, dtype=torch.uint8, device="cuda")
+        # the batch values' table of device pointers: three 40-base sequences inside d_seq (and one with a NULL entry)
+        for name, ptrs in (("h_bptrs", [0, 10, 20]), ("h_bptrs_null", [0, None, 20])):
+            b = np.zeros(size, dtype=np.uint8)
+            b[:24] = np.array([0 if p is None else self.buf["d_seq"].data_ptr() + p for p in ptrs], dtype=np.uint64).view(np.uint8)
+            self.buf[name] = b
         torch.cuda.synchronize()
 
     def address(self, name):
