@@ -523,6 +523,66 @@ int mm_debug_values_read_of(const uint64_t *offsets /* [n_reads + 1] */, uint64_
                             uint64_t n, int64_t *out_read);
 uint32_t mm_values_reads_lds_stage(void);
 
+/* ------------------------------------------------- one minimizer per record */
+
+/* one_minimizer(seq, hasher) (src/minimizers.rs:22-28, re-exported at src/lib.rs:211) of EVERY record of a batch in one
+ * call: out[r] is the smallest p in [0, len_r - k] whose h(p) & 0xffff0000 is minimal over the k-mers of record r - the
+ * leftmost position of the minimal masked hash.  h is the hasher as mm_hasher_t / mm_text_hasher_t define it, the
+ * canonical sum h_fw + h_rc when hasher->canonical is set.  Positions are record-local.
+ *   - A record with len_r < k - the empty record included - gets MM_NO_MINIMIZER.  The reference's unwrap() panics there
+ *     (src/minimizers.rs:27); in a batch short records are data, not an error.  The value differs from the reference's
+ *     SKIPPED (u32::MAX - 1).
+ *   - There is NO strand vote: the reference has no one_canonical_minimizer (FIXME at src/minimizers.rs:30), so a canonical
+ *     hasher only changes the hash.
+ * k is a run-time value (any k >= 1, no plan); uses: bucketing reads by their minimizer, assigning super-k-mers, unitigs or
+ * query k-mers to a partition, one anchor per protein.
+ *
+ * mm_one_minimizer_reads_device_async: the two layouts of mm_values_u64_reads_device_async.
+ *   d_packed / packed_bytes / base_offset   the packed buffer (any alignment); no byte outside it is loaded
+ *   d_read_starts [n_reads + 1] (device)    read r = bases [starts[r], starts[r + 1]) from base_offset - what
+ *                                           mm_fasta_pack_device and mm_fastq_pack_device_async write; or NULL:
+ *   read_stride / read_len                  read r = the read_len bases at r * read_stride (a 64-bit product),
+ *                                           read_len <= read_stride (else MM_ERR_BAD_MODE); ignored with starts
+ *   d_out_pos [n_reads]                     exactly n_reads words are written
+ * mm_one_minimizer_text_batch_device_async: records of byte text in the mm_run_text_batch_device_async layout (what
+ * mm_fasta_text_device writes); the 256-entry tables travel as the text runs' tables do (a ring of page-locked slots).
+ * Checks, in this order: MM_ERR_NULL (workspace, hasher, a buffer or output needed for n_reads > 0), MM_ERR_K_ZERO, then the
+ * layout: MM_ERR_LEN_TOO_LARGE (n_reads >= 2^32; host forms: a record of 2^32 - 1 symbols or more), MM_ERR_CAPACITY
+ * (base_offset, a fixed-stride layout's last read or - host forms - starts[n] past the buffer), MM_ERR_UNSORTED (host forms:
+ * decreasing starts).  n_reads == 0 returns MM_OK with nothing launched.  Device forms: unordered starts are the caller's
+ * breach - the output is then undefined, but nothing outside the buffers named here is read or written.  n_reads comes from
+ * the host (no counts-on-device form).  Every call runs on the workspace's stream and restores the caller's current device;
+ * results are valid after mm_workspace_sync.  Kernels (mm_one_min.hip): a fill of one 64-bit key per record, one workgroup
+ * per mm_one_minimizer_tile() k-mer start positions that ends in one 64-bit atomic minimum per (tile, record) pair, and a
+ * small kernel that turns keys into positions. */
+#define MM_NO_MINIMIZER 0xFFFFFFFFu
+int mm_one_minimizer_reads_device_async(mm_workspace_t *ws, const mm_hasher_t *hasher, uint32_t k, const void *d_packed,
+                                        uint64_t packed_bytes, uint64_t base_offset, uint64_t n_reads,
+                                        const uint64_t *d_read_starts /* [n_reads + 1] or NULL */, uint32_t read_stride,
+                                        uint32_t read_len, uint32_t *d_out_pos /* [n_reads] */);
+int mm_one_minimizer_text_batch_device_async(mm_workspace_t *ws, const mm_text_hasher_t *hasher, uint32_t k,
+                                             const void *d_text, uint64_t text_bytes, uint64_t n_records,
+                                             const uint64_t *d_starts /* [n_records + 1] */,
+                                             uint32_t *d_out_pos /* [n_records] */);
+/* The same from HOST memory: one upload (the bytes and the starts), the launches, one download; they wait. */
+int mm_one_minimizer_reads_host(mm_workspace_t *ws, const mm_hasher_t *hasher, uint32_t k, const uint8_t *packed,
+                                uint64_t packed_bytes, uint64_t base_offset, uint64_t n_reads,
+                                const uint64_t *read_starts /* [n_reads + 1] or NULL */, uint32_t read_stride,
+                                uint32_t read_len, uint32_t *out_pos /* [n_reads] */);
+int mm_one_minimizer_text_batch_host(mm_workspace_t *ws, const mm_text_hasher_t *hasher, uint32_t k, const uint8_t *text,
+                                     uint64_t text_bytes, uint64_t n_records, const uint64_t *starts /* [n_records + 1] */,
+                                     uint32_t *out_pos /* [n_records] */);
+/* K-mer start positions one workgroup covers (tests place their boundaries by it). */
+uint32_t mm_one_minimizer_tile(void);
+/* The kernel's own per-tile function on the host, tile after tile, the per-tile keys combined by minimum (no device; for
+ * tests).  `tile` overrides the tile size (0: mm_one_minimizer_tile()).  The host forms' checks and codes, minus the
+ * workspace. */
+int mm_debug_one_minimizer_reads(const mm_hasher_t *hasher, uint32_t k, const uint8_t *packed, uint64_t packed_bytes,
+                                 uint64_t base_offset, uint64_t n_reads, const uint64_t *read_starts, uint32_t read_stride,
+                                 uint32_t read_len, uint32_t tile, uint32_t *out_pos);
+int mm_debug_one_minimizer_text_batch(const mm_text_hasher_t *hasher, uint32_t k, const uint8_t *text, uint64_t text_bytes,
+                                      uint64_t n_records, const uint64_t *starts, uint32_t tile, uint32_t *out_pos);
+
 /* Output::values_u64 / values_u128 (src/lib.rs:584-629) of EVERY sequence of a device batch in one launch: what the loop
  * over the contigs (bench/src/bin/paper.rs:410-431: Builder::run per sequence) and Output::values_* per sequence computes,
  * in place of one mm_values_*_device_async call per sequence.  The inputs are what mm_run_batch_device takes and returns;

@@ -768,6 +768,60 @@ class DeviceGroup {
     mm_device_group_t *g_ = nullptr;
 };
 
+// ---- one_minimizer(seq, hasher) (src/minimizers.rs:22-28, re-exported at src/lib.rs:211): the leftmost position that
+// minimises hash & 0xffff0000 over the k-mers of a sequence; no strand vote (the reference has no one_canonical_minimizer,
+// FIXME at src/minimizers.rs:30).  `Hasher` is any of the hasher structs above (its `tables` go to the C call).  The
+// *_many forms take every record in ONE call (mm_one_minimizer_reads_host / mm_one_minimizer_text_batch_host) and give
+// MM_NO_MINIMIZER for a record shorter than k; the single forms throw Error(MM_ERR_CAPACITY) there,
+// where the reference's unwrap() panics.
+inline std::vector<uint32_t> one_minimizer_many(const std::vector<PackedSeq> &reads, const mm_hasher_t &hasher, uint32_t k,
+                                                Workspace *ws = nullptr) {
+    Workspace &w = ws ? *ws : Workspace::thread_default();
+    std::vector<uint64_t> starts(reads.size() + 1, 0);
+    for (size_t r = 0; r < reads.size(); ++r) starts[r + 1] = starts[r] + reads[r].len;
+    std::vector<uint8_t> packed((starts.back() + 3) / 4 + 1, 0);
+    for (size_t r = 0; r < reads.size(); ++r)  // (base by base: any source offset to any destination offset)
+        for (uint64_t i = 0; i < reads[r].len; ++i) {
+            const uint64_t s = reads[r].offset + i, d = starts[r] + i;
+            packed[d >> 2] |= (uint8_t)(((reads[r].data[s >> 2] >> (2 * (s & 3))) & 3u) << (2 * (d & 3)));
+        }
+    std::vector<uint32_t> out(reads.size());
+    check(mm_one_minimizer_reads_host(w.get(), &hasher, k, packed.data(), packed.size(), 0, reads.size(), starts.data(), 0, 0,
+                                      out.data()));
+    return out;
+}
+inline std::vector<uint32_t> one_minimizer_many(const std::vector<TextSeq> &records, const mm_text_hasher_t &hasher, uint32_t k,
+                                                Workspace *ws = nullptr) {
+    Workspace &w = ws ? *ws : Workspace::thread_default();
+    std::vector<uint64_t> starts(records.size() + 1, 0);
+    for (size_t r = 0; r < records.size(); ++r) starts[r + 1] = starts[r] + records[r].len;
+    std::vector<uint8_t> text(starts.back() + 1, 0);
+    for (size_t r = 0; r < records.size(); ++r)
+        if (records[r].len) std::memcpy(text.data() + starts[r], records[r].data, records[r].len);
+    std::vector<uint32_t> out(records.size());
+    check(mm_one_minimizer_text_batch_host(w.get(), &hasher, k, text.data(), starts.back(), records.size(), starts.data(),
+                                           out.data()));
+    return out;
+}
+template <class Hasher>
+inline std::vector<uint32_t> one_minimizer_many(const std::vector<PackedSeq> &reads, const Hasher &hasher, uint32_t k) {
+    return one_minimizer_many(reads, hasher.tables, k);
+}
+template <class Hasher>
+inline std::vector<uint32_t> one_minimizer_many(const std::vector<TextSeq> &records, const Hasher &hasher, uint32_t k) {
+    return one_minimizer_many(records, hasher.tables, k);
+}
+template <class Hasher>
+inline uint32_t one_minimizer(PackedSeq seq, const Hasher &hasher, uint32_t k) {
+    if (seq.len < k) throw Error(MM_ERR_CAPACITY);
+    return one_minimizer_many(std::vector<PackedSeq>{seq}, hasher.tables, k)[0];
+}
+template <class Hasher>
+inline uint32_t one_minimizer(TextSeq seq, const Hasher &hasher, uint32_t k) {
+    if (seq.len < k) throw Error(MM_ERR_CAPACITY);
+    return one_minimizer_many(std::vector<TextSeq>{seq}, hasher.tables, k)[0];
+}
+
 // constructors, src/lib.rs:240-321
 inline Builder<false, 0> minimizers(uint32_t k, uint32_t w) { return {k, w}; }
 inline Builder<true, 0> canonical_minimizers(uint32_t k, uint32_t w) { return {k, w}; }

@@ -247,6 +247,16 @@ def _load_lib():
         L.mm_debug_values_read_of.argtypes = [u64p, C.c_uint64, u64p, C.c_uint64, C.POINTER(C.c_int64)]
         L.mm_values_reads_lds_stage.argtypes = []
         L.mm_values_reads_lds_stage.restype = C.c_uint32
+        one_min_reads_tail = [C.c_uint64, C.c_uint64, C.c_uint64, vp, C.c_uint32, C.c_uint32]
+        L.mm_one_minimizer_reads_device_async.argtypes = [vp, vp, C.c_uint32, vp] + one_min_reads_tail + [vp]
+        L.mm_one_minimizer_reads_host.argtypes = [vp, vp, C.c_uint32, vp] + one_min_reads_tail + [vp]
+        L.mm_debug_one_minimizer_reads.argtypes = [vp, C.c_uint32, vp] + one_min_reads_tail + [C.c_uint32, vp]
+        one_min_text_tail = [C.c_uint64, C.c_uint64, vp]
+        L.mm_one_minimizer_text_batch_device_async.argtypes = [vp, vp, C.c_uint32, vp] + one_min_text_tail + [vp]
+        L.mm_one_minimizer_text_batch_host.argtypes = [vp, vp, C.c_uint32, vp] + one_min_text_tail + [vp]
+        L.mm_debug_one_minimizer_text_batch.argtypes = [vp, C.c_uint32, vp] + one_min_text_tail + [C.c_uint32, vp]
+        L.mm_one_minimizer_tile.argtypes = []
+        L.mm_one_minimizer_tile.restype = C.c_uint32
         values_batch_args = [vp, C.c_uint64, C.POINTER(vp), u64p, u64p, u64p, C.c_uint32, C.c_int, vp, u64p, vp]
         L.mm_values_u64_batch_device_async.argtypes = values_batch_args
         L.mm_values_u128_batch_device_async.argtypes = values_batch_args
@@ -400,6 +410,9 @@ EXPORTED_SYMBOLS = [
     "mm_debug_lane_counts_view",
     "mm_fastx_stream_create", "mm_fastx_stream_feed", "mm_fastx_stream_finish", "mm_fastx_stream_next",
     "mm_fastx_stream_destroy", "mm_debug_fastx_cut", "mm_fastx_stream_pieces", "mm_debug_fastx_split",
+    "mm_one_minimizer_reads_device_async", "mm_one_minimizer_text_batch_device_async", "mm_one_minimizer_reads_host",
+    "mm_one_minimizer_text_batch_host", "mm_one_minimizer_tile", "mm_debug_one_minimizer_reads",
+    "mm_debug_one_minimizer_text_batch",
 ]
 
 
@@ -2401,6 +2414,143 @@ def values_reads_host(builder: "Builder", reads, pos, offsets, u128=False):
     if u128:
         return [int(vals[2 * i]) | (int(vals[2 * i + 1]) << 64) for i in range(n)]
     return vals[:n]
+
+
+# ------------------------------------------------------------------ one minimizer per record (src/minimizers.rs:22-28)
+
+NO_MINIMIZER = 0xFFFFFFFF  # MM_NO_MINIMIZER: the record is shorter than k
+
+
+def one_minimizer_tile() -> int:
+    """K-mer start positions one workgroup of the one-minimizer kernel covers (``mm_one_minimizer_tile``)."""
+    return int(lib().mm_one_minimizer_tile())
+
+
+def _vp_of(a):
+    """void * of a numpy array or a torch tensor (None stays None)."""
+    if a is None:
+        return None
+    return C.c_void_p(a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr())
+
+
+def debug_one_minimizer_reads(hasher: Hasher, k: int, packed, n_reads: int, read_starts=None, read_stride=0, read_len=0,
+                              base_offset=0, tile=0) -> np.ndarray:
+    """The one-minimizer kernel's per-tile function on the host, tile after tile (``mm_debug_one_minimizer_reads``, no
+    GPU): ``packed`` a uint8 array, the layout as ``one_minimizer_reads_device`` takes it (``read_starts``: uint64 array
+    of n + 1), ``tile`` overrides the tile size (0: the kernel's).  Returns ``np.uint32[n_reads]``."""
+    packed = np.ascontiguousarray(packed, dtype=np.uint8)
+    starts = np.ascontiguousarray(read_starts, dtype=np.uint64) if read_starts is not None else None
+    out = np.zeros(max(1, int(n_reads)), dtype=np.uint32)
+    _check(lib().mm_debug_one_minimizer_reads(C.byref(hasher), int(k), _vp_of(packed), len(packed), int(base_offset),
+                                              int(n_reads), _vp_of(starts), int(read_stride), int(read_len), int(tile),
+                                              _vp_of(out)))
+    return out[:int(n_reads)]
+
+
+def debug_one_minimizer_text_batch(hasher: TextHasher, k: int, text, starts, tile=0) -> np.ndarray:
+    """The same for records of byte text (``mm_debug_one_minimizer_text_batch``, no GPU): ``text`` a uint8 array,
+    ``starts`` the n + 1 record starts."""
+    text = np.ascontiguousarray(text, dtype=np.uint8)
+    starts = np.ascontiguousarray(starts, dtype=np.uint64)
+    n = len(starts) - 1
+    out = np.zeros(max(1, n), dtype=np.uint32)
+    _check(lib().mm_debug_one_minimizer_text_batch(C.byref(hasher), int(k), _vp_of(text), len(text), n, _vp_of(starts),
+                                                   int(tile), _vp_of(out)))
+    return out[:n]
+
+
+def one_minimizer_reads_device(hasher: Hasher, k: int, d_packed, n_reads=None, out_pos=None, read_starts=None, read_stride=0,
+                               read_len=0, base_offset=0, ws=None):
+    """``one_minimizer`` (src/minimizers.rs:22-28) of EVERY read of a packed device buffer in one call
+    (``mm_one_minimizer_reads_device_async``): ``d_packed`` a uint8 CUDA tensor - or a ``FastaRecords``, whose starts are
+    then taken - and the layout: ``read_starts`` (int64 CUDA tensor of n + 1) or ``read_stride`` / ``read_len``.
+    ``out_pos`` (int32 CUDA tensor, n_reads) receives the read-local position of the leftmost minimal
+    ``hash & 0xffff0000`` per read, ``NO_MINIMIZER`` for a read shorter than k; a new tensor is returned when it is None.
+    Asynchronous on ``ws`` (default: the device's default workspace): ``Workspace.sync`` before reading."""
+    import torch
+    if isinstance(d_packed, FastaRecords):
+        rec = d_packed
+        d_packed, n_reads = rec.packed, len(rec)
+        read_starts = torch.from_numpy(np.ascontiguousarray(rec.base, dtype=np.uint64).view(np.int64)).to(d_packed.device)
+    n_reads = int(n_reads)
+    dev = d_packed.device
+    if ws is None:
+        ws = default_workspace(dev.index or 0)
+    if out_pos is None:
+        out_pos = torch.zeros(n_reads, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+    elif out_pos.numel() < n_reads:
+        raise ValueError(f"out_pos holds {out_pos.numel()} words, {n_reads} needed")
+    if read_starts is not None and read_starts.numel() < n_reads + 1:
+        raise ValueError(f"{n_reads} reads need {n_reads + 1} starts")
+    _check(lib().mm_one_minimizer_reads_device_async(ws.h, C.byref(hasher), int(k), _vp_of(d_packed), int(d_packed.numel()),
+                                                     int(base_offset), n_reads, _vp_of(read_starts), int(read_stride),
+                                                     int(read_len), _vp_of(out_pos)))
+    return out_pos
+
+
+def one_minimizer_text_batch_device(hasher: TextHasher, k: int, d_text, d_starts=None, n_records=None, out_pos=None, ws=None):
+    """``one_minimizer`` of EVERY record of a device text batch in one call
+    (``mm_one_minimizer_text_batch_device_async``): ``d_text`` a uint8 CUDA tensor and ``d_starts`` an int64 CUDA tensor of
+    n + 1 starts - or a ``FastaTextRecords`` in place of both.  ``out_pos`` as for ``one_minimizer_reads_device``."""
+    import torch
+    if isinstance(d_text, FastaTextRecords):
+        d_text, d_starts = d_text.seq, d_text.starts
+    if n_records is None:
+        n_records = d_starts.numel() - 1
+    n_records = int(n_records)
+    if n_records < 0 or d_starts.numel() < n_records + 1:
+        raise ValueError("d_starts holds n + 1 starts")
+    dev = d_starts.device
+    if ws is None:
+        ws = default_workspace(dev.index or 0)
+    if out_pos is None:
+        out_pos = torch.zeros(n_records, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+    elif out_pos.numel() < n_records:
+        raise ValueError(f"out_pos holds {out_pos.numel()} words, {n_records} needed")
+    _check(lib().mm_one_minimizer_text_batch_device_async(ws.h, C.byref(hasher), int(k),
+                                                          _vp_of(d_text) if d_text.numel() else None, int(d_text.numel()),
+                                                          n_records, _vp_of(d_starts), _vp_of(out_pos)))
+    return out_pos
+
+
+def one_minimizer_reads_host(reads, hasher: Hasher, k: int, ws=None) -> np.ndarray:
+    """``one_minimizer`` of many host reads (``PackedSeq`` views / ASCII ``bytes``) in ONE call
+    (``mm_one_minimizer_reads_host``): ``np.uint32[n]``, ``NO_MINIMIZER`` for a read shorter than k."""
+    packed, starts = _pack_reads(reads)
+    n = len(starts) - 1
+    out = np.zeros(max(1, n), dtype=np.uint32)
+    ws = ws or default_workspace(0)
+    _check(lib().mm_one_minimizer_reads_host(ws.h, C.byref(hasher), int(k), _vp_of(packed), len(packed), 0, n, _vp_of(starts),
+                                             0, 0, _vp_of(out)))
+    return out[:n]
+
+
+def one_minimizer_text_batch_host(records, hasher: TextHasher, k: int, ws=None) -> np.ndarray:
+    """``one_minimizer`` of many host records of byte text in ONE call (``mm_one_minimizer_text_batch_host``)."""
+    text, starts = _text_records(records)
+    n = len(starts) - 1
+    out = np.zeros(max(1, n), dtype=np.uint32)
+    ws = ws or default_workspace(0)
+    _check(lib().mm_one_minimizer_text_batch_host(ws.h, C.byref(hasher), int(k), _vp_of(text), len(text), n, _vp_of(starts),
+                                                  _vp_of(out)))
+    return out[:n]
+
+
+def one_minimizer(seq, hasher, k: int) -> int:
+    """``one_minimizer(seq, hasher)`` (src/minimizers.rs:22-28): the leftmost position that minimises
+    ``hash & 0xffff0000`` over the k-mers of ``seq`` (``PackedSeq``, ``AsciiSeq`` or byte text).  A ``Hasher`` over
+    ``AsciiSeq`` / bytes reads them as ASCII DNA (``TextHasher.from_dna``).  Raises ``ValueError`` when ``len(seq) < k``,
+    where the reference panics."""
+    if len(seq) < k:
+        raise ValueError(f"one_minimizer: the sequence has {len(seq)} symbols, k is {k}")
+    if isinstance(seq, PackedSeq):
+        return int(one_minimizer_reads_host([seq], hasher, k)[0])
+    data = seq.seq if isinstance(seq, AsciiSeq) else seq
+    if isinstance(hasher, Hasher):
+        hasher = TextHasher.from_dna(hasher)
+    return int(one_minimizer_text_batch_host([data], hasher, k)[0])
 
 
 def run_fasta_device(builder: "Builder", records: FastaRecords, out_pos, out_sk=None):

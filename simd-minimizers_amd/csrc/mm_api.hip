@@ -23,6 +23,7 @@
 #include "mm_lane_counts.h"
 #include "mm_text_counts.h"
 #include "mm_values_batch.h"
+#include "mm_one_min.h"
 #include "mm_values_reads.h"
 #include "mm_values_text.h"
 
@@ -242,6 +243,9 @@ struct mm_workspace {
     uint64_t d_amb_bytes = 0;
     unsigned long long *d_vals = nullptr;
     uint64_t d_vals_elems = 0;
+    // one minimizer per record (mm_one_minimizer_*): one 64-bit key per record
+    unsigned long long *d_one_min_keys = nullptr;
+    uint64_t d_one_min_keys_elems = 0;
     // text runs: a ring of device copies of text plans' tables, staged through page-locked slots; a slot is rewritten only
     // after the event of its last upload (kTextTableSlots - 1 other uploads later), so no text call waits for the stream
     static const int kTextTableSlots = 8;
@@ -948,6 +952,7 @@ void mm_workspace_destroy(mm_workspace_t *ws) {
     if (ws->h_small) hipHostFree(ws->h_small);
     if (ws->d_amb) hipFree(ws->d_amb);
     if (ws->d_vals) hipFree(ws->d_vals);
+    if (ws->d_one_min_keys) hipFree(ws->d_one_min_keys);
     if (ws->d_text_tables) hipFree(ws->d_text_tables);
     if (ws->d_text_tiles) hipFree(ws->d_text_tiles);
     if (ws->h_text_tables) hipHostFree(ws->h_text_tables);
@@ -3506,6 +3511,253 @@ int mm_debug_values_read_of(const uint64_t *offsets, uint64_t n_reads, const uin
 }
 
 uint32_t mm_values_reads_lds_stage(void) { return mm::kValuesReadsStage; }
+
+// ---- one_minimizer(seq, hasher) (src/minimizers.rs:22-28, re-exported at src/lib.rs:211) of EVERY record of a packed
+// buffer or of a byte text in one call (mm_one_min.hip): out[r] = the leftmost position that minimises hash & 0xffff0000
+// over record r's k-mers, MM_NO_MINIMIZER for a record shorter than k.  No strand vote: the reference has no
+// one_canonical_minimizer (FIXME at src/minimizers.rs:30), a canonical hasher only changes the hash.
+namespace {
+
+// The rolling tables over the 4 packed symbols: make_text_tables' algebra.
+struct OneMinDnaTables {
+    mm::OneMinPair t_in[4], t_out[4];
+    uint32_t fw0, rc0, rot, canonical;
+};
+OneMinDnaTables one_min_dna_tables(const mm_hasher_t &h, uint32_t k) {
+    OneMinDnaTables t;
+    const uint32_t R = h.rot & 31u;
+    const uint32_t df = rotl32(h.fw_xor, R) ^ h.fw_xor, dr = rotr32(h.rc_xor, R) ^ h.rc_xor;
+    for (int c = 0; c < 4; ++c) {
+        t.t_in[c].x = h.fw[c] ^ df;
+        t.t_in[c].y = rotl32(h.rc[c], (uint32_t)(((uint64_t)R * (k - 1)) & 31u)) ^ dr;
+        t.t_out[c].x = rotl32(h.fw[c], (uint32_t)(((uint64_t)R * k) & 31u));
+        t.t_out[c].y = rotr32(h.rc[c], R);
+    }
+    t.fw0 = h.fw_xor;
+    t.rc0 = h.rc_xor;
+    t.rot = R;
+    t.canonical = h.canonical ? 1u : 0u;
+    return t;
+}
+
+// The checks that need no device, in the order the header states: MM_ERR_NULL, MM_ERR_K_ZERO, then the layout.  `symbols`:
+// what the buffer holds from symbol 0 (packed: 4 * packed_bytes - base_offset, checked here; text: text_bytes).
+// host_starts: the starts when the caller has them on the host (host and debug forms), else null.  MM_OK with n == 0:
+// nothing to do.
+int one_min_check(const void *hasher, uint32_t k, const void *data, uint64_t data_bytes, bool packed, uint64_t base_offset,
+                  uint64_t n, bool have_starts, const uint64_t *host_starts, uint32_t stride, uint32_t len, const void *out) {
+    if (!hasher) return MM_ERR_NULL;
+    if (n && (!out || (!data && data_bytes))) return MM_ERR_NULL;
+    if (k == 0) return MM_ERR_K_ZERO;
+    if (n == 0) return MM_OK;
+    if (n >= (1ull << 32) || data_bytes >= (1ull << 60)) return MM_ERR_LEN_TOO_LARGE;
+    const uint64_t buffer = packed ? 4 * data_bytes : data_bytes;
+    if (base_offset > buffer) return MM_ERR_CAPACITY;
+    const uint64_t symbols = buffer - base_offset;
+    if (!have_starts) {
+        if (len > stride) return MM_ERR_BAD_MODE;
+        if ((n - 1) * (uint64_t)stride + len > symbols) return MM_ERR_CAPACITY;
+    } else if (host_starts) {
+        for (uint64_t r = 0; r < n; ++r) {
+            if (host_starts[r] > host_starts[r + 1]) return MM_ERR_UNSORTED;
+            if (host_starts[r + 1] - host_starts[r] >= 0xFFFFFFFFull) return MM_ERR_LEN_TOO_LARGE;
+        }
+        if (host_starts[n] > symbols) return MM_ERR_CAPACITY;
+    }
+    return MM_OK;
+}
+
+int one_min_keys(mm_workspace_t *ws, uint64_t n) {
+    return grow(ws->d_one_min_keys, ws->d_one_min_keys_elems, n, sizeof(unsigned long long));
+}
+
+int one_min_launch(mm_workspace_t *ws, const mm::OneMinArgs &a, const char *what) {
+    const int r = mm::launch_one_min(a, ws->stream);
+    if (r == -3) return MM_ERR_LEN_TOO_LARGE;
+    if (r) return hip_fail(hipGetLastError(), what);
+    return MM_OK;
+}
+
+// (after the checks, the workspace's device current)
+int one_min_reads_queue(mm_workspace_t *ws, const mm_hasher_t *hasher, uint32_t k, const void *d_packed, uint64_t packed_bytes,
+                        uint64_t base_offset, uint64_t n_reads, const uint64_t *d_read_starts, uint32_t read_stride,
+                        uint32_t read_len, uint32_t *d_out_pos) {
+    int r = one_min_keys(ws, n_reads);
+    if (r) return r;
+    const OneMinDnaTables t = one_min_dna_tables(*hasher, k);
+    mm::OneMinArgs a = {};
+    a.syms = static_cast<const uint8_t *>(d_packed);
+    a.base0 = base_offset;
+    a.avail = 4 * packed_bytes - base_offset;
+    a.n = n_reads;
+    a.starts = reinterpret_cast<const unsigned long long *>(d_read_starts);
+    a.stride = read_stride;
+    a.len = read_len;
+    a.k = k;
+    a.text = false;
+    for (int c = 0; c < 4; ++c) {
+        a.small_in[c] = make_uint2(t.t_in[c].x, t.t_in[c].y);
+        a.small_out[c] = make_uint2(t.t_out[c].x, t.t_out[c].y);
+    }
+    a.tables = nullptr;
+    a.fw0 = t.fw0, a.rc0 = t.rc0, a.rot = t.rot, a.canonical = t.canonical;
+    a.keys = ws->d_one_min_keys;
+    a.out = d_out_pos;
+    return one_min_launch(ws, a, "one_minimizer_reads");
+}
+
+int one_min_text_queue(mm_workspace_t *ws, const mm_text_hasher_t *hasher, uint32_t k, const void *d_text, uint64_t text_bytes,
+                       uint64_t n_records, const uint64_t *d_starts, uint32_t *d_out_pos) {
+    int r = one_min_keys(ws, n_records);
+    if (r) return r;
+    const mm::TextTables tt = make_text_tables(*hasher, k);
+    mm::OneMinArgs a = {};
+    r = text_tables_on_device(ws, tt, &a.tables);
+    if (r) return r;
+    a.syms = static_cast<const uint8_t *>(d_text);
+    a.base0 = 0;
+    a.avail = text_bytes;
+    a.n = n_records;
+    a.starts = reinterpret_cast<const unsigned long long *>(d_starts);
+    a.k = k;
+    a.text = true;
+    a.fw0 = tt.fw0, a.rc0 = tt.rc0, a.rot = tt.rot, a.canonical = tt.canonical;
+    a.keys = ws->d_one_min_keys;
+    a.out = d_out_pos;
+    return one_min_launch(ws, a, "one_minimizer_text_batch");
+}
+
+}  // namespace
+
+int mm_one_minimizer_reads_device_async(mm_workspace_t *ws, const mm_hasher_t *hasher, uint32_t k, const void *d_packed,
+                                        uint64_t packed_bytes, uint64_t base_offset, uint64_t n_reads,
+                                        const uint64_t *d_read_starts, uint32_t read_stride, uint32_t read_len,
+                                        uint32_t *d_out_pos) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (!ws) return MM_ERR_NULL;
+    const int r = one_min_check(hasher, k, d_packed, packed_bytes, true, base_offset, n_reads, d_read_starts != nullptr, nullptr,
+                                read_stride, read_len, d_out_pos);
+    if (r || n_reads == 0) return r;
+    MM_HIP(set_device(ws->device));
+    return one_min_reads_queue(ws, hasher, k, d_packed, packed_bytes, base_offset, n_reads, d_read_starts, read_stride, read_len,
+                               d_out_pos);
+}
+
+int mm_one_minimizer_text_batch_device_async(mm_workspace_t *ws, const mm_text_hasher_t *hasher, uint32_t k, const void *d_text,
+                                             uint64_t text_bytes, uint64_t n_records, const uint64_t *d_starts,
+                                             uint32_t *d_out_pos) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (!ws || (n_records && !d_starts)) return MM_ERR_NULL;
+    const int r = one_min_check(hasher, k, d_text, text_bytes, false, 0, n_records, true, nullptr, 0, 0, d_out_pos);
+    if (r || n_records == 0) return r;
+    MM_HIP(set_device(ws->device));
+    return one_min_text_queue(ws, hasher, k, d_text, text_bytes, n_records, d_starts, d_out_pos);
+}
+
+// The same from HOST memory: one upload (the bytes the records cover, the starts), the launches, one download.
+int mm_one_minimizer_reads_host(mm_workspace_t *ws, const mm_hasher_t *hasher, uint32_t k, const uint8_t *packed,
+                                uint64_t packed_bytes, uint64_t base_offset, uint64_t n_reads, const uint64_t *read_starts,
+                                uint32_t read_stride, uint32_t read_len, uint32_t *out_pos) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (!ws) return MM_ERR_NULL;
+    int r = one_min_check(hasher, k, packed, packed_bytes, true, base_offset, n_reads, read_starts != nullptr, read_starts,
+                          read_stride, read_len, out_pos);
+    if (r || n_reads == 0) return r;
+    MM_HIP(set_device(ws->device));
+    // staging: [packed bytes | starts] in d_in, positions in d_out
+    const uint64_t words = n_reads + 1;
+    const uint64_t starts_at = (packed_bytes + 15) & ~15ull;
+    r = grow_bytes(ws->d_in, ws->d_in_bytes, starts_at + (read_starts ? words * sizeof(uint64_t) : 0) + 16);
+    if (r) return r;
+    r = grow(ws->d_out, ws->d_out_elems, n_reads, sizeof(uint32_t));
+    if (r) return r;
+    uint8_t *const din = static_cast<uint8_t *>(ws->d_in);
+    if (packed_bytes) MM_HIP(hipMemcpyAsync(din, packed, packed_bytes, hipMemcpyHostToDevice, ws->stream));
+    if (read_starts)
+        MM_HIP(hipMemcpyAsync(din + starts_at, read_starts, words * sizeof(uint64_t), hipMemcpyHostToDevice, ws->stream));
+    r = one_min_reads_queue(ws, hasher, k, din, packed_bytes, base_offset, n_reads,
+                            read_starts ? reinterpret_cast<const uint64_t *>(din + starts_at) : nullptr, read_stride, read_len,
+                            ws->d_out);
+    if (r) return r;
+    MM_HIP(hipMemcpyAsync(out_pos, ws->d_out, n_reads * sizeof(uint32_t), hipMemcpyDeviceToHost, ws->stream));
+    MM_HIP(hipStreamSynchronize(ws->stream));
+    return MM_OK;
+}
+
+int mm_one_minimizer_text_batch_host(mm_workspace_t *ws, const mm_text_hasher_t *hasher, uint32_t k, const uint8_t *text,
+                                     uint64_t text_bytes, uint64_t n_records, const uint64_t *starts, uint32_t *out_pos) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (!ws || (n_records && !starts)) return MM_ERR_NULL;
+    int r = one_min_check(hasher, k, text, text_bytes, false, 0, n_records, true, starts, 0, 0, out_pos);
+    if (r || n_records == 0) return r;
+    MM_HIP(set_device(ws->device));
+    const uint64_t words = n_records + 1;
+    const uint64_t n_chars = starts[n_records];  // (<= text_bytes: checked)
+    const uint64_t starts_at = (n_chars + 15) & ~15ull;
+    r = grow_bytes(ws->d_in, ws->d_in_bytes, starts_at + words * sizeof(uint64_t));
+    if (r) return r;
+    r = grow(ws->d_out, ws->d_out_elems, n_records, sizeof(uint32_t));
+    if (r) return r;
+    uint8_t *const din = static_cast<uint8_t *>(ws->d_in);
+    if (n_chars) MM_HIP(hipMemcpyAsync(din, text, n_chars, hipMemcpyHostToDevice, ws->stream));
+    MM_HIP(hipMemcpyAsync(din + starts_at, starts, words * sizeof(uint64_t), hipMemcpyHostToDevice, ws->stream));
+    r = one_min_text_queue(ws, hasher, k, din, n_chars, n_records, reinterpret_cast<const uint64_t *>(din + starts_at), ws->d_out);
+    if (r) return r;
+    MM_HIP(hipMemcpyAsync(out_pos, ws->d_out, n_records * sizeof(uint32_t), hipMemcpyDeviceToHost, ws->stream));
+    MM_HIP(hipStreamSynchronize(ws->stream));
+    return MM_OK;
+}
+
+uint32_t mm_one_minimizer_tile(void) { return mm::kOneMinTile; }
+
+// The kernel's per-tile function on the host (no device), tile after tile, the per-tile keys combined by minimum; `tile`
+// overrides the tile size (0: the kernel's).  The refusals are the host forms', by the same function.
+extern "C++" {
+namespace {
+template <class Sym, class Lay>
+void one_min_debug_run(const Sym &sym, const Lay &lay, uint64_t n, uint64_t symbols, const mm::OneMinTables &t, uint32_t k,
+                       uint32_t tile, uint32_t *out_pos) {
+    std::vector<uint64_t> keys(n, mm::kOneMinNoKey);
+    mm::one_min_host(sym, lay, n, symbols, t, k, tile, keys.data());
+    for (uint64_t r = 0; r < n; ++r) out_pos[r] = mm::one_min_position(keys[r]);
+}
+}  // namespace
+}  // extern "C++"
+
+int mm_debug_one_minimizer_reads(const mm_hasher_t *hasher, uint32_t k, const uint8_t *packed, uint64_t packed_bytes,
+                                 uint64_t base_offset, uint64_t n_reads, const uint64_t *read_starts, uint32_t read_stride,
+                                 uint32_t read_len, uint32_t tile, uint32_t *out_pos) {
+    const int r = one_min_check(hasher, k, packed, packed_bytes, true, base_offset, n_reads, read_starts != nullptr, read_starts,
+                                read_stride, read_len, out_pos);
+    if (r || n_reads == 0) return r;
+    if (tile == 0) tile = mm::kOneMinTile;
+    const OneMinDnaTables d = one_min_dna_tables(*hasher, k);
+    const mm::OneMinTables t = {d.t_in, d.t_out, d.fw0, d.rc0, d.rot, d.canonical};
+    const mm::OneMinPacked sym{packed, base_offset};
+    const uint64_t symbols = 4 * packed_bytes - base_offset;
+    if (read_starts) {
+        one_min_debug_run(sym, mm::OneMinStarts{read_starts}, n_reads, symbols, t, k, tile, out_pos);
+    } else if (read_len < k) {
+        for (uint64_t i = 0; i < n_reads; ++i) out_pos[i] = MM_NO_MINIMIZER;
+    } else {
+        one_min_debug_run(sym, mm::OneMinStride{read_stride, read_len}, n_reads, symbols, t, k, tile, out_pos);
+    }
+    return MM_OK;
+}
+
+int mm_debug_one_minimizer_text_batch(const mm_text_hasher_t *hasher, uint32_t k, const uint8_t *text, uint64_t text_bytes,
+                                      uint64_t n_records, const uint64_t *starts, uint32_t tile, uint32_t *out_pos) {
+    if (n_records && !starts) return MM_ERR_NULL;
+    const int r = one_min_check(hasher, k, text, text_bytes, false, 0, n_records, true, starts, 0, 0, out_pos);
+    if (r || n_records == 0) return r;
+    if (tile == 0) tile = mm::kOneMinTile;
+    const mm::TextTables tt = make_text_tables(*hasher, k);
+    static_assert(sizeof(mm::OneMinPair) == sizeof(uint2), "OneMinPair has uint2's layout");
+    const mm::OneMinTables t = {reinterpret_cast<const mm::OneMinPair *>(tt.t_in),
+                                reinterpret_cast<const mm::OneMinPair *>(tt.t_out), tt.fw0, tt.rc0, tt.rot, tt.canonical};
+    one_min_debug_run(mm::OneMinText{text, 0}, mm::OneMinStarts{starts}, n_records, text_bytes, t, k, tile, out_pos);
+    return MM_OK;
+}
 
 // ---- Output::values_u64 / values_u128 (src/lib.rs:584-629) of every sequence of a device batch in ONE launch: what the
 // loop over Builder::run per contig (bench/src/bin/paper.rs:410-431) and Output::values_* per sequence computes, from the

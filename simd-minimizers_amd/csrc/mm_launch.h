@@ -279,6 +279,23 @@ struct ValuesReadsArgs {
     unsigned long long *out;                   // u64: one word per value; u128: {lo, hi}
 };
 int launch_values_reads(const ValuesReadsArgs &a, bool u128, hipStream_t stream);  // 0, -1 (HIP failure), -3 (grid too large)
+// ---- one minimizer per record (mm_one_min.hip): records of a packed buffer (2-bit symbols) or of a byte text
+struct OneMinArgs {
+    const uint8_t *syms;                 // the packed bytes / the text, any alignment
+    unsigned long long base0;            // packed: the base that is symbol 0 (base_offset); text: 0
+    unsigned long long avail;            // symbols from symbol 0 to the end of the buffer: none at or past it is loaded
+    unsigned long long n;                // records
+    const unsigned long long *starts;    // [n + 1] (device), or null (packed only): record r = [r * stride, r * stride + len)
+    unsigned long long stride, len;
+    uint32_t k;
+    bool text;
+    uint2 small_in[4], small_out[4];     // packed: the rolling tables (TextTables' algebra over 4 symbols)
+    const TextTables *tables;            // text: device
+    uint32_t fw0, rc0, rot, canonical;
+    unsigned long long *keys;            // [n] scratch
+    uint32_t *out;                       // [n]
+};
+int launch_one_min(const OneMinArgs &a, hipStream_t stream);  // 0, -1 (HIP failure), -3 (grid too large)
 int launch_pack_ascii(const uint8_t *d_ascii, uint64_t n, uint8_t *d_packed, hipStream_t stream);
 int launch_pack_ascii_n(const uint8_t *d_ascii, uint64_t n, uint8_t *d_packed, uint8_t *d_amb,
                         hipStream_t stream);

@@ -1,0 +1,159 @@
+// mm_one_min.hip — one minimizer per record in one call: one_minimizer(seq, hasher) (src/minimizers.rs:22-28, re-exported
+// at src/lib.rs:211) of EVERY record of a packed buffer or of a byte text, the leftmost position that minimises
+// hash & 0xffff_0000 over the record's k-mers.  It is a segmented argmin over records of any lengths laid back to back: a
+// record may span thousands of workgroups or share one with thousands of others.
+//
+// The arithmetic and the per-lane walk are mm_one_min.h (shared with the host: mm_debug_one_minimizer_*).  Here:
+//   - the k-mer start positions, numbered from the first record's start, are cut into tiles of kOneMinTile = 4096, one
+//     workgroup of 256 lanes each, 16 consecutive positions per lane; the grid covers what the HOST knows (the buffer's
+//     size), workgroups past the last record's end leave at once;
+//   - thread 0 finds the records of the tile's first and last position (one search and one gallop over the starts), every
+//     lane searches only between them;
+//   - the tile's symbols - T + k - 1 of them, every k up to a tile's own size - are copied to LDS by whole dwords, so the
+//     lanes' dependent chain of symbol and table look-ups never waits for global memory (a larger k reads them there);
+//   - a lane hashes its first k-mer from the definition and rolls the rest (the "simple form": (k + 16) / 16 table steps per
+//     position), tables in LDS; it keeps the minimum key per record and hands each (record, key) pair to an LDS slot
+//     (ds_min_u64), slot = record - the tile's first record; pairs of records beyond kOneMinSlots slots - more than that
+//     many records, empty ones included, inside a tile - go to global memory directly;
+//   - after a barrier the used slots go out with ONE atomicMin(unsigned long long) per (tile, record) pair into the key
+//     array (n words preset to all-ones on the same stream), a single global_atomic_umin_x2 without a return value;
+//   - a second small kernel turns keys into positions: all-ones -> MM_NO_MINIMIZER.
+// Nothing outside the symbols [0, limit), starts[0 .. n] and keys / out [0, n) is touched, whatever the starts hold: every
+// record index is clamped to [0, n - 1] by the searches and every symbol index lies below the limit, which is itself
+// clamped to the buffer.  All stores are vector stores or atomics; no inline assembly.
+#include "mm_common.h"
+#include "mm_launch.h"
+#include "mm_one_min.h"
+
+namespace mm {
+
+namespace {
+
+// A tile's symbols in LDS: the bytes [src, src + count) copied by whole dwords where the global address allows it (single
+// bytes at both ends: no byte outside [src, src + count) is loaded).  dst has src's alignment modulo 4.
+__device__ __forceinline__ void stage_bytes(uint8_t *dst, const uint8_t *src, uint32_t count, uint32_t tid) {
+    uint32_t head = (4u - (uint32_t)(reinterpret_cast<uintptr_t>(src) & 3u)) & 3u;
+    if (head > count) head = count;
+    const uint32_t dwords = (count - head) / 4, tail_at = head + 4 * dwords;
+    if (tid < head) dst[tid] = src[tid];
+    const uint32_t *s4 = reinterpret_cast<const uint32_t *>(src + head);
+    uint32_t *d4 = reinterpret_cast<uint32_t *>(dst + head);
+    for (uint32_t i = tid; i < dwords; i += kOneMinThreads) d4[i] = s4[i];
+    if (tid < count - tail_at) dst[tail_at + tid] = src[tail_at + tid];
+}
+
+// TEXT: byte symbols and 256-entry tables (else 2-bit symbols, 4 entries).  kStage: bytes of a tile's symbols kept in LDS -
+// every k up to a tile's own size; a larger k reads its symbols from global memory.
+template <bool TEXT, class Lay, bool CANON>
+__global__ __launch_bounds__(kOneMinThreads) void one_min_kernel(Lay lay, OneMinArgs a) {
+    constexpr int NTAB = TEXT ? 256 : 4;
+    constexpr uint32_t kStage = TEXT ? 2 * kOneMinTile : 2 * kOneMinTile / 4 + 4;
+    __shared__ OneMinPair s_in[NTAB], s_out[NTAB];
+    __shared__ unsigned long long s_keys[kOneMinSlots];
+    __shared__ uint32_t s_stage[kStage / 4 + 1];
+    __shared__ OneMinTileRange s_range;
+    __shared__ int s_any;
+    const uint32_t tid = threadIdx.x;
+    if (tid == 0) {
+        unsigned long long limit = lay.end(a.n - 1);
+        if (limit > a.avail) limit = a.avail;
+        s_any = one_min_tile_range(lay, (uint64_t)a.n, (uint64_t)limit, a.k, (uint64_t)blockIdx.x, kOneMinTile, &s_range) ? 1 : 0;
+    }
+    __syncthreads();
+    if (!s_any) return;
+    const OneMinTileRange range = s_range;
+    const uint64_t span = range.r_hi - range.r_lo + 1;
+    const uint32_t n_slots = span < kOneMinSlots ? (uint32_t)span : kOneMinSlots;
+    for (uint32_t i = tid; i < n_slots; i += kOneMinThreads) s_keys[i] = kOneMinNoKey;
+    if (!TEXT) {
+        if (tid < 4) {
+            s_in[tid] = OneMinPair{a.small_in[tid].x, a.small_in[tid].y};
+            s_out[tid] = OneMinPair{a.small_out[tid].x, a.small_out[tid].y};
+        }
+    } else {
+        for (uint32_t i = tid; i < (uint32_t)NTAB; i += kOneMinThreads) {
+            const uint2 e = a.tables->t_in[i], o = a.tables->t_out[i];
+            s_in[i] = OneMinPair{e.x, e.y};
+            s_out[i] = OneMinPair{o.x, o.y};
+        }
+    }
+    // the symbols [g_begin, g_end + k - 1) of the tile (all below the limit): their bytes
+    const uint64_t sym_lo = (TEXT ? 0 : a.base0) + range.g_begin, sym_hi = sym_lo + (range.g_end - range.g_begin) + a.k - 2;
+    const uint64_t byte_lo = TEXT ? sym_lo : sym_lo >> 2, byte_hi = TEXT ? sym_hi : sym_hi >> 2;  // (inclusive)
+    const bool staged = byte_hi - byte_lo < kStage;
+    const uint8_t *const src = a.syms + byte_lo;
+    uint8_t *const stage = reinterpret_cast<uint8_t *>(s_stage) + (reinterpret_cast<uintptr_t>(src) & 3u);
+    if (staged) stage_bytes(stage, src, (uint32_t)(byte_hi - byte_lo + 1), tid);
+    __syncthreads();
+    const uint64_t g0 = range.g_begin + (uint64_t)tid * kOneMinPerLane;
+    if (g0 < range.g_end) {
+        const uint64_t g1 = range.g_end - g0 < kOneMinPerLane ? range.g_end : g0 + kOneMinPerLane;
+        OneMinTables t;
+        t.t_in = s_in;
+        t.t_out = s_out;
+        t.fw0 = a.fw0;
+        t.rc0 = a.rc0;
+        t.rot = a.rot;
+        t.canonical = CANON ? 1u : 0u;
+        auto emit = [&](uint64_t r, uint64_t key) {
+            const uint64_t slot = r - range.r_lo;
+            if (slot < n_slots) atomicMin(&s_keys[slot], (unsigned long long)key);
+            else if (r < a.n) atomicMin(a.keys + r, (unsigned long long)key);
+        };
+        if constexpr (TEXT) {
+            if (staged) one_min_lane(OneMinText{stage, range.g_begin}, lay, range, t, a.k, g0, g1, emit);
+            else one_min_lane(OneMinText{a.syms, 0}, lay, range, t, a.k, g0, g1, emit);
+        } else {
+            // (the staged copy starts at byte byte_lo: symbol i is base a.base0 + i - 4 * byte_lo of it)
+            if (staged) one_min_lane(OneMinPacked{stage, a.base0 - 4 * byte_lo}, lay, range, t, a.k, g0, g1, emit);
+            else one_min_lane(OneMinPacked{a.syms, a.base0}, lay, range, t, a.k, g0, g1, emit);
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = tid; i < n_slots; i += kOneMinThreads) {
+        const unsigned long long key = s_keys[i];
+        if (key != kOneMinNoKey) atomicMin(a.keys + (range.r_lo + i), key);
+    }
+}
+
+__global__ __launch_bounds__(256) void one_min_finish_kernel(const unsigned long long *__restrict__ keys, uint32_t *__restrict__ out,
+                                                             unsigned long long n) {
+    const unsigned long long r = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    if (r < n) out[r] = one_min_position(keys[r]);
+}
+
+template <bool TEXT, class Lay>
+void launch_main(const Lay &lay, const OneMinArgs &a, uint32_t blocks, hipStream_t stream) {
+    if (a.canonical)
+        hipLaunchKernelGGL((one_min_kernel<TEXT, Lay, true>), dim3(blocks), dim3(kOneMinThreads), 0, stream, lay, a);
+    else
+        hipLaunchKernelGGL((one_min_kernel<TEXT, Lay, false>), dim3(blocks), dim3(kOneMinThreads), 0, stream, lay, a);
+}
+
+}  // namespace
+
+int launch_one_min(const OneMinArgs &a, hipStream_t stream) {
+    if (a.n == 0) return 0;
+    const uint64_t finish_blocks = (a.n + 255) / 256;
+    if (finish_blocks > 0x7fffffffull) return -3;
+    if (hipMemsetAsync(a.keys, 0xff, a.n * sizeof(unsigned long long), stream) != hipSuccess) return -1;
+    // what the host knows of the positions: the symbols of the buffer (a fixed-stride layout: up to its last read's end)
+    uint64_t symbols = a.avail;
+    if (!a.starts) {
+        const uint64_t end = (a.n - 1) * a.stride + a.len;
+        if (end < symbols) symbols = end;
+    }
+    if (symbols >= a.k && (a.starts || a.len >= a.k)) {
+        const uint64_t tiles = one_min_tiles(symbols - a.k + 1, kOneMinTile);
+        if (tiles > 0x7fffffffull) return -3;
+        const OneMinStarts by_starts{reinterpret_cast<const uint64_t *>(a.starts)};
+        if (a.text) launch_main<true>(by_starts, a, (uint32_t)tiles, stream);
+        else if (a.starts) launch_main<false>(by_starts, a, (uint32_t)tiles, stream);
+        else launch_main<false>(OneMinStride{a.stride, a.len}, a, (uint32_t)tiles, stream);
+        if (hipGetLastError() != hipSuccess) return -1;
+    }
+    hipLaunchKernelGGL(one_min_finish_kernel, dim3((uint32_t)finish_blocks), dim3(256), 0, stream, a.keys, a.out, a.n);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+}  // namespace mm
