@@ -910,6 +910,11 @@ class Plan:
         return lib().mm_plan_value_len(self.h)
 
 
+def _u128_list(words, n: int) -> list:
+    """The first ``n`` values of {lo, hi} word pairs as Python ints."""
+    return [int(words[2 * i]) | (int(words[2 * i + 1]) << 64) for i in range(n)]
+
+
 class Output:
     """``Output`` of src/lib.rs:232-237: positions + lazily computed k-mer values."""
 
@@ -936,14 +941,14 @@ class Output:
             text = _text_array(seq)
             _check(lib().mm_values_u128_text_host(self._ws.h, _p(text, C.c_uint8), len(text), TEXT_VALUES_BYTES, self.len,
                                                   int(self.canonical), _p(pos, C.c_uint32), len(pos), _p(vals, C.c_uint64)))
-            return pos, [int(vals[2 * i]) | (int(vals[2 * i + 1]) << 64) for i in range(len(pos))]
+            return pos, _u128_list(vals, len(pos))
         if isinstance(seq, AsciiSeq):
             seq = PackedSeqVec.from_ascii(seq.seq)
         if len(pos):
             _check(lib().mm_values_u128_host(self._ws.h, _p(seq.data, C.c_uint8), seq.offset, seq.length,
                                              self.len, int(self.canonical), _p(pos, C.c_uint32),
                                              len(pos), _p(vals, C.c_uint64)))
-        return pos, [int(vals[2 * i]) | (int(vals[2 * i + 1]) << 64) for i in range(len(pos))]
+        return pos, _u128_list(vals, len(pos))
 
     def pos_and_values_u64(self):
         """``Output::pos_and_values_u64`` (src/lib.rs:598-612)."""
@@ -2214,19 +2219,10 @@ def values_batch_view(address: int, packed_bytes: int, base_offset: int = 0) -> 
     return dict(zip(("address", "byte_lo", "byte_hi", "q_lo", "q_hi", "base0"), (int(x) for x in out)))
 
 
-def values_batch_device(builder: "Builder", d_seqs, n_bases, d_pos, offsets, base_offsets=None, u128=False, out=None):
-    """K-mer values of EVERY sequence of a device batch in one launch (``mm_values_u64_batch_device_async`` /
-    ``mm_values_u128_batch_device_async``): ``d_seqs`` (list of torch uint8 CUDA tensors; ``None`` for a sequence without
-    values), ``n_bases`` and ``base_offsets`` as ``run_batch_device`` took them, ``d_pos`` the positions it wrote (int32
-    tensor) and ``offsets`` the n_seqs + 1 offsets it returned.  ``len`` and ``canonical`` come from the builder like
-    ``Output.values_u64`` takes them.  Fills ``out`` (int64 tensor of ``offsets[-1]`` words, twice that for ``u128``:
-    {lo, hi}) or returns a new zero-filled one; the call is asynchronous on the builder's workspace (``Workspace.sync``)."""
+def _values_out(d_pos, out, count: int, u128: bool, count_is: str):
+    """``out`` of the device values wrappers, for ``count`` values: the caller's tensor checked for its size, or a new
+    zero-filled one (waited for).  ``d_pos`` must hold ``count`` positions; ``count_is`` names the count in the message."""
     import torch
-    n = len(d_seqs)
-    offsets = [int(o) for o in offsets]
-    if len(offsets) != n + 1 or len(n_bases) != n or (base_offsets is not None and len(base_offsets) != n):
-        raise ValueError(f"{n} sequences need {n} lengths (and base offsets) and {n + 1} offsets")
-    count = offsets[-1]
     per = 2 if u128 else 1
     if out is None:
         out = torch.zeros(per * count, dtype=torch.int64, device=d_pos.device)
@@ -2234,7 +2230,22 @@ def values_batch_device(builder: "Builder", d_seqs, n_bases, d_pos, offsets, bas
     elif out.numel() < per * count:
         raise ValueError(f"out holds {out.numel()} words, {per * count} needed")
     if d_pos.numel() < count:
-        raise ValueError(f"d_pos holds {d_pos.numel()} positions, offsets end at {count}")
+        raise ValueError(f"d_pos holds {d_pos.numel()} positions, {count_is} {count}")
+    return out
+
+
+def values_batch_device(builder: "Builder", d_seqs, n_bases, d_pos, offsets, base_offsets=None, u128=False, out=None):
+    """K-mer values of EVERY sequence of a device batch in one launch (``mm_values_u64_batch_device_async`` /
+    ``mm_values_u128_batch_device_async``): ``d_seqs`` (list of torch uint8 CUDA tensors; ``None`` for a sequence without
+    values), ``n_bases`` and ``base_offsets`` as ``run_batch_device`` took them, ``d_pos`` the positions it wrote (int32
+    tensor) and ``offsets`` the n_seqs + 1 offsets it returned.  ``len`` and ``canonical`` come from the builder like
+    ``Output.values_u64`` takes them.  Fills ``out`` (int64 tensor of ``offsets[-1]`` words, twice that for ``u128``:
+    {lo, hi}) or returns a new zero-filled one; the call is asynchronous on the builder's workspace (``Workspace.sync``)."""
+    n = len(d_seqs)
+    offsets = [int(o) for o in offsets]
+    if len(offsets) != n + 1 or len(n_bases) != n or (base_offsets is not None and len(base_offsets) != n):
+        raise ValueError(f"{n} sequences need {n} lengths (and base offsets) and {n + 1} offsets")
+    out = _values_out(d_pos, out, offsets[-1], u128, "offsets end at")
     ptrs = (C.c_void_p * max(n, 1))(*[t.data_ptr() if t is not None and t.numel() else None for t in d_seqs])
     nbytes = (C.c_uint64 * max(n, 1))(*[int(t.numel()) if t is not None else 0 for t in d_seqs])
     lens = (C.c_uint64 * max(n, 1))(*[int(x) for x in n_bases])
@@ -2256,17 +2267,9 @@ def values_reads_device(builder: "Builder", d_packed, n_reads, d_pos, d_out_offs
     nothing waits for the host, values at or past it stay as they were.  Fills ``out`` (int64 tensor of ``n_pos_max``
     words, twice that for ``u128``: {lo, hi}) or returns a new zero-filled one; the call is asynchronous on the
     builder's workspace (``Workspace.sync``)."""
-    import torch
     if n_pos_max is None:
         n_pos_max = int(d_pos.numel())
-    per = 2 if u128 else 1
-    if out is None:
-        out = torch.zeros(per * n_pos_max, dtype=torch.int64, device=d_pos.device)
-        torch.cuda.synchronize(d_pos.device)
-    elif out.numel() < per * n_pos_max:
-        raise ValueError(f"out holds {out.numel()} words, {per * n_pos_max} needed")
-    if d_pos.numel() < n_pos_max:
-        raise ValueError(f"d_pos holds {d_pos.numel()} positions, n_pos_max is {n_pos_max}")
+    out = _values_out(d_pos, out, n_pos_max, u128, "n_pos_max is")
     f = lib().mm_values_u128_reads_device_async if u128 else lib().mm_values_u64_reads_device_async
     _check(f(builder._ws().h, C.c_void_p(d_packed.data_ptr()), int(d_packed.numel()), int(base_offset), int(n_reads),
              C.c_void_p(read_starts.data_ptr()) if read_starts is not None else None, int(read_stride),
@@ -2295,7 +2298,7 @@ def debug_values_text(text, encoding, length, canonical=False, u128=False, abs_p
     _check(lib().mm_debug_values_text(C.c_void_p(buf.ctypes.data + at), len(text), int(encoding), int(length),
                                       int(canonical), int(u128), _p(pos, C.c_uint64), len(pos), _p(out, C.c_uint64)))
     if u128:
-        return [int(out[2 * i]) | (int(out[2 * i + 1]) << 64) for i in range(len(pos))]
+        return _u128_list(out, len(pos))
     return out[:len(pos)]
 
 
@@ -2307,16 +2310,8 @@ def values_text_device(builder: "Builder", d_text, n, d_pos, n_pos, encoding, u1
     bits).  ``len`` and ``canonical`` come from the builder like ``Output.values_u64`` takes them.  Fills ``out`` (int64
     tensor of ``n_pos`` words, twice that for ``u128``: {lo, hi}) or returns a new zero-filled one; the call is
     asynchronous on the builder's workspace (``Workspace.sync``)."""
-    import torch
     n_pos = int(n_pos)
-    per = 2 if u128 else 1
-    if out is None:
-        out = torch.zeros(per * n_pos, dtype=torch.int64, device=d_pos.device)
-        torch.cuda.synchronize(d_pos.device)
-    elif out.numel() < per * n_pos:
-        raise ValueError(f"out holds {out.numel()} words, {per * n_pos} needed")
-    if d_pos.numel() < n_pos:
-        raise ValueError(f"d_pos holds {d_pos.numel()} positions, n_pos is {n_pos}")
+    out = _values_out(d_pos, out, n_pos, u128, "n_pos is")
     f = lib().mm_values_u128_text_device_async if u128 else lib().mm_values_u64_text_device_async
     _check(f(builder._ws().h, C.c_void_p(d_text.data_ptr()), int(d_text.numel()), int(n), int(encoding),
              _value_len(builder), int(builder.canonical), C.c_void_p(d_pos.data_ptr()), n_pos,
@@ -2331,19 +2326,11 @@ def values_text_batch_device(builder: "Builder", d_text, d_starts, n_chars, d_po
     them, ``d_pos`` the record-local positions and ``d_out_offsets`` the n + 1 offsets it wrote.  The true count is read
     on the device: nothing waits for the host, values at or past it (or past ``n_pos_max``) stay as they were.
     ``encoding`` / ``u128`` / ``out`` as for ``values_text_device`` (``out`` holds ``n_pos_max`` values)."""
-    import torch
     n_rec = d_starts.numel() - 1
     if n_rec < 0 or d_out_offsets.numel() != n_rec + 1:
         raise ValueError("d_starts and d_out_offsets hold n + 1 entries each")
     n_pos_max = int(n_pos_max)
-    per = 2 if u128 else 1
-    if out is None:
-        out = torch.zeros(per * n_pos_max, dtype=torch.int64, device=d_pos.device)
-        torch.cuda.synchronize(d_pos.device)
-    elif out.numel() < per * n_pos_max:
-        raise ValueError(f"out holds {out.numel()} words, {per * n_pos_max} needed")
-    if d_pos.numel() < n_pos_max:
-        raise ValueError(f"d_pos holds {d_pos.numel()} positions, n_pos_max is {n_pos_max}")
+    out = _values_out(d_pos, out, n_pos_max, u128, "n_pos_max is")
     f = lib().mm_values_u128_text_batch_device_async if u128 else lib().mm_values_u64_text_batch_device_async
     _check(f(builder._ws().h, C.c_void_p(d_text.data_ptr()), int(d_text.numel()), n_rec, C.c_void_p(d_starts.data_ptr()),
              int(n_chars), int(encoding), _value_len(builder), int(builder.canonical), C.c_void_p(d_pos.data_ptr()),
@@ -2371,7 +2358,7 @@ def values_text_batch_host(builder: "Builder", records, pos, offsets, encoding, 
              _value_len(builder), int(builder.canonical), _p(pos, C.c_uint32) if len(pos) else None,
              _p(offsets, C.c_uint64), _p(vals, C.c_uint64)))
     if u128:
-        return [int(vals[2 * i]) | (int(vals[2 * i + 1]) << 64) for i in range(n)]
+        return _u128_list(vals, n)
     return vals[:n]
 
 
@@ -2412,7 +2399,7 @@ def values_reads_host(builder: "Builder", reads, pos, offsets, u128=False):
              _value_len(builder), int(builder.canonical), _p(pos, C.c_uint32) if len(pos) else None,
              _p(offsets, C.c_uint64), _p(vals, C.c_uint64)))
     if u128:
-        return [int(vals[2 * i]) | (int(vals[2 * i + 1]) << 64) for i in range(n)]
+        return _u128_list(vals, n)
     return vals[:n]
 
 

@@ -23,6 +23,7 @@
 #include "mm_lane_counts.h"
 #include "mm_text_counts.h"
 #include "mm_values_batch.h"
+#include "mm_values_block.h"  // values_grid
 #include "mm_one_min.h"
 #include "mm_values_reads.h"
 #include "mm_values_text.h"
@@ -3321,8 +3322,52 @@ static int values_async_impl(mm_workspace_t *ws, const void *d_packed, uint64_t 
     return MM_OK;
 }
 
-// The same from HOST memory: packed bytes (+ slack for the loads behind the last value) in d_in, positions in d_out,
-// values in d_vals.
+// ---- host staging of the whole values family (the *_host entry points): what a value is read from in d_in, the
+// positions in d_out, the values in d_vals, `per` 64-bit words each.
+// Before anything is queued: `in_bytes` of d_in, room for n_pos positions and their values.
+static int values_host_grow(mm_workspace_t *ws, uint64_t in_bytes, uint64_t n_pos, uint64_t per) {
+    int r = grow_bytes(ws->d_in, ws->d_in_bytes, in_bytes);
+    if (r) return r;
+    r = grow(ws->d_out, ws->d_out_elems, n_pos, sizeof(uint32_t));
+    if (r) return r;
+    return grow(ws->d_vals, ws->d_vals_elems, per * n_pos, sizeof(unsigned long long));
+}
+// Behind the uploads into d_in: the positions.
+static int values_host_upload_pos(mm_workspace_t *ws, const uint32_t *pos, uint64_t n_pos) {
+    MM_HIP(hipMemcpyAsync(ws->d_out, pos, n_pos * sizeof(uint32_t), hipMemcpyHostToDevice, ws->stream));
+    return MM_OK;
+}
+// Behind the launch: the values, and the call's one wait.
+static int values_host_download(mm_workspace_t *ws, uint64_t *values, uint64_t n_pos, uint64_t per) {
+    MM_HIP(hipMemcpyAsync(values, ws->d_vals, per * n_pos * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
+    MM_HIP(hipStreamSynchronize(ws->stream));
+    return MM_OK;
+}
+// The batch-shaped calls' d_in: [payload | starts | offsets], the tables of n + 1 words each at a 16-byte boundary, the
+// starts optional (null: a fixed-stride layout).  Grows the three buffers (values_host_grow), then uploads all of d_in;
+// d_starts is null with `starts`.
+struct ValuesHostTables {
+    const uint8_t *d_payload;
+    const uint64_t *d_starts, *d_offsets;
+};
+static int values_host_upload_tables(mm_workspace_t *ws, const uint8_t *payload, uint64_t payload_bytes, uint64_t n,
+                                     const uint64_t *starts, const uint64_t *offsets, uint64_t n_pos, uint64_t per,
+                                     ValuesHostTables *t) {
+    const uint64_t table_bytes = (n + 1) * sizeof(uint64_t);
+    const uint64_t starts_at = (payload_bytes + 15) & ~15ull, offsets_at = starts_at + (starts ? table_bytes : 0);
+    const int r = values_host_grow(ws, offsets_at + table_bytes, n_pos, per);
+    if (r) return r;
+    uint8_t *const din = static_cast<uint8_t *>(ws->d_in);
+    if (payload_bytes) MM_HIP(hipMemcpyAsync(din, payload, payload_bytes, hipMemcpyHostToDevice, ws->stream));
+    if (starts) MM_HIP(hipMemcpyAsync(din + starts_at, starts, table_bytes, hipMemcpyHostToDevice, ws->stream));
+    MM_HIP(hipMemcpyAsync(din + offsets_at, offsets, table_bytes, hipMemcpyHostToDevice, ws->stream));
+    t->d_payload = din;
+    t->d_starts = starts ? reinterpret_cast<const uint64_t *>(din + starts_at) : nullptr;
+    t->d_offsets = reinterpret_cast<const uint64_t *>(din + offsets_at);
+    return MM_OK;
+}
+
+// The same from HOST memory: packed bytes (+ slack for the loads behind the last value) in d_in.
 static int values_host_impl(mm_workspace_t *ws, const uint8_t *packed, uint64_t base_offset, uint64_t n_bases, uint32_t len,
                             int canonical, const uint32_t *pos, uint64_t n_pos, uint64_t *values, int words) {
     if (!ws) return MM_ERR_NULL;
@@ -3331,20 +3376,15 @@ static int values_host_impl(mm_workspace_t *ws, const uint8_t *packed, uint64_t 
     if (!packed || !pos || !values) return MM_ERR_NULL;
     MM_HIP(set_device(ws->device));
     const uint64_t bytes = (base_offset + n_bases + 3) / 4, slack = 16 * words;
-    int r = grow_bytes(ws->d_in, ws->d_in_bytes, bytes + slack);
-    if (r) return r;
-    r = grow(ws->d_out, ws->d_out_elems, n_pos, sizeof(uint32_t));
-    if (r) return r;
-    r = grow(ws->d_vals, ws->d_vals_elems, words * n_pos, sizeof(unsigned long long));
+    int r = values_host_grow(ws, bytes + slack, n_pos, words);
     if (r) return r;
     MM_HIP(hipMemcpyAsync(ws->d_in, packed, bytes, hipMemcpyHostToDevice, ws->stream));
-    MM_HIP(hipMemcpyAsync(ws->d_out, pos, n_pos * sizeof(uint32_t), hipMemcpyHostToDevice, ws->stream));
+    r = values_host_upload_pos(ws, pos, n_pos);
+    if (r) return r;
     r = values_async_impl(ws, ws->d_in, bytes + slack, base_offset, n_bases, len, canonical, ws->d_out, n_pos,
                           reinterpret_cast<uint64_t *>(ws->d_vals), words);
     if (r) return r;
-    MM_HIP(hipMemcpyAsync(values, ws->d_vals, words * n_pos * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
-    MM_HIP(hipStreamSynchronize(ws->stream));
-    return MM_OK;
+    return values_host_download(ws, values, n_pos, words);
 }
 
 int mm_values_u64_device_async(mm_workspace_t *ws, const void *d_packed, uint64_t packed_bytes,
@@ -3397,14 +3437,7 @@ static int values_reads_async_impl(mm_workspace_t *ws, const void *d_packed, uin
     if (!d_read_starts && (n_reads - 1) * (uint64_t)read_stride > buffer_bases - base_offset) return MM_ERR_CAPACITY;
     MM_HIP(set_device(ws->device));
     mm::ValuesReadsArgs a;
-    const uintptr_t addr = reinterpret_cast<uintptr_t>(d_packed);
-    const uint64_t byte_shift = addr & 3u;
-    a.view.d = reinterpret_cast<const uint32_t *>(addr - byte_shift);
-    a.view.byte_lo = byte_shift;
-    a.view.byte_hi = byte_shift + packed_bytes;
-    a.view.q_lo = byte_shift ? 1 : 0;
-    a.view.q_hi = a.view.byte_hi / 4;
-    a.view.base0 = base_offset + 4 * byte_shift;
+    a.view = mm::packed_view((uint64_t)reinterpret_cast<uintptr_t>(d_packed), packed_bytes, base_offset, 4);
     a.n_reads = n_reads;
     a.read_starts = reinterpret_cast<const unsigned long long *>(d_read_starts);
     a.read_stride = read_stride;
@@ -3459,30 +3492,16 @@ static int values_reads_host_impl(mm_workspace_t *ws, const uint8_t *packed, uin
     if (read_starts && read_starts[n_reads] > 4 * packed_bytes - base_offset) return MM_ERR_CAPACITY;
     if (!read_starts && (n_reads - 1) * (uint64_t)read_stride > 4 * packed_bytes - base_offset) return MM_ERR_CAPACITY;
     MM_HIP(set_device(ws->device));
-    // staging: [packed bytes | starts | offsets] in d_in, positions in d_out, values in d_vals
-    const uint64_t words = n_reads + 1, per = u128 ? 2 : 1;
-    const uint64_t starts_at = (packed_bytes + 15) & ~15ull;
-    const uint64_t offsets_at = starts_at + (read_starts ? words * sizeof(uint64_t) : 0);
-    int r = grow_bytes(ws->d_in, ws->d_in_bytes, offsets_at + words * sizeof(uint64_t));
+    const uint64_t per = u128 ? 2 : 1;
+    ValuesHostTables t;
+    int r = values_host_upload_tables(ws, packed, packed_bytes, n_reads, read_starts, offsets, n_pos, per, &t);
     if (r) return r;
-    uint8_t *const din = static_cast<uint8_t *>(ws->d_in);
-    r = grow(ws->d_out, ws->d_out_elems, n_pos, sizeof(uint32_t));
+    r = values_host_upload_pos(ws, pos, n_pos);
     if (r) return r;
-    r = grow(ws->d_vals, ws->d_vals_elems, per * n_pos, sizeof(unsigned long long));
+    r = values_reads_async_impl(ws, t.d_payload, packed_bytes, base_offset, n_reads, t.d_starts, read_stride, len, canonical,
+                                ws->d_out, t.d_offsets, n_pos, reinterpret_cast<uint64_t *>(ws->d_vals), u128);
     if (r) return r;
-    MM_HIP(hipMemcpyAsync(din, packed, packed_bytes, hipMemcpyHostToDevice, ws->stream));
-    if (read_starts)
-        MM_HIP(hipMemcpyAsync(din + starts_at, read_starts, words * sizeof(uint64_t), hipMemcpyHostToDevice, ws->stream));
-    MM_HIP(hipMemcpyAsync(din + offsets_at, offsets, words * sizeof(uint64_t), hipMemcpyHostToDevice, ws->stream));
-    MM_HIP(hipMemcpyAsync(ws->d_out, pos, n_pos * sizeof(uint32_t), hipMemcpyHostToDevice, ws->stream));
-    r = values_reads_async_impl(ws, din, packed_bytes, base_offset, n_reads,
-                                read_starts ? reinterpret_cast<const uint64_t *>(din + starts_at) : nullptr, read_stride, len,
-                                canonical, ws->d_out, reinterpret_cast<const uint64_t *>(din + offsets_at), n_pos,
-                                reinterpret_cast<uint64_t *>(ws->d_vals), u128);
-    if (r) return r;
-    MM_HIP(hipMemcpyAsync(values, ws->d_vals, per * n_pos * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
-    MM_HIP(hipStreamSynchronize(ws->stream));
-    return MM_OK;
+    return values_host_download(ws, values, n_pos, per);
 }
 
 int mm_values_u64_reads_host(mm_workspace_t *ws, const uint8_t *packed, uint64_t packed_bytes, uint64_t base_offset,
@@ -3796,8 +3815,8 @@ static int values_batch_async_impl(mm_workspace_t *ws, uint64_t n_seqs, const vo
     uint64_t total = 0;
     int r = values_batch_check(n_seqs, d_packed, packed_bytes, base_offsets, n_bases, len, d_pos, offsets, d_values, u128, &total);
     if (r || total == 0) return r;
-    const uint64_t per_block = u128 ? 256 : 1024;
-    if ((total + per_block - 1) / per_block > 0x7fffffffull) return MM_ERR_LEN_TOO_LARGE;  // (more workgroups than a grid holds)
+    uint32_t blocks;
+    if (mm::values_grid(total, u128, &blocks)) return MM_ERR_LEN_TOO_LARGE;  // (more workgroups than a grid holds)
     MM_HIP(set_device(ws->device));
     // the tables: [n_seqs + 1 offsets | pad to 16 bytes | n_seqs descriptors], built in a page-locked area that is the
     // workspace's own - the caller's arrays are the caller's again on return - and copied to the device tables on the
@@ -3873,13 +3892,13 @@ uint32_t mm_values_batch_lds_stage(void) { return mm::kValuesBatchStage; }
 // base0}, what the kernel reads out of the sequence's descriptor.
 int mm_debug_values_batch_view(uint64_t address, uint64_t packed_bytes, uint64_t base_offset, uint64_t out6[6]) {
     if (!out6) return MM_ERR_NULL;
-    const mm::ValuesBatchSeq s = mm::values_batch_seq(address, packed_bytes, base_offset);
-    out6[0] = s.d;
-    out6[1] = s.byte_lo;
-    out6[2] = s.byte_hi;
-    out6[3] = mm::values_batch_q_lo(s);
-    out6[4] = mm::values_batch_q_hi(s);
-    out6[5] = s.base0;
+    const mm::PackedView v = mm::view_of(mm::values_batch_seq(address, packed_bytes, base_offset));
+    out6[0] = (uint64_t)reinterpret_cast<uintptr_t>(v.d);
+    out6[1] = v.byte_lo;
+    out6[2] = v.byte_hi;
+    out6[3] = v.q_lo;
+    out6[4] = v.q_hi;
+    out6[5] = v.base0;
     return MM_OK;
 }
 
@@ -3920,8 +3939,7 @@ static int values_text_async_impl(mm_workspace_t *ws, const void *d_text, uint64
     return MM_OK;
 }
 
-// The same from HOST memory: the text in d_in (text_bytes = n: a k-mer past the end reads zeros), positions in d_out,
-// values in d_vals.
+// The same from HOST memory: the text in d_in (text_bytes = n: a k-mer past the end reads zeros).
 static int values_text_host_impl(mm_workspace_t *ws, const uint8_t *text, uint64_t n, int encoding, uint32_t len,
                                  int canonical, const uint32_t *pos, uint64_t n_pos, uint64_t *values, bool u128) {
     if (!ws) return MM_ERR_NULL;
@@ -3931,20 +3949,15 @@ static int values_text_host_impl(mm_workspace_t *ws, const uint8_t *text, uint64
     if (n >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
     MM_HIP(set_device(ws->device));
     const uint64_t per = u128 ? 2 : 1;
-    int r = grow_bytes(ws->d_in, ws->d_in_bytes, n ? n : 1);
-    if (r) return r;
-    r = grow(ws->d_out, ws->d_out_elems, n_pos, sizeof(uint32_t));
-    if (r) return r;
-    r = grow(ws->d_vals, ws->d_vals_elems, per * n_pos, sizeof(unsigned long long));
+    int r = values_host_grow(ws, n ? n : 1, n_pos, per);
     if (r) return r;
     if (n) MM_HIP(hipMemcpyAsync(ws->d_in, text, n, hipMemcpyHostToDevice, ws->stream));
-    MM_HIP(hipMemcpyAsync(ws->d_out, pos, n_pos * sizeof(uint32_t), hipMemcpyHostToDevice, ws->stream));
+    r = values_host_upload_pos(ws, pos, n_pos);
+    if (r) return r;
     r = values_text_async_impl(ws, ws->d_in, n, n, encoding, len, canonical, ws->d_out, n_pos,
                                reinterpret_cast<uint64_t *>(ws->d_vals), u128);
     if (r) return r;
-    MM_HIP(hipMemcpyAsync(values, ws->d_vals, per * n_pos * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
-    MM_HIP(hipStreamSynchronize(ws->stream));
-    return MM_OK;
+    return values_host_download(ws, values, n_pos, per);
 }
 
 int mm_values_u64_text_device_async(mm_workspace_t *ws, const void *d_text, uint64_t text_bytes, uint64_t n, int encoding,
@@ -4017,27 +4030,17 @@ static int values_text_batch_host_impl(mm_workspace_t *ws, const uint8_t *text, 
     if (!text || !pos || !values) return MM_ERR_NULL;
     if (n_chars >= (1ull << 32)) return MM_ERR_LEN_TOO_LARGE;
     MM_HIP(set_device(ws->device));
-    const uint64_t words = n_records + 1, per = u128 ? 2 : 1;
-    const uint64_t starts_at = (n_chars + 15) & ~15ull, offsets_at = starts_at + words * sizeof(uint64_t);
-    int r = grow_bytes(ws->d_in, ws->d_in_bytes, offsets_at + words * sizeof(uint64_t));
+    const uint64_t per = u128 ? 2 : 1;
+    ValuesHostTables t;
+    int r = values_host_upload_tables(ws, text, n_chars, n_records, starts, offsets, n_pos, per, &t);
     if (r) return r;
-    uint8_t *const din = static_cast<uint8_t *>(ws->d_in);
-    r = grow(ws->d_out, ws->d_out_elems, n_pos, sizeof(uint32_t));
+    r = values_host_upload_pos(ws, pos, n_pos);
     if (r) return r;
-    r = grow(ws->d_vals, ws->d_vals_elems, per * n_pos, sizeof(unsigned long long));
-    if (r) return r;
-    if (n_chars) MM_HIP(hipMemcpyAsync(din, text, n_chars, hipMemcpyHostToDevice, ws->stream));
-    MM_HIP(hipMemcpyAsync(din + starts_at, starts, words * sizeof(uint64_t), hipMemcpyHostToDevice, ws->stream));
-    MM_HIP(hipMemcpyAsync(din + offsets_at, offsets, words * sizeof(uint64_t), hipMemcpyHostToDevice, ws->stream));
-    MM_HIP(hipMemcpyAsync(ws->d_out, pos, n_pos * sizeof(uint32_t), hipMemcpyHostToDevice, ws->stream));
     // (text_bytes = n_chars: a k-mer that leaves the last record reads zeros, not the staged starts)
-    r = values_text_batch_async_impl(ws, din, n_chars, n_records, reinterpret_cast<const uint64_t *>(din + starts_at), n_chars,
-                                     encoding, len, canonical, ws->d_out, reinterpret_cast<const uint64_t *>(din + offsets_at),
-                                     n_pos, reinterpret_cast<uint64_t *>(ws->d_vals), u128);
+    r = values_text_batch_async_impl(ws, t.d_payload, n_chars, n_records, t.d_starts, n_chars, encoding, len, canonical,
+                                     ws->d_out, t.d_offsets, n_pos, reinterpret_cast<uint64_t *>(ws->d_vals), u128);
     if (r) return r;
-    MM_HIP(hipMemcpyAsync(values, ws->d_vals, per * n_pos * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
-    MM_HIP(hipStreamSynchronize(ws->stream));
-    return MM_OK;
+    return values_host_download(ws, values, n_pos, per);
 }
 
 int mm_values_u64_text_batch_device_async(mm_workspace_t *ws, const void *d_text, uint64_t text_bytes, uint64_t n_records,

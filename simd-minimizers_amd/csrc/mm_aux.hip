@@ -4,6 +4,7 @@
 #include "mm_common.h"
 #include "mm_launch.h"
 #include "mm_values.h"  // value_of, value128_of
+#include "mm_values_block.h"
 
 namespace mm {
 
@@ -24,20 +25,12 @@ __global__ __launch_bounds__(kBlockThreads) void values_u64_kernel(SeqView seq, 
                                                                    const uint32_t *__restrict__ pos,
                                                                    uint64_t n_pos,
                                                                    unsigned long long *__restrict__ out) {
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    constexpr uint64_t kPerBlock = (uint64_t)kBlockThreads * kValuesPerThread;
-    const uint64_t i0 = (uint64_t)blockIdx.x * kPerBlock;  // first value of the block
-    const uint64_t left = n_pos - i0;
-    const uint32_t here = left < kPerBlock ? (uint32_t)left : (uint32_t)kPerBlock;
-    // block-local bounds-checked views: positions in, values out (lanes past the end load 0 / store nothing)
-    const __amdgpu_buffer_rsrc_t rpos = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(pos + i0), 0, (int)(here * 4u), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(out + i0, 0, (int)(here * 8u), 0x00020000);
+    const unsigned long long i0 = values_block_first<kValuesPerThread>();  // (the grid is exact: i0 < n_pos)
+    const ValuesBlock<kValuesPerThread, false> b(pos, out, i0, values_block_here<kValuesPerThread>(i0, n_pos));
     const __amdgpu_buffer_rsrc_t rseq = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<uint32_t *>(seq.d), 0, seq.n_dwords >= 0x3fffffffu ? (int)0xfffffffcu : (int)(seq.n_dwords * 4u), 0x00020000);
-    const uint32_t t = threadIdx.x;
-    // (the position array may start at any 4-byte boundary: a 16-byte load needs no more)
-    const u32x4 pp = __builtin_amdgcn_raw_buffer_load_b128(rpos, t * 16u, 0, 0);
-    const uint32_t ps[4] = {pp.x, pp.y, pp.z, pp.w};
+    uint32_t ps[kValuesPerThread];
+    b.load_positions(ps);
     const unsigned long long mask = len >= 32 ? ~0ull : ((1ull << (2u * len)) - 1ull);
     u32x4 w[kValuesPerThread];
     uint32_t sh[kValuesPerThread];
@@ -51,16 +44,7 @@ __global__ __launch_bounds__(kBlockThreads) void values_u64_kernel(SeqView seq, 
     unsigned long long v[kValuesPerThread];
 #pragma unroll
     for (int u = 0; u < kValuesPerThread; ++u) v[u] = value_of(w[u].x, w[u].y, w[u].z, sh[u], len, canonical, mask);
-#pragma unroll
-    for (int u = 0; u < kValuesPerThread; u += 2) {
-        u32x4 o;
-        o.x = (uint32_t)v[u];
-        o.y = (uint32_t)(v[u] >> 32);
-        o.z = (uint32_t)v[u + 1];
-        o.w = (uint32_t)(v[u + 1] >> 32);
-        // (the last pair of the array may be half inside: the bounds check works per dword, so its inner half is stored)
-        __builtin_amdgcn_raw_buffer_store_b128(o, rout, t * 32u + (uint32_t)u * 8u, 0, 0);
-    }
+    b.store_u64(v);
 }
 
 int launch_values_u64(SeqView seq, uint32_t len, int canonical, const uint32_t *d_pos,

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "mm_common.h"
+#include "mm_values_reads.h"  // PackedView
 
 namespace mm {
 
@@ -258,16 +259,8 @@ int launch_values_u64(SeqView seq, uint32_t len, int canonical, const uint32_t *
 int launch_values_u128(SeqView seq, uint32_t len, int canonical, const uint32_t *d_pos,
                        uint64_t n_pos, unsigned long long *d_values, hipStream_t stream);
 // ---- values of every read's positions in one launch (mm_values_reads.hip)
-// The packed buffer as whole dwords plus its byte range: d = d_packed rounded down to a dword, bytes [byte_lo, byte_hi)
-// of d are the caller's, dwords [q_lo, q_hi) lie wholly inside them; base0 = base_offset + 4 * byte_lo.
-struct PackedView {
-    const uint32_t *d;
-    unsigned long long q_lo, q_hi;
-    unsigned long long byte_lo, byte_hi;
-    unsigned long long base0;
-};
 struct ValuesReadsArgs {
-    PackedView view;
+    PackedView view;                           // the packed buffer (packed_view, mm_values_reads.h)
     unsigned long long n_reads;                // > 0
     const unsigned long long *read_starts;     // [n_reads + 1], or null: read r starts at r * read_stride
     uint32_t read_stride;

@@ -4,7 +4,7 @@
 #pragma once
 #include <stdint.h>
 
-#include "mm_values_reads.h"  // MM_HOST_DEVICE, values_read_of
+#include "mm_values_reads.h"  // MM_HOST_DEVICE, values_read_of, PackedView
 
 namespace mm {
 
@@ -19,16 +19,19 @@ struct ValuesBatchSeq {
 };
 
 MM_HOST_DEVICE inline ValuesBatchSeq values_batch_seq(uint64_t address, uint64_t packed_bytes, uint64_t base_offset) {
-    ValuesBatchSeq s;
-    s.byte_lo = address & 3u;
-    s.d = address - s.byte_lo;
-    s.byte_hi = s.byte_lo + packed_bytes;
-    s.base0 = base_offset + 4 * s.byte_lo;
-    return s;
+    const PackedView v = packed_view(address, packed_bytes, base_offset, 4);
+    return ValuesBatchSeq{(unsigned long long)reinterpret_cast<uintptr_t>(v.d), v.byte_lo, v.byte_hi, v.base0};
 }
-// the dwords [q_lo, q_hi) of `d` lie wholly inside the sequence's bytes (none when q_lo >= q_hi)
-MM_HOST_DEVICE inline unsigned long long values_batch_q_lo(const ValuesBatchSeq &s) { return s.byte_lo ? 1u : 0u; }
-MM_HOST_DEVICE inline unsigned long long values_batch_q_hi(const ValuesBatchSeq &s) { return s.byte_hi >> 2; }
+// the view again, as the kernel reads it out of a descriptor: the whole dwords are derived from the byte range
+MM_HOST_DEVICE inline PackedView view_of(const ValuesBatchSeq &s) {
+    PackedView v;
+    v.d = reinterpret_cast<const uint32_t *>(s.d);
+    v.byte_lo = s.byte_lo;
+    v.byte_hi = s.byte_hi;
+    v.base0 = s.base0;
+    view_whole_dwords(v);
+    return v;
+}
 
 // Entries of the LDS stage: an offset (8 bytes) and a descriptor (32 bytes) each, 20 KiB in all.  The kernels are
 // register-bound at 8 workgroups of 256 threads per CU (the 32-wave cap); 8 x 20 KiB is exactly the CU's 160 KiB, so the

@@ -105,19 +105,9 @@ __host__ __device__ __forceinline__ void text_value128(uint32_t len, int canonic
     finish_value128(DNA ? len : 4u * len, DNA ? canonical : 0, lo, hi);
 }
 
-// The text as whole dwords plus its byte range (PackedView, mm_launch.h): d = the address rounded down to a dword,
-// base0 = byte_lo, so character p of the text is byte base0 + p of d.
-inline PackedView text_view(uint64_t address, uint64_t text_bytes) {
-    PackedView v;
-    const uint64_t shift = address & 3u;
-    v.d = reinterpret_cast<const uint32_t *>(static_cast<uintptr_t>(address - shift));
-    v.byte_lo = shift;
-    v.byte_hi = shift + text_bytes;
-    v.q_lo = shift ? 1 : 0;
-    v.q_hi = v.byte_hi / 4;
-    v.base0 = shift;
-    return v;
-}
+// The text as whole dwords plus its byte range (packed_view, mm_values_reads.h): base0 = byte_lo, so character p of the
+// text is byte base0 + p of d.
+inline PackedView text_view(uint64_t address, uint64_t text_bytes) { return packed_view(address, text_bytes, 0, 1); }
 
 struct ValuesTextArgs {
     PackedView view;

@@ -4,9 +4,7 @@
 // offsets[r] <= i < offsets[r + 1] and its k-mer starts at character starts[r] + pos[i]).  The text stands for one of two
 // reference Seqs (mm_values_text.h): `&[u8]` at 8 bits per character, or packed-seq AsciiSeq at 2.
 //
-// The shape is that of the packed values kernels (mm_aux.hip, mm_values_reads.hip): a workgroup of 256 threads takes 1024
-// consecutive values (u64: four per thread, one 16-byte position load and two 16-byte stores each) or 256 (u128: one per
-// thread, one 16-byte store).  What is new:
+// The workgroup's shape, and the batch kernels' record lookup, are mm_values_block.h.  This file's own:
 //   - the gather: a k-mer is len bytes at ANY byte address.  A thread loads the whole dwords that cover it (NDW = 3 for 8
 //     bytes, 5 for 16, 9 for 32 characters, 17 for 64: consecutive dwords, which the compiler merges into 16-byte
 //     loads - a dword-aligned address is all those need) and shifts by the byte phase with v_alignbyte, the byte
@@ -14,30 +12,22 @@
 //     the rolled edge path instead (edge_dword, mm_values_load.h): single bytes inside, zeros outside;
 //   - the DNA compression: the four characters of a shifted dword become eight bits by SWAR (dna_codes_of), eight dwords
 //     the 64-bit forward value; the canonical step is the packed kernels' (mm_values.h);
-//   - BYTES is the gather plus a mask.
-// The batch kernel looks records up as the reads kernel looks reads up (values_read_of, mm_values_reads.h): ONE search per
-// workgroup for the records of its first and last value; if the offsets between them fit the LDS stage
-// (kValuesTextStage) they are staged, every thread searches LDS once and steps forward, skipping empty records;
-// otherwise every value is searched in global memory within that span, from its predecessor's record on.  The searches
-// stay inside [0, n_records - 1] whatever the offsets hold, and the true count is offsets[n_records], read on the device.
-// All stores are vector stores.
+//   - BYTES is the gather plus a mask;
+//   - the batch kernels' true count is offsets[n_records], read on the device, n_records itself the device's own when
+//     the launch carries counts.
 #include "mm_common.h"
 #include "mm_launch.h"
-#include "mm_values_reads.h"
+#include "mm_values_block.h"
 #include "mm_values_text.h"
 
 namespace mm {
 
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 // NDW dwords per value (mm_values_text.h); VPT values per thread: 4 (u64) or 1 (u128)
 template <int NDW, bool DNA, bool U128, bool BATCH>
 __global__ __launch_bounds__(kBlockThreads) void values_text_kernel(ValuesTextArgs a) {
     constexpr int VPT = U128 ? 1 : 4;
-    constexpr unsigned long long kPerBlock = (unsigned long long)kBlockThreads * VPT;
-    constexpr uint32_t kOutBytes = U128 ? 16u : 8u;
 
     unsigned long long total = a.n_pos_max;
     unsigned long long n_records = a.n_records;
@@ -50,25 +40,12 @@ __global__ __launch_bounds__(kBlockThreads) void values_text_kernel(ValuesTextAr
         const unsigned long long total0 = a.offsets[n_records];
         if (total0 < total) total = total0;  // (never past what the buffers hold)
     }
-    const unsigned long long i0 = (unsigned long long)blockIdx.x * kPerBlock;  // first value of the workgroup
+    const unsigned long long i0 = values_block_first<VPT>();
     if (i0 >= total) return;
-    const unsigned long long left = total - i0;
-    const uint32_t here = left < kPerBlock ? (uint32_t)left : (uint32_t)kPerBlock;
-
-    // workgroup-local bounds-checked views: positions in, values out (lanes past the end load 0 / store nothing)
-    const __amdgpu_buffer_rsrc_t rpos =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(a.pos + i0), 0, (int)(here * 4u), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rout =
-        __builtin_amdgcn_make_buffer_rsrc(a.out + i0 * (U128 ? 2u : 1u), 0, (int)(here * kOutBytes), 0x00020000);
-    const uint32_t t = threadIdx.x;
+    const uint32_t here = values_block_here<VPT>(i0, total);
+    const ValuesBlock<VPT, U128> b(a.pos, a.out, i0, here);
     uint32_t ps[VPT];
-    if constexpr (VPT == 4) {
-        // (the position array may start at any 4-byte boundary: a 16-byte load needs no more)
-        const u32x4 pp = __builtin_amdgcn_raw_buffer_load_b128(rpos, t * 16u, 0, 0);
-        ps[0] = pp.x, ps[1] = pp.y, ps[2] = pp.z, ps[3] = pp.w;
-    } else {
-        ps[0] = __builtin_amdgcn_raw_buffer_load_b32(rpos, t * 4u, 0, 0);
-    }
+    b.load_positions(ps);
 
     // the byte of view.d at which each of the thread's k-mers starts
     unsigned long long p[VPT];
@@ -78,46 +55,20 @@ __global__ __launch_bounds__(kBlockThreads) void values_text_kernel(ValuesTextAr
     } else {
         __shared__ unsigned long long stage[kValuesTextStage];
         const unsigned long long *__restrict__ offsets = a.offsets;
-        // one search per workgroup: the records of its first and last value (uniform: scalar loads).  A value's record is
-        // at most n_records - 1 (i < offsets[n_records]); searching no further keeps offsets[r + 1] and starts[r] inside
-        // their arrays whatever the offsets hold.
+        // one search per workgroup: a value's record is at most n_records - 1 (the bounds: mm_values_block.h)
         const unsigned long long r_first = values_read_of(offsets, 0ull, n_records - 1ull, i0);
         const unsigned long long r_last = values_read_of(offsets, r_first, n_records - 1ull, i0 + here - 1u);
         const unsigned long long span = r_last - r_first + 2ull;  // offsets[r_first .. r_last + 1]
         const bool staged = span <= (unsigned long long)kValuesTextStage;
         if (staged) {
-            for (uint32_t j = t; j < (uint32_t)span; j += kBlockThreads) stage[j] = offsets[r_first + j];
+            values_stage_offsets(stage, offsets, r_first, span);
             __syncthreads();
         }
-        const uint32_t first = t * (uint32_t)VPT;  // workgroup-local index of the thread's first value
-        const uint32_t mine = first < here ? (here - first < (uint32_t)VPT ? here - first : (uint32_t)VPT) : 0u;
-        // the record of each of the thread's values (r_last for the lanes past the end: a valid record, nothing is stored)
         unsigned long long rd[VPT];
-        if (staged) {
-            // LDS path: search the stage for the first value, step forward for the others (stage[j] = offsets[r_first + j];
-            // the bound on j ends every step inside the stage)
-            uint32_t j = mine ? (uint32_t)values_read_of(stage, 0ull, span - 2ull, i0 + first) : (uint32_t)(span - 2ull);
-#pragma unroll
-            for (int u = 0; u < VPT; ++u) {
-                if ((uint32_t)u < mine)
-                    while (j + 2u < (uint32_t)span && stage[j + 1u] <= i0 + first + (uint32_t)u) ++j;
-                rd[u] = r_first + j;
-            }
-        } else {
-            // global path: every value searched within the workgroup's span, from its predecessor's record on
-            unsigned long long r = r_first;
-#pragma unroll
-            for (int u = 0; u < VPT; ++u) {
-                if ((uint32_t)u < mine) r = values_read_of(offsets, r, r_last, i0 + first + (uint32_t)u);
-                rd[u] = (uint32_t)u < mine ? r : r_last;
-            }
-        }
-        unsigned long long r_have = rd[0], s_have = a.starts[rd[0]];
-#pragma unroll
-        for (int u = 0; u < VPT; ++u) {
-            if (rd[u] != r_have) r_have = rd[u], s_have = a.starts[rd[u]];
-            p[u] = a.view.base0 + s_have + ps[u];
-        }
+        MM_VALUES_RECORDS(VPT, rd, stage, offsets, r_first, r_last, span, staged, i0, here)
+        values_by_record<VPT>(
+            rd, [&](unsigned long long r) { return a.starts[r]; },
+            [&](int u, unsigned long long start) { p[u] = a.view.base0 + start + ps[u]; });
     }
 
     // the gathered characters of each value, unmasked.  Hot path: every k-mer of the thread lies in whole dwords inside
@@ -144,25 +95,11 @@ __global__ __launch_bounds__(kBlockThreads) void values_text_kernel(ValuesTextAr
         unsigned long long v[VPT];
 #pragma unroll
         for (int u = 0; u < VPT; ++u) v[u] = text_value64<DNA>(lo[u], a.len, a.canonical);
-#pragma unroll
-        for (int u = 0; u < VPT; u += 2) {
-            u32x4 o;
-            o.x = (uint32_t)v[u];
-            o.y = (uint32_t)(v[u] >> 32);
-            o.z = (uint32_t)v[u + 1];
-            o.w = (uint32_t)(v[u + 1] >> 32);
-            // (the last pair may be half inside: the bounds check works per dword, so its inner half is stored)
-            __builtin_amdgcn_raw_buffer_store_b128(o, rout, t * 32u + (uint32_t)u * 8u, 0, 0);
-        }
+        b.store_u64(v);
     } else {
         unsigned long long vlo = lo[0], vhi = hi[0];
         text_value128<DNA>(a.len, a.canonical, vlo, vhi);
-        u32x4 o;
-        o.x = (uint32_t)vlo;
-        o.y = (uint32_t)(vlo >> 32);
-        o.z = (uint32_t)vhi;
-        o.w = (uint32_t)(vhi >> 32);
-        __builtin_amdgcn_raw_buffer_store_b128(o, rout, t * 16u, 0, 0);
+        b.store_u128(vlo, vhi);
     }
 }
 
@@ -179,10 +116,8 @@ int launch_one(const ValuesTextArgs &a, bool batch, uint32_t blocks, hipStream_t
 
 int launch_values_text(const ValuesTextArgs &a, int encoding, bool u128, bool batch, hipStream_t stream) {
     if (a.n_pos_max == 0 || (batch && a.n_records == 0)) return 0;
-    const uint64_t per_block = (uint64_t)kBlockThreads * (u128 ? 1 : 4);
-    const uint64_t blocks64 = (a.n_pos_max + per_block - 1) / per_block;
-    if (blocks64 > 0x7fffffffull) return -3;
-    const uint32_t blocks = (uint32_t)blocks64;
+    uint32_t blocks;
+    if (values_grid(a.n_pos_max, u128, &blocks)) return -3;
     if (encoding == kTextValuesBytes)
         return u128 ? launch_one<text_value_dwords(16), false, true>(a, batch, blocks, stream)
                     : launch_one<text_value_dwords(8), false, false>(a, batch, blocks, stream);
