@@ -551,7 +551,7 @@ uint32_t mm_values_reads_lds_stage(void);
  * (base_offset, a fixed-stride layout's last read or - host forms - starts[n] past the buffer), MM_ERR_UNSORTED (host forms:
  * decreasing starts).  n_reads == 0 returns MM_OK with nothing launched.  Device forms: unordered starts are the caller's
  * breach - the output is then undefined, but nothing outside the buffers named here is read or written.  n_reads comes from
- * the host (no counts-on-device form).  Every call runs on the workspace's stream and restores the caller's current device;
+ * the host here; the *_counts_* forms below read it on the device.  Every call runs on the workspace's stream and restores the caller's current device;
  * results are valid after mm_workspace_sync.  Kernels (mm_one_min.hip): a fill of one 64-bit key per record, one workgroup
  * per mm_one_minimizer_tile() k-mer start positions that ends in one 64-bit atomic minimum per (tile, record) pair, and a
  * small kernel that turns keys into positions. */
@@ -564,6 +564,34 @@ int mm_one_minimizer_text_batch_device_async(mm_workspace_t *ws, const mm_text_h
                                              const void *d_text, uint64_t text_bytes, uint64_t n_records,
                                              const uint64_t *d_starts /* [n_records + 1] */,
                                              uint32_t *d_out_pos /* [n_records] */);
+/* The same with the two counts read on the DEVICE, so that the call queues behind a loader with no host wait (the reference
+ * has no counterpart: one_minimizer, src/minimizers.rs:22-28, is synchronous host code over one sequence).
+ *   d_counts [2] (device)      {symbols, records} in the loaders' layout (mm_fasta_text_device_async; the packers'
+ *                              mm_fasta_pack_device_async / mm_fastq_pack_device_async: bases, records), read at kernel time
+ *   max_chars / max_bases      bound of d_counts[0]: sizes the grid; max_chars <= text_bytes, base_offset + max_bases inside
+ *                              the packed buffer
+ *   max_records                bound of d_counts[1]: d_starts holds max_records + 1 words, d_out_pos max_records words
+ * With (n_sym, n) = d_counts[0 .. 1]: d_out_pos[0 .. n) is bit for bit what the host-n call above writes for n_reads = n on
+ * a buffer cut at n_sym symbols (no symbol at or past min(starts[n], n_sym) is loaded), d_out_pos[n .. max_records) is
+ * MM_NO_MINIMIZER, nothing at or past max_records is written.  Counts beyond a bound (n_sym > max_chars, n > max_records):
+ * every d_out_pos[0 .. max_records) is MM_NO_MINIMIZER, the starts are not read, and mm_workspace_check returns
+ * MM_ERR_CAPACITY once (kernel error 8, raised in the workspace's sticky error word as 6 and 7 are by the counts runs); the
+ * workspace stays usable.  The packed form takes the starts layout only (the fixed-stride layout has no loader behind it).
+ * Checks, in this order: MM_ERR_NULL (workspace, hasher, d_counts; for max_records > 0 the starts, the output and a buffer
+ * when the bound is not 0), MM_ERR_K_ZERO, [max_records == 0: MM_OK, nothing launched], MM_ERR_LEN_TOO_LARGE (max_chars /
+ * max_bases >= 2^32, max_records >= 2^31), MM_ERR_CAPACITY (max_chars > text_bytes; base_offset + max_bases past the packed
+ * buffer).  Kernels: the same per-tile code, instantiated with the counts read by thread 0 of each workgroup
+ * (one_min_counts_view, mm_one_min.h); workgroups past the real last tile leave at once. */
+int mm_one_minimizer_text_batch_counts_device_async(mm_workspace_t *ws, const mm_text_hasher_t *hasher, uint32_t k,
+                                                    const void *d_text, uint64_t text_bytes, uint64_t max_chars,
+                                                    uint64_t max_records, const uint64_t *d_starts /* [max_records + 1] */,
+                                                    const uint64_t *d_counts /* [2]: characters, records */,
+                                                    uint32_t *d_out_pos /* [max_records] */);
+int mm_one_minimizer_reads_counts_device_async(mm_workspace_t *ws, const mm_hasher_t *hasher, uint32_t k, const void *d_packed,
+                                               uint64_t packed_bytes, uint64_t base_offset, uint64_t max_bases,
+                                               uint64_t max_records, const uint64_t *d_read_starts /* [max_records + 1] */,
+                                               const uint64_t *d_counts /* [2]: bases, records */,
+                                               uint32_t *d_out_pos /* [max_records] */);
 /* The same from HOST memory: one upload (the bytes and the starts), the launches, one download; they wait. */
 int mm_one_minimizer_reads_host(mm_workspace_t *ws, const mm_hasher_t *hasher, uint32_t k, const uint8_t *packed,
                                 uint64_t packed_bytes, uint64_t base_offset, uint64_t n_reads,
@@ -582,6 +610,21 @@ int mm_debug_one_minimizer_reads(const mm_hasher_t *hasher, uint32_t k, const ui
                                  uint32_t read_len, uint32_t tile, uint32_t *out_pos);
 int mm_debug_one_minimizer_text_batch(const mm_text_hasher_t *hasher, uint32_t k, const uint8_t *text, uint64_t text_bytes,
                                       uint64_t n_records, const uint64_t *starts, uint32_t tile, uint32_t *out_pos);
+/* The counts forms on the host (no device; for tests).  mm_debug_one_minimizer_counts_view: the function every workgroup
+ * turns {counts, bounds} into what it works on with - out = {n, limit, refused}; `starts` is read at [n] only, and not at
+ * all for a refused view or n == 0 (it may then be NULL).  The two runs: the per-tile function with the view's (n, limit),
+ * out_pos[0 .. max_records) as the device forms write it; their checks and codes minus the workspace, and MM_ERR_CAPACITY -
+ * the output written all the same - for a refused view (what mm_workspace_check reports behind the device forms). */
+int mm_debug_one_minimizer_counts_view(uint64_t max_sym, uint64_t max_records, uint64_t n_sym, uint64_t n,
+                                       const uint64_t *starts, uint64_t out[3]);
+int mm_debug_one_minimizer_text_batch_counts(const mm_text_hasher_t *hasher, uint32_t k, const uint8_t *text,
+                                             uint64_t text_bytes, uint64_t max_chars, uint64_t max_records,
+                                             const uint64_t *starts, const uint64_t *counts /* [2], host */, uint32_t tile,
+                                             uint32_t *out_pos /* [max_records] */);
+int mm_debug_one_minimizer_reads_counts(const mm_hasher_t *hasher, uint32_t k, const uint8_t *packed, uint64_t packed_bytes,
+                                        uint64_t base_offset, uint64_t max_bases, uint64_t max_records,
+                                        const uint64_t *read_starts, const uint64_t *counts /* [2], host */, uint32_t tile,
+                                        uint32_t *out_pos /* [max_records] */);
 
 /* Output::values_u64 / values_u128 (src/lib.rs:584-629) of EVERY sequence of a device batch in one launch: what the loop
  * over the contigs (bench/src/bin/paper.rs:410-431: Builder::run per sequence) and Output::values_* per sequence computes,
@@ -1088,6 +1131,48 @@ int  mm_fastx_stream_feed(mm_fastx_stream_t *s, const uint8_t *text, uint64_t n_
 int  mm_fastx_stream_finish(mm_fastx_stream_t *s);
 int  mm_fastx_stream_next(mm_fastx_stream_t *s, mm_fastx_batch_t *out);
 void mm_fastx_stream_destroy(mm_fastx_stream_t *s);
+/* ---- The same for BYTE TEXT (protein FASTA of any size): a text plan (mm_plan_create_text) in place of the packed one; the
+ * handle is the same type and mm_fastx_stream_feed / _finish / _next / _destroy serve it unchanged.  The reference reads such
+ * a file record by record on the CPU too (needletail::parse_fastx_file, bench/src/lib.rs:51-82; Builder::run on &[u8],
+ * src/lib.rs:378) and has no other counterpart.  Every chunk runs, on its slot's stream, the slot pipeline of the DNA stream
+ * step for step: upload, the previous chunk's tail, mm_fasta_text_device_async (the sequence bytes as they stand, into a
+ * buffer of 2 * chunk_bytes), the trim step with the FASTA rule, mm_run_text_batch_counts_device_async with max_chars = the
+ * chunk's text length, mm_values_*_text_batch_counts_device_async with `values_encoding`, and with
+ * MM_FASTX_TEXT_ONE_MINIMIZER mm_one_minimizer_text_batch_counts_device_async with the plan's k and hasher (one_minimizer,
+ * src/minimizers.rs:22-28, per record); one mm_workspace_check judges a chunk, a look-back time-out repeats run, values and
+ * one minimizer.  Exactly the filled parts are downloaded.
+ * The batch: mm_fastx_batch_t with n_bases = characters and rec_base = the records' starts in the chunk's byte sequence;
+ * mm_fastx_text_stream_extras hands out, for the batch last returned, one_min ([n_records], record-local, MM_NO_MINIMIZER for
+ * a record shorter than k; NULL without the flag) and seq (rec_base[n_records] bytes; NULL without MM_FASTX_TEXT_SEQ).
+ * Offsets as above: rec_text_pos, text_begin, text_end absolute and 64-bit, everything else chunk-local.
+ * Format: FASTA only (FASTQ to byte records is not provided): MM_FASTX_FASTQ is MM_ERR_FORMAT at create; with MM_FASTX_AUTO
+ * a first non-blank byte '@' - or any other but '>' - is MM_ERR_FORMAT at feed.
+ * Flags: MM_FASTX_SK, MM_FASTX_VALUES_U64, MM_FASTX_VALUES_U128 as above; MM_FASTX_TEXT_ONE_MINIMIZER and MM_FASTX_TEXT_SEQ
+ * for this entry only; MM_FASTX_SKIP_AMBIGUOUS and MM_FASTX_LONG_RECORDS are refused (byte text has neither).
+ * Refusals of mm_fastx_text_stream_create before any device is touched, in this order: NULL arguments (MM_ERR_NULL); a plan
+ * that is not a text plan (MM_ERR_BAD_MODE); chunk_bytes outside [64, 2^31) or max_records >= 2^31 (MM_ERR_LEN_TOO_LARGE);
+ * MM_FASTX_SK with syncmers (MM_ERR_BAD_MODE); MM_FASTX_SKIP_AMBIGUOUS or MM_FASTX_LONG_RECORDS (MM_ERR_BAD_MODE); both values
+ * flags (MM_ERR_BAD_MODE); an unknown values_encoding (MM_ERR_BAD_MODE); with a values flag MM_TEXT_VALUES_BYTES and a
+ * canonical hasher (MM_ERR_BAD_MODE), then a value length beyond the encoding's limit - 8 / 16 for BYTES, 32 / 64 for DNA
+ * (MM_ERR_VALUE_LEN); a plan the fused text kernel does not take, w > 128 or k > 1024 (MM_ERR_BAD_MODE, mm_last_error() as
+ * mm_run_text_batch_counts_device_async sets it); format MM_FASTX_FASTQ (MM_ERR_FORMAT); an unknown format, flag or slots
+ * outside 0, 2..8 (MM_ERR_BAD_MODE); no device (MM_ERR_NO_DEVICE).
+ * Errors while streaming as above (the stream stays failed): MM_ERR_CAPACITY for a record longer than a chunk, more than
+ * max_records records or more than max_positions positions in a chunk.  Memory per slot: DESIGN.md 4.4e. */
+enum { MM_FASTX_TEXT_ONE_MINIMIZER = 32, MM_FASTX_TEXT_SEQ = 64 };
+typedef struct mm_fastx_text_stream_config {
+    int device; int format; uint32_t flags; uint32_t slots;    /* as mm_fastx_stream_config_t */
+    uint64_t chunk_bytes, max_records, max_positions, first_byte;
+    int values_encoding;       /* MM_TEXT_VALUES_BYTES / MM_TEXT_VALUES_DNA */
+} mm_fastx_text_stream_config_t;
+typedef struct mm_fastx_text_extras {
+    const uint32_t *one_min;   /* [n_records] record-local, MM_NO_MINIMIZER: shorter than k; NULL without the flag */
+    const uint8_t *seq;        /* [rec_base[n_records]] the records' bytes back to back; NULL without the flag */
+} mm_fastx_text_extras_t;
+int mm_fastx_text_stream_create(mm_fastx_stream_t **out, const mm_plan_t *text_plan, const mm_fastx_text_stream_config_t *cfg);
+/* Of the batch last returned by mm_fastx_stream_next (valid as long as the batch is; NULLs before the first batch and for a
+ * stream of mm_fastx_stream_create). */
+int mm_fastx_text_stream_extras(const mm_fastx_stream_t *s, mm_fastx_text_extras_t *out);
 /* The cut rule on a text in HOST memory, by the function the trim kernel calls itself (csrc/mm_fastx_cut.h; no device, like
  * mm_debug_lane_counts_view): format MM_FASTX_FASTA / MM_FASTX_FASTQ (MM_ERR_BAD_MODE otherwise), last != 0 keeps everything;
  * out = {cut, kept records, dropped records}. */

@@ -384,42 +384,37 @@ class Builder {  // src/lib.rs:225-230
         mm_fastx_stream_t *st = nullptr;
         int r = mm_fastx_stream_create(&st, plan, &options);
         if (r == MM_OK) {
-            std::vector<uint8_t> buf(read_bytes ? read_bytes : 1);
-            mm_fastx_batch_t batch;
             auto deliver = [&](const mm_fastx_batch_t &b) {
                 if constexpr (std::is_invocable_v<OnBatch &, const mm_fastx_batch_t &, const mm_fastx_pieces_t &>)
                     on_batch(b, fastx_pieces(st));
                 else
                     on_batch(b);
             };
-            try {
-                for (;;) {
-                    const size_t got = reader(buf.data(), buf.size());
-                    if (got == 0) break;
-                    for (uint64_t done = 0; done < got && r == MM_OK;) {
-                        uint64_t took = 0;
-                        r = mm_fastx_stream_feed(st, buf.data() + done, got - done, &took);
-                        done += took;
-                        if (r == MM_OK && done < got) {
-                            r = mm_fastx_stream_next(st, &batch);
-                            if (r == MM_OK) deliver(batch);
-                            else if (r == MM_FASTX_NEED_INPUT) r = MM_OK;
-                        }
-                    }
-                    if (r != MM_OK) break;
-                }
-                if (r == MM_OK) r = mm_fastx_stream_finish(st);
-                while (r == MM_OK) {
-                    r = mm_fastx_stream_next(st, &batch);
-                    if (r == MM_OK) deliver(batch);
-                }
-                if (r == MM_FASTX_END) r = MM_OK;
-            } catch (...) {
-                mm_fastx_stream_destroy(st);
-                mm_plan_destroy(plan);
-                throw;
-            }
-            mm_fastx_stream_destroy(st);
+            r = pump_stream(st, plan, reader, deliver, read_bytes);
+        }
+        mm_plan_destroy(plan);
+        check(r);
+    }
+
+    // The same for a FASTA of BYTE TEXT (protein; mm_fastx_text_stream_create on this builder's text plan and
+    // .text_hasher(..)): `on_batch(const mm_fastx_batch_t &, const mm_fastx_text_extras_t &)` receives every batch with its
+    // one minimizer per record (MM_FASTX_TEXT_ONE_MINIMIZER) and the records' bytes (MM_FASTX_TEXT_SEQ); n_bases counts
+    // characters, rec_base holds the records' starts.  The reference reads such a file record by record on the CPU
+    // (bench/src/lib.rs:51-82) and runs Builder::run on &[u8] per record (src/lib.rs:378).
+    template <class Reader, class OnBatch>
+    void stream_fasta_text(Reader &&reader, OnBatch &&on_batch, const mm_fastx_text_stream_config_t &options,
+                           size_t read_bytes = size_t(1) << 22) const {
+        mm_plan_t *plan = nullptr;
+        check(mm_plan_create_text(&plan, k_, w_, CANONICAL, (mm_mode_t)SYNCMER, has_text_hasher_ ? &text_hasher_ : nullptr));
+        mm_fastx_stream_t *st = nullptr;
+        int r = mm_fastx_text_stream_create(&st, plan, &options);
+        if (r == MM_OK) {
+            auto deliver = [&](const mm_fastx_batch_t &b) {
+                mm_fastx_text_extras_t x;
+                check(mm_fastx_text_stream_extras(st, &x));
+                on_batch(b, x);
+            };
+            r = pump_stream(st, plan, reader, deliver, read_bytes);
         }
         mm_plan_destroy(plan);
         check(r);
@@ -542,6 +537,43 @@ class Builder {  // src/lib.rs:225-230
     uint32_t w() const { return w_; }
 
   private:
+    // The feed / next loop of both streams; destroys the stream (and, when `deliver` throws, the plan) before it returns.
+    template <class Reader, class Deliver>
+    static int pump_stream(mm_fastx_stream_t *st, mm_plan_t *plan, Reader &&reader, Deliver &&deliver, size_t read_bytes) {
+        int r = MM_OK;
+        std::vector<uint8_t> buf(read_bytes ? read_bytes : 1);
+        mm_fastx_batch_t batch;
+        try {
+            for (;;) {
+                const size_t got = reader(buf.data(), buf.size());
+                if (got == 0) break;
+                for (uint64_t done = 0; done < got && r == MM_OK;) {
+                    uint64_t took = 0;
+                    r = mm_fastx_stream_feed(st, buf.data() + done, got - done, &took);
+                    done += took;
+                    if (r == MM_OK && done < got) {
+                        r = mm_fastx_stream_next(st, &batch);
+                        if (r == MM_OK) deliver(batch);
+                        else if (r == MM_FASTX_NEED_INPUT) r = MM_OK;
+                    }
+                }
+                if (r != MM_OK) break;
+            }
+            if (r == MM_OK) r = mm_fastx_stream_finish(st);
+            while (r == MM_OK) {
+                r = mm_fastx_stream_next(st, &batch);
+                if (r == MM_OK) deliver(batch);
+            }
+            if (r == MM_FASTX_END) r = MM_OK;
+        } catch (...) {
+            mm_fastx_stream_destroy(st);
+            mm_plan_destroy(plan);
+            throw;
+        }
+        mm_fastx_stream_destroy(st);
+        return r;
+    }
+
     // one pass of the hot path over `seq` on the device; fills pos (and sk), returns the count
     uint64_t compute(PackedSeq seq, Workspace &ws, std::vector<uint32_t> &pos, std::vector<uint32_t> &sk) const {
         mm_plan_t *plan = nullptr;
@@ -802,6 +834,25 @@ inline std::vector<uint32_t> one_minimizer_many(const std::vector<TextSeq> &reco
     check(mm_one_minimizer_text_batch_host(w.get(), &hasher, k, text.data(), starts.back(), records.size(), starts.data(),
                                            out.data()));
     return out;
+}
+// The *_many_counts_device forms: records already on the device with their two counts {symbols, records} in DEVICE memory,
+// as a loader wrote them (mm_one_minimizer_text_batch_counts_device_async / mm_one_minimizer_reads_counts_device_async):
+// asynchronous on `ws`, d_out_pos[0 .. n) filled, MM_NO_MINIMIZER up to max_records; mm_workspace_check reports counts
+// beyond the bounds as MM_ERR_CAPACITY.  The reference has no counterpart (one_minimizer is synchronous host code).
+inline void one_minimizer_many_counts_device(const mm_text_hasher_t &hasher, uint32_t k, const void *d_text, uint64_t text_bytes,
+                                             uint64_t max_chars, uint64_t max_records, const uint64_t *d_starts,
+                                             const uint64_t *d_counts, uint32_t *d_out_pos, Workspace *ws = nullptr) {
+    Workspace &w = ws ? *ws : Workspace::thread_default();
+    check(mm_one_minimizer_text_batch_counts_device_async(w.get(), &hasher, k, d_text, text_bytes, max_chars, max_records,
+                                                          d_starts, d_counts, d_out_pos));
+}
+inline void one_minimizer_many_counts_device(const mm_hasher_t &hasher, uint32_t k, const void *d_packed, uint64_t packed_bytes,
+                                             uint64_t base_offset, uint64_t max_bases, uint64_t max_records,
+                                             const uint64_t *d_read_starts, const uint64_t *d_counts, uint32_t *d_out_pos,
+                                             Workspace *ws = nullptr) {
+    Workspace &w = ws ? *ws : Workspace::thread_default();
+    check(mm_one_minimizer_reads_counts_device_async(w.get(), &hasher, k, d_packed, packed_bytes, base_offset, max_bases,
+                                                     max_records, d_read_starts, d_counts, d_out_pos));
 }
 template <class Hasher>
 inline std::vector<uint32_t> one_minimizer_many(const std::vector<PackedSeq> &reads, const Hasher &hasher, uint32_t k) {

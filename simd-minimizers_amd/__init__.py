@@ -255,6 +255,12 @@ def _load_lib():
         L.mm_one_minimizer_text_batch_device_async.argtypes = [vp, vp, C.c_uint32, vp] + one_min_text_tail + [vp]
         L.mm_one_minimizer_text_batch_host.argtypes = [vp, vp, C.c_uint32, vp] + one_min_text_tail + [vp]
         L.mm_debug_one_minimizer_text_batch.argtypes = [vp, C.c_uint32, vp] + one_min_text_tail + [C.c_uint32, vp]
+        # (the counts forms: bounds in place of the counts, d_counts behind the starts)
+        L.mm_one_minimizer_text_batch_counts_device_async.argtypes = [vp, vp, C.c_uint32, vp] + [C.c_uint64] * 3 + [vp, vp, vp]
+        L.mm_one_minimizer_reads_counts_device_async.argtypes = [vp, vp, C.c_uint32, vp] + [C.c_uint64] * 4 + [vp, vp, vp]
+        L.mm_debug_one_minimizer_counts_view.argtypes = [C.c_uint64] * 4 + [vp, vp]
+        L.mm_debug_one_minimizer_text_batch_counts.argtypes = [vp, C.c_uint32, vp] + [C.c_uint64] * 3 + [vp, vp, C.c_uint32, vp]
+        L.mm_debug_one_minimizer_reads_counts.argtypes = [vp, C.c_uint32, vp] + [C.c_uint64] * 4 + [vp, vp, C.c_uint32, vp]
         L.mm_one_minimizer_tile.argtypes = []
         L.mm_one_minimizer_tile.restype = C.c_uint32
         values_batch_args = [vp, C.c_uint64, C.POINTER(vp), u64p, u64p, u64p, C.c_uint32, C.c_int, vp, u64p, vp]
@@ -355,6 +361,8 @@ def _load_lib():
             L.mm_fastx_stream_destroy.argtypes = [vp]
             L.mm_fastx_stream_destroy.restype = None
             L.mm_debug_fastx_cut.argtypes = [vp, C.c_uint64, C.c_int, C.c_int, u64p]
+        L.mm_fastx_text_stream_create.argtypes = [C.POINTER(vp), vp, vp]
+        L.mm_fastx_text_stream_extras.argtypes = [vp, vp]
         if hasattr(L, "mm_fastx_stream_pieces"):  # (FASTA records longer than a chunk: MM_FASTX_LONG_RECORDS)
             L.mm_fastx_stream_pieces.argtypes = [vp, vp]
             L.mm_debug_fastx_split.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_int, u64p]
@@ -413,6 +421,9 @@ EXPORTED_SYMBOLS = [
     "mm_one_minimizer_reads_device_async", "mm_one_minimizer_text_batch_device_async", "mm_one_minimizer_reads_host",
     "mm_one_minimizer_text_batch_host", "mm_one_minimizer_tile", "mm_debug_one_minimizer_reads",
     "mm_debug_one_minimizer_text_batch",
+    "mm_one_minimizer_text_batch_counts_device_async", "mm_one_minimizer_reads_counts_device_async",
+    "mm_debug_one_minimizer_counts_view", "mm_debug_one_minimizer_text_batch_counts", "mm_debug_one_minimizer_reads_counts",
+    "mm_fastx_text_stream_create", "mm_fastx_text_stream_extras",
 ]
 
 
@@ -1894,7 +1905,7 @@ class FastxBatch:
     ``first_overlap`` bases repeat the previous piece and ``first_base`` is the record-global index of its first base);
     ``last_open`` - the last record goes on in the next batch.  ``fastx_join`` puts the pieces together."""
 
-    def __init__(self, c: _FastxBatchC, u128: bool, views=True, pieces: "_FastxPiecesC" = None):
+    def __init__(self, c: _FastxBatchC, u128: bool, views=True, pieces: "_FastxPiecesC" = None, extras=None):
         n, p = int(c.n_records), int(c.n_positions)
         self.u128 = u128
         self.first_continues = bool(pieces.first_continues) if pieces is not None else False
@@ -1909,9 +1920,15 @@ class FastxBatch:
         self.pos = _view(c.pos, p, C.c_uint32, np.uint32)
         self.sk = _view(c.sk, p, C.c_uint32, np.uint32) if c.sk else None
         self.values = _view(c.values, p * (2 if u128 else 1), C.c_uint64, np.uint64) if c.values else None
+        # a ``FastxTextStream``'s extras (None elsewhere): one minimizer per record, the records' bytes back to back
+        self.one_min = self.seq = None
+        if extras is not None:
+            self.one_min = _view(extras.one_min, n, C.c_uint32, np.uint32) if extras.one_min else None
+            if extras.seq:
+                self.seq = _view(extras.seq, int(self.rec_base[n]) if n else 0, C.c_uint8, np.uint8)
 
     def copy(self) -> "FastxBatch":
-        for name in ("rec_text_pos", "rec_base", "offsets", "pos", "sk", "values"):
+        for name in ("rec_text_pos", "rec_base", "offsets", "pos", "sk", "values", "one_min", "seq"):
             a = getattr(self, name)
             if a is not None:
                 setattr(self, name, np.array(a, copy=True))
@@ -2014,6 +2031,65 @@ class FastxStream:
         return b
 
 
+FASTX_TEXT_ONE_MINIMIZER, FASTX_TEXT_SEQ = 32, 64
+
+
+class FastxTextStreamConfig(C.Structure):
+    """``mm_fastx_text_stream_config_t``."""
+    _fields_ = FastxStreamConfig._fields_ + [("values_encoding", C.c_int)]
+
+
+class _FastxTextExtrasC(C.Structure):
+    _fields_ = [("one_min", C.c_void_p), ("seq", C.c_void_p)]
+
+
+class FastxTextStream(FastxStream):
+    """A FASTA of BYTE TEXT (protein, any alphabet) of any size through the device in chunks
+    (``mm_fastx_text_stream_create``; feed / finish / next as ``FastxStream``): ``builder`` a text builder, ``values``
+    None / "u64" / "u128" with ``encoding`` ``TEXT_VALUES_BYTES`` (the default) / ``TEXT_VALUES_DNA``, ``super_kmers``,
+    ``one_minimizer`` (``FastxBatch.one_min``: per record the leftmost position of the minimal ``hash & 0xffff0000`` with
+    the builder's k and hasher, ``NO_MINIMIZER`` for a record shorter than k), ``seq`` (``FastxBatch.seq``: the records'
+    bytes, record r = ``seq[rec_base[r]:rec_base[r + 1]]``).  ``fmt`` "auto" / "fasta": FASTQ raises ``MM_ERR_FORMAT``.
+    ``n_bases`` counts characters."""
+
+    def __init__(self, builder: "Builder", chunk_bytes: int, max_records: int, values=None, encoding=None, super_kmers=False,
+                 one_minimizer=False, seq=False, fmt="auto", max_positions=0, first_byte=0, slots=0, device=None):
+        if fmt not in _FASTX_FORMATS:
+            raise ValueError('fmt is "auto" or "fasta"')
+        if values not in (None, "u64", "u128"):
+            raise ValueError('values is None, "u64" or "u128"')
+        flags = (FASTX_SK if super_kmers else 0) | {None: 0, "u64": FASTX_VALUES_U64, "u128": FASTX_VALUES_U128}[values]
+        flags |= (FASTX_TEXT_ONE_MINIMIZER if one_minimizer else 0) | (FASTX_TEXT_SEQ if seq else 0)
+        self.h = None
+        self.long_records = False
+        self.u128 = values == "u128"
+        self.builder = builder
+        self._plan = builder.text_plan()  # (the stream keeps the plan's handle: it must outlive the stream)
+        dev = builder._ws().device if device is None and builder._workspace is not None else (device or 0)
+        self.config = FastxTextStreamConfig(int(dev), _FASTX_FORMATS[fmt], flags, int(slots), int(chunk_bytes), int(max_records),
+                                            int(max_positions), int(first_byte),
+                                            TEXT_VALUES_BYTES if encoding is None else int(encoding))
+        h = C.c_void_p()
+        code = lib().mm_fastx_text_stream_create(C.byref(h), self._plan.h, C.byref(self.config))
+        if code:
+            self._raise(code)
+        self.h = h
+        self.finished = False
+
+    def next(self):
+        c = _FastxBatchC()
+        code = lib().mm_fastx_stream_next(self.h, C.byref(c))
+        if code == FASTX_NEED_INPUT:
+            return None
+        if code == FASTX_END:
+            raise StopIteration
+        if code:
+            self._raise(code)
+        extras = _FastxTextExtrasC()
+        _check(lib().mm_fastx_text_stream_extras(self.h, C.byref(extras)))
+        return FastxBatch(c, self.u128, extras=extras)
+
+
 def fastx_cut(text: bytes, fmt: str, last: bool = False) -> dict:
     """The stream's cut rule on a host text (``mm_debug_fastx_cut``: the function the trim kernel calls, no GPU)."""
     buf = np.frombuffer(text, dtype=np.uint8)
@@ -2069,11 +2145,8 @@ def fastx_join(batches):
         yield done(held)
 
 
-def stream_fastx(builder: "Builder", source, chunk_bytes: int = 64 << 20, max_records: int = 1 << 20, read_bytes: int = 8 << 20,
-                 **options):
-    """Generator over the batches (``FastxBatch``, numpy COPIES) of a FASTA / FASTQ ``source``: a path, a binary file
-    object or an iterable of bytes, of any size.  ``options`` as ``FastxStream`` takes them; ``read_bytes``: how much a
-    path or file object is read at a time."""
+def _stream_batches(st, source, read_bytes):
+    """The feed / next loop of ``stream_fastx`` and ``stream_fasta_text`` over an open stream ``st``: numpy COPIES."""
     import os
 
     def pieces():
@@ -2093,7 +2166,7 @@ def stream_fastx(builder: "Builder", source, chunk_bytes: int = 64 << 20, max_re
         else:
             yield from source
 
-    with FastxStream(builder, chunk_bytes, max_records, **options) as st:
+    with st:
         for piece in pieces():
             view = memoryview(piece)
             done = 0
@@ -2106,6 +2179,21 @@ def stream_fastx(builder: "Builder", source, chunk_bytes: int = 64 << 20, max_re
         st.finish()
         for b in st:
             yield b.copy()
+
+
+def stream_fastx(builder: "Builder", source, chunk_bytes: int = 64 << 20, max_records: int = 1 << 20, read_bytes: int = 8 << 20,
+                 **options):
+    """Generator over the batches (``FastxBatch``, numpy COPIES) of a FASTA / FASTQ ``source``: a path, a binary file
+    object or an iterable of bytes, of any size.  ``options`` as ``FastxStream`` takes them; ``read_bytes``: how much a
+    path or file object is read at a time."""
+    yield from _stream_batches(FastxStream(builder, chunk_bytes, max_records, **options), source, read_bytes)
+
+
+def stream_fasta_text(builder: "Builder", source, chunk_bytes: int = 64 << 20, max_records: int = 1 << 20,
+                      read_bytes: int = 8 << 20, **options):
+    """``stream_fastx`` for a FASTA of byte text (protein): generator over the batches (``FastxBatch`` with ``one_min`` /
+    ``seq``, numpy COPIES) of a ``FastxTextStream`` over ``source``; ``options`` as ``FastxTextStream`` takes them."""
+    yield from _stream_batches(FastxTextStream(builder, chunk_bytes, max_records, **options), source, read_bytes)
 
 
 def run_packed_reads_device(builder: "Builder", records: FastaRecords, out_pos, out_offsets, out_sk=None, max_read_len=None):
@@ -2499,6 +2587,113 @@ def one_minimizer_text_batch_device(hasher: TextHasher, k: int, d_text, d_starts
     _check(lib().mm_one_minimizer_text_batch_device_async(ws.h, C.byref(hasher), int(k),
                                                           _vp_of(d_text) if d_text.numel() else None, int(d_text.numel()),
                                                           n_records, _vp_of(d_starts), _vp_of(out_pos)))
+    return out_pos
+
+
+def debug_one_minimizer_counts_view(max_sym: int, max_records: int, n_sym: int, n: int, starts=None) -> tuple:
+    """What every workgroup of the counts forms turns {counts, bounds} into (``mm_debug_one_minimizer_counts_view``, no
+    GPU): ``(n, limit, refused)``.  ``starts`` (uint64 array) is read at ``[n]`` only, and not at all for a refused view."""
+    starts = np.ascontiguousarray(starts, dtype=np.uint64) if starts is not None else None
+    out = np.zeros(3, dtype=np.uint64)
+    _check(lib().mm_debug_one_minimizer_counts_view(int(max_sym), int(max_records), int(n_sym), int(n), _vp_of(starts),
+                                                    _vp_of(out)))
+    return int(out[0]), int(out[1]), bool(out[2])
+
+
+def debug_one_minimizer_text_batch_counts(hasher: TextHasher, k: int, text, starts, counts, max_chars=None, tile=0,
+                                          refused_ok=False) -> np.ndarray:
+    """The counts form's per-tile function on the host (``mm_debug_one_minimizer_text_batch_counts``, no GPU): ``starts``
+    holds max_records + 1 words, ``counts`` = (characters, records); returns ``np.uint32[max_records]``.  A refused view
+    raises (MM_ERR_CAPACITY) unless ``refused_ok``."""
+    text = np.ascontiguousarray(text, dtype=np.uint8)
+    starts = np.ascontiguousarray(starts, dtype=np.uint64)
+    counts = np.ascontiguousarray(counts, dtype=np.uint64)
+    max_records = len(starts) - 1
+    out = np.zeros(max(1, max_records), dtype=np.uint32)
+    rc = lib().mm_debug_one_minimizer_text_batch_counts(C.byref(hasher), int(k), _vp_of(text), len(text),
+                                                        len(text) if max_chars is None else int(max_chars), max_records,
+                                                        _vp_of(starts), _vp_of(counts), int(tile), _vp_of(out))
+    if not (refused_ok and rc == ERR["CAPACITY"]):
+        _check(rc)
+    return out[:max_records]
+
+
+def debug_one_minimizer_reads_counts(hasher: Hasher, k: int, packed, read_starts, counts, max_bases=None, base_offset=0,
+                                     tile=0, refused_ok=False) -> np.ndarray:
+    """The same for reads of a packed buffer (``mm_debug_one_minimizer_reads_counts``, no GPU); ``max_bases`` defaults to
+    what the buffer holds behind ``base_offset``."""
+    packed = np.ascontiguousarray(packed, dtype=np.uint8)
+    starts = np.ascontiguousarray(read_starts, dtype=np.uint64)
+    counts = np.ascontiguousarray(counts, dtype=np.uint64)
+    max_records = len(starts) - 1
+    if max_bases is None:
+        max_bases = 4 * len(packed) - int(base_offset)
+    out = np.zeros(max(1, max_records), dtype=np.uint32)
+    rc = lib().mm_debug_one_minimizer_reads_counts(C.byref(hasher), int(k), _vp_of(packed), len(packed), int(base_offset),
+                                                   int(max_bases), max_records, _vp_of(starts), _vp_of(counts), int(tile),
+                                                   _vp_of(out))
+    if not (refused_ok and rc == ERR["CAPACITY"]):
+        _check(rc)
+    return out[:max_records]
+
+
+def one_minimizer_text_batch_counts_device(hasher: TextHasher, k: int, d_text, d_starts=None, d_counts=None, max_records=None,
+                                           max_chars=None, out_pos=None, ws=None):
+    """``one_minimizer`` of every record of a device text batch whose two counts (characters, records) are read on the
+    DEVICE (``mm_one_minimizer_text_batch_counts_device_async``): the call queues behind ``fasta_text_device_async`` with no
+    host wait.  ``d_text`` uint8, ``d_starts`` int64 of max_records + 1, ``d_counts`` int64 of 2 (what the
+    loader writes; ``max_chars`` defaults to all of ``d_text``).  ``out_pos`` (int32, max_records) receives the
+    positions of the records there are and ``NO_MINIMIZER`` behind them; counts beyond the bounds give ``NO_MINIMIZER``
+    everywhere and MM_ERR_CAPACITY from ``Workspace.check``.  Asynchronous on ``ws``."""
+    import torch
+    if max_records is None:
+        max_records = d_starts.numel() - 1
+    max_records = int(max_records)
+    if max_records < 0 or d_starts.numel() < max_records + 1:
+        raise ValueError("d_starts holds max_records + 1 starts")
+    if d_counts is None or d_counts.numel() < 2:
+        raise ValueError("d_counts holds two words: characters, records")
+    max_chars = int(d_text.numel()) if max_chars is None else int(max_chars)
+    dev = d_starts.device
+    if ws is None:
+        ws = default_workspace(dev.index or 0)
+    if out_pos is None:
+        out_pos = torch.zeros(max_records, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+    elif out_pos.numel() < max_records:
+        raise ValueError(f"out_pos holds {out_pos.numel()} words, {max_records} needed")
+    _check(lib().mm_one_minimizer_text_batch_counts_device_async(
+        ws.h, C.byref(hasher), int(k), _vp_of(d_text) if d_text.numel() else None, int(d_text.numel()), max_chars,
+        max_records, _vp_of(d_starts), _vp_of(d_counts), _vp_of(out_pos)))
+    return out_pos
+
+
+def one_minimizer_reads_counts_device(hasher: Hasher, k: int, d_packed, read_starts, d_counts, max_records=None,
+                                      max_bases=None, out_pos=None, base_offset=0, ws=None):
+    """The same for the reads of a packed device buffer (``mm_one_minimizer_reads_counts_device_async``; starts layout
+    only): behind ``fasta_pack_device_async`` / ``fastq_pack_device_async`` with no host wait.  ``max_bases`` defaults to
+    what the buffer holds behind ``base_offset``."""
+    import torch
+    if max_records is None:
+        max_records = read_starts.numel() - 1
+    max_records = int(max_records)
+    if max_records < 0 or read_starts.numel() < max_records + 1:
+        raise ValueError("read_starts holds max_records + 1 starts")
+    if d_counts is None or d_counts.numel() < 2:
+        raise ValueError("d_counts holds two words: bases, records")
+    if max_bases is None:
+        max_bases = 4 * int(d_packed.numel()) - int(base_offset)
+    dev = d_packed.device
+    if ws is None:
+        ws = default_workspace(dev.index or 0)
+    if out_pos is None:
+        out_pos = torch.zeros(max_records, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+    elif out_pos.numel() < max_records:
+        raise ValueError(f"out_pos holds {out_pos.numel()} words, {max_records} needed")
+    _check(lib().mm_one_minimizer_reads_counts_device_async(
+        ws.h, C.byref(hasher), int(k), _vp_of(d_packed), int(d_packed.numel()), int(base_offset), int(max_bases), max_records,
+        _vp_of(read_starts), _vp_of(d_counts), _vp_of(out_pos)))
     return out_pos
 
 

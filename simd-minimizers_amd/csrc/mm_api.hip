@@ -418,6 +418,10 @@ const char *const kTextCountsRefused =
 const char *const kLaneCountsRefused =
     "mm_run_packed_reads_counts_device_async: d_counts exceed max_bases / max_records (the packer overflowed its table or "
     "buffer?); count 0 and offsets of 0 were written, no position";
+// (kernel error 8: the counts of a one-minimizer call, read on the device, lie beyond the bounds the caller gave)
+const char *const kOneMinCountsRefused =
+    "mm_one_minimizer_*_counts_device_async: d_counts exceed the symbol / record bounds (the loader overflowed its tables?); "
+    "every output word is MM_NO_MINIMIZER";
 int judge_run_error(mm_workspace *ws) {
     const uint32_t code = (uint32_t)ws->h_total[1];
     if (code == 0) return 0;
@@ -1009,6 +1013,10 @@ int mm_workspace_check(mm_workspace_t *ws) {
     }
     if (code == 7u) {
         g_last_error = kLaneCountsRefused;
+        return MM_ERR_CAPACITY;
+    }
+    if (code == 8u) {
+        g_last_error = kOneMinCountsRefused;
         return MM_ERR_CAPACITY;
     }
     char buf[128];
@@ -3646,6 +3654,21 @@ int one_min_text_queue(mm_workspace_t *ws, const mm_text_hasher_t *hasher, uint3
     return one_min_launch(ws, a, "one_minimizer_text_batch");
 }
 
+// The counts forms' checks, before anything is touched, in the order of one_min_check: MM_ERR_NULL (d_counts included),
+// MM_ERR_K_ZERO, [max_records == 0: MM_OK], MM_ERR_LEN_TOO_LARGE, MM_ERR_CAPACITY.  `symbols`: what the buffer holds
+// (text: text_bytes; packed: 4 * packed_bytes, base_offset + max_sym must lie inside).
+int one_min_counts_check(const mm_workspace_t *ws, const void *hasher, uint32_t k, const void *data, uint64_t symbols,
+                         uint64_t base_offset, uint64_t max_sym, uint64_t max_records, const void *d_starts,
+                         const void *d_counts, const void *out) {
+    if (!ws || !hasher || !d_counts) return MM_ERR_NULL;
+    if (max_records && (!d_starts || !out || (!data && max_sym))) return MM_ERR_NULL;
+    if (k == 0) return MM_ERR_K_ZERO;
+    if (max_records == 0) return MM_OK;
+    if (max_sym >= (1ull << 32) || max_records >= (1ull << 31)) return MM_ERR_LEN_TOO_LARGE;
+    if (base_offset > symbols || max_sym > symbols - base_offset) return MM_ERR_CAPACITY;
+    return MM_OK;
+}
+
 }  // namespace
 
 int mm_one_minimizer_reads_device_async(mm_workspace_t *ws, const mm_hasher_t *hasher, uint32_t k, const void *d_packed,
@@ -3671,6 +3694,82 @@ int mm_one_minimizer_text_batch_device_async(mm_workspace_t *ws, const mm_text_h
     if (r || n_records == 0) return r;
     MM_HIP(set_device(ws->device));
     return one_min_text_queue(ws, hasher, k, d_text, text_bytes, n_records, d_starts, d_out_pos);
+}
+
+static int one_min_text_counts_queue(mm_workspace_t *ws, const mm::TextTables &tt, uint32_t k, const void *d_text,
+                                     uint64_t max_chars, uint64_t max_records, const uint64_t *d_starts,
+                                     const uint64_t *d_counts, uint32_t *d_out_pos);
+// The same with the two counts (symbols, records) in DEVICE memory, read when the kernels run (mm_one_min.h,
+// one_min_counts_view): the call queues behind a loader with no host wait.  The reference has no counterpart (one_minimizer
+// is synchronous host code over one sequence, src/minimizers.rs:22-28); out[0 .. n) is what the host-n call writes.
+int mm_one_minimizer_text_batch_counts_device_async(mm_workspace_t *ws, const mm_text_hasher_t *hasher, uint32_t k,
+                                                    const void *d_text, uint64_t text_bytes, uint64_t max_chars,
+                                                    uint64_t max_records, const uint64_t *d_starts, const uint64_t *d_counts,
+                                                    uint32_t *d_out_pos) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    const int r = one_min_counts_check(ws, hasher, k, d_text, text_bytes, 0, max_chars, max_records, d_starts, d_counts, d_out_pos);
+    if (r || max_records == 0) return r;
+    return one_min_text_counts_queue(ws, make_text_tables(*hasher, k), k, d_text, max_chars, max_records, d_starts, d_counts,
+                                     d_out_pos);
+}
+
+// (after the checks; the tables of one (text hasher, k))
+static int one_min_text_counts_queue(mm_workspace_t *ws, const mm::TextTables &tt, uint32_t k, const void *d_text,
+                                     uint64_t max_chars, uint64_t max_records, const uint64_t *d_starts,
+                                     const uint64_t *d_counts, uint32_t *d_out_pos) {
+    MM_HIP(set_device(ws->device));
+    ws->async_unchecked = true;  // (a refusal is raised in the sticky error word: mm_workspace_check reports it)
+    int r = one_min_keys(ws, max_records);
+    if (r) return r;
+    mm::OneMinArgs a = {};
+    r = text_tables_on_device(ws, tt, &a.tables);
+    if (r) return r;
+    a.syms = static_cast<const uint8_t *>(d_text);
+    a.avail = max_chars;
+    a.n = max_records;
+    a.starts = reinterpret_cast<const unsigned long long *>(d_starts);
+    a.k = k;
+    a.text = true;
+    a.fw0 = tt.fw0, a.rc0 = tt.rc0, a.rot = tt.rot, a.canonical = tt.canonical;
+    a.keys = ws->d_one_min_keys;
+    a.out = d_out_pos;
+    a.counts = reinterpret_cast<const unsigned long long *>(d_counts);
+    a.error = error_word(ws);
+    return one_min_launch(ws, a, "one_minimizer_text_batch_counts");
+}
+
+int mm_one_minimizer_reads_counts_device_async(mm_workspace_t *ws, const mm_hasher_t *hasher, uint32_t k, const void *d_packed,
+                                               uint64_t packed_bytes, uint64_t base_offset, uint64_t max_bases,
+                                               uint64_t max_records, const uint64_t *d_read_starts, const uint64_t *d_counts,
+                                               uint32_t *d_out_pos) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    const uint64_t buffer = packed_bytes >= (1ull << 62) ? ~0ull : 4 * packed_bytes;  // (bases; saturated, never wraps)
+    int r = one_min_counts_check(ws, hasher, k, d_packed, buffer, base_offset, max_bases, max_records, d_read_starts, d_counts,
+                                 d_out_pos);
+    if (r || max_records == 0) return r;
+    MM_HIP(set_device(ws->device));
+    ws->async_unchecked = true;  // (a refusal is raised in the sticky error word: mm_workspace_check reports it)
+    r = one_min_keys(ws, max_records);
+    if (r) return r;
+    const OneMinDnaTables t = one_min_dna_tables(*hasher, k);
+    mm::OneMinArgs a = {};
+    a.syms = static_cast<const uint8_t *>(d_packed);
+    a.base0 = base_offset;
+    a.avail = max_bases;
+    a.n = max_records;
+    a.starts = reinterpret_cast<const unsigned long long *>(d_read_starts);
+    a.k = k;
+    a.text = false;
+    for (int c = 0; c < 4; ++c) {
+        a.small_in[c] = make_uint2(t.t_in[c].x, t.t_in[c].y);
+        a.small_out[c] = make_uint2(t.t_out[c].x, t.t_out[c].y);
+    }
+    a.fw0 = t.fw0, a.rc0 = t.rc0, a.rot = t.rot, a.canonical = t.canonical;
+    a.keys = ws->d_one_min_keys;
+    a.out = d_out_pos;
+    a.counts = reinterpret_cast<const unsigned long long *>(d_counts);
+    a.error = error_word(ws);
+    return one_min_launch(ws, a, "one_minimizer_reads_counts");
 }
 
 // The same from HOST memory: one upload (the bytes the records cover, the starts), the launches, one download.
@@ -3776,6 +3875,65 @@ int mm_debug_one_minimizer_text_batch(const mm_text_hasher_t *hasher, uint32_t k
                                 reinterpret_cast<const mm::OneMinPair *>(tt.t_out), tt.fw0, tt.rc0, tt.rot, tt.canonical};
     one_min_debug_run(mm::OneMinText{text, 0}, mm::OneMinStarts{starts}, n_records, text_bytes, t, k, tile, out_pos);
     return MM_OK;
+}
+
+// The counts forms on the host (no device): the view, and the per-tile function run with the view's (n, limit).
+int mm_debug_one_minimizer_counts_view(uint64_t max_sym, uint64_t max_records, uint64_t n_sym, uint64_t n,
+                                       const uint64_t *starts, uint64_t out[3]) {
+    if (!out) return MM_ERR_NULL;
+    if (!starts && n && n <= max_records && n_sym <= max_sym) return MM_ERR_NULL;  // (a refused view reads no start)
+    const mm::OneMinCountsView v = mm::one_min_counts_view(starts, max_sym, max_records, n_sym, n);
+    out[0] = v.n, out[1] = v.limit, out[2] = v.refused;
+    return MM_OK;
+}
+
+extern "C++" {
+namespace {
+// out_pos[0 .. max_records): the view's records from the tiles, MM_NO_MINIMIZER at and past them.  MM_ERR_CAPACITY for a
+// refused view (what mm_workspace_check reports behind the device form), the output filled all the same.
+template <class Sym>
+int one_min_debug_counts_run(const Sym &sym, const uint64_t *starts, uint64_t max_sym, uint64_t max_records,
+                             const uint64_t *counts, const mm::OneMinTables &t, uint32_t k, uint32_t tile, uint32_t *out_pos) {
+    const mm::OneMinCountsView v = mm::one_min_counts_view(starts, max_sym, max_records, counts[0], counts[1]);
+    std::vector<uint64_t> keys(max_records, mm::kOneMinNoKey);
+    if (v.n) mm::one_min_host(sym, mm::OneMinStarts{starts}, v.n, v.limit, t, k, tile, keys.data());
+    for (uint64_t r = 0; r < max_records; ++r) out_pos[r] = r < v.n ? mm::one_min_position(keys[r]) : MM_NO_MINIMIZER;
+    return v.refused ? MM_ERR_CAPACITY : MM_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int mm_debug_one_minimizer_text_batch_counts(const mm_text_hasher_t *hasher, uint32_t k, const uint8_t *text,
+                                             uint64_t text_bytes, uint64_t max_chars, uint64_t max_records,
+                                             const uint64_t *starts, const uint64_t *counts, uint32_t tile, uint32_t *out_pos) {
+    if (!hasher || !counts) return MM_ERR_NULL;
+    if (max_records && (!starts || !out_pos || (!text && max_chars))) return MM_ERR_NULL;
+    if (k == 0) return MM_ERR_K_ZERO;
+    if (max_records == 0) return MM_OK;
+    if (max_chars >= (1ull << 32) || max_records >= (1ull << 31)) return MM_ERR_LEN_TOO_LARGE;
+    if (max_chars > text_bytes) return MM_ERR_CAPACITY;
+    if (tile == 0) tile = mm::kOneMinTile;
+    const mm::TextTables tt = make_text_tables(*hasher, k);
+    const mm::OneMinTables t = {reinterpret_cast<const mm::OneMinPair *>(tt.t_in),
+                                reinterpret_cast<const mm::OneMinPair *>(tt.t_out), tt.fw0, tt.rc0, tt.rot, tt.canonical};
+    return one_min_debug_counts_run(mm::OneMinText{text, 0}, starts, max_chars, max_records, counts, t, k, tile, out_pos);
+}
+
+int mm_debug_one_minimizer_reads_counts(const mm_hasher_t *hasher, uint32_t k, const uint8_t *packed, uint64_t packed_bytes,
+                                        uint64_t base_offset, uint64_t max_bases, uint64_t max_records,
+                                        const uint64_t *read_starts, const uint64_t *counts, uint32_t tile, uint32_t *out_pos) {
+    if (!hasher || !counts) return MM_ERR_NULL;
+    if (max_records && (!read_starts || !out_pos || (!packed && max_bases))) return MM_ERR_NULL;
+    if (k == 0) return MM_ERR_K_ZERO;
+    if (max_records == 0) return MM_OK;
+    if (max_bases >= (1ull << 32) || max_records >= (1ull << 31)) return MM_ERR_LEN_TOO_LARGE;
+    const uint64_t buffer = packed_bytes >= (1ull << 62) ? ~0ull : 4 * packed_bytes;  // (bases; saturated, never wraps)
+    if (base_offset > buffer || max_bases > buffer - base_offset) return MM_ERR_CAPACITY;
+    if (tile == 0) tile = mm::kOneMinTile;
+    const OneMinDnaTables d = one_min_dna_tables(*hasher, k);
+    const mm::OneMinTables t = {d.t_in, d.t_out, d.fw0, d.rc0, d.rot, d.canonical};
+    return one_min_debug_counts_run(mm::OneMinPacked{packed, base_offset}, read_starts, max_bases, max_records, counts, t, k,
+                                    tile, out_pos);
 }
 
 // ---- Output::values_u64 / values_u128 (src/lib.rs:584-629) of every sequence of a device batch in ONE launch: what the
@@ -5560,6 +5718,23 @@ int api_reads_counts_refusal(const mm_plan_t *plan, uint64_t max_bases, uint64_t
                         .d_read_starts = &some, .d_counts = &some, .d_out_sk = want_sk ? reinterpret_cast<uint32_t *>(&some) : nullptr,
                         .d_out_offsets = &some, .amb = want_amb ? &amb : nullptr});
     return r == MM_ERR_NULL && plan ? (int)MM_OK : r;  // (MM_ERR_NULL with a plan: the missing workspace, refused last)
+}
+int api_text_counts_refusal(const mm_plan_t *plan, uint64_t max_chars, uint64_t max_records, int want_sk) {
+    // (the check reads no pointer: any non-null value stands for the buffers)
+    static uint64_t some = 0;
+    return text_batch_counts_check(plan, {.d_text = &some, .text_bytes = ~0ull, .max_chars = max_chars, .max_records = max_records,
+                                          .d_starts = &some, .d_counts = &some,
+                                          .d_out_sk = want_sk ? reinterpret_cast<uint32_t *>(&some) : nullptr,
+                                          .d_out_offsets = &some});
+}
+int api_one_min_text_plan_counts(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_text, uint64_t text_bytes,
+                                 uint64_t max_chars, uint64_t max_records, const uint64_t *d_starts, const uint64_t *d_counts,
+                                 uint32_t *d_out_pos) {
+    if (!plan || !plan->text) return MM_ERR_BAD_MODE;
+    const int r = one_min_counts_check(ws, plan, plan->k, d_text, text_bytes, 0, max_chars, max_records, d_starts, d_counts,
+                                       d_out_pos);
+    if (r || max_records == 0) return r;
+    return one_min_text_counts_queue(ws, plan->tt, plan->k, d_text, max_chars, max_records, d_starts, d_counts, d_out_pos);
 }
 hipStream_t api_workspace_stream(mm_workspace_t *ws) { return ws->stream; }
 void api_set_last_error(const char *text) { g_last_error = text; }

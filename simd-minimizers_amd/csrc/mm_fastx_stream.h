@@ -32,6 +32,14 @@ ApiPlanInfo api_plan_info(const mm_plan_t *plan);
 // What mm_run_packed_reads_counts_device_async would say to this plan and these bounds before it touches a device, pointers
 // and workspace aside: MM_OK or its refusal (mm_last_error() set as that call sets it).
 int api_reads_counts_refusal(const mm_plan_t *plan, uint64_t max_bases, uint64_t max_records, int want_sk, int want_amb);
+// The byte-text stream (mm_fastx_text_stream_create).  What mm_run_text_batch_counts_device_async would say to this plan
+// and these bounds before it touches a device, pointers and workspace aside (mm_last_error() set as that call sets it) ...
+int api_text_counts_refusal(const mm_plan_t *plan, uint64_t max_chars, uint64_t max_records, int want_sk);
+// ... and mm_one_minimizer_text_batch_counts_device_async with the text plan's own k and hasher tables (a plan keeps the
+// tables of its hasher, not the mm_text_hasher_t they were made from).
+int api_one_min_text_plan_counts(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_text, uint64_t text_bytes,
+                                 uint64_t max_chars, uint64_t max_records, const uint64_t *d_starts, const uint64_t *d_counts,
+                                 uint32_t *d_out_pos);
 hipStream_t api_workspace_stream(mm_workspace_t *ws);
 void api_set_last_error(const char *text);
 

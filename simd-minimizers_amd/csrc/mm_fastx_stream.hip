@@ -21,6 +21,11 @@
 // out in text order, drops a minimizer piece's first position when the record emitted it last (the reference's rule for
 // joining lanes, src/collect.rs:265-271).  Nothing crosses from slot to slot on the device, so a repeated run repeats
 // nothing but its own slot's work.
+//
+// BYTE TEXT (mm_fastx_text_stream_create: a text plan, protein FASTA): the same slots and steps; the loader is
+// mm_fasta_text_device_async, whose sequence bytes go where the packed bases go (d_packed: 2 * chunk_bytes bytes), whose
+// starts go into d_rec_base and whose counts have the packers' layout, so the trim step is used as it is; the run and the
+// values are the text batch counts calls, and MM_FASTX_TEXT_ONE_MINIMIZER adds the one-minimizer counts call behind them.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -46,11 +51,14 @@ struct Slot {
     unsigned long long *d_meta = nullptr;  // [0..1] bases, records  [2..6] cut, overflow, T, open, overlap  [7] positions  [8] newlines
     uint32_t *d_pos = nullptr, *d_sk = nullptr;
     uint64_t *d_values = nullptr;
+    uint32_t *d_one = nullptr;  // byte text, MM_FASTX_TEXT_ONE_MINIMIZER: one word per record
     // page-locked host
     uint8_t *h_text = nullptr;
     unsigned long long *h_meta = nullptr;  // words 0..7 of d_meta; bytes 120..121: the synthetic header line ">\n"
     uint64_t *h_rec_pos = nullptr, *h_rec_base = nullptr, *h_offsets = nullptr, *h_values = nullptr;
     uint32_t *h_pos = nullptr, *h_sk = nullptr;
+    uint32_t *h_one = nullptr;  // byte text: the one-minimizer words ...
+    uint8_t *h_seq = nullptr;   // ... and the records' bytes (MM_FASTX_TEXT_SEQ)
     hipEvent_t ev_cut = nullptr, ev_run = nullptr, ev_done = nullptr, ev_tail = nullptr;
     bool tail_pending = false;  // the chunk behind this slot's copies its tail out of d_text: ev_tail says when it has
     // the chunk in the slot
@@ -88,6 +96,10 @@ struct mm_fastx_stream {
     bool have_last = false;
     uint32_t last_emitted = 0;
     mm_fastx_pieces_t pieces{};  // of the batch handed out last
+    // a stream of mm_fastx_text_stream_create: byte text, d_packed holds the sequence bytes (packed_cap of them)
+    bool text = false;
+    int values_encoding = 0;
+    mm_fastx_text_extras_t extras{};  // of the batch handed out last
     int n_slots = 0;
     Slot slots[8];
     int fill = 0;      // the slot that takes the bytes fed next
@@ -138,6 +150,28 @@ int queue_run(mm_fastx_stream *s, Slot &sl) {
     uint64_t *const d_counts = reinterpret_cast<uint64_t *>(sl.d_meta), *const d_count = reinterpret_cast<uint64_t *>(sl.d_meta + 7);
     const uint64_t max_bases = sl.n_text - (sl.continues ? 2 : 0);  // (the synthetic header line holds no base)
     int r;
+    if (s->text) {
+        // (max_chars = the chunk's text length: it bounds the characters the loader can have written)
+        r = mm_run_text_batch_counts_device_async(s->plan, sl.ws, sl.d_packed, s->packed_cap, sl.n_text, s->max_records,
+                                                  sl.d_rec_base, d_counts, sl.d_pos, sl.d_sk, s->max_positions, sl.d_offsets, d_count);
+        if (r) return fail_call(s, r);
+        if (sl.d_values && s->max_records) {
+            r = (flags & MM_FASTX_VALUES_U128 ? mm_values_u128_text_batch_counts_device_async
+                                              : mm_values_u64_text_batch_counts_device_async)(
+                sl.ws, sl.d_packed, s->packed_cap, sl.n_text, s->max_records, sl.d_rec_base, d_counts, s->values_encoding,
+                s->value_len, s->info.canonical_hasher, sl.d_pos, sl.d_offsets, s->max_positions, sl.d_values);
+            if (r) return fail_call(s, r);
+        }
+        if (sl.d_one && s->max_records) {
+            r = mm::api_one_min_text_plan_counts(s->plan, sl.ws, sl.d_packed, s->packed_cap, sl.n_text, s->max_records,
+                                                 sl.d_rec_base, d_counts, sl.d_one);
+            if (r) return fail_call(s, r);
+        }
+        FX_HIP(hipSetDevice(s->cfg.device));
+        FX_HIP(hipMemcpyAsync(sl.h_meta + 7, sl.d_meta + 7, sizeof(unsigned long long), hipMemcpyDeviceToHost, sl.stream));
+        FX_HIP(hipEventRecord(sl.ev_run, sl.stream));
+        return MM_OK;
+    }
     if (flags & MM_FASTX_SKIP_AMBIGUOUS)
         r = mm_run_packed_reads_skip_ambiguous_counts_device_async(s->plan, sl.ws, sl.d_packed, s->packed_cap, 0, sl.d_amb, s->amb_cap, 0,
                                                                    max_bases, s->max_records, sl.d_rec_base, d_counts, sl.d_pos,
@@ -240,7 +274,10 @@ int launch(mm_fastx_stream *s, int last) {
     const uint8_t *text = sl.d_text + sl.text_off;
     uint64_t *const d_counts = reinterpret_cast<uint64_t *>(sl.d_meta);
     int r;
-    if (s->cfg.flags & MM_FASTX_SKIP_AMBIGUOUS)
+    if (s->text)
+        r = mm_fasta_text_device_async(sl.ws, text, sl.n_text, sl.d_packed, s->packed_cap, sl.d_rec_base, sl.d_rec_pos,
+                                       s->max_records, d_counts);
+    else if (s->cfg.flags & MM_FASTX_SKIP_AMBIGUOUS)
         r = (s->format == MM_FASTX_FASTQ ? mm_fastq_pack_n_device_async : mm_fasta_pack_n_device_async)(
             sl.ws, text, sl.n_text, sl.d_packed, s->packed_cap, sl.d_amb, s->amb_cap, sl.d_rec_base, sl.d_rec_pos, s->max_records, d_counts);
     else
@@ -299,6 +336,9 @@ int collect(mm_fastx_stream *s, Slot &sl, bool block) {
         if (n_records > s->max_records || n_bases > sl.n_text || cut > sl.n_text)
             return fail(s, MM_ERR_HIP, "mm_fastx_stream: the trim step left counts beyond their bounds");
         FX_HIP(hipSetDevice(s->cfg.device));
+        if (sl.d_one && n_records) FX_HIP(hipMemcpyAsync(sl.h_one, sl.d_one, n_records * 4, hipMemcpyDeviceToHost, sl.stream));
+        // (byte text: the kept characters are starts[R'], and they lie at the front of the sequence bytes)
+        if (sl.h_seq && n_bases) FX_HIP(hipMemcpyAsync(sl.h_seq, sl.d_packed, n_bases, hipMemcpyDeviceToHost, sl.stream));
         if (n_records) FX_HIP(hipMemcpyAsync(sl.h_rec_pos, sl.d_rec_pos, n_records * 8, hipMemcpyDeviceToHost, sl.stream));
         FX_HIP(hipMemcpyAsync(sl.h_rec_base, sl.d_rec_base, (n_records + 1) * 8, hipMemcpyDeviceToHost, sl.stream));
         FX_HIP(hipMemcpyAsync(sl.h_offsets, sl.d_offsets, (n_records + 1) * 8, hipMemcpyDeviceToHost, sl.stream));
@@ -347,10 +387,10 @@ void destroy_slots(mm_fastx_stream *s) {
     }
     for (int i = 0; i < s->n_slots; ++i) {
         Slot &sl = s->slots[i];
-        void *dev[] = {sl.d_text, sl.d_packed, sl.d_amb, sl.d_rec_base, sl.d_rec_pos, sl.d_offsets, sl.d_meta, sl.d_pos, sl.d_sk, sl.d_values};
+        void *dev[] = {sl.d_text, sl.d_packed, sl.d_amb, sl.d_rec_base, sl.d_rec_pos, sl.d_offsets, sl.d_meta, sl.d_pos, sl.d_sk, sl.d_values, sl.d_one};
         for (void *p : dev)
             if (p) (void)hipFree(p);
-        void *host[] = {sl.h_text, sl.h_meta, sl.h_rec_pos, sl.h_rec_base, sl.h_offsets, sl.h_values, sl.h_pos, sl.h_sk};
+        void *host[] = {sl.h_text, sl.h_meta, sl.h_rec_pos, sl.h_rec_base, sl.h_offsets, sl.h_values, sl.h_pos, sl.h_sk, sl.h_one, sl.h_seq};
         for (void *p : host)
             if (p) (void)hipHostFree(p);
         hipEvent_t ev[] = {sl.ev_cut, sl.ev_run, sl.ev_done, sl.ev_tail};
@@ -360,9 +400,139 @@ void destroy_slots(mm_fastx_stream *s) {
     }
 }
 
+// Behind the refusals of the create entries: the device, the stream and its slots.  `text`: a byte-text stream - d_packed
+// takes the sequence bytes of a text of 2 * chunk_bytes, and the flags MM_FASTX_TEXT_* add their buffers.
+int open_stream(mm_fastx_stream_t **out, const mm_plan_t *plan, const mm::ApiPlanInfo &info, const mm_fastx_stream_config_t &cfg,
+                uint32_t value_len, bool text, int values_encoding) {
+    const uint32_t flags = cfg.flags;
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
+        (void)hipGetLastError();
+        mm::api_set_last_error("no HIP device visible");
+        return MM_ERR_NO_DEVICE;
+    }
+    if (cfg.device < 0 || cfg.device >= n_dev) return MM_ERR_NO_DEVICE;
+    DeviceGuard guard;
+    mm_fastx_stream *s = new (std::nothrow) mm_fastx_stream;
+    if (!s) return MM_ERR_ALLOC;
+    s->plan = plan;
+    s->info = info;
+    s->cfg = cfg;
+    s->text = text;
+    s->values_encoding = values_encoding;
+    s->value_len = value_len;
+    s->C = cfg.chunk_bytes;
+    s->A = s->C + ((flags & MM_FASTX_LONG_RECORDS) ? 16 : 0);
+    s->max_records = cfg.max_records;
+    s->max_positions = (cfg.max_positions == 0 || cfg.max_positions > 2 * s->C) ? 2 * s->C : cfg.max_positions;
+    s->packed_cap = text ? 2 * s->C + 64 : ((2 * s->C / 4 + 8 + 3) & ~3ull) + 64;
+    s->amb_cap = ((2 * s->C / 8 + 8 + 3) & ~3ull) + 64;
+    s->n_slots = cfg.slots ? (int)cfg.slots : 3;
+    s->format = cfg.format;  // (MM_FASTX_AUTO = 0: not known yet)
+    const uint64_t R = s->max_records, P = s->max_positions;
+    const uint64_t per_value = flags & MM_FASTX_VALUES_U128 ? 16 : 8;
+    const bool want_values = (flags & (MM_FASTX_VALUES_U64 | MM_FASTX_VALUES_U128)) != 0;
+    const bool want_one = text && (flags & MM_FASTX_TEXT_ONE_MINIMIZER), want_seq = text && (flags & MM_FASTX_TEXT_SEQ);
+    int rc = MM_OK;
+    hipError_t e = hipSetDevice(cfg.device);
+    for (int i = 0; i < s->n_slots && e == hipSuccess && rc == MM_OK; ++i) {
+        Slot &sl = s->slots[i];
+        rc = mm_workspace_create(&sl.ws, cfg.device, nullptr);
+        if (rc) break;
+        sl.stream = mm::api_workspace_stream(sl.ws);
+        e = hipSetDevice(cfg.device);
+        if (e == hipSuccess) e = dev_alloc(sl.d_text, s->A + s->C + 64);
+        if (e == hipSuccess) e = dev_alloc(sl.d_packed, s->packed_cap);
+        if (e == hipSuccess && (flags & MM_FASTX_SKIP_AMBIGUOUS)) e = dev_alloc(sl.d_amb, s->amb_cap);
+        if (e == hipSuccess) e = dev_alloc(sl.d_rec_base, (R + 1) * 8);
+        if (e == hipSuccess) e = dev_alloc(sl.d_rec_pos, (R + 1) * 8);
+        if (e == hipSuccess) e = dev_alloc(sl.d_offsets, (R + 1) * 8);
+        if (e == hipSuccess) e = dev_alloc(sl.d_meta, 128);
+        if (e == hipSuccess) e = hipMemset(sl.d_meta, 0, 128);
+        if (e == hipSuccess) e = dev_alloc(sl.d_pos, P * 4);
+        if (e == hipSuccess && (flags & MM_FASTX_SK)) e = dev_alloc(sl.d_sk, P * 4);
+        if (e == hipSuccess && want_values) e = dev_alloc(sl.d_values, P * per_value);
+        if (e == hipSuccess && want_one) e = dev_alloc(sl.d_one, R * 4);
+        if (e == hipSuccess) e = host_alloc(sl.h_text, s->C);
+        if (e == hipSuccess) e = host_alloc(sl.h_meta, 128);
+        if (e == hipSuccess) e = host_alloc(sl.h_rec_pos, (R + 1) * 8);
+        if (e == hipSuccess) e = host_alloc(sl.h_rec_base, (R + 1) * 8);
+        if (e == hipSuccess) e = host_alloc(sl.h_offsets, (R + 1) * 8);
+        if (e == hipSuccess) e = host_alloc(sl.h_pos, P * 4);
+        if (e == hipSuccess && (flags & MM_FASTX_SK)) e = host_alloc(sl.h_sk, P * 4);
+        if (e == hipSuccess && want_values) e = host_alloc(sl.h_values, P * per_value);
+        if (e == hipSuccess && want_one) e = host_alloc(sl.h_one, R * 4);
+        if (e == hipSuccess && want_seq) e = host_alloc(sl.h_seq, 2 * s->C);
+        hipEvent_t *ev[] = {&sl.ev_cut, &sl.ev_run, &sl.ev_done, &sl.ev_tail};
+        for (hipEvent_t *p : ev)
+            if (e == hipSuccess) e = hipEventCreateWithFlags(p, hipEventDisableTiming);
+        if (e == hipSuccess) {
+            memset(sl.h_meta, 0, 128);
+            memcpy(reinterpret_cast<uint8_t *>(sl.h_meta) + 120, ">\n", 2);
+        }
+    }
+    if (rc == MM_OK && e != hipSuccess) {
+        mm::api_set_last_error((std::string("mm_fastx_stream_create: ") + hipGetErrorString(e)).c_str());
+        (void)hipGetLastError();
+        rc = (e == hipErrorOutOfMemory) ? MM_ERR_ALLOC : MM_ERR_HIP;
+    }
+    if (rc) {
+        destroy_slots(s);
+        delete s;
+        return rc;
+    }
+    *out = s;
+    return MM_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int mm_fastx_text_stream_extras(const mm_fastx_stream_t *s, mm_fastx_text_extras_t *out) {
+    if (!s || !out) return MM_ERR_NULL;
+    if (s->delivered >= 0 && s->text) *out = s->extras;
+    else memset(out, 0, sizeof *out);
+    return MM_OK;
+}
+
+int mm_fastx_text_stream_create(mm_fastx_stream_t **out, const mm_plan_t *text_plan, const mm_fastx_text_stream_config_t *cfg) {
+    if (out) *out = nullptr;
+    if (!out || !text_plan || !cfg) return MM_ERR_NULL;
+    const mm::ApiPlanInfo info = mm::api_plan_info(text_plan);
+    const auto refuse = [](int code, const char *why) {
+        mm::api_set_last_error((std::string("mm_fastx_text_stream_create: ") + why).c_str());
+        return code;
+    };
+    if (!info.text) return refuse(MM_ERR_BAD_MODE, "a plan of mm_plan_create: use mm_fastx_stream_create");
+    if (cfg->chunk_bytes < 64 || cfg->chunk_bytes >= (1ull << 31) || cfg->max_records >= (1ull << 31)) return MM_ERR_LEN_TOO_LARGE;
+    const uint32_t flags = cfg->flags;
+    if ((flags & MM_FASTX_SK) && info.mode != MM_MINIMIZERS) return refuse(MM_ERR_BAD_MODE, "MM_FASTX_SK needs a minimizer plan");
+    if (flags & (MM_FASTX_SKIP_AMBIGUOUS | MM_FASTX_LONG_RECORDS))
+        return refuse(MM_ERR_BAD_MODE, "byte text has neither MM_FASTX_SKIP_AMBIGUOUS nor MM_FASTX_LONG_RECORDS");
+    if ((flags & MM_FASTX_VALUES_U64) && (flags & MM_FASTX_VALUES_U128)) return refuse(MM_ERR_BAD_MODE, "both values flags");
+    const int enc = cfg->values_encoding;
+    if (enc != MM_TEXT_VALUES_BYTES && enc != MM_TEXT_VALUES_DNA)
+        return refuse(MM_ERR_BAD_MODE, "values_encoding is MM_TEXT_VALUES_BYTES or MM_TEXT_VALUES_DNA");
+    const uint32_t value_len = mm_plan_value_len(text_plan);
+    if (flags & (MM_FASTX_VALUES_U64 | MM_FASTX_VALUES_U128)) {
+        if (enc == MM_TEXT_VALUES_BYTES && info.canonical_hasher)
+            return refuse(MM_ERR_BAD_MODE, "MM_TEXT_VALUES_BYTES with a canonical hasher (general text has no reverse complement)");
+        const uint32_t per_word = enc == MM_TEXT_VALUES_BYTES ? 8 : 32;
+        if (value_len > ((flags & MM_FASTX_VALUES_U128) ? 2 * per_word : per_word)) return MM_ERR_VALUE_LEN;
+    }
+    const int refusal = mm::api_text_counts_refusal(text_plan, 2 * cfg->chunk_bytes, cfg->max_records, (flags & MM_FASTX_SK) != 0);
+    if (refusal) return refusal;
+    if (cfg->format == MM_FASTX_FASTQ) return refuse(MM_ERR_FORMAT, "FASTQ to byte records is not provided");
+    if (cfg->format < MM_FASTX_AUTO || cfg->format > MM_FASTX_FASTQ || (cfg->slots != 0 && (cfg->slots < 2 || cfg->slots > 8)) ||
+        (flags & ~127u))
+        return refuse(MM_ERR_BAD_MODE, "format is MM_FASTX_AUTO / _FASTA, slots 0 or 2..8, flags MM_FASTX_*");
+    mm_fastx_stream_config_t base{};
+    base.device = cfg->device, base.format = cfg->format, base.flags = flags, base.slots = cfg->slots;
+    base.chunk_bytes = cfg->chunk_bytes, base.max_records = cfg->max_records, base.max_positions = cfg->max_positions;
+    base.first_byte = cfg->first_byte;
+    return open_stream(out, text_plan, info, base, value_len, true, enc);
+}
 
 int mm_debug_fastx_cut(const uint8_t *text, uint64_t n, int format, int last, uint64_t out[3]) {
     if (!out || (!text && n)) return MM_ERR_NULL;
@@ -411,78 +581,7 @@ int mm_fastx_stream_create(mm_fastx_stream_t **out, const mm_plan_t *plan, const
                                    .c_str());
         return MM_ERR_CAPACITY;
     }
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
-        (void)hipGetLastError();
-        mm::api_set_last_error("no HIP device visible");
-        return MM_ERR_NO_DEVICE;
-    }
-    if (cfg->device < 0 || cfg->device >= n_dev) return MM_ERR_NO_DEVICE;
-    DeviceGuard guard;
-    mm_fastx_stream *s = new (std::nothrow) mm_fastx_stream;
-    if (!s) return MM_ERR_ALLOC;
-    s->plan = plan;
-    s->info = info;
-    s->cfg = *cfg;
-    s->value_len = value_len;
-    s->C = cfg->chunk_bytes;
-    s->A = s->C + ((flags & MM_FASTX_LONG_RECORDS) ? 16 : 0);
-    s->max_records = cfg->max_records;
-    s->max_positions = (cfg->max_positions == 0 || cfg->max_positions > 2 * s->C) ? 2 * s->C : cfg->max_positions;
-    s->packed_cap = ((2 * s->C / 4 + 8 + 3) & ~3ull) + 64;
-    s->amb_cap = ((2 * s->C / 8 + 8 + 3) & ~3ull) + 64;
-    s->n_slots = cfg->slots ? (int)cfg->slots : 3;
-    s->format = cfg->format;  // (MM_FASTX_AUTO = 0: not known yet)
-    const uint64_t R = s->max_records, P = s->max_positions;
-    const uint64_t per_value = flags & MM_FASTX_VALUES_U128 ? 16 : 8;
-    const bool want_values = (flags & (MM_FASTX_VALUES_U64 | MM_FASTX_VALUES_U128)) != 0;
-    int rc = MM_OK;
-    hipError_t e = hipSetDevice(cfg->device);
-    for (int i = 0; i < s->n_slots && e == hipSuccess && rc == MM_OK; ++i) {
-        Slot &sl = s->slots[i];
-        rc = mm_workspace_create(&sl.ws, cfg->device, nullptr);
-        if (rc) break;
-        sl.stream = mm::api_workspace_stream(sl.ws);
-        e = hipSetDevice(cfg->device);
-        if (e == hipSuccess) e = dev_alloc(sl.d_text, s->A + s->C + 64);
-        if (e == hipSuccess) e = dev_alloc(sl.d_packed, s->packed_cap);
-        if (e == hipSuccess && (flags & MM_FASTX_SKIP_AMBIGUOUS)) e = dev_alloc(sl.d_amb, s->amb_cap);
-        if (e == hipSuccess) e = dev_alloc(sl.d_rec_base, (R + 1) * 8);
-        if (e == hipSuccess) e = dev_alloc(sl.d_rec_pos, (R + 1) * 8);
-        if (e == hipSuccess) e = dev_alloc(sl.d_offsets, (R + 1) * 8);
-        if (e == hipSuccess) e = dev_alloc(sl.d_meta, 128);
-        if (e == hipSuccess) e = hipMemset(sl.d_meta, 0, 128);
-        if (e == hipSuccess) e = dev_alloc(sl.d_pos, P * 4);
-        if (e == hipSuccess && (flags & MM_FASTX_SK)) e = dev_alloc(sl.d_sk, P * 4);
-        if (e == hipSuccess && want_values) e = dev_alloc(sl.d_values, P * per_value);
-        if (e == hipSuccess) e = host_alloc(sl.h_text, s->C);
-        if (e == hipSuccess) e = host_alloc(sl.h_meta, 128);
-        if (e == hipSuccess) e = host_alloc(sl.h_rec_pos, (R + 1) * 8);
-        if (e == hipSuccess) e = host_alloc(sl.h_rec_base, (R + 1) * 8);
-        if (e == hipSuccess) e = host_alloc(sl.h_offsets, (R + 1) * 8);
-        if (e == hipSuccess) e = host_alloc(sl.h_pos, P * 4);
-        if (e == hipSuccess && (flags & MM_FASTX_SK)) e = host_alloc(sl.h_sk, P * 4);
-        if (e == hipSuccess && want_values) e = host_alloc(sl.h_values, P * per_value);
-        hipEvent_t *ev[] = {&sl.ev_cut, &sl.ev_run, &sl.ev_done, &sl.ev_tail};
-        for (hipEvent_t *p : ev)
-            if (e == hipSuccess) e = hipEventCreateWithFlags(p, hipEventDisableTiming);
-        if (e == hipSuccess) {
-            memset(sl.h_meta, 0, 128);
-            memcpy(reinterpret_cast<uint8_t *>(sl.h_meta) + 120, ">\n", 2);
-        }
-    }
-    if (rc == MM_OK && e != hipSuccess) {
-        mm::api_set_last_error((std::string("mm_fastx_stream_create: ") + hipGetErrorString(e)).c_str());
-        (void)hipGetLastError();
-        rc = (e == hipErrorOutOfMemory) ? MM_ERR_ALLOC : MM_ERR_HIP;
-    }
-    if (rc) {
-        destroy_slots(s);
-        delete s;
-        return rc;
-    }
-    *out = s;
-    return MM_OK;
+    return open_stream(out, plan, info, *cfg, value_len, false, 0);
 }
 
 void mm_fastx_stream_destroy(mm_fastx_stream_t *s) {
@@ -514,7 +613,10 @@ int mm_fastx_stream_feed(mm_fastx_stream_t *s, const uint8_t *text, uint64_t n_b
             continue;
         }
         if (s->format != 0) break;
-        if (c == '@') {
+        if (c == '@' && s->text) {
+            *consumed = taken;
+            return fail(s, MM_ERR_FORMAT, "mm_fastx_stream_feed: the first non-blank byte is '@': FASTQ to byte records is not provided");
+        } else if (c == '@') {
             s->format = MM_FASTX_FASTQ;
         } else if (c == '>') {
             // (blank lines in front are gone; blank bytes on the header's own line stay, they make it no header)
@@ -632,6 +734,8 @@ int mm_fastx_stream_next(mm_fastx_stream_t *s, mm_fastx_batch_t *out) {
     out->pos = sl.h_pos + drop;
     out->sk = sl.h_sk ? sl.h_sk + drop : nullptr;
     out->values = sl.h_values ? sl.h_values + drop * (s->cfg.flags & MM_FASTX_VALUES_U128 ? 2 : 1) : nullptr;
+    s->extras.one_min = sl.h_one;
+    s->extras.seq = sl.h_seq;
     sl.state = kDelivered;
     s->delivered = s->oldest;
     s->oldest = (s->oldest + 1) % s->n_slots;

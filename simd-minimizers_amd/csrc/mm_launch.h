@@ -287,6 +287,11 @@ struct OneMinArgs {
     uint32_t fw0, rc0, rot, canonical;
     unsigned long long *keys;            // [n] scratch
     uint32_t *out;                       // [n]
+    // starts only, or null: the true {symbols, records} in device memory, read by the kernels (mm_one_min.h,
+    // one_min_counts_view); n and avail are then upper bounds that size the launch, keys and out hold n words, and
+    // `error` (the workspace's error words, OutParams::error) receives code 8 in its sticky word when a count exceeds them
+    const unsigned long long *counts = nullptr;
+    uint32_t *error = nullptr;
 };
 int launch_one_min(const OneMinArgs &a, hipStream_t stream);  // 0, -1 (HIP failure), -3 (grid too large)
 int launch_pack_ascii(const uint8_t *d_ascii, uint64_t n, uint8_t *d_packed, hipStream_t stream);

@@ -170,6 +170,30 @@ inline void one_min_host(const Sym &sym, const Lay &lay, uint64_t n, uint64_t sy
     for (uint64_t i = 0; i < tiles; ++i) one_min_tile_host(sym, lay, n, limit, t, k, i, tile, keys);
 }
 
+// The record count and the symbol count read on the DEVICE (mm_one_minimizer_*_counts_device_async; d_counts in the
+// loaders' layout: symbols, records): the host sizes the launch from the bounds it was given, thread 0 of every workgroup
+// turns {counts, bounds} into what the tile works on with the one function below (the pattern of text_counts_view,
+// mm_text_counts.h).  The host runs the same function (mm_debug_one_minimizer_counts_view): no device needed.
+struct OneMinCountsView {
+    uint64_t n;        // records the kernels work on (0 when refused)
+    uint64_t limit;    // symbols at or past it are never loaded: min(starts[n], n_sym) (0 when refused or n == 0)
+    uint32_t refused;  // a count exceeds its bound: every output word is "none", the starts are not read
+};
+// max_sym <= the buffer's symbols (the entry points check it), so the limit never passes the buffer.  Counts within the
+// bounds give what a host-n launch with n_reads = n computes on a buffer cut at n_sym symbols.
+MM_HOST_DEVICE inline OneMinCountsView one_min_counts_view(const uint64_t *starts, uint64_t max_sym, uint64_t max_records,
+                                                           uint64_t n_sym, uint64_t n) {
+    OneMinCountsView v;
+    v.refused = (n_sym > max_sym || n > max_records) ? 1u : 0u;
+    v.n = v.refused ? 0 : n;
+    v.limit = 0;
+    if (v.n) {
+        const uint64_t end = starts[v.n];
+        v.limit = end < n_sym ? end : n_sym;
+    }
+    return v;
+}
+
 // A key as the caller sees it.
 MM_HOST_DEVICE inline uint32_t one_min_position(uint64_t key) { return key == kOneMinNoKey ? 0xFFFFFFFFu : (uint32_t)key; }
 

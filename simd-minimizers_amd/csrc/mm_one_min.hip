@@ -17,7 +17,12 @@
 //     many records, empty ones included, inside a tile - go to global memory directly;
 //   - after a barrier the used slots go out with ONE atomicMin(unsigned long long) per (tile, record) pair into the key
 //     array (n words preset to all-ones on the same stream), a single global_atomic_umin_x2 without a return value;
-//   - a second small kernel turns keys into positions: all-ones -> MM_NO_MINIMIZER.
+//   - a second small kernel turns keys into positions: all-ones -> MM_NO_MINIMIZER;
+//   - the COUNTS instances (mm_one_minimizer_*_counts_device_async) read the record and symbol counts on the device: grid
+//     and keys are sized from the caller's bounds, thread 0 turns {counts, bounds} into (n, limit) with
+//     one_min_counts_view (mm_one_min.h) where the others use a.n and a.avail, and a finish kernel of their own writes
+//     MM_NO_MINIMIZER at and past n and raises kernel error 8 for counts beyond the bounds.  The host-n instances are the
+//     code they were: the flag is a template parameter, the position loop has no run-time branch.
 // Nothing outside the symbols [0, limit), starts[0 .. n] and keys / out [0, n) is touched, whatever the starts hold: every
 // record index is clamped to [0, n - 1] by the searches and every symbol index lies below the limit, which is itself
 // clamped to the buffer.  All stores are vector stores or atomics; no inline assembly.
@@ -42,9 +47,17 @@ __device__ __forceinline__ void stage_bytes(uint8_t *dst, const uint8_t *src, ui
     if (tid < count - tail_at) dst[tail_at + tid] = src[tail_at + tid];
 }
 
+// The COUNTS instances' record count, from thread 0 to the workgroup.  A function of its own, called only under
+// `if constexpr (COUNTS)`: the host-n instances never name the word, so their LDS is what it was by construction.
+__device__ __forceinline__ unsigned long long &one_min_counts_n() {
+    __shared__ unsigned long long s_n;
+    return s_n;
+}
+
 // TEXT: byte symbols and 256-entry tables (else 2-bit symbols, 4 entries).  kStage: bytes of a tile's symbols kept in LDS -
 // every k up to a tile's own size; a larger k reads its symbols from global memory.
-template <bool TEXT, class Lay, bool CANON>
+// COUNTS: a.n and a.avail are bounds, the true counts are read from a.counts (starts layout only).
+template <bool TEXT, class Lay, bool CANON, bool COUNTS = false>
 __global__ __launch_bounds__(kOneMinThreads) void one_min_kernel(Lay lay, OneMinArgs a) {
     constexpr int NTAB = TEXT ? 256 : 4;
     constexpr uint32_t kStage = TEXT ? 2 * kOneMinTile : 2 * kOneMinTile / 4 + 4;
@@ -55,12 +68,22 @@ __global__ __launch_bounds__(kOneMinThreads) void one_min_kernel(Lay lay, OneMin
     __shared__ int s_any;
     const uint32_t tid = threadIdx.x;
     if (tid == 0) {
-        unsigned long long limit = lay.end(a.n - 1);
-        if (limit > a.avail) limit = a.avail;
-        s_any = one_min_tile_range(lay, (uint64_t)a.n, (uint64_t)limit, a.k, (uint64_t)blockIdx.x, kOneMinTile, &s_range) ? 1 : 0;
+        if constexpr (COUNTS) {
+            // (a refused view and one without a record have n = 0: the starts are not read, the tile leaves)
+            const OneMinCountsView v = one_min_counts_view(lay.s, (uint64_t)a.avail, (uint64_t)a.n, (uint64_t)a.counts[0],
+                                                           (uint64_t)a.counts[1]);
+            one_min_counts_n() = v.n;
+            s_any = v.n != 0 && one_min_tile_range(lay, v.n, v.limit, a.k, (uint64_t)blockIdx.x, kOneMinTile, &s_range) ? 1 : 0;
+        } else {
+            unsigned long long limit = lay.end(a.n - 1);
+            if (limit > a.avail) limit = a.avail;
+            s_any = one_min_tile_range(lay, (uint64_t)a.n, (uint64_t)limit, a.k, (uint64_t)blockIdx.x, kOneMinTile, &s_range) ? 1 : 0;
+        }
     }
     __syncthreads();
     if (!s_any) return;
+    [[maybe_unused]] unsigned long long n_counts = 0;
+    if constexpr (COUNTS) n_counts = one_min_counts_n();
     const OneMinTileRange range = s_range;
     const uint64_t span = range.r_hi - range.r_lo + 1;
     const uint32_t n_slots = span < kOneMinSlots ? (uint32_t)span : kOneMinSlots;
@@ -98,7 +121,9 @@ __global__ __launch_bounds__(kOneMinThreads) void one_min_kernel(Lay lay, OneMin
         auto emit = [&](uint64_t r, uint64_t key) {
             const uint64_t slot = r - range.r_lo;
             if (slot < n_slots) atomicMin(&s_keys[slot], (unsigned long long)key);
-            else if (r < a.n) atomicMin(a.keys + r, (unsigned long long)key);
+            else if constexpr (COUNTS) {
+                if (r < n_counts) atomicMin(a.keys + r, (unsigned long long)key);
+            } else if (r < a.n) atomicMin(a.keys + r, (unsigned long long)key);
         };
         if constexpr (TEXT) {
             if (staged) one_min_lane(OneMinText{stage, range.g_begin}, lay, range, t, a.k, g0, g1, emit);
@@ -122,6 +147,29 @@ __global__ __launch_bounds__(256) void one_min_finish_kernel(const unsigned long
     if (r < n) out[r] = one_min_position(keys[r]);
 }
 
+// The counts form: the words [0, n) of the view from the keys, "none" at and past it up to the bound `max_records`; the
+// view's refusal is raised here (this kernel always runs, the main one has no workgroup when max_sym < k) in the sticky
+// error word mm_workspace_check reads.
+__global__ __launch_bounds__(256) void one_min_finish_counts_kernel(const unsigned long long *__restrict__ keys,
+                                                                    uint32_t *__restrict__ out, const uint64_t *starts,
+                                                                    const unsigned long long *__restrict__ counts,
+                                                                    unsigned long long max_sym, unsigned long long max_records,
+                                                                    uint32_t *error) {
+    const OneMinCountsView v = one_min_counts_view(starts, (uint64_t)max_sym, (uint64_t)max_records, (uint64_t)counts[0],
+                                                   (uint64_t)counts[1]);
+    const unsigned long long r = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    if (r < max_records) out[r] = r < v.n ? one_min_position(keys[r]) : 0xFFFFFFFFu;
+    if (v.refused && r == 0) error[2] = 8u;
+}
+
+template <bool TEXT>
+void launch_main_counts(const OneMinStarts &lay, const OneMinArgs &a, uint32_t blocks, hipStream_t stream) {
+    if (a.canonical)
+        hipLaunchKernelGGL((one_min_kernel<TEXT, OneMinStarts, true, true>), dim3(blocks), dim3(kOneMinThreads), 0, stream, lay, a);
+    else
+        hipLaunchKernelGGL((one_min_kernel<TEXT, OneMinStarts, false, true>), dim3(blocks), dim3(kOneMinThreads), 0, stream, lay, a);
+}
+
 template <bool TEXT, class Lay>
 void launch_main(const Lay &lay, const OneMinArgs &a, uint32_t blocks, hipStream_t stream) {
     if (a.canonical)
@@ -137,6 +185,22 @@ int launch_one_min(const OneMinArgs &a, hipStream_t stream) {
     const uint64_t finish_blocks = (a.n + 255) / 256;
     if (finish_blocks > 0x7fffffffull) return -3;
     if (hipMemsetAsync(a.keys, 0xff, a.n * sizeof(unsigned long long), stream) != hipSuccess) return -1;
+    if (a.counts) {
+        // grid, keys and the finish for the BOUNDS (a.avail symbols, a.n records); workgroups past the view's last tile
+        // leave at once
+        if (!a.starts || !a.error) return -1;
+        const OneMinStarts by_starts{reinterpret_cast<const uint64_t *>(a.starts)};
+        if (a.avail >= a.k) {
+            const uint64_t tiles = one_min_tiles(a.avail - a.k + 1, kOneMinTile);
+            if (tiles > 0x7fffffffull) return -3;
+            if (a.text) launch_main_counts<true>(by_starts, a, (uint32_t)tiles, stream);
+            else launch_main_counts<false>(by_starts, a, (uint32_t)tiles, stream);
+            if (hipGetLastError() != hipSuccess) return -1;
+        }
+        hipLaunchKernelGGL(one_min_finish_counts_kernel, dim3((uint32_t)finish_blocks), dim3(256), 0, stream, a.keys, a.out,
+                           by_starts.s, a.counts, a.avail, a.n, a.error);
+        return hipGetLastError() == hipSuccess ? 0 : -1;
+    }
     // what the host knows of the positions: the symbols of the buffer (a fixed-stride layout: up to its last read's end)
     uint64_t symbols = a.avail;
     if (!a.starts) {
