@@ -592,6 +592,46 @@ int mm_one_minimizer_reads_counts_device_async(mm_workspace_t *ws, const mm_hash
                                                uint64_t max_records, const uint64_t *d_read_starts /* [max_records + 1] */,
                                                const uint64_t *d_counts /* [2]: bases, records */,
                                                uint32_t *d_out_pos /* [max_records] */);
+/* ---- One minimizer per read that SKIPS ambiguous bases (N): k-mer-level skipping.  The reference has no counterpart:
+ * one_minimizer takes a plain Seq (src/minimizers.rs:22-28), which has no N.  For record r with bases [s_r, e_r) and the
+ * ambiguity bits the N packers write (mm_fastq_pack_n_device_async, mm_fasta_pack_n_device_async):
+ *   - a k-mer start p in [0, len_r - k] is CLEAN when none of the bases s_r + p .. s_r + p + k - 1 has its bit set;
+ *   - out[r] is the smallest clean p whose h(p) & 0xffff0000 is minimal over the clean p of record r;
+ *   - out[r] is MM_NO_MINIMIZER when the record has no clean k-mer: len_r < k, a record that is all N, a record in which
+ *     every clean run is shorter than k;
+ *   - h is exactly the plain call's hash (the canonical sum with a canonical hasher, no strand vote);
+ *   - bits outside [s_r, e_r) never influence record r: a neighbour's N, junk in front of the first record or behind the
+ *     last;
+ *   - with all bits clear the result is bit for bit the plain call's.
+ * (A window-level rule - skip the window len - k + 1 when it holds an N - would give MM_NO_MINIMIZER to every read with one
+ * N: useless for bucketing.)
+ *   d_amb / amb_bytes / amb_offset   bit numbering of mm_run_packed_reads_skip_ambiguous_device_async: base j of the run,
+ *                                    counted from base_offset, is bit amb_offset + j; bit i is bit i % 8 of byte i / 8.  No
+ *                                    byte outside [d_amb, d_amb + amb_bytes) is loaded: a k-mer that reaches past the packed
+ *                                    buffer OR past the bits (8 * amb_bytes - amb_offset of them) does not exist.
+ * Everything else - layouts, output, stream, the counts form's contract (kernel error 8, MM_NO_MINIMIZER at and past n, the
+ * refusal of counts beyond the bounds) - is word for word the plain forms'.  Checks: the plain forms' in their order, with
+ * MM_ERR_NULL for a NULL d_amb where a NULL packed buffer is refused, MM_ERR_CAPACITY for amb_offset > 8 * amb_bytes behind
+ * the base_offset check, and in the counts form MM_ERR_CAPACITY for amb_offset + max_bases > 8 * amb_bytes.  Kernels: the
+ * same per-tile code instantiated with the tile's ambiguity bits staged in LDS next to its symbols; a lane carries the
+ * length of the clean run that ends at its newest symbol (mm_one_min.h). */
+int mm_one_minimizer_reads_skip_ambiguous_device_async(mm_workspace_t *ws, const mm_hasher_t *hasher, uint32_t k,
+                                                       const void *d_packed, uint64_t packed_bytes, uint64_t base_offset,
+                                                       const void *d_amb, uint64_t amb_bytes, uint64_t amb_offset, uint64_t n_reads,
+                                                       const uint64_t *d_read_starts /* [n_reads + 1] or NULL */,
+                                                       uint32_t read_stride, uint32_t read_len, uint32_t *d_out_pos /* [n_reads] */);
+int mm_one_minimizer_reads_skip_ambiguous_counts_device_async(mm_workspace_t *ws, const mm_hasher_t *hasher, uint32_t k,
+                                                              const void *d_packed, uint64_t packed_bytes, uint64_t base_offset,
+                                                              const void *d_amb, uint64_t amb_bytes, uint64_t amb_offset,
+                                                              uint64_t max_bases, uint64_t max_records,
+                                                              const uint64_t *d_read_starts /* [max_records + 1] */,
+                                                              const uint64_t *d_counts /* [2]: bases, records */,
+                                                              uint32_t *d_out_pos /* [max_records] */);
+int mm_one_minimizer_reads_skip_ambiguous_host(mm_workspace_t *ws, const mm_hasher_t *hasher, uint32_t k, const uint8_t *packed,
+                                               uint64_t packed_bytes, uint64_t base_offset, const uint8_t *amb, uint64_t amb_bytes,
+                                               uint64_t amb_offset, uint64_t n_reads,
+                                               const uint64_t *read_starts /* [n_reads + 1] or NULL */, uint32_t read_stride,
+                                               uint32_t read_len, uint32_t *out_pos /* [n_reads] */);
 /* The same from HOST memory: one upload (the bytes and the starts), the launches, one download; they wait. */
 int mm_one_minimizer_reads_host(mm_workspace_t *ws, const mm_hasher_t *hasher, uint32_t k, const uint8_t *packed,
                                 uint64_t packed_bytes, uint64_t base_offset, uint64_t n_reads,
@@ -610,6 +650,10 @@ int mm_debug_one_minimizer_reads(const mm_hasher_t *hasher, uint32_t k, const ui
                                  uint32_t read_len, uint32_t tile, uint32_t *out_pos);
 int mm_debug_one_minimizer_text_batch(const mm_text_hasher_t *hasher, uint32_t k, const uint8_t *text, uint64_t text_bytes,
                                       uint64_t n_records, const uint64_t *starts, uint32_t tile, uint32_t *out_pos);
+int mm_debug_one_minimizer_reads_skip_ambiguous(const mm_hasher_t *hasher, uint32_t k, const uint8_t *packed, uint64_t packed_bytes,
+                                                uint64_t base_offset, const uint8_t *amb, uint64_t amb_bytes, uint64_t amb_offset,
+                                                uint64_t n_reads, const uint64_t *read_starts, uint32_t read_stride,
+                                                uint32_t read_len, uint32_t tile, uint32_t *out_pos);
 /* The counts forms on the host (no device; for tests).  mm_debug_one_minimizer_counts_view: the function every workgroup
  * turns {counts, bounds} into what it works on with - out = {n, limit, refused}; `starts` is read at [n] only, and not at
  * all for a refused view or n == 0 (it may then be NULL).  The two runs: the per-tile function with the view's (n, limit),
@@ -625,6 +669,12 @@ int mm_debug_one_minimizer_reads_counts(const mm_hasher_t *hasher, uint32_t k, c
                                         uint64_t base_offset, uint64_t max_bases, uint64_t max_records,
                                         const uint64_t *read_starts, const uint64_t *counts /* [2], host */, uint32_t tile,
                                         uint32_t *out_pos /* [max_records] */);
+int mm_debug_one_minimizer_reads_skip_ambiguous_counts(const mm_hasher_t *hasher, uint32_t k, const uint8_t *packed,
+                                                       uint64_t packed_bytes, uint64_t base_offset, const uint8_t *amb,
+                                                       uint64_t amb_bytes, uint64_t amb_offset, uint64_t max_bases,
+                                                       uint64_t max_records, const uint64_t *read_starts,
+                                                       const uint64_t *counts /* [2], host */, uint32_t tile,
+                                                       uint32_t *out_pos /* [max_records] */);
 
 /* Output::values_u64 / values_u128 (src/lib.rs:584-629) of EVERY sequence of a device batch in one launch: what the loop
  * over the contigs (bench/src/bin/paper.rs:410-431: Builder::run per sequence) and Output::values_* per sequence computes,
@@ -1101,14 +1151,20 @@ int mm_debug_lane_counts_view(uint64_t max_bases, uint64_t max_records, uint64_t
  * or with MM_FASTX_SKIP_AMBIGUOUS (MM_ERR_BAD_MODE); a forward plan with MM_FASTX_SKIP_AMBIGUOUS
  * (MM_ERR_HASHER_NOT_CANONICAL); both values flags (MM_ERR_BAD_MODE); a value length above 32 / 64 (MM_ERR_VALUE_LEN); a plan
  * without a lane-table launch (MM_ERR_BAD_MODE, as mm_run_packed_reads_counts_device_async says); an unknown format, flag or
- * slots outside 0, 2..8 (MM_ERR_BAD_MODE); MM_FASTX_LONG_RECORDS with chunk_bytes < 4 * (k + w - 1) (MM_ERR_CAPACITY); no
- * device (MM_ERR_NO_DEVICE).
+ * slots outside 0, 2..8 (MM_ERR_BAD_MODE); MM_FASTX_ONE_MINIMIZER with MM_FASTX_LONG_RECORDS (MM_ERR_BAD_MODE: a split
+ * record's minimizer is not joined across its pieces); MM_FASTX_LONG_RECORDS with chunk_bytes < 4 * (k + w - 1)
+ * (MM_ERR_CAPACITY); no device (MM_ERR_NO_DEVICE).
+ * MM_FASTX_ONE_MINIMIZER (this entry only; the values 32, 64 and 128 stay refused here): behind the run and the values every
+ * chunk queues, on its slot's stream, mm_one_minimizer_reads_counts_device_async - with MM_FASTX_SKIP_AMBIGUOUS
+ * mm_one_minimizer_reads_skip_ambiguous_counts_device_async over the slot's ambiguity bits - with the plan's k and hasher;
+ * a repeated run queues it again, the delivered records' words are downloaded with the batch, and the stream still waits
+ * for the host once per chunk.  mm_fastx_stream_one_minimizer hands them out; mm_fastx_batch_t keeps its layout.
  * A stream is used by one thread at a time, like a workspace; the plan must outlive it; every entry restores the caller's
  * current device.  Memory per slot: csrc/mm_fastx_stream.hip and DESIGN.md 4.4e. */
 typedef struct mm_fastx_stream mm_fastx_stream_t;
 enum { MM_FASTX_AUTO = 0, MM_FASTX_FASTA = 1, MM_FASTX_FASTQ = 2 };
 enum { MM_FASTX_SK = 1, MM_FASTX_SKIP_AMBIGUOUS = 2, MM_FASTX_VALUES_U64 = 4, MM_FASTX_VALUES_U128 = 8,
-       MM_FASTX_LONG_RECORDS = 16 };
+       MM_FASTX_LONG_RECORDS = 16, MM_FASTX_ONE_MINIMIZER = 256 };
 enum { MM_FASTX_NEED_INPUT = 1, MM_FASTX_END = 2 };           /* positive: not errors */
 typedef struct mm_fastx_stream_config {
     int device; int format; uint32_t flags; uint32_t slots;    /* slots: 0 = default (3), else 2..8 */
@@ -1131,6 +1187,10 @@ int  mm_fastx_stream_feed(mm_fastx_stream_t *s, const uint8_t *text, uint64_t n_
 int  mm_fastx_stream_finish(mm_fastx_stream_t *s);
 int  mm_fastx_stream_next(mm_fastx_stream_t *s, mm_fastx_batch_t *out);
 void mm_fastx_stream_destroy(mm_fastx_stream_t *s);
+/* Of the batch last returned by mm_fastx_stream_next (valid as long as the batch is): one word per record, record-local,
+ * MM_NO_MINIMIZER for a record without a (clean) k-mer.  NULL and 0 without MM_FASTX_ONE_MINIMIZER, before the first batch
+ * and on a byte-text stream (mm_fastx_text_stream_extras serves that one).  MM_ERR_NULL for a NULL argument. */
+int mm_fastx_stream_one_minimizer(const mm_fastx_stream_t *s, const uint32_t **one_min, uint64_t *n_records);
 /* ---- The same for BYTE TEXT (protein FASTA of any size): a text plan (mm_plan_create_text) in place of the packed one; the
  * handle is the same type and mm_fastx_stream_feed / _finish / _next / _destroy serve it unchanged.  The reference reads such
  * a file record by record on the CPU too (needletail::parse_fastx_file, bench/src/lib.rs:51-82; Builder::run on &[u8],

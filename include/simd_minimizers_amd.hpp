@@ -375,7 +375,10 @@ class Builder {  // src/lib.rs:225-230
     // reference's loader reads any file record by record on the CPU (bench/src/lib.rs:51-82); it has no other counterpart.
     // With MM_FASTX_LONG_RECORDS among the flags a FASTA record longer than a chunk arrives in pieces: an `on_batch` that
     // takes (const mm_fastx_batch_t &, const mm_fastx_pieces_t &) receives mm_fastx_stream_pieces() of every batch with it
-    // (fastx_pieces() below for a stream driven by hand).
+    // (fastx_pieces() below for a stream driven by hand).  With MM_FASTX_ONE_MINIMIZER an `on_batch` that takes
+    // (const mm_fastx_batch_t &, const uint32_t *one_min) receives the batch's one minimizer per record with it
+    // (mm_fastx_stream_one_minimizer: [n_records] words, MM_NO_MINIMIZER for a record without a k-mer - with
+    // MM_FASTX_SKIP_AMBIGUOUS without a clean one; nullptr without the flag).
     template <class Reader, class OnBatch>
     void stream_fastx(Reader &&reader, OnBatch &&on_batch, const mm_fastx_stream_config_t &options,
                       size_t read_bytes = size_t(1) << 22) const {
@@ -387,6 +390,8 @@ class Builder {  // src/lib.rs:225-230
             auto deliver = [&](const mm_fastx_batch_t &b) {
                 if constexpr (std::is_invocable_v<OnBatch &, const mm_fastx_batch_t &, const mm_fastx_pieces_t &>)
                     on_batch(b, fastx_pieces(st));
+                else if constexpr (std::is_invocable_v<OnBatch &, const mm_fastx_batch_t &, const uint32_t *>)
+                    on_batch(b, fastx_one_minimizer(st));
                 else
                     on_batch(b);
             };
@@ -426,6 +431,15 @@ class Builder {  // src/lib.rs:225-230
         mm_fastx_pieces_t p;
         check(mm_fastx_stream_pieces(st, &p));
         return p;
+    }
+
+    // The one minimizer per record of the batch last returned by mm_fastx_stream_next (mm_fastx_stream_one_minimizer;
+    // nullptr without MM_FASTX_ONE_MINIMIZER).
+    static const uint32_t *fastx_one_minimizer(const mm_fastx_stream_t *st) {
+        const uint32_t *one_min = nullptr;
+        uint64_t n = 0;
+        check(mm_fastx_stream_one_minimizer(st, &one_min, &n));
+        return one_min;
     }
 
     // Output::values_u64 / values_u128 (src/lib.rs:584-629) of EVERY read of run_many in ONE call (mm_values_u64_reads_host /
@@ -835,6 +849,26 @@ inline std::vector<uint32_t> one_minimizer_many(const std::vector<TextSeq> &reco
                                            out.data()));
     return out;
 }
+// Reads with ambiguity bits (PackedNSeq): only k-mers without an ambiguous base count, MM_NO_MINIMIZER for a read without one
+// (mm_one_minimizer_reads_skip_ambiguous_host: k-mer-level skipping; the reference's one_minimizer takes a plain Seq and
+// has no counterpart).  The reads are laid back to back with their bits.
+inline std::vector<uint32_t> one_minimizer_many(const std::vector<PackedNSeq> &reads, const mm_hasher_t &hasher, uint32_t k,
+                                                Workspace *ws = nullptr) {
+    Workspace &w = ws ? *ws : Workspace::thread_default();
+    std::vector<uint64_t> starts(reads.size() + 1, 0);
+    for (size_t r = 0; r < reads.size(); ++r) starts[r + 1] = starts[r] + reads[r].seq.len;
+    std::vector<uint8_t> packed((starts.back() + 3) / 4 + 1, 0), amb((starts.back() + 7) / 8 + 1, 0);
+    for (size_t r = 0; r < reads.size(); ++r)
+        for (uint64_t i = 0; i < reads[r].seq.len; ++i) {
+            const uint64_t s = reads[r].seq.offset + i, a = reads[r].amb_offset + i, d = starts[r] + i;
+            packed[d >> 2] |= (uint8_t)(((reads[r].seq.data[s >> 2] >> (2 * (s & 3))) & 3u) << (2 * (d & 3)));
+            amb[d >> 3] |= (uint8_t)(((reads[r].amb[a >> 3] >> (a & 7)) & 1u) << (d & 7));
+        }
+    std::vector<uint32_t> out(reads.size());
+    check(mm_one_minimizer_reads_skip_ambiguous_host(w.get(), &hasher, k, packed.data(), packed.size(), 0, amb.data(), amb.size(),
+                                                     0, reads.size(), starts.data(), 0, 0, out.data()));
+    return out;
+}
 // The *_many_counts_device forms: records already on the device with their two counts {symbols, records} in DEVICE memory,
 // as a loader wrote them (mm_one_minimizer_text_batch_counts_device_async / mm_one_minimizer_reads_counts_device_async):
 // asynchronous on `ws`, d_out_pos[0 .. n) filled, MM_NO_MINIMIZER up to max_records; mm_workspace_check reports counts
@@ -853,6 +887,26 @@ inline void one_minimizer_many_counts_device(const mm_hasher_t &hasher, uint32_t
     Workspace &w = ws ? *ws : Workspace::thread_default();
     check(mm_one_minimizer_reads_counts_device_async(w.get(), &hasher, k, d_packed, packed_bytes, base_offset, max_bases,
                                                      max_records, d_read_starts, d_counts, d_out_pos));
+}
+// (the packed form over the N packers' ambiguity bits: mm_one_minimizer_reads_skip_ambiguous_counts_device_async)
+inline void one_minimizer_many_counts_device(const mm_hasher_t &hasher, uint32_t k, const void *d_packed, uint64_t packed_bytes,
+                                             uint64_t base_offset, const void *d_amb, uint64_t amb_bytes, uint64_t amb_offset,
+                                             uint64_t max_bases, uint64_t max_records, const uint64_t *d_read_starts,
+                                             const uint64_t *d_counts, uint32_t *d_out_pos, Workspace *ws = nullptr) {
+    Workspace &w = ws ? *ws : Workspace::thread_default();
+    check(mm_one_minimizer_reads_skip_ambiguous_counts_device_async(w.get(), &hasher, k, d_packed, packed_bytes, base_offset,
+                                                                    d_amb, amb_bytes, amb_offset, max_bases, max_records,
+                                                                    d_read_starts, d_counts, d_out_pos));
+}
+template <class Hasher>
+inline std::vector<uint32_t> one_minimizer_many(const std::vector<PackedNSeq> &reads, const Hasher &hasher, uint32_t k) {
+    return one_minimizer_many(reads, hasher.tables, k);
+}
+// (MM_NO_MINIMIZER when the read has no clean k-mer; Error(MM_ERR_CAPACITY) when it is shorter than k, as the plain form)
+template <class Hasher>
+inline uint32_t one_minimizer(PackedNSeq seq, const Hasher &hasher, uint32_t k) {
+    if (seq.seq.len < k) throw Error(MM_ERR_CAPACITY);
+    return one_minimizer_many(std::vector<PackedNSeq>{seq}, hasher.tables, k)[0];
 }
 template <class Hasher>
 inline std::vector<uint32_t> one_minimizer_many(const std::vector<PackedSeq> &reads, const Hasher &hasher, uint32_t k) {

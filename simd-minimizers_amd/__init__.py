@@ -261,6 +261,18 @@ def _load_lib():
         L.mm_debug_one_minimizer_counts_view.argtypes = [C.c_uint64] * 4 + [vp, vp]
         L.mm_debug_one_minimizer_text_batch_counts.argtypes = [vp, C.c_uint32, vp] + [C.c_uint64] * 3 + [vp, vp, C.c_uint32, vp]
         L.mm_debug_one_minimizer_reads_counts.argtypes = [vp, C.c_uint32, vp] + [C.c_uint64] * 4 + [vp, vp, C.c_uint32, vp]
+        amb3 = [vp, C.c_uint64, C.c_uint64]  # (the skip-ambiguous forms: d_amb, amb_bytes, amb_offset)
+        L.mm_one_minimizer_reads_skip_ambiguous_device_async.argtypes = (
+            [vp, vp, C.c_uint32, vp, C.c_uint64, C.c_uint64] + amb3 + [C.c_uint64, vp, C.c_uint32, C.c_uint32, vp])
+        L.mm_one_minimizer_reads_skip_ambiguous_host.argtypes = (
+            [vp, vp, C.c_uint32, vp, C.c_uint64, C.c_uint64] + amb3 + [C.c_uint64, vp, C.c_uint32, C.c_uint32, vp])
+        L.mm_one_minimizer_reads_skip_ambiguous_counts_device_async.argtypes = (
+            [vp, vp, C.c_uint32, vp, C.c_uint64, C.c_uint64] + amb3 + [C.c_uint64, C.c_uint64, vp, vp, vp])
+        L.mm_debug_one_minimizer_reads_skip_ambiguous.argtypes = (
+            [vp, C.c_uint32, vp, C.c_uint64, C.c_uint64] + amb3 + [C.c_uint64, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp])
+        L.mm_debug_one_minimizer_reads_skip_ambiguous_counts.argtypes = (
+            [vp, C.c_uint32, vp, C.c_uint64, C.c_uint64] + amb3 + [C.c_uint64, C.c_uint64, vp, vp, C.c_uint32, vp])
+        L.mm_fastx_stream_one_minimizer.argtypes = [vp, C.POINTER(vp), u64p]
         L.mm_one_minimizer_tile.argtypes = []
         L.mm_one_minimizer_tile.restype = C.c_uint32
         values_batch_args = [vp, C.c_uint64, C.POINTER(vp), u64p, u64p, u64p, C.c_uint32, C.c_int, vp, u64p, vp]
@@ -424,6 +436,9 @@ EXPORTED_SYMBOLS = [
     "mm_one_minimizer_text_batch_counts_device_async", "mm_one_minimizer_reads_counts_device_async",
     "mm_debug_one_minimizer_counts_view", "mm_debug_one_minimizer_text_batch_counts", "mm_debug_one_minimizer_reads_counts",
     "mm_fastx_text_stream_create", "mm_fastx_text_stream_extras",
+    "mm_one_minimizer_reads_skip_ambiguous_device_async", "mm_one_minimizer_reads_skip_ambiguous_counts_device_async",
+    "mm_one_minimizer_reads_skip_ambiguous_host", "mm_debug_one_minimizer_reads_skip_ambiguous",
+    "mm_debug_one_minimizer_reads_skip_ambiguous_counts", "mm_fastx_stream_one_minimizer",
 ]
 
 
@@ -1865,6 +1880,7 @@ def fastx_pipeline_device(builder: "Builder", text, max_records: int, fmt: str, 
 # ---- FASTA / FASTQ files of any size through the device in chunks (mm_fastx_stream_*)
 FASTX_AUTO, FASTX_FASTA, FASTX_FASTQ = 0, 1, 2
 FASTX_SK, FASTX_SKIP_AMBIGUOUS, FASTX_VALUES_U64, FASTX_VALUES_U128, FASTX_LONG_RECORDS = 1, 2, 4, 8, 16
+FASTX_ONE_MINIMIZER = 256  # (mm_fastx_stream_create only; the byte-text stream has FASTX_TEXT_ONE_MINIMIZER)
 FASTX_NEED_INPUT, FASTX_END = 1, 2
 _FASTX_FORMATS = {"auto": FASTX_AUTO, "fasta": FASTX_FASTA, "fastq": FASTX_FASTQ}
 
@@ -1905,7 +1921,7 @@ class FastxBatch:
     ``first_overlap`` bases repeat the previous piece and ``first_base`` is the record-global index of its first base);
     ``last_open`` - the last record goes on in the next batch.  ``fastx_join`` puts the pieces together."""
 
-    def __init__(self, c: _FastxBatchC, u128: bool, views=True, pieces: "_FastxPiecesC" = None, extras=None):
+    def __init__(self, c: _FastxBatchC, u128: bool, views=True, pieces: "_FastxPiecesC" = None, extras=None, one_min=None):
         n, p = int(c.n_records), int(c.n_positions)
         self.u128 = u128
         self.first_continues = bool(pieces.first_continues) if pieces is not None else False
@@ -1920,8 +1936,11 @@ class FastxBatch:
         self.pos = _view(c.pos, p, C.c_uint32, np.uint32)
         self.sk = _view(c.sk, p, C.c_uint32, np.uint32) if c.sk else None
         self.values = _view(c.values, p * (2 if u128 else 1), C.c_uint64, np.uint64) if c.values else None
-        # a ``FastxTextStream``'s extras (None elsewhere): one minimizer per record, the records' bytes back to back
+        # ``one_min``: one minimizer per record (a stream with ``one_minimizer``, else None); ``seq``: a
+        # ``FastxTextStream``'s records' bytes back to back
         self.one_min = self.seq = None
+        if one_min:
+            self.one_min = _view(one_min, n, C.c_uint32, np.uint32)
         if extras is not None:
             self.one_min = _view(extras.one_min, n, C.c_uint32, np.uint32) if extras.one_min else None
             if extras.seq:
@@ -1943,11 +1962,14 @@ class FastxStream:
     2 * chunk_bytes positions), ``fmt`` "auto" / "fasta" / "fastq", ``values`` None / "u64" / "u128",
     ``super_kmers`` / ``skip_ambiguous`` as the one-shot calls have them, ``first_byte`` the absolute offset of the
     first byte fed, ``slots`` chunks in flight (0: the default of 3), ``long_records`` FASTA records longer than a chunk
-    come in pieces (``MM_FASTX_LONG_RECORDS``; see ``FastxBatch`` and ``fastx_join``).  Iterating yields the remaining batches (after
+    come in pieces (``MM_FASTX_LONG_RECORDS``; see ``FastxBatch`` and ``fastx_join``), ``one_minimizer`` one minimizer
+    per read in ``FastxBatch.one_min`` (``MM_FASTX_ONE_MINIMIZER``: the builder's k and hasher, with ``skip_ambiguous``
+    over clean k-mers only, ``NO_MINIMIZER`` for a read without one; refused with ``long_records``).  Iterating yields the remaining batches (after
     ``finish()``).  A failing stream raises ``MinimizerError`` from every later call."""
 
     def __init__(self, builder: "Builder", chunk_bytes: int, max_records: int, fmt="auto", values=None, super_kmers=False,
-                 skip_ambiguous=False, max_positions=0, first_byte=0, slots=0, device=None, long_records=False):
+                 skip_ambiguous=False, max_positions=0, first_byte=0, slots=0, device=None, long_records=False,
+                 one_minimizer=False):
         if fmt not in _FASTX_FORMATS:
             raise ValueError('fmt is "auto", "fasta" or "fastq"')
         if values not in (None, "u64", "u128"):
@@ -1955,8 +1977,10 @@ class FastxStream:
         flags = (FASTX_SK if super_kmers else 0) | (FASTX_SKIP_AMBIGUOUS if skip_ambiguous else 0)
         flags |= {None: 0, "u64": FASTX_VALUES_U64, "u128": FASTX_VALUES_U128}[values]
         flags |= FASTX_LONG_RECORDS if long_records else 0
+        flags |= FASTX_ONE_MINIMIZER if one_minimizer else 0
         self.h = None
         self.long_records = bool(long_records)
+        self.one_minimizer = bool(one_minimizer)
         self.u128 = values == "u128"
         self.builder = builder
         self._plan = builder.plan()  # (the stream keeps the plan's handle: it must outlive the stream)
@@ -2019,7 +2043,12 @@ class FastxStream:
         if self.long_records:
             pieces = _FastxPiecesC()
             _check(lib().mm_fastx_stream_pieces(self.h, C.byref(pieces)))
-        return FastxBatch(c, self.u128, pieces=pieces)
+        one_min = None
+        if self.one_minimizer:
+            words, n = C.c_void_p(), C.c_uint64()
+            _check(lib().mm_fastx_stream_one_minimizer(self.h, C.byref(words), C.byref(n)))
+            one_min = words.value
+        return FastxBatch(c, self.u128, pieces=pieces, one_min=one_min)
 
     def __iter__(self):
         return self
@@ -2062,6 +2091,7 @@ class FastxTextStream(FastxStream):
         flags |= (FASTX_TEXT_ONE_MINIMIZER if one_minimizer else 0) | (FASTX_TEXT_SEQ if seq else 0)
         self.h = None
         self.long_records = False
+        self.one_minimizer = False  # (the text stream's words come with its extras)
         self.u128 = values == "u128"
         self.builder = builder
         self._plan = builder.text_plan()  # (the stream keeps the plan's handle: it must outlive the stream)
@@ -2509,13 +2539,21 @@ def _vp_of(a):
 
 
 def debug_one_minimizer_reads(hasher: Hasher, k: int, packed, n_reads: int, read_starts=None, read_stride=0, read_len=0,
-                              base_offset=0, tile=0) -> np.ndarray:
+                              base_offset=0, tile=0, amb=None, amb_offset=0) -> np.ndarray:
     """The one-minimizer kernel's per-tile function on the host, tile after tile (``mm_debug_one_minimizer_reads``, no
     GPU): ``packed`` a uint8 array, the layout as ``one_minimizer_reads_device`` takes it (``read_starts``: uint64 array
-    of n + 1), ``tile`` overrides the tile size (0: the kernel's).  Returns ``np.uint32[n_reads]``."""
+    of n + 1), ``tile`` overrides the tile size (0: the kernel's).  With ``amb`` (a uint8 array of ambiguity bits, base j
+    = bit ``amb_offset + j``) the skip-ambiguous form (``mm_debug_one_minimizer_reads_skip_ambiguous``).  Returns
+    ``np.uint32[n_reads]``."""
     packed = np.ascontiguousarray(packed, dtype=np.uint8)
     starts = np.ascontiguousarray(read_starts, dtype=np.uint64) if read_starts is not None else None
     out = np.zeros(max(1, int(n_reads)), dtype=np.uint32)
+    if amb is not None:
+        amb = np.ascontiguousarray(amb, dtype=np.uint8)
+        _check(lib().mm_debug_one_minimizer_reads_skip_ambiguous(
+            C.byref(hasher), int(k), _vp_of(packed), len(packed), int(base_offset), _vp_of(amb), len(amb), int(amb_offset),
+            int(n_reads), _vp_of(starts), int(read_stride), int(read_len), int(tile), _vp_of(out)))
+        return out[:int(n_reads)]
     _check(lib().mm_debug_one_minimizer_reads(C.byref(hasher), int(k), _vp_of(packed), len(packed), int(base_offset),
                                               int(n_reads), _vp_of(starts), int(read_stride), int(read_len), int(tile),
                                               _vp_of(out)))
@@ -2535,17 +2573,23 @@ def debug_one_minimizer_text_batch(hasher: TextHasher, k: int, text, starts, til
 
 
 def one_minimizer_reads_device(hasher: Hasher, k: int, d_packed, n_reads=None, out_pos=None, read_starts=None, read_stride=0,
-                               read_len=0, base_offset=0, ws=None):
+                               read_len=0, base_offset=0, ws=None, amb=None, amb_offset=0):
     """``one_minimizer`` (src/minimizers.rs:22-28) of EVERY read of a packed device buffer in one call
     (``mm_one_minimizer_reads_device_async``): ``d_packed`` a uint8 CUDA tensor - or a ``FastaRecords``, whose starts are
     then taken - and the layout: ``read_starts`` (int64 CUDA tensor of n + 1) or ``read_stride`` / ``read_len``.
     ``out_pos`` (int32 CUDA tensor, n_reads) receives the read-local position of the leftmost minimal
     ``hash & 0xffff0000`` per read, ``NO_MINIMIZER`` for a read shorter than k; a new tensor is returned when it is None.
+    With ``amb`` (a uint8 CUDA tensor of ambiguity bits, base j from ``base_offset`` = bit ``amb_offset + j``; a
+    ``FastaRecords`` of ``fasta_pack_n_device`` supplies its own) the skip-ambiguous form
+    (``mm_one_minimizer_reads_skip_ambiguous_device_async``): only k-mers without an ambiguous base count,
+    ``NO_MINIMIZER`` for a read without one.
     Asynchronous on ``ws`` (default: the device's default workspace): ``Workspace.sync`` before reading."""
     import torch
     if isinstance(d_packed, FastaRecords):
         rec = d_packed
         d_packed, n_reads = rec.packed, len(rec)
+        if amb is None and rec.amb is not None:
+            amb, amb_offset = rec.amb, 0
         read_starts = torch.from_numpy(np.ascontiguousarray(rec.base, dtype=np.uint64).view(np.int64)).to(d_packed.device)
     n_reads = int(n_reads)
     dev = d_packed.device
@@ -2558,6 +2602,11 @@ def one_minimizer_reads_device(hasher: Hasher, k: int, d_packed, n_reads=None, o
         raise ValueError(f"out_pos holds {out_pos.numel()} words, {n_reads} needed")
     if read_starts is not None and read_starts.numel() < n_reads + 1:
         raise ValueError(f"{n_reads} reads need {n_reads + 1} starts")
+    if amb is not None:
+        _check(lib().mm_one_minimizer_reads_skip_ambiguous_device_async(
+            ws.h, C.byref(hasher), int(k), _vp_of(d_packed), int(d_packed.numel()), int(base_offset), _vp_of(amb),
+            int(amb.numel()), int(amb_offset), n_reads, _vp_of(read_starts), int(read_stride), int(read_len), _vp_of(out_pos)))
+        return out_pos
     _check(lib().mm_one_minimizer_reads_device_async(ws.h, C.byref(hasher), int(k), _vp_of(d_packed), int(d_packed.numel()),
                                                      int(base_offset), n_reads, _vp_of(read_starts), int(read_stride),
                                                      int(read_len), _vp_of(out_pos)))
@@ -2619,19 +2668,28 @@ def debug_one_minimizer_text_batch_counts(hasher: TextHasher, k: int, text, star
 
 
 def debug_one_minimizer_reads_counts(hasher: Hasher, k: int, packed, read_starts, counts, max_bases=None, base_offset=0,
-                                     tile=0, refused_ok=False) -> np.ndarray:
+                                     tile=0, refused_ok=False, amb=None, amb_offset=0) -> np.ndarray:
     """The same for reads of a packed buffer (``mm_debug_one_minimizer_reads_counts``, no GPU); ``max_bases`` defaults to
-    what the buffer holds behind ``base_offset``."""
+    what the buffer holds behind ``base_offset``.  With ``amb`` / ``amb_offset`` the skip-ambiguous form
+    (``mm_debug_one_minimizer_reads_skip_ambiguous_counts``)."""
     packed = np.ascontiguousarray(packed, dtype=np.uint8)
     starts = np.ascontiguousarray(read_starts, dtype=np.uint64)
     counts = np.ascontiguousarray(counts, dtype=np.uint64)
     max_records = len(starts) - 1
     if max_bases is None:
         max_bases = 4 * len(packed) - int(base_offset)
+        if amb is not None:
+            max_bases = min(max_bases, 8 * len(amb) - int(amb_offset))
     out = np.zeros(max(1, max_records), dtype=np.uint32)
-    rc = lib().mm_debug_one_minimizer_reads_counts(C.byref(hasher), int(k), _vp_of(packed), len(packed), int(base_offset),
-                                                   int(max_bases), max_records, _vp_of(starts), _vp_of(counts), int(tile),
-                                                   _vp_of(out))
+    if amb is not None:
+        amb = np.ascontiguousarray(amb, dtype=np.uint8)
+        rc = lib().mm_debug_one_minimizer_reads_skip_ambiguous_counts(
+            C.byref(hasher), int(k), _vp_of(packed), len(packed), int(base_offset), _vp_of(amb), len(amb), int(amb_offset),
+            int(max_bases), max_records, _vp_of(starts), _vp_of(counts), int(tile), _vp_of(out))
+    else:
+        rc = lib().mm_debug_one_minimizer_reads_counts(C.byref(hasher), int(k), _vp_of(packed), len(packed), int(base_offset),
+                                                       int(max_bases), max_records, _vp_of(starts), _vp_of(counts), int(tile),
+                                                       _vp_of(out))
     if not (refused_ok and rc == ERR["CAPACITY"]):
         _check(rc)
     return out[:max_records]
@@ -2669,10 +2727,11 @@ def one_minimizer_text_batch_counts_device(hasher: TextHasher, k: int, d_text, d
 
 
 def one_minimizer_reads_counts_device(hasher: Hasher, k: int, d_packed, read_starts, d_counts, max_records=None,
-                                      max_bases=None, out_pos=None, base_offset=0, ws=None):
+                                      max_bases=None, out_pos=None, base_offset=0, ws=None, amb=None, amb_offset=0):
     """The same for the reads of a packed device buffer (``mm_one_minimizer_reads_counts_device_async``; starts layout
     only): behind ``fasta_pack_device_async`` / ``fastq_pack_device_async`` with no host wait.  ``max_bases`` defaults to
-    what the buffer holds behind ``base_offset``."""
+    what the buffer holds behind ``base_offset`` (with ``amb``: what both buffers hold).  With ``amb`` / ``amb_offset``
+    (the N packers' bits) the skip-ambiguous form (``mm_one_minimizer_reads_skip_ambiguous_counts_device_async``)."""
     import torch
     if max_records is None:
         max_records = read_starts.numel() - 1
@@ -2683,6 +2742,8 @@ def one_minimizer_reads_counts_device(hasher: Hasher, k: int, d_packed, read_sta
         raise ValueError("d_counts holds two words: bases, records")
     if max_bases is None:
         max_bases = 4 * int(d_packed.numel()) - int(base_offset)
+        if amb is not None:
+            max_bases = min(max_bases, 8 * int(amb.numel()) - int(amb_offset))
     dev = d_packed.device
     if ws is None:
         ws = default_workspace(dev.index or 0)
@@ -2691,19 +2752,33 @@ def one_minimizer_reads_counts_device(hasher: Hasher, k: int, d_packed, read_sta
         torch.cuda.synchronize(dev)
     elif out_pos.numel() < max_records:
         raise ValueError(f"out_pos holds {out_pos.numel()} words, {max_records} needed")
+    if amb is not None:
+        _check(lib().mm_one_minimizer_reads_skip_ambiguous_counts_device_async(
+            ws.h, C.byref(hasher), int(k), _vp_of(d_packed), int(d_packed.numel()), int(base_offset), _vp_of(amb),
+            int(amb.numel()), int(amb_offset), int(max_bases), max_records, _vp_of(read_starts), _vp_of(d_counts),
+            _vp_of(out_pos)))
+        return out_pos
     _check(lib().mm_one_minimizer_reads_counts_device_async(
         ws.h, C.byref(hasher), int(k), _vp_of(d_packed), int(d_packed.numel()), int(base_offset), int(max_bases), max_records,
         _vp_of(read_starts), _vp_of(d_counts), _vp_of(out_pos)))
     return out_pos
 
 
-def one_minimizer_reads_host(reads, hasher: Hasher, k: int, ws=None) -> np.ndarray:
+def one_minimizer_reads_host(reads, hasher: Hasher, k: int, ws=None, amb=None, amb_offset=0) -> np.ndarray:
     """``one_minimizer`` of many host reads (``PackedSeq`` views / ASCII ``bytes``) in ONE call
-    (``mm_one_minimizer_reads_host``): ``np.uint32[n]``, ``NO_MINIMIZER`` for a read shorter than k."""
+    (``mm_one_minimizer_reads_host``): ``np.uint32[n]``, ``NO_MINIMIZER`` for a read shorter than k.  With ``amb`` (a
+    uint8 array of ambiguity bits over the reads laid back to back, base j = bit ``amb_offset + j``) the skip-ambiguous
+    form (``mm_one_minimizer_reads_skip_ambiguous_host``): ``NO_MINIMIZER`` for a read without a clean k-mer."""
     packed, starts = _pack_reads(reads)
     n = len(starts) - 1
     out = np.zeros(max(1, n), dtype=np.uint32)
     ws = ws or default_workspace(0)
+    if amb is not None:
+        amb = np.ascontiguousarray(amb, dtype=np.uint8)
+        _check(lib().mm_one_minimizer_reads_skip_ambiguous_host(ws.h, C.byref(hasher), int(k), _vp_of(packed), len(packed), 0,
+                                                                _vp_of(amb), len(amb), int(amb_offset), n, _vp_of(starts), 0, 0,
+                                                                _vp_of(out)))
+        return out[:n]
     _check(lib().mm_one_minimizer_reads_host(ws.h, C.byref(hasher), int(k), _vp_of(packed), len(packed), 0, n, _vp_of(starts),
                                              0, 0, _vp_of(out)))
     return out[:n]

@@ -3570,16 +3570,24 @@ OneMinDnaTables one_min_dna_tables(const mm_hasher_t &h, uint32_t k) {
 // The checks that need no device, in the order the header states: MM_ERR_NULL, MM_ERR_K_ZERO, then the layout.  `symbols`:
 // what the buffer holds from symbol 0 (packed: 4 * packed_bytes - base_offset, checked here; text: text_bytes).
 // host_starts: the starts when the caller has them on the host (host and debug forms), else null.  MM_OK with n == 0:
-// nothing to do.
+// nothing to do.  amb (the skip-ambiguous forms, else null): a null buffer is MM_ERR_NULL where a null packed buffer is, an
+// amb_offset past its bits MM_ERR_CAPACITY behind the base_offset check.
+struct OneMinAmbBits {
+    const void *bits;
+    uint64_t bytes, offset;
+    uint64_t held() const { return bytes >= (1ull << 61) ? ~0ull : 8 * bytes; }  // (bits; saturated, never wraps)
+};
 int one_min_check(const void *hasher, uint32_t k, const void *data, uint64_t data_bytes, bool packed, uint64_t base_offset,
-                  uint64_t n, bool have_starts, const uint64_t *host_starts, uint32_t stride, uint32_t len, const void *out) {
+                  uint64_t n, bool have_starts, const uint64_t *host_starts, uint32_t stride, uint32_t len, const void *out,
+                  const OneMinAmbBits *amb = nullptr) {
     if (!hasher) return MM_ERR_NULL;
-    if (n && (!out || (!data && data_bytes))) return MM_ERR_NULL;
+    if (n && (!out || (!data && data_bytes) || (amb && !amb->bits))) return MM_ERR_NULL;
     if (k == 0) return MM_ERR_K_ZERO;
     if (n == 0) return MM_OK;
     if (n >= (1ull << 32) || data_bytes >= (1ull << 60)) return MM_ERR_LEN_TOO_LARGE;
     const uint64_t buffer = packed ? 4 * data_bytes : data_bytes;
     if (base_offset > buffer) return MM_ERR_CAPACITY;
+    if (amb && amb->offset > amb->held()) return MM_ERR_CAPACITY;
     const uint64_t symbols = buffer - base_offset;
     if (!have_starts) {
         if (len > stride) return MM_ERR_BAD_MODE;
@@ -3605,21 +3613,19 @@ int one_min_launch(mm_workspace_t *ws, const mm::OneMinArgs &a, const char *what
     return MM_OK;
 }
 
-// (after the checks, the workspace's device current)
-int one_min_reads_queue(mm_workspace_t *ws, const mm_hasher_t *hasher, uint32_t k, const void *d_packed, uint64_t packed_bytes,
-                        uint64_t base_offset, uint64_t n_reads, const uint64_t *d_read_starts, uint32_t read_stride,
-                        uint32_t read_len, uint32_t *d_out_pos) {
-    int r = one_min_keys(ws, n_reads);
-    if (r) return r;
-    const OneMinDnaTables t = one_min_dna_tables(*hasher, k);
-    mm::OneMinArgs a = {};
+// The launch arguments of the packed forms: `avail` symbols behind base_offset (host-n: what the buffer holds; counts: the
+// bound max_bases), n records (or their bound).  amb (device bits, or null): a k-mer beyond EITHER buffer does not exist,
+// so avail is cut to the bits the ambiguity buffer holds behind amb_offset - the kernels then load no byte outside it.
+void one_min_dna_args(mm::OneMinArgs &a, mm_workspace_t *ws, const mm_hasher_t &hasher, uint32_t k, const void *d_packed,
+                      uint64_t base_offset, uint64_t avail, uint64_t n, const uint64_t *d_read_starts, uint32_t *d_out_pos,
+                      const OneMinAmbBits *amb) {
+    const OneMinDnaTables t = one_min_dna_tables(hasher, k);
+    a = {};
     a.syms = static_cast<const uint8_t *>(d_packed);
     a.base0 = base_offset;
-    a.avail = 4 * packed_bytes - base_offset;
-    a.n = n_reads;
+    a.avail = avail;
+    a.n = n;
     a.starts = reinterpret_cast<const unsigned long long *>(d_read_starts);
-    a.stride = read_stride;
-    a.len = read_len;
     a.k = k;
     a.text = false;
     for (int c = 0; c < 4; ++c) {
@@ -3630,7 +3636,26 @@ int one_min_reads_queue(mm_workspace_t *ws, const mm_hasher_t *hasher, uint32_t 
     a.fw0 = t.fw0, a.rc0 = t.rc0, a.rot = t.rot, a.canonical = t.canonical;
     a.keys = ws->d_one_min_keys;
     a.out = d_out_pos;
-    return one_min_launch(ws, a, "one_minimizer_reads");
+    if (amb) {
+        a.amb = static_cast<const uint8_t *>(amb->bits);
+        a.amb0 = amb->offset;
+        const uint64_t bits = amb->held() - amb->offset;  // (offset <= held(): checked)
+        if (bits < a.avail) a.avail = bits;
+    }
+}
+
+// (after the checks, the workspace's device current)
+int one_min_reads_queue(mm_workspace_t *ws, const mm_hasher_t *hasher, uint32_t k, const void *d_packed, uint64_t packed_bytes,
+                        uint64_t base_offset, uint64_t n_reads, const uint64_t *d_read_starts, uint32_t read_stride,
+                        uint32_t read_len, uint32_t *d_out_pos, const OneMinAmbBits *amb = nullptr) {
+    const int r = one_min_keys(ws, n_reads);
+    if (r) return r;
+    mm::OneMinArgs a;
+    one_min_dna_args(a, ws, *hasher, k, d_packed, base_offset, 4 * packed_bytes - base_offset, n_reads, d_read_starts, d_out_pos,
+                     amb);
+    a.stride = read_stride;
+    a.len = read_len;
+    return one_min_launch(ws, a, amb ? "one_minimizer_reads_skip_ambiguous" : "one_minimizer_reads");
 }
 
 int one_min_text_queue(mm_workspace_t *ws, const mm_text_hasher_t *hasher, uint32_t k, const void *d_text, uint64_t text_bytes,
@@ -3657,16 +3682,45 @@ int one_min_text_queue(mm_workspace_t *ws, const mm_text_hasher_t *hasher, uint3
 // The counts forms' checks, before anything is touched, in the order of one_min_check: MM_ERR_NULL (d_counts included),
 // MM_ERR_K_ZERO, [max_records == 0: MM_OK], MM_ERR_LEN_TOO_LARGE, MM_ERR_CAPACITY.  `symbols`: what the buffer holds
 // (text: text_bytes; packed: 4 * packed_bytes, base_offset + max_sym must lie inside).
+// amb (the skip-ambiguous form, else null): as in one_min_check, and amb_offset + max_sym must lie inside its bits.
 int one_min_counts_check(const mm_workspace_t *ws, const void *hasher, uint32_t k, const void *data, uint64_t symbols,
                          uint64_t base_offset, uint64_t max_sym, uint64_t max_records, const void *d_starts,
-                         const void *d_counts, const void *out) {
+                         const void *d_counts, const void *out, const OneMinAmbBits *amb = nullptr) {
     if (!ws || !hasher || !d_counts) return MM_ERR_NULL;
-    if (max_records && (!d_starts || !out || (!data && max_sym))) return MM_ERR_NULL;
+    if (max_records && (!d_starts || !out || (!data && max_sym) || (amb && !amb->bits))) return MM_ERR_NULL;
     if (k == 0) return MM_ERR_K_ZERO;
     if (max_records == 0) return MM_OK;
     if (max_sym >= (1ull << 32) || max_records >= (1ull << 31)) return MM_ERR_LEN_TOO_LARGE;
     if (base_offset > symbols || max_sym > symbols - base_offset) return MM_ERR_CAPACITY;
+    if (amb && (amb->offset > amb->held() || max_sym > amb->held() - amb->offset)) return MM_ERR_CAPACITY;
     return MM_OK;
+}
+
+// The packed counts forms behind their checks: the hasher of the caller or of a plan (mm_fastx_stream.hip).
+int one_min_reads_counts_queue(mm_workspace_t *ws, const mm_hasher_t &hasher, uint32_t k, const void *d_packed,
+                               uint64_t base_offset, uint64_t max_bases, uint64_t max_records, const uint64_t *d_read_starts,
+                               const uint64_t *d_counts, uint32_t *d_out_pos, const OneMinAmbBits *amb) {
+    MM_HIP(set_device(ws->device));
+    ws->async_unchecked = true;  // (a refusal is raised in the sticky error word: mm_workspace_check reports it)
+    const int r = one_min_keys(ws, max_records);
+    if (r) return r;
+    mm::OneMinArgs a;
+    one_min_dna_args(a, ws, hasher, k, d_packed, base_offset, max_bases, max_records, d_read_starts, d_out_pos, amb);
+    a.counts = reinterpret_cast<const unsigned long long *>(d_counts);
+    a.error = error_word(ws);
+    return one_min_launch(ws, a, amb ? "one_minimizer_reads_skip_ambiguous_counts" : "one_minimizer_reads_counts");
+}
+
+// The checks of both packed counts forms, then the queue.
+int one_min_reads_counts(mm_workspace_t *ws, const mm_hasher_t *hasher, uint32_t k, const void *d_packed, uint64_t packed_bytes,
+                         uint64_t base_offset, uint64_t max_bases, uint64_t max_records, const uint64_t *d_read_starts,
+                         const uint64_t *d_counts, uint32_t *d_out_pos, const OneMinAmbBits *amb) {
+    const uint64_t buffer = packed_bytes >= (1ull << 62) ? ~0ull : 4 * packed_bytes;  // (bases; saturated, never wraps)
+    const int r = one_min_counts_check(ws, hasher, k, d_packed, buffer, base_offset, max_bases, max_records, d_read_starts,
+                                       d_counts, d_out_pos, amb);
+    if (r || max_records == 0) return r;
+    return one_min_reads_counts_queue(ws, *hasher, k, d_packed, base_offset, max_bases, max_records, d_read_starts, d_counts,
+                                      d_out_pos, amb);
 }
 
 }  // namespace
@@ -3683,6 +3737,26 @@ int mm_one_minimizer_reads_device_async(mm_workspace_t *ws, const mm_hasher_t *h
     MM_HIP(set_device(ws->device));
     return one_min_reads_queue(ws, hasher, k, d_packed, packed_bytes, base_offset, n_reads, d_read_starts, read_stride, read_len,
                                d_out_pos);
+}
+
+// The skip-ambiguous form: out[r] = the leftmost CLEAN position (no ambiguity bit among its k bases) that minimises
+// hash & 0xffff0000 over record r's clean positions, MM_NO_MINIMIZER without one.  K-mer-level skipping; the reference has
+// no counterpart (one_minimizer takes a plain Seq, src/minimizers.rs:22-28).  Bit numbering:
+// mm_run_packed_reads_skip_ambiguous_device_async's.
+int mm_one_minimizer_reads_skip_ambiguous_device_async(mm_workspace_t *ws, const mm_hasher_t *hasher, uint32_t k,
+                                                       const void *d_packed, uint64_t packed_bytes, uint64_t base_offset,
+                                                       const void *d_amb, uint64_t amb_bytes, uint64_t amb_offset, uint64_t n_reads,
+                                                       const uint64_t *d_read_starts, uint32_t read_stride, uint32_t read_len,
+                                                       uint32_t *d_out_pos) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    if (!ws) return MM_ERR_NULL;
+    const OneMinAmbBits amb{d_amb, amb_bytes, amb_offset};
+    const int r = one_min_check(hasher, k, d_packed, packed_bytes, true, base_offset, n_reads, d_read_starts != nullptr, nullptr,
+                                read_stride, read_len, d_out_pos, &amb);
+    if (r || n_reads == 0) return r;
+    MM_HIP(set_device(ws->device));
+    return one_min_reads_queue(ws, hasher, k, d_packed, packed_bytes, base_offset, n_reads, d_read_starts, read_stride, read_len,
+                               d_out_pos, &amb);
 }
 
 int mm_one_minimizer_text_batch_device_async(mm_workspace_t *ws, const mm_text_hasher_t *hasher, uint32_t k, const void *d_text,
@@ -3743,49 +3817,39 @@ int mm_one_minimizer_reads_counts_device_async(mm_workspace_t *ws, const mm_hash
                                                uint64_t max_records, const uint64_t *d_read_starts, const uint64_t *d_counts,
                                                uint32_t *d_out_pos) {
     ApiScope api_scope;  // (restores the calling thread's current device on return)
-    const uint64_t buffer = packed_bytes >= (1ull << 62) ? ~0ull : 4 * packed_bytes;  // (bases; saturated, never wraps)
-    int r = one_min_counts_check(ws, hasher, k, d_packed, buffer, base_offset, max_bases, max_records, d_read_starts, d_counts,
-                                 d_out_pos);
-    if (r || max_records == 0) return r;
-    MM_HIP(set_device(ws->device));
-    ws->async_unchecked = true;  // (a refusal is raised in the sticky error word: mm_workspace_check reports it)
-    r = one_min_keys(ws, max_records);
-    if (r) return r;
-    const OneMinDnaTables t = one_min_dna_tables(*hasher, k);
-    mm::OneMinArgs a = {};
-    a.syms = static_cast<const uint8_t *>(d_packed);
-    a.base0 = base_offset;
-    a.avail = max_bases;
-    a.n = max_records;
-    a.starts = reinterpret_cast<const unsigned long long *>(d_read_starts);
-    a.k = k;
-    a.text = false;
-    for (int c = 0; c < 4; ++c) {
-        a.small_in[c] = make_uint2(t.t_in[c].x, t.t_in[c].y);
-        a.small_out[c] = make_uint2(t.t_out[c].x, t.t_out[c].y);
-    }
-    a.fw0 = t.fw0, a.rc0 = t.rc0, a.rot = t.rot, a.canonical = t.canonical;
-    a.keys = ws->d_one_min_keys;
-    a.out = d_out_pos;
-    a.counts = reinterpret_cast<const unsigned long long *>(d_counts);
-    a.error = error_word(ws);
-    return one_min_launch(ws, a, "one_minimizer_reads_counts");
+    return one_min_reads_counts(ws, hasher, k, d_packed, packed_bytes, base_offset, max_bases, max_records, d_read_starts,
+                                d_counts, d_out_pos, nullptr);
+}
+
+// The skip-ambiguous counts form: word for word the plain counts form's contract, over clean k-mers only.
+int mm_one_minimizer_reads_skip_ambiguous_counts_device_async(mm_workspace_t *ws, const mm_hasher_t *hasher, uint32_t k,
+                                                              const void *d_packed, uint64_t packed_bytes, uint64_t base_offset,
+                                                              const void *d_amb, uint64_t amb_bytes, uint64_t amb_offset,
+                                                              uint64_t max_bases, uint64_t max_records,
+                                                              const uint64_t *d_read_starts, const uint64_t *d_counts,
+                                                              uint32_t *d_out_pos) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    const OneMinAmbBits amb{d_amb, amb_bytes, amb_offset};
+    return one_min_reads_counts(ws, hasher, k, d_packed, packed_bytes, base_offset, max_bases, max_records, d_read_starts,
+                                d_counts, d_out_pos, &amb);
 }
 
 // The same from HOST memory: one upload (the bytes the records cover, the starts), the launches, one download.
-int mm_one_minimizer_reads_host(mm_workspace_t *ws, const mm_hasher_t *hasher, uint32_t k, const uint8_t *packed,
-                                uint64_t packed_bytes, uint64_t base_offset, uint64_t n_reads, const uint64_t *read_starts,
-                                uint32_t read_stride, uint32_t read_len, uint32_t *out_pos) {
-    ApiScope api_scope;  // (restores the calling thread's current device on return)
+// (amb: host bits for the skip-ambiguous form, uploaded behind the starts; else null)
+static int one_min_reads_host(mm_workspace_t *ws, const mm_hasher_t *hasher, uint32_t k, const uint8_t *packed,
+                              uint64_t packed_bytes, uint64_t base_offset, uint64_t n_reads, const uint64_t *read_starts,
+                              uint32_t read_stride, uint32_t read_len, uint32_t *out_pos, const OneMinAmbBits *amb) {
     if (!ws) return MM_ERR_NULL;
     int r = one_min_check(hasher, k, packed, packed_bytes, true, base_offset, n_reads, read_starts != nullptr, read_starts,
-                          read_stride, read_len, out_pos);
+                          read_stride, read_len, out_pos, amb);
     if (r || n_reads == 0) return r;
+    if (amb && amb->bytes >= (1ull << 60)) return MM_ERR_LEN_TOO_LARGE;
     MM_HIP(set_device(ws->device));
-    // staging: [packed bytes | starts] in d_in, positions in d_out
+    // staging: [packed bytes | starts | ambiguity bits] in d_in, positions in d_out
     const uint64_t words = n_reads + 1;
     const uint64_t starts_at = (packed_bytes + 15) & ~15ull;
-    r = grow_bytes(ws->d_in, ws->d_in_bytes, starts_at + (read_starts ? words * sizeof(uint64_t) : 0) + 16);
+    const uint64_t amb_at = starts_at + (read_starts ? words * sizeof(uint64_t) : 0) + 16;
+    r = grow_bytes(ws->d_in, ws->d_in_bytes, amb_at + (amb ? amb->bytes : 0));
     if (r) return r;
     r = grow(ws->d_out, ws->d_out_elems, n_reads, sizeof(uint32_t));
     if (r) return r;
@@ -3793,13 +3857,33 @@ int mm_one_minimizer_reads_host(mm_workspace_t *ws, const mm_hasher_t *hasher, u
     if (packed_bytes) MM_HIP(hipMemcpyAsync(din, packed, packed_bytes, hipMemcpyHostToDevice, ws->stream));
     if (read_starts)
         MM_HIP(hipMemcpyAsync(din + starts_at, read_starts, words * sizeof(uint64_t), hipMemcpyHostToDevice, ws->stream));
+    OneMinAmbBits d_amb{din + amb_at, amb ? amb->bytes : 0, amb ? amb->offset : 0};
+    if (amb && amb->bytes) MM_HIP(hipMemcpyAsync(din + amb_at, amb->bits, amb->bytes, hipMemcpyHostToDevice, ws->stream));
     r = one_min_reads_queue(ws, hasher, k, din, packed_bytes, base_offset, n_reads,
                             read_starts ? reinterpret_cast<const uint64_t *>(din + starts_at) : nullptr, read_stride, read_len,
-                            ws->d_out);
+                            ws->d_out, amb ? &d_amb : nullptr);
     if (r) return r;
     MM_HIP(hipMemcpyAsync(out_pos, ws->d_out, n_reads * sizeof(uint32_t), hipMemcpyDeviceToHost, ws->stream));
     MM_HIP(hipStreamSynchronize(ws->stream));
     return MM_OK;
+}
+
+int mm_one_minimizer_reads_host(mm_workspace_t *ws, const mm_hasher_t *hasher, uint32_t k, const uint8_t *packed,
+                                uint64_t packed_bytes, uint64_t base_offset, uint64_t n_reads, const uint64_t *read_starts,
+                                uint32_t read_stride, uint32_t read_len, uint32_t *out_pos) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    return one_min_reads_host(ws, hasher, k, packed, packed_bytes, base_offset, n_reads, read_starts, read_stride, read_len,
+                              out_pos, nullptr);
+}
+
+int mm_one_minimizer_reads_skip_ambiguous_host(mm_workspace_t *ws, const mm_hasher_t *hasher, uint32_t k, const uint8_t *packed,
+                                               uint64_t packed_bytes, uint64_t base_offset, const uint8_t *amb, uint64_t amb_bytes,
+                                               uint64_t amb_offset, uint64_t n_reads, const uint64_t *read_starts,
+                                               uint32_t read_stride, uint32_t read_len, uint32_t *out_pos) {
+    ApiScope api_scope;  // (restores the calling thread's current device on return)
+    const OneMinAmbBits bits{amb, amb_bytes, amb_offset};
+    return one_min_reads_host(ws, hasher, k, packed, packed_bytes, base_offset, n_reads, read_starts, read_stride, read_len,
+                              out_pos, &bits);
 }
 
 int mm_one_minimizer_text_batch_host(mm_workspace_t *ws, const mm_text_hasher_t *hasher, uint32_t k, const uint8_t *text,
@@ -3842,25 +3926,52 @@ void one_min_debug_run(const Sym &sym, const Lay &lay, uint64_t n, uint64_t symb
 }  // namespace
 }  // extern "C++"
 
-int mm_debug_one_minimizer_reads(const mm_hasher_t *hasher, uint32_t k, const uint8_t *packed, uint64_t packed_bytes,
-                                 uint64_t base_offset, uint64_t n_reads, const uint64_t *read_starts, uint32_t read_stride,
-                                 uint32_t read_len, uint32_t tile, uint32_t *out_pos) {
+extern "C++" {
+namespace {
+// Both packed debug forms (amb: host bits, or null); the symbols are cut to the ambiguity buffer's bits as the device
+// forms cut them (one_min_dna_args).
+int one_min_debug_reads(const mm_hasher_t *hasher, uint32_t k, const uint8_t *packed, uint64_t packed_bytes, uint64_t base_offset,
+                        uint64_t n_reads, const uint64_t *read_starts, uint32_t read_stride, uint32_t read_len, uint32_t tile,
+                        uint32_t *out_pos, const OneMinAmbBits *amb) {
     const int r = one_min_check(hasher, k, packed, packed_bytes, true, base_offset, n_reads, read_starts != nullptr, read_starts,
-                                read_stride, read_len, out_pos);
+                                read_stride, read_len, out_pos, amb);
     if (r || n_reads == 0) return r;
     if (tile == 0) tile = mm::kOneMinTile;
     const OneMinDnaTables d = one_min_dna_tables(*hasher, k);
     const mm::OneMinTables t = {d.t_in, d.t_out, d.fw0, d.rc0, d.rot, d.canonical};
-    const mm::OneMinPacked sym{packed, base_offset};
-    const uint64_t symbols = 4 * packed_bytes - base_offset;
-    if (read_starts) {
-        one_min_debug_run(sym, mm::OneMinStarts{read_starts}, n_reads, symbols, t, k, tile, out_pos);
-    } else if (read_len < k) {
-        for (uint64_t i = 0; i < n_reads; ++i) out_pos[i] = MM_NO_MINIMIZER;
-    } else {
-        one_min_debug_run(sym, mm::OneMinStride{read_stride, read_len}, n_reads, symbols, t, k, tile, out_pos);
-    }
+    const mm::OneMinPacked packed_sym{packed, base_offset};
+    uint64_t symbols = 4 * packed_bytes - base_offset;
+    if (amb && amb->held() - amb->offset < symbols) symbols = amb->held() - amb->offset;
+    const auto run = [&](const auto &sym) {
+        if (read_starts) {
+            one_min_debug_run(sym, mm::OneMinStarts{read_starts}, n_reads, symbols, t, k, tile, out_pos);
+        } else if (read_len < k) {
+            for (uint64_t i = 0; i < n_reads; ++i) out_pos[i] = MM_NO_MINIMIZER;
+        } else {
+            one_min_debug_run(sym, mm::OneMinStride{read_stride, read_len}, n_reads, symbols, t, k, tile, out_pos);
+        }
+    };
+    if (amb) run(mm::OneMinPackedAmb{packed_sym, static_cast<const uint8_t *>(amb->bits), amb->offset});
+    else run(packed_sym);
     return MM_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int mm_debug_one_minimizer_reads(const mm_hasher_t *hasher, uint32_t k, const uint8_t *packed, uint64_t packed_bytes,
+                                 uint64_t base_offset, uint64_t n_reads, const uint64_t *read_starts, uint32_t read_stride,
+                                 uint32_t read_len, uint32_t tile, uint32_t *out_pos) {
+    return one_min_debug_reads(hasher, k, packed, packed_bytes, base_offset, n_reads, read_starts, read_stride, read_len, tile,
+                               out_pos, nullptr);
+}
+
+int mm_debug_one_minimizer_reads_skip_ambiguous(const mm_hasher_t *hasher, uint32_t k, const uint8_t *packed, uint64_t packed_bytes,
+                                                uint64_t base_offset, const uint8_t *amb, uint64_t amb_bytes, uint64_t amb_offset,
+                                                uint64_t n_reads, const uint64_t *read_starts, uint32_t read_stride,
+                                                uint32_t read_len, uint32_t tile, uint32_t *out_pos) {
+    const OneMinAmbBits bits{amb, amb_bytes, amb_offset};
+    return one_min_debug_reads(hasher, k, packed, packed_bytes, base_offset, n_reads, read_starts, read_stride, read_len, tile,
+                               out_pos, &bits);
 }
 
 int mm_debug_one_minimizer_text_batch(const mm_text_hasher_t *hasher, uint32_t k, const uint8_t *text, uint64_t text_bytes,
@@ -3919,21 +4030,42 @@ int mm_debug_one_minimizer_text_batch_counts(const mm_text_hasher_t *hasher, uin
     return one_min_debug_counts_run(mm::OneMinText{text, 0}, starts, max_chars, max_records, counts, t, k, tile, out_pos);
 }
 
-int mm_debug_one_minimizer_reads_counts(const mm_hasher_t *hasher, uint32_t k, const uint8_t *packed, uint64_t packed_bytes,
-                                        uint64_t base_offset, uint64_t max_bases, uint64_t max_records,
-                                        const uint64_t *read_starts, const uint64_t *counts, uint32_t tile, uint32_t *out_pos) {
+static int one_min_debug_reads_counts(const mm_hasher_t *hasher, uint32_t k, const uint8_t *packed, uint64_t packed_bytes,
+                                      uint64_t base_offset, uint64_t max_bases, uint64_t max_records, const uint64_t *read_starts,
+                                      const uint64_t *counts, uint32_t tile, uint32_t *out_pos, const OneMinAmbBits *amb) {
     if (!hasher || !counts) return MM_ERR_NULL;
-    if (max_records && (!read_starts || !out_pos || (!packed && max_bases))) return MM_ERR_NULL;
+    if (max_records && (!read_starts || !out_pos || (!packed && max_bases) || (amb && !amb->bits))) return MM_ERR_NULL;
     if (k == 0) return MM_ERR_K_ZERO;
     if (max_records == 0) return MM_OK;
     if (max_bases >= (1ull << 32) || max_records >= (1ull << 31)) return MM_ERR_LEN_TOO_LARGE;
     const uint64_t buffer = packed_bytes >= (1ull << 62) ? ~0ull : 4 * packed_bytes;  // (bases; saturated, never wraps)
     if (base_offset > buffer || max_bases > buffer - base_offset) return MM_ERR_CAPACITY;
+    if (amb && (amb->offset > amb->held() || max_bases > amb->held() - amb->offset)) return MM_ERR_CAPACITY;
     if (tile == 0) tile = mm::kOneMinTile;
     const OneMinDnaTables d = one_min_dna_tables(*hasher, k);
     const mm::OneMinTables t = {d.t_in, d.t_out, d.fw0, d.rc0, d.rot, d.canonical};
-    return one_min_debug_counts_run(mm::OneMinPacked{packed, base_offset}, read_starts, max_bases, max_records, counts, t, k,
-                                    tile, out_pos);
+    const mm::OneMinPacked sym{packed, base_offset};
+    if (amb)
+        return one_min_debug_counts_run(mm::OneMinPackedAmb{sym, static_cast<const uint8_t *>(amb->bits), amb->offset}, read_starts,
+                                        max_bases, max_records, counts, t, k, tile, out_pos);
+    return one_min_debug_counts_run(sym, read_starts, max_bases, max_records, counts, t, k, tile, out_pos);
+}
+
+int mm_debug_one_minimizer_reads_counts(const mm_hasher_t *hasher, uint32_t k, const uint8_t *packed, uint64_t packed_bytes,
+                                        uint64_t base_offset, uint64_t max_bases, uint64_t max_records,
+                                        const uint64_t *read_starts, const uint64_t *counts, uint32_t tile, uint32_t *out_pos) {
+    return one_min_debug_reads_counts(hasher, k, packed, packed_bytes, base_offset, max_bases, max_records, read_starts, counts,
+                                      tile, out_pos, nullptr);
+}
+
+int mm_debug_one_minimizer_reads_skip_ambiguous_counts(const mm_hasher_t *hasher, uint32_t k, const uint8_t *packed,
+                                                       uint64_t packed_bytes, uint64_t base_offset, const uint8_t *amb,
+                                                       uint64_t amb_bytes, uint64_t amb_offset, uint64_t max_bases,
+                                                       uint64_t max_records, const uint64_t *read_starts, const uint64_t *counts,
+                                                       uint32_t tile, uint32_t *out_pos) {
+    const OneMinAmbBits bits{amb, amb_bytes, amb_offset};
+    return one_min_debug_reads_counts(hasher, k, packed, packed_bytes, base_offset, max_bases, max_records, read_starts, counts,
+                                      tile, out_pos, &bits);
 }
 
 // ---- Output::values_u64 / values_u128 (src/lib.rs:584-629) of every sequence of a device batch in ONE launch: what the
@@ -5735,6 +5867,14 @@ int api_one_min_text_plan_counts(const mm_plan_t *plan, mm_workspace_t *ws, cons
                                        d_out_pos);
     if (r || max_records == 0) return r;
     return one_min_text_counts_queue(ws, plan->tt, plan->k, d_text, max_chars, max_records, d_starts, d_counts, d_out_pos);
+}
+int api_one_min_reads_plan_counts(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed, uint64_t packed_bytes,
+                                  const void *d_amb, uint64_t amb_bytes, uint64_t max_bases, uint64_t max_records,
+                                  const uint64_t *d_read_starts, const uint64_t *d_counts, uint32_t *d_out_pos) {
+    if (!plan || plan->text) return MM_ERR_BAD_MODE;
+    const OneMinAmbBits amb{d_amb, amb_bytes, 0};
+    return one_min_reads_counts(ws, &plan->hasher, plan->k, d_packed, packed_bytes, 0, max_bases, max_records, d_read_starts,
+                                d_counts, d_out_pos, d_amb ? &amb : nullptr);
 }
 hipStream_t api_workspace_stream(mm_workspace_t *ws) { return ws->stream; }
 void api_set_last_error(const char *text) { g_last_error = text; }

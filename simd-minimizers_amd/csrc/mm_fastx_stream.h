@@ -40,6 +40,11 @@ int api_text_counts_refusal(const mm_plan_t *plan, uint64_t max_chars, uint64_t 
 int api_one_min_text_plan_counts(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_text, uint64_t text_bytes,
                                  uint64_t max_chars, uint64_t max_records, const uint64_t *d_starts, const uint64_t *d_counts,
                                  uint32_t *d_out_pos);
+// The DNA stream (MM_FASTX_ONE_MINIMIZER): mm_one_minimizer_reads_counts_device_async - with d_amb (amb_bytes of bits,
+// bit 0 = base 0) its skip-ambiguous form - with the plan's own k and hasher, base_offset 0.
+int api_one_min_reads_plan_counts(const mm_plan_t *plan, mm_workspace_t *ws, const void *d_packed, uint64_t packed_bytes,
+                                  const void *d_amb, uint64_t amb_bytes, uint64_t max_bases, uint64_t max_records,
+                                  const uint64_t *d_read_starts, const uint64_t *d_counts, uint32_t *d_out_pos);
 hipStream_t api_workspace_stream(mm_workspace_t *ws);
 void api_set_last_error(const char *text);
 

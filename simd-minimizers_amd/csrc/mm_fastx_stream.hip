@@ -26,6 +26,11 @@
 // mm_fasta_text_device_async, whose sequence bytes go where the packed bases go (d_packed: 2 * chunk_bytes bytes), whose
 // starts go into d_rec_base and whose counts have the packers' layout, so the trim step is used as it is; the run and the
 // values are the text batch counts calls, and MM_FASTX_TEXT_ONE_MINIMIZER adds the one-minimizer counts call behind them.
+//
+// MM_FASTX_ONE_MINIMIZER (the DNA stream): behind the run and the values, on the slot's stream, the packed one-minimizer
+// counts call - with MM_FASTX_SKIP_AMBIGUOUS its skip-ambiguous form over the slot's d_amb - writes one word per record
+// into d_one; the delivered records' words are downloaded with the batch (mm_fastx_stream_one_minimizer).  Still one host
+// wait per chunk.  Refused with MM_FASTX_LONG_RECORDS: a split record's minimizer is not joined across its pieces.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -51,14 +56,14 @@ struct Slot {
     unsigned long long *d_meta = nullptr;  // [0..1] bases, records  [2..6] cut, overflow, T, open, overlap  [7] positions  [8] newlines
     uint32_t *d_pos = nullptr, *d_sk = nullptr;
     uint64_t *d_values = nullptr;
-    uint32_t *d_one = nullptr;  // byte text, MM_FASTX_TEXT_ONE_MINIMIZER: one word per record
+    uint32_t *d_one = nullptr;  // MM_FASTX_TEXT_ONE_MINIMIZER / MM_FASTX_ONE_MINIMIZER: one word per record
     // page-locked host
     uint8_t *h_text = nullptr;
     unsigned long long *h_meta = nullptr;  // words 0..7 of d_meta; bytes 120..121: the synthetic header line ">\n"
     uint64_t *h_rec_pos = nullptr, *h_rec_base = nullptr, *h_offsets = nullptr, *h_values = nullptr;
     uint32_t *h_pos = nullptr, *h_sk = nullptr;
-    uint32_t *h_one = nullptr;  // byte text: the one-minimizer words ...
-    uint8_t *h_seq = nullptr;   // ... and the records' bytes (MM_FASTX_TEXT_SEQ)
+    uint32_t *h_one = nullptr;  // the one-minimizer words ...
+    uint8_t *h_seq = nullptr;   // ... and, byte text, the records' bytes (MM_FASTX_TEXT_SEQ)
     hipEvent_t ev_cut = nullptr, ev_run = nullptr, ev_done = nullptr, ev_tail = nullptr;
     bool tail_pending = false;  // the chunk behind this slot's copies its tail out of d_text: ev_tail says when it has
     // the chunk in the slot
@@ -184,6 +189,13 @@ int queue_run(mm_fastx_stream *s, Slot &sl) {
         r = (flags & MM_FASTX_VALUES_U128 ? mm_values_u128_reads_device_async : mm_values_u64_reads_device_async)(
             sl.ws, sl.d_packed, s->packed_cap, 0, s->max_records, sl.d_rec_base, 0, s->value_len, s->info.canonical_windows, sl.d_pos,
             sl.d_offsets, s->max_positions, sl.d_values);
+        if (r) return fail_call(s, r);
+    }
+    // (the trimmed counts: the records the batch delivers; a repeated run queues the call again)
+    if (sl.d_one && s->max_records) {
+        r = mm::api_one_min_reads_plan_counts(s->plan, sl.ws, sl.d_packed, s->packed_cap,
+                                              (flags & MM_FASTX_SKIP_AMBIGUOUS) ? sl.d_amb : nullptr, s->amb_cap, max_bases,
+                                              s->max_records, sl.d_rec_base, d_counts, sl.d_one);
         if (r) return fail_call(s, r);
     }
     FX_HIP(hipSetDevice(s->cfg.device));
@@ -432,7 +444,7 @@ int open_stream(mm_fastx_stream_t **out, const mm_plan_t *plan, const mm::ApiPla
     const uint64_t R = s->max_records, P = s->max_positions;
     const uint64_t per_value = flags & MM_FASTX_VALUES_U128 ? 16 : 8;
     const bool want_values = (flags & (MM_FASTX_VALUES_U64 | MM_FASTX_VALUES_U128)) != 0;
-    const bool want_one = text && (flags & MM_FASTX_TEXT_ONE_MINIMIZER), want_seq = text && (flags & MM_FASTX_TEXT_SEQ);
+    const bool want_one = (flags & (text ? MM_FASTX_TEXT_ONE_MINIMIZER : MM_FASTX_ONE_MINIMIZER)) != 0, want_seq = text && (flags & MM_FASTX_TEXT_SEQ);
     int rc = MM_OK;
     hipError_t e = hipSetDevice(cfg.device);
     for (int i = 0; i < s->n_slots && e == hipSuccess && rc == MM_OK; ++i) {
@@ -493,6 +505,14 @@ int mm_fastx_text_stream_extras(const mm_fastx_stream_t *s, mm_fastx_text_extras
     if (!s || !out) return MM_ERR_NULL;
     if (s->delivered >= 0 && s->text) *out = s->extras;
     else memset(out, 0, sizeof *out);
+    return MM_OK;
+}
+
+int mm_fastx_stream_one_minimizer(const mm_fastx_stream_t *s, const uint32_t **one_min, uint64_t *n_records) {
+    if (!s || !one_min || !n_records) return MM_ERR_NULL;
+    const bool have = s->delivered >= 0 && !s->text && s->slots[s->delivered].h_one;
+    *one_min = have ? s->slots[s->delivered].h_one : nullptr;
+    *n_records = have ? s->slots[s->delivered].h_meta[1] : 0;
     return MM_OK;
 }
 
@@ -570,8 +590,13 @@ int mm_fastx_stream_create(mm_fastx_stream_t **out, const mm_plan_t *plan, const
                                                      (flags & MM_FASTX_SKIP_AMBIGUOUS) != 0);
     if (refusal) return refusal;
     if (cfg->format < MM_FASTX_AUTO || cfg->format > MM_FASTX_FASTQ || (cfg->slots != 0 && (cfg->slots < 2 || cfg->slots > 8)) ||
-        (flags & ~31u)) {
+        (flags & ~(31u | MM_FASTX_ONE_MINIMIZER))) {
         mm::api_set_last_error("mm_fastx_stream_create: format is MM_FASTX_AUTO / _FASTA / _FASTQ, slots 0 or 2..8, flags MM_FASTX_*");
+        return MM_ERR_BAD_MODE;
+    }
+    if ((flags & MM_FASTX_ONE_MINIMIZER) && (flags & MM_FASTX_LONG_RECORDS)) {
+        mm::api_set_last_error("mm_fastx_stream_create: MM_FASTX_ONE_MINIMIZER with MM_FASTX_LONG_RECORDS: a split record's "
+                               "minimizer is not joined across its pieces");
         return MM_ERR_BAD_MODE;
     }
     // (a piece must be able to move past its own overlap: l - 1 bases, up to three bytes each with "\r\n" behind every base)

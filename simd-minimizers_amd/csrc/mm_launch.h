@@ -292,6 +292,10 @@ struct OneMinArgs {
     // `error` (the workspace's error words, OutParams::error) receives code 8 in its sticky word when a count exceeds them
     const unsigned long long *counts = nullptr;
     uint32_t *error = nullptr;
+    // packed only, or null: the ambiguity bits (device); symbol i is bit amb0 + i, bit b = bit b % 8 of byte b / 8.  A k-mer
+    // over a set bit has no key.  `avail` must not pass the bits the buffer holds (8 * amb_bytes - amb0).
+    const uint8_t *amb = nullptr;
+    unsigned long long amb0 = 0;
 };
 int launch_one_min(const OneMinArgs &a, hipStream_t stream);  // 0, -1 (HIP failure), -3 (grid too large)
 int launch_pack_ascii(const uint8_t *d_ascii, uint64_t n, uint8_t *d_packed, hipStream_t stream);

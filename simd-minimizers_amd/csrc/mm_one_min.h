@@ -49,6 +49,29 @@ struct OneMinText {
     MM_HOST_DEVICE uint32_t operator()(uint64_t i) const { return p[i - origin]; }
 };
 
+// The packed symbols with their ambiguity bits (the skip-ambiguous forms): symbol i is bit bit0 + i of `bits`, bit b being
+// bit b % 8 of byte b / 8 (mm_run_packed_reads_skip_ambiguous_device_async's numbering).  A k-mer with a set bit among its
+// k symbols does not exist: one_min_lane gives it no key.
+struct OneMinPackedAmb {
+    OneMinPacked sym;
+    const uint8_t *bits;
+    uint64_t bit0;
+    MM_HOST_DEVICE uint32_t operator()(uint64_t i) const { return sym(i); }
+    MM_HOST_DEVICE bool amb(uint64_t i) const {
+        const uint64_t b = bit0 + i;
+        return ((bits[b >> 3] >> (uint32_t)(b & 7u)) & 1u) != 0;
+    }
+};
+// The compile-time switch of one_min_lane: only a symbol functor that answers amb(i) makes it count clean runs.
+template <class Sym>
+struct OneMinHasAmb {
+    static constexpr bool value = false;
+};
+template <>
+struct OneMinHasAmb<OneMinPackedAmb> {
+    static constexpr bool value = true;
+};
+
 // The records: record r is the symbols [lay[r], lay.end(r)); lay[r] is non-decreasing over [0, n].
 struct OneMinStarts {
     const uint64_t *s;  // [n + 1]
@@ -97,9 +120,12 @@ MM_HOST_DEVICE inline bool one_min_tile_range(const Lay &lay, uint64_t n, uint64
 
 // One lane: the positions [g0, g1) of a tile (g0 < g1 <= range.g_end), every symbol it loads lies below g1 + k - 1.
 // emit(r, key) is called once per record that owns one of them, with the minimum of that record's keys in the lane.
+// With ambiguity bits (OneMinHasAmb<Sym>) the lane carries, beside its hash, the length of the clean run that ends at its
+// newest symbol, saturated at k and built during the warm-up: a position has a key only when that run holds its k symbols.
 template <class Sym, class Lay, class Emit>
 MM_HOST_DEVICE inline void one_min_lane(const Sym &sym, const Lay &lay, const OneMinTileRange &range, const OneMinTables &t,
                                         uint32_t k, uint64_t g0, uint64_t g1, Emit &&emit) {
+    constexpr bool AMB = OneMinHasAmb<Sym>::value;
     const uint32_t R = t.rot;
     const bool canon = t.canonical != 0;
     uint64_t r = values_read_of(lay, range.r_lo, range.r_hi, g0);
@@ -112,10 +138,12 @@ MM_HOST_DEVICE inline void one_min_lane(const Sym &sym, const Lay &lay, const On
         if (none_here && (r >= range.r_hi || lay[r + 1] >= g1)) return;
     }
     uint32_t fw = t.fw0, rc = t.rc0;
+    [[maybe_unused]] uint32_t clean = 0;  // (AMB) symbols of the clean run that ends at the newest symbol, at most k
     for (uint32_t j = 0; j < k; ++j) {
         const OneMinPair e = t.t_in[sym(g0 + j)];
         fw = one_min_rotl(fw, R) ^ e.x;
         if (canon) rc = one_min_rotr(rc, R) ^ e.y;
+        if constexpr (AMB) clean = sym.amb(g0 + j) ? 0u : clean + 1u;
     }
     uint64_t best = kOneMinNoKey;
     for (uint64_t g = g0;;) {
@@ -126,7 +154,7 @@ MM_HOST_DEVICE inline void one_min_lane(const Sym &sym, const Lay &lay, const On
             rs = lay[r];
             re = lay.end(r);
         }
-        if (g >= rs && g + k <= re) {
+        if (g >= rs && g + k <= re && (!AMB || clean >= k)) {
             const uint32_t h = canon ? fw + rc : fw;
             const uint64_t key = ((uint64_t)(h & 0xffff0000u) << 32) | (uint64_t)(uint32_t)(g - rs);
             if (key < best) best = key;
@@ -135,6 +163,7 @@ MM_HOST_DEVICE inline void one_min_lane(const Sym &sym, const Lay &lay, const On
         const OneMinPair in = t.t_in[sym(g + k - 1)], out = t.t_out[sym(g - 1)];
         fw = one_min_rotl(fw, R) ^ in.x ^ out.x;
         if (canon) rc = one_min_rotr(rc, R) ^ in.y ^ out.y;
+        if constexpr (AMB) clean = sym.amb(g + k - 1) ? 0u : (clean < k ? clean + 1u : k);
     }
     if (best != kOneMinNoKey) emit(r, best);
 }

@@ -22,10 +22,16 @@
 //     and keys are sized from the caller's bounds, thread 0 turns {counts, bounds} into (n, limit) with
 //     one_min_counts_view (mm_one_min.h) where the others use a.n and a.avail, and a finish kernel of their own writes
 //     MM_NO_MINIMIZER at and past n and raises kernel error 8 for counts beyond the bounds.  The host-n instances are the
-//     code they were: the flag is a template parameter, the position loop has no run-time branch.
+//     code they were: the flag is a template parameter, the position loop has no run-time branch;
+//   - the AMB instances (mm_one_minimizer_reads_skip_ambiguous_*: packed symbols only, starts x forward / canonical x
+//     host-n / COUNTS and fixed stride x forward / canonical) skip every k-mer that holds an ambiguous base: the tile's
+//     ambiguity bits, T + k - 1 of them, are staged in LDS next to the symbols (read from global memory where the symbols
+//     are), a lane counts the clean run that ends at its newest symbol (mm_one_min.h) and a position has a key only when
+//     the run holds its k symbols.  Again a template parameter: the other instances are the code they were.
 // Nothing outside the symbols [0, limit), starts[0 .. n] and keys / out [0, n) is touched, whatever the starts hold: every
 // record index is clamped to [0, n - 1] by the searches and every symbol index lies below the limit, which is itself
-// clamped to the buffer.  All stores are vector stores or atomics; no inline assembly.
+// clamped to the buffer - for the AMB instances to the bits of the ambiguity buffer as well (the host folds both into
+// a.avail), so no byte outside [amb, amb + amb_bytes) is loaded.  All stores are vector stores or atomics; no inline assembly.
 #include "mm_common.h"
 #include "mm_launch.h"
 #include "mm_one_min.h"
@@ -54,10 +60,20 @@ __device__ __forceinline__ unsigned long long &one_min_counts_n() {
     return s_n;
 }
 
+// The AMB instances' ambiguity bits of a tile, T + k - 1 of them whenever the symbols are staged: at most 4 * kStage bits
+// from any bit of a byte, placed at the global address's alignment modulo 4.  A function of its own for the reason above.
+constexpr uint32_t kOneMinAmbStage = (2 * kOneMinTile / 4 + 4) / 2 + 1 + 3;  // bytes
+__device__ __forceinline__ uint8_t *one_min_amb_stage() {
+    __shared__ uint32_t s_amb[kOneMinAmbStage / 4 + 1];
+    return reinterpret_cast<uint8_t *>(s_amb);
+}
+
 // TEXT: byte symbols and 256-entry tables (else 2-bit symbols, 4 entries).  kStage: bytes of a tile's symbols kept in LDS -
 // every k up to a tile's own size; a larger k reads its symbols from global memory.
 // COUNTS: a.n and a.avail are bounds, the true counts are read from a.counts (starts layout only).
-template <bool TEXT, class Lay, bool CANON, bool COUNTS = false>
+// AMB (packed only): symbol i has the ambiguity bit a.amb0 + i of a.amb, a k-mer over a set bit has no key; a.avail is
+// already cut to the bits the buffer holds, so no bit at or past the limit is loaded either.
+template <bool TEXT, class Lay, bool CANON, bool COUNTS = false, bool AMB = false>
 __global__ __launch_bounds__(kOneMinThreads) void one_min_kernel(Lay lay, OneMinArgs a) {
     constexpr int NTAB = TEXT ? 256 : 4;
     constexpr uint32_t kStage = TEXT ? 2 * kOneMinTile : 2 * kOneMinTile / 4 + 4;
@@ -107,6 +123,17 @@ __global__ __launch_bounds__(kOneMinThreads) void one_min_kernel(Lay lay, OneMin
     const uint8_t *const src = a.syms + byte_lo;
     uint8_t *const stage = reinterpret_cast<uint8_t *>(s_stage) + (reinterpret_cast<uintptr_t>(src) & 3u);
     if (staged) stage_bytes(stage, src, (uint32_t)(byte_hi - byte_lo + 1), tid);
+    [[maybe_unused]] const uint8_t *amb_stage = nullptr;
+    [[maybe_unused]] uint64_t amb_byte_lo = 0;
+    if constexpr (AMB) {
+        // the bits of the same symbols: [a.amb0 + g_begin, a.amb0 + g_end + k - 1), staged whenever the symbols are
+        const uint64_t bit_lo = a.amb0 + range.g_begin, bit_hi = bit_lo + (range.g_end - range.g_begin) + a.k - 2;
+        amb_byte_lo = bit_lo >> 3;
+        const uint8_t *const amb_src = a.amb + amb_byte_lo;
+        uint8_t *const dst = one_min_amb_stage() + (reinterpret_cast<uintptr_t>(amb_src) & 3u);
+        if (staged) stage_bytes(dst, amb_src, (uint32_t)((bit_hi >> 3) - amb_byte_lo + 1), tid);
+        amb_stage = dst;
+    }
     __syncthreads();
     const uint64_t g0 = range.g_begin + (uint64_t)tid * kOneMinPerLane;
     if (g0 < range.g_end) {
@@ -128,6 +155,13 @@ __global__ __launch_bounds__(kOneMinThreads) void one_min_kernel(Lay lay, OneMin
         if constexpr (TEXT) {
             if (staged) one_min_lane(OneMinText{stage, range.g_begin}, lay, range, t, a.k, g0, g1, emit);
             else one_min_lane(OneMinText{a.syms, 0}, lay, range, t, a.k, g0, g1, emit);
+        } else if constexpr (AMB) {
+            // (the staged copies start at bytes byte_lo and amb_byte_lo: symbol i is base a.base0 + i - 4 * byte_lo of the
+            // one, bit a.amb0 + i - 8 * amb_byte_lo of the other)
+            if (staged)
+                one_min_lane(OneMinPackedAmb{OneMinPacked{stage, a.base0 - 4 * byte_lo}, amb_stage, a.amb0 - 8 * amb_byte_lo}, lay,
+                             range, t, a.k, g0, g1, emit);
+            else one_min_lane(OneMinPackedAmb{OneMinPacked{a.syms, a.base0}, a.amb, a.amb0}, lay, range, t, a.k, g0, g1, emit);
         } else {
             // (the staged copy starts at byte byte_lo: symbol i is base a.base0 + i - 4 * byte_lo of it)
             if (staged) one_min_lane(OneMinPacked{stage, a.base0 - 4 * byte_lo}, lay, range, t, a.k, g0, g1, emit);
@@ -162,6 +196,14 @@ __global__ __launch_bounds__(256) void one_min_finish_counts_kernel(const unsign
     if (v.refused && r == 0) error[2] = 8u;
 }
 
+template <class Lay, bool COUNTS>
+void launch_main_amb(const Lay &lay, const OneMinArgs &a, uint32_t blocks, hipStream_t stream) {
+    if (a.canonical)
+        hipLaunchKernelGGL((one_min_kernel<false, Lay, true, COUNTS, true>), dim3(blocks), dim3(kOneMinThreads), 0, stream, lay, a);
+    else
+        hipLaunchKernelGGL((one_min_kernel<false, Lay, false, COUNTS, true>), dim3(blocks), dim3(kOneMinThreads), 0, stream, lay, a);
+}
+
 template <bool TEXT>
 void launch_main_counts(const OneMinStarts &lay, const OneMinArgs &a, uint32_t blocks, hipStream_t stream) {
     if (a.canonical)
@@ -182,6 +224,7 @@ void launch_main(const Lay &lay, const OneMinArgs &a, uint32_t blocks, hipStream
 
 int launch_one_min(const OneMinArgs &a, hipStream_t stream) {
     if (a.n == 0) return 0;
+    if (a.amb && a.text) return -1;  // (byte text has no ambiguity bits)
     const uint64_t finish_blocks = (a.n + 255) / 256;
     if (finish_blocks > 0x7fffffffull) return -3;
     if (hipMemsetAsync(a.keys, 0xff, a.n * sizeof(unsigned long long), stream) != hipSuccess) return -1;
@@ -194,6 +237,7 @@ int launch_one_min(const OneMinArgs &a, hipStream_t stream) {
             const uint64_t tiles = one_min_tiles(a.avail - a.k + 1, kOneMinTile);
             if (tiles > 0x7fffffffull) return -3;
             if (a.text) launch_main_counts<true>(by_starts, a, (uint32_t)tiles, stream);
+            else if (a.amb) launch_main_amb<OneMinStarts, true>(by_starts, a, (uint32_t)tiles, stream);
             else launch_main_counts<false>(by_starts, a, (uint32_t)tiles, stream);
             if (hipGetLastError() != hipSuccess) return -1;
         }
@@ -212,6 +256,8 @@ int launch_one_min(const OneMinArgs &a, hipStream_t stream) {
         if (tiles > 0x7fffffffull) return -3;
         const OneMinStarts by_starts{reinterpret_cast<const uint64_t *>(a.starts)};
         if (a.text) launch_main<true>(by_starts, a, (uint32_t)tiles, stream);
+        else if (a.amb && a.starts) launch_main_amb<OneMinStarts, false>(by_starts, a, (uint32_t)tiles, stream);
+        else if (a.amb) launch_main_amb<OneMinStride, false>(OneMinStride{a.stride, a.len}, a, (uint32_t)tiles, stream);
         else if (a.starts) launch_main<false>(by_starts, a, (uint32_t)tiles, stream);
         else launch_main<false>(OneMinStride{a.stride, a.len}, a, (uint32_t)tiles, stream);
         if (hipGetLastError() != hipSuccess) return -1;

@@ -16,10 +16,14 @@ Rows
      the filled parts - each step waits for the one before.
 a / b says how close the stream is to the link, a / c what the overlap buys.
 
+--one-minimizer adds MM_FASTX_ONE_MINIMIZER to every stream of row a (one minimizer per read delivered with each batch),
+--skip-ambiguous MM_FASTX_SKIP_AMBIGUOUS (the N packer, skipped windows and, with the flag above, clean k-mers only); rows b
+and c are the plain ones either way.
+
 Protocol: an untimed ramp of 200 ms of each measured step, warm-up steps, then the median of the timed steps.
 
   python tools/gpu_fastx_stream_bench.py [--total 4831838208] [--block 67108864] [--steps 3] [--warmup 1]
-         [--chunks 4,16,64,256] [--slots 2,3,4] [--out profiles/fastx_stream_bench.json]
+         [--chunks 4,16,64,256] [--slots 2,3,4] [--one-minimizer] [--skip-ambiguous] [--out profiles/fastx_stream_bench.json]
 """
 from __future__ import annotations
 
@@ -47,6 +51,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--chunks", default="4,16,64,256")
     ap.add_argument("--slots", default="2,3,4")
+    ap.add_argument("--one-minimizer", action="store_true")
+    ap.add_argument("--skip-ambiguous", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -94,10 +100,17 @@ def main():
     batch = sm._FastxBatchC()
     took = C.c_uint64()
 
+    options = {}
+    if args.one_minimizer:
+        options["one_minimizer"] = True
+    if args.skip_ambiguous:
+        options["skip_ambiguous"] = True
+    result["one_minimizer"], result["skip_ambiguous"] = args.one_minimizer, args.skip_ambiguous
+
     def stream_pass(chunk, slots, values, blocks):
         """One stream over `blocks` blocks; returns (seconds, records, positions, last text_end)."""
         st = sm.FastxStream(b, chunk, 2 * chunk // REC + 16, fmt="fastq", values=values, max_positions=chunk // 4 + 4096,
-                            slots=slots)
+                            slots=slots, **options)
         records = positions = end = 0
         t0 = time.perf_counter()
         for _ in range(blocks):
