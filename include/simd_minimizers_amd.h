@@ -1401,6 +1401,33 @@ int mm_debug_launch_lds(uint32_t w, int canonical_windows, int mode, uint64_t n_
  * mm_debug_* family: for tests and tools, no part of the drop-in interface.  In the EXPERIMENTS build of the library the
  * answer follows its switches - MM_NO_KC, MM_JIT_FORCE and a non-zero MM_DEBUG all make it 0. */
 int mm_debug_fixed_k_kernel(uint32_t k, uint32_t w, int canonical_windows);
+/* Diagnostics: what the fused kernel's walk decides at COMPILE time from its window size, for one flavour - window strand,
+ * mode (0 minimizers, 1 / 2 closed / open syncmers), super-k-mer indices, reads mode, the skip-ambiguous walk.  Every window
+ * size up to 128 is a kernel of its own (prebuilt, or compiled at first use), and the kernel source branches on the window size in
+ * these places; the values come from the constexpr functions the kernel itself calls, so the test-suite
+ * can tell which window sizes are the same combination of branches and check that it runs each combination.  Writes
+ * min(capacity, MM_WALK_TRAITS) values to out (may be null with capacity 0) in the order below and returns MM_WALK_TRAITS;
+ * 0 for w == 0 or a mode out of range.  No device needed.  MM_TRAIT_LAST_VIEW_BASES - the bases in the last 16-base view of a
+ * block, plus the strand window's extra base for canonical windows - takes every value from 1 to 17 within one
+ * combination of the others: it names the edge a window size sits at, not a branch. */
+#define MM_TRAIT_WIDE_GROUP_BLOCKS 0 /* blocks that share one wide sequence load (0: 8-byte loads per block) */
+#define MM_TRAIT_WIDE_DWORDS 1       /* dwords of a wide load, 4 or 5 */
+#define MM_TRAIT_V2_LOAD 2           /* the strand window's leaving base has a load stream of its own */
+#define MM_TRAIT_VIEW_WORDS 3        /* 16-base view words per block, ceil(w / 16) */
+#define MM_TRAIT_AMB_VIEW_WORDS 4    /* 32-window words of ambiguity bits per block (1 without them) */
+#define MM_TRAIT_SK_SHIFT 5          /* shift of the packed super-k-mer list entries (0 without indices) */
+#define MM_TRAIT_AMBI_LAND 6         /* the skip-ambiguous look-ahead lands in LDS */
+#define MM_TRAIT_AMBI_ROWS 7         /* ... and the window bits arrive in chunks of rows */
+#define MM_TRAIT_AMB_ROW_DWORDS 8    /* rows of such a chunk (0 without chunks) */
+#define MM_TRAIT_LAZY_VOTE 9         /* the strand vote is resolved only where a window ties */
+#define MM_TRAIT_TABLE_PREFETCH 10   /* steps the hash-table look-ups run ahead */
+#define MM_TRAIT_TWO_BODIES 11       /* partial walks carry a fast and a flag body per block */
+#define MM_TRAIT_ENTRY8 12           /* 8-bit list entries */
+#define MM_TRAIT_ONE_STREAM 13       /* one sequence load stream (always 0 here: k is read at run time) */
+#define MM_TRAIT_LAST_VIEW_BASES 14
+#define MM_WALK_TRAITS 15
+int mm_debug_walk_traits(uint32_t w, int canonical_windows, int mode, int super_kmers, int reads, int ambiguous,
+                         uint32_t *out, int capacity);
 /* Diagnostics of the lane-table launches (round 6).  mm_debug_lane_plan: the lane length and grid the host
  * chooses for n_reads reads of total_bases bases - out6 = {blocks per lane, windows per lane S, entries per lane list, bytes of
  * the lane lists, upper bound of the lanes (a multiple of 256), tiles}; mode as in mm_debug_launch_plan (3: with super-k-mer

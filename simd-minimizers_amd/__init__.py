@@ -189,6 +189,9 @@ def _load_lib():
         L.mm_link_probe.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(C.c_double)]
         L.mm_debug_launch_lds.argtypes = [C.c_uint32, C.c_int, C.c_int, C.c_uint64, u64p]
         L.mm_debug_fixed_k_kernel.argtypes = [C.c_uint32, C.c_uint32, C.c_int]
+        if hasattr(L, "mm_debug_walk_traits"):  # (absent from older libraries loaded through MM_LIB_PATH for A/B runs)
+            L.mm_debug_walk_traits.argtypes = [C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u32p, C.c_int]
+            L.mm_debug_walk_traits.restype = C.c_int
         L.mm_debug_lane_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, u64p]
         L.mm_debug_last_lane_table.argtypes = [vp, u32p, C.c_uint64, u64p]
         L.mm_fused_overread_bytes.argtypes = []
@@ -439,7 +442,26 @@ EXPORTED_SYMBOLS = [
     "mm_one_minimizer_reads_skip_ambiguous_device_async", "mm_one_minimizer_reads_skip_ambiguous_counts_device_async",
     "mm_one_minimizer_reads_skip_ambiguous_host", "mm_debug_one_minimizer_reads_skip_ambiguous",
     "mm_debug_one_minimizer_reads_skip_ambiguous_counts", "mm_fastx_stream_one_minimizer",
+    "mm_debug_walk_traits",
 ]
+
+# the order of mm_debug_walk_traits' values (MM_TRAIT_* of the header)
+WALK_TRAITS = ("wide_group_blocks", "wide_dwords", "v2_load", "view_words", "amb_view_words", "sk_shift", "ambi_land",
+               "ambi_rows", "amb_row_dwords", "lazy_vote", "table_prefetch", "two_bodies", "entry8", "one_stream",
+               "last_view_bases")
+
+
+def walk_traits(w: int, canonical: bool, mode: int = 0, super_kmers: bool = False, reads: bool = False,
+                ambiguous: bool = False) -> dict:
+    """What the fused kernel's walk decides at compile time from its window size, for one flavour (mm_debug_walk_traits;
+    no device): a dict keyed by WALK_TRAITS."""
+    L = lib()
+    n = L.mm_debug_walk_traits(int(w), int(canonical), int(mode), int(super_kmers), int(reads), int(ambiguous), None, 0)
+    if n != len(WALK_TRAITS):
+        raise RuntimeError(f"mm_debug_walk_traits lists {n} values, this package knows {len(WALK_TRAITS)}")
+    buf = (C.c_uint32 * n)()
+    L.mm_debug_walk_traits(int(w), int(canonical), int(mode), int(super_kmers), int(reads), int(ambiguous), buf, n)
+    return dict(zip(WALK_TRAITS, (int(x) for x in buf)))
 
 
 def prebuilt_window_sizes(canonical: bool, reads: bool = False) -> list:

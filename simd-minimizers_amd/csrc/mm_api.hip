@@ -1103,6 +1103,14 @@ int mm_debug_fixed_k_kernel(uint32_t k, uint32_t w, int canonical_windows) {
     return mm::fused_fixed_k(k, w, canonical_windows, canonical_windows) ? 1 : 0;
 }
 
+static_assert(MM_WALK_TRAITS == mm::kWalkTraits, "the header's trait indices and fused_walk_traits list the same fields");
+int mm_debug_walk_traits(uint32_t w, int canonical_windows, int mode, int super_kmers, int reads, int ambiguous, uint32_t *out,
+                         int capacity) {
+    if (w == 0 || mode < 0 || mode > 2) return 0;
+    return mm::fused_walk_traits(w, canonical_windows != 0, (uint32_t)mode, super_kmers != 0, reads != 0, ambiguous != 0, out,
+                                 capacity < 0 ? 0 : capacity);
+}
+
 int mm_debug_launch_plan(uint32_t w, int canonical_windows, int mode, uint64_t n_seqs, const uint64_t *n_windows,
                          uint64_t *out7, uint32_t *tile_seq, uint32_t *tile_win0, uint32_t *tile_nblk, uint64_t tile_capacity,
                          uint64_t *n_tiles) {

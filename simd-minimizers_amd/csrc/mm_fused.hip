@@ -311,6 +311,36 @@ bool fused_fixed_k(uint32_t k, uint32_t w, int canonical_windows, int hasher_can
     return !force_jit_wanted() && find_kc_instance(w, k, canonical_windows, hasher_canonical) != nullptr;
 }
 
+// What lane_walk<W, CANON, ..., MODE, SK, ..., AMBI> decides at compile time from its window size, in the order of the
+// header's MM_TRAIT_* (mm_debug_walk_traits).  Every line calls the function the kernel calls; the flavour gates
+// (AMBI, SK, READS) are the ones at the kernel's use of each.
+int fused_walk_traits(uint32_t w, bool canon, uint32_t mode, bool sk, bool reads, bool ambiguous, uint32_t *out, int capacity) {
+    const int W = (int)w;
+    sk = sk && mode == 0;
+    const int MG = wide_group_blocks(W), NSUB = view_words(W);
+    const bool land = ambiguous && ambi_land_rule(W), rows = ambiguous && ambi_rows_rule(W);
+    const uint32_t t[kWalkTraits] = {
+        (uint32_t)MG,                                     // MM_TRAIT_WIDE_GROUP_BLOCKS
+        (uint32_t)wide_dwords(W),                         // MM_TRAIT_WIDE_DWORDS
+        v2_load_rule(W, canon) ? 1u : 0u,                 // MM_TRAIT_V2_LOAD
+        (uint32_t)NSUB,                                   // MM_TRAIT_VIEW_WORDS
+        ambiguous ? (uint32_t)amb_view_words(W) : 1u,     // MM_TRAIT_AMB_VIEW_WORDS
+        sk ? (uint32_t)sk_shift_rule(W) : 0u,             // MM_TRAIT_SK_SHIFT
+        land ? 1u : 0u,                                   // MM_TRAIT_AMBI_LAND
+        rows ? 1u : 0u,                                   // MM_TRAIT_AMBI_ROWS
+        rows ? amb_row_dwords(W) : 0u,                    // MM_TRAIT_AMB_ROW_DWORDS
+        lazy_vote_rule(W, canon) ? 1u : 0u,               // MM_TRAIT_LAZY_VOTE
+        (uint32_t)table_prefetch_rule(W, canon, MG),      // MM_TRAIT_TABLE_PREFETCH
+        two_bodies_rule(W) ? 1u : 0u,                     // MM_TRAIT_TWO_BODIES
+        !reads && kEntry8Rule(w, canon, sk) ? 1u : 0u,    // MM_TRAIT_ENTRY8
+        !ambiguous && kc_rule(W, 0) ? 1u : 0u,            // MM_TRAIT_ONE_STREAM (k is read at run time: KC = 0)
+        (uint32_t)(view_bases(W, NSUB - 1) + (canon ? 1 : 0)),  // MM_TRAIT_LAST_VIEW_BASES
+    };
+    for (int i = 0; i < kWalkTraits && i < capacity; ++i)
+        if (out) out[i] = t[i];
+    return kWalkTraits;
+}
+
 // lower end of the lane lengths tune_whole_rounds may choose from (blocks per lane)
 static uint32_t whole_rounds_lo(uint32_t nblk) { return nblk * 85u / 100u > 6u ? nblk * 85u / 100u : 6u; }
 

@@ -283,14 +283,45 @@ __device__ __forceinline__ uint32_t select3(uint32_t m, uint32_t a, uint32_t b) 
 // a range, skip-ambiguous runs) carry two bodies per block: the fast exec-masked emit for blocks that
 // qualify, the flag path otherwise.  For larger W that costs registers and with them occupancy of the
 // whole kernel, so only small window sizes get it (the others take the flag path throughout).
+constexpr bool two_bodies_rule(int W) { return W <= 12; }
 template <int W>
-constexpr bool kTwoBodies = W <= 12;
+constexpr bool kTwoBodies = two_bodies_rule(W);
 
 // Super-k-mer runs keep ONE 16-bit list per lane as well: an entry packs the window index i (lane-
 // relative) and the minimizer's offset inside that window, rel = element - i in [1, W], as
 // (i << kSkShift<W>) + rel = element + i * (2^shift - 1); the launcher keeps S << shift <= 65536.
+constexpr int sk_shift_rule(int W) { return W < 2 ? 1 : W < 4 ? 2 : W < 8 ? 3 : W < 16 ? 4 : W < 32 ? 5 : W < 64 ? 6 : W < 128 ? 7 : 8; }
 template <int W>
-constexpr int kSkShift = W < 2 ? 1 : W < 4 ? 2 : W < 8 ? 3 : W < 16 ? 4 : W < 32 ? 5 : W < 64 ? 6 : W < 128 ? 7 : 8;
+constexpr int kSkShift = sk_shift_rule(W);
+
+// The walk's other compile-time choices that depend on the window size, as functions of it: lane_walk calls them, and so
+// does the host (fused_walk_traits in mm_fused.hip, behind mm_debug_walk_traits) - the tests read from there which window
+// sizes are distinct kernels, so that a changed rule shows as a class no test runs.
+constexpr int view_words(int W) { return (W + 15) / 16; }      // NSUB: 16-base view words per W-block
+constexpr int amb_view_words(int W) { return (W + 31) / 32; }  // NSUBA: 32-window words of ambiguity bits per W-block
+// bases of a block in its view word g; the LAST view holds one more for the strand window (see wide_group_blocks_nd)
+constexpr int view_bases(int W, int g) { return W - 16 * g < 16 ? W - 16 * g : 16; }
+// the strand window's leaving base has a load stream of its own only where the hash-out view cannot hold it (lane_walk)
+constexpr bool v2_load_rule(int W, bool canon) { return canon && (W % 16 == 0); }
+#ifndef MM_VOTE_LAZY_MAXW
+#define MM_VOTE_LAZY_MAXW 35
+#endif
+// (see kLazyVote in lane_walk for the why of 36 and 37)
+constexpr bool lazy_vote_rule(int W, bool canon) {
+#ifdef MM_VOTE_EAGER
+    return false;
+#else
+    return canon && (W <= MM_VOTE_LAZY_MAXW || W >= 38);
+#endif
+}
+// steps the hash-table look-ups run ahead of their use (see PF in lane_walk); MG = wide_group_blocks(W)
+constexpr int table_prefetch_rule(int W, bool canon, int MG) {
+#ifdef MM_PF
+    return W < MM_PF ? W : MM_PF;
+#else
+    return (canon && MG != 0 && W < 19) ? 4 : (W < 12 ? W : (canon && W >= 19 ? (W >= 48 ? 1 : 2) : 12));
+#endif
+}
 
 // Wide sequence loads (round 3).  The walk reads its bases through per-lane loads: lanes sit S / 4 bytes apart, so ONE
 // wave-level load costs the CU's vector memory pipeline about one cycle per cache line it touches whatever its width
@@ -311,7 +342,7 @@ constexpr int kSkShift = W < 2 ? 1 : W < 4 ? 2 : W < 8 ? 3 : W < 16 ? 4 : W < 32
 #endif
 constexpr int wide_group_blocks_nd(int W, int nd) {
     if (!MM_WIDE_LOADS || W % 16 == 0) return 0;
-    const int nsub = (W + 15) / 16, valid = 32 * nd - 24;
+    const int nsub = view_words(W), valid = 32 * nd - 24;
     int m = 0;
     for (; m < 8; ++m) {
         bool ok = true;
@@ -322,7 +353,7 @@ constexpr int wide_group_blocks_nd(int W, int nd) {
             // w = 49 and w = 65 - one base in their last view, right at the edge of the valid bits - read a zero there for
             // lanes at the worst alignment, and a tie whose strand count was off by one took the wrong side:
             // tests/test_gpu_round5.py::test_skip_ambiguous_large_windows_landing found it, on the plain walk too.)
-            const int bases = (W - 16 * g < 16 ? W - 16 * g : 16) + (g == nsub - 1 ? 1 : 0);
+            const int bases = view_bases(W, g) + (g == nsub - 1 ? 1 : 0);
             if (low > 24 || off + 6 + 2 * bases > valid) ok = false;
         }
         if (!ok) break;
@@ -364,13 +395,13 @@ constexpr bool kc_rule(int W, int KC) {
     // first base of the lane's load group 0 and pb >= -1 the lane's element 0 (lane_walk): A is smallest at pb = -1, and
     // the warm-up reaches at most one dword (four bytes) in front of the span.
     if ((KC + 2 * W - 1) / 4 - MG * W / 4 < -4) return false;
-    const int nsub = (W + 15) / 16, valid = 32 * ND - 24, span = 2 * MG * W;
+    const int nsub = view_words(W), valid = 32 * ND - 24, span = 2 * MG * W;
     for (int K = 0; K < MG; ++K)
         for (int g = 0; g < nsub; ++g) {
             int off = 2 * W * K + 32 * g - 2 * KC;
             if (off < 0) off += span;
             if (off < 0) return false;
-            const int bases = (W - 16 * g < 16 ? W - 16 * g : 16) + (g == nsub - 1 ? 1 : 0);
+            const int bases = view_bases(W, g) + (g == nsub - 1 ? 1 : 0);
             if (off % 32 > 24 || off + 6 + 2 * bases > valid) return false;
         }
     return true;
@@ -456,7 +487,7 @@ template <int W, bool CANON, bool HASH_RC, int MODE, bool SK, bool DIRECT, bool 
 __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCtx &ctx, bool &overflowed) {
     static_assert(!E8 || !SK, "8-bit list entries hold positions only");
     constexpr uint32_t kStride = list_stride(E8);  // bytes between consecutive entries of the lane's list
-    constexpr int NSUB = (W + 15) / 16;  // 16-base view words per W-block
+    constexpr int NSUB = view_words(W);  // 16-base view words per W-block
     const uint32_t nblk = ctx.nblk;
 
     // Element 0 of a lane is the k-mer one position before its first window (that window is the
@@ -554,7 +585,7 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
     // The base leaving the strand window lags the base leaving the hash by exactly one W-block minus
     // one base, so its view of block b is the hash-out view of block b - 1 moved on by one base: no
     // third load stream unless W is a multiple of 16 (then the last base of the block is missing).
-    constexpr bool kV2Load = CANON && (W % 16 == 0);
+    constexpr bool kV2Load = v2_load_rule(W, CANON);
     auto next_base_view = [&](const uint32_t (&v)[NSUB], int g) -> uint32_t {
         return g + 1 < NSUB ? __builtin_amdgcn_alignbit(v[g + 1 < NSUB ? g + 1 : g], v[g], 2u) : (v[g] >> 2);
     };
@@ -762,17 +793,10 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
 #ifndef MM_VOTE_NO_DEFER
 #define MM_VOTE_NO_DEFER 0  // (1: A/B, the branch of the lazy vote right behind its compare)
 #endif
-#ifdef MM_VOTE_EAGER
-    constexpr bool kLazyVote = false;
-#else
-#ifndef MM_VOTE_LAZY_MAXW
-#define MM_VOTE_LAZY_MAXW 35
-#endif
     // (not for w = 36, 37: those kernels are bounded to 128 registers - four waves per SIMD - and the pending step's
     // two values push them further into scratch: w = 36 1.69 ms against 1.58, w = 37 2.27 against 1.62, where w = 35
-    // still gains 6 %; from w = 38 on the bound is 168 registers)
-    constexpr bool kLazyVote = CANON && (W <= MM_VOTE_LAZY_MAXW || W >= 38);
-#endif
+    // still gains 6 %; from w = 38 on the bound is 168 registers.  -DMM_VOTE_EAGER: A/B, never)
+    constexpr bool kLazyVote = lazy_vote_rule(W, CANON);
     int dn = 0;
     const uint32_t l = k + (uint32_t)W - 1;
     const int thr = (int)(l / 2);
@@ -805,7 +829,7 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
     // skip-ambiguous windows: one bit per window, 32-window views prefetched one block ahead.
     // A skipped window emits nothing and (like the SIMD collector, src/intrinsics/dedup.rs:147-155)
     // never equals its successor, so the first clean window after it always emits.
-    constexpr int NSUBA = AMBI ? (W + 31) / 32 : 1;
+    constexpr int NSUBA = AMBI ? amb_view_words(W) : 1;
     const __amdgpu_buffer_rsrc_t arsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<uint32_t *>(AMBI ? p.wamb : ctx.seq_d), 0, AMBI ? (int)(p.wamb_dwords * 4u) : 0, 0x00020000);
     auto aview = [&](uint32_t bit) -> uint32_t {
@@ -1097,18 +1121,14 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
         // Table look-ups do not depend on the hash state: issue them PF steps ahead so that the
         // LDS latency is off the serial fw/rc chain (the emit below ends a scheduling region at
         // every step, so the compiler cannot hoist them by itself).
-#ifdef MM_PF
-        constexpr int PF = W < MM_PF ? W : MM_PF;
-#else
-        // Canonical walks with w >= 19 look only one or two steps ahead: the registers a deeper look-ahead
+        // (-DMM_PF=n: experiments, n steps ahead everywhere.)  Canonical walks with w >= 19 look only one or two steps ahead: the registers a deeper look-ahead
         // costs are worth more as an extra wave per SIMD, which hides the LDS latency just as well
         // (round 2, 3.1 Gbp, against 12 steps ahead: w = 25 +4 %, 31 +5 %, and together with the tighter
         // register bounds below w = 33 +11 %, 37 +19 %, 51 +18 %; tools/gpu_jit_w.py).  Smaller windows
         // and forward walks are indifferent to it.
         // (canonical walks over small windows: 4 steps ahead since round 3 - the wide loads need the registers, and
         // the depth was measured indifferent there: w = 11 1.786 ms at 11 steps, 1.791 at 4)
-        constexpr int PF = (CANON && MG != 0 && W < 19) ? 4 : (W < 12 ? W : (CANON && W >= 19 ? (W >= 48 ? 1 : 2) : 12));
-#endif
+        constexpr int PF = table_prefetch_rule(W, CANON, MG);
         uint2 tq[W];
         auto lookup = [&](int j) -> uint2 {
             const int jj = j & 15, g = j >> 4, m = jj >> 1;

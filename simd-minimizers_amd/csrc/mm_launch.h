@@ -72,6 +72,11 @@ uint32_t fused_batch_nblk(const RunArgs &a, const uint64_t *n_windows, uint64_t 
 // launch plan of a single-sequence run as the kernel would get it (MM_TAPER_SLOTS set: no device needed); see mm_fused.hip
 int fused_debug_plan(const RunArgs &a, unsigned long long *out /* [7] */);
 void fused_debug_lds(const RunArgs &a, unsigned long long *out2);  // {bytes of the lane lists, bytes of the skip-ambiguous landing area}
+// the compile-time choices of the fused kernel's walk for one flavour and window size, from the kernel's own constexpr
+// rules (mm_fused_impl.h); no device.  Writes up to `capacity` of them in the order of MM_TRAIT_*, returns how many there are.
+constexpr int kWalkTraits = 15;  // (MM_WALK_TRAITS of the header)
+int fused_walk_traits(uint32_t w, bool canonical_windows, uint32_t mode, bool sk, bool reads, bool ambiguous, uint32_t *out,
+                      int capacity);
 // *nblk_out receives the longest lane of the table (RunArgs::nblk of the launch: it sizes the lists).
 bool fused_batch_tiles(const RunArgs &a, const uint64_t *n_windows, uint64_t n_seqs, std::vector<BatchTile> &tiles,
                        uint32_t *nblk_out);

@@ -6,7 +6,22 @@ import os
 import numpy as np
 import pytest
 
+from jit_window_cases import REPS, prepare_ahead, wait
+
 pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _rep_kernels(sm, gpu):
+    """The cases that draw their window size from REPS run kernels that hiprtc compiles at first use, seconds each: the
+    45 of them (per size one strand; minimizers of a sequence with and without super-k-mer indices, and of reads) are
+    prepared by worker processes before the first case (jit_window_cases.prepare_ahead).  Only the time depends on it."""
+    jobs = [(21, w, i % 2 == 1, 0, seq, not seq, seq) for i, w in enumerate(REPS) for seq in (True, False)]
+    pool, futures = prepare_ahead(jobs)
+    try:
+        wait(futures)
+    finally:
+        pool.shutdown(wait=True, cancel_futures=True)
 
 _PREBUILT = {}
 
@@ -20,10 +35,14 @@ def _prebuilt(canonical):
     return _PREBUILT[canonical]
 
 
-def _plan(rng):
+def _plan(rng, jit=False):
+    """`jit`: the window size comes from the class representatives of the sizes WITHOUT a prebuilt kernel
+    (tests/jit_window_cases.py; one case in ten, by the callers' iteration count)."""
     canonical = bool(rng.integers(0, 2))
-    w = int(rng.choice(_prebuilt(canonical)))
+    w = int(rng.choice(REPS if jit else _prebuilt(canonical)))
     mode = int(rng.choice([0, 0, 0, 1, 2]))
+    if jit:  # (the kernels _rep_kernels got ready: the strand of tests/test_gpu_jit_windows.py::test_flavours, minimizers)
+        canonical, mode = REPS.index(w) % 2 == 1, 0
     if mode == 2 and w % 2 == 0:
         mode = 1
     k = int(rng.integers(1, 65))
@@ -48,9 +67,10 @@ def _length(rng, k, w):
 def test_fuzz_device_runs(sm, oracle, gpu, seed):
     import torch
     rng = np.random.default_rng(1000 + seed + int(os.environ.get("MM_FUZZ_OFFSET", "0")))  # other streams on demand
-    tally = dict(cases=0, bases=0, positions=0, range_checks=0, sk=0)
+    tally = dict(cases=0, bases=0, positions=0, range_checks=0, sk=0, jit=0)
     for it in range(150):
-        k, w, canonical, mode = _plan(rng)
+        k, w, canonical, mode = _plan(rng, jit=it % 10 == 7)
+        assert (w in _prebuilt(canonical)) == (it % 10 != 7)
         n = _length(rng, k, w)
         off = int(rng.integers(0, 40))
         shift = int(rng.integers(0, 4))  # pointer misalignment in bytes
@@ -76,6 +96,7 @@ def test_fuzz_device_runs(sm, oracle, gpu, seed):
             assert np.array_equal(out[:c].cpu().numpy().view(np.uint32), want), case
             assert int(out[c].item()) == -7, case  # nothing written past the count
             tally["cases"] += 1
+            tally["jit"] += it % 10 == 7
             tally["bases"] += n
             tally["positions"] += c
             if use_sk:
@@ -93,16 +114,17 @@ def test_fuzz_device_runs(sm, oracle, gpu, seed):
     print("fuzz tally", seed, tally)
     # the loop must have done real work: every case ran, millions of bases, non-trivial outputs
     assert tally["cases"] == 150 and tally["bases"] > 5_000_000 and tally["positions"] > 300_000
-    assert tally["range_checks"] >= 10 and tally["sk"] >= 10
+    assert tally["range_checks"] >= 10 and tally["sk"] >= 10 and tally["jit"] >= 5
 
 
 @pytest.mark.parametrize("seed", [1, 2, 3, 4])
 def test_fuzz_batch_reads_and_ambiguous(sm, oracle, gpu, seed):
     import torch
     rng = np.random.default_rng(2000 + seed + int(os.environ.get("MM_FUZZ_OFFSET", "0")))
-    tally = dict(batches=0, batch_bases=0, reads=0, reads_checked=0, ambiguous=0, ambiguous_bases=0)
+    tally = dict(batches=0, batch_bases=0, reads=0, reads_checked=0, ambiguous=0, ambiguous_bases=0, jit=0)
     for it in range(60):
-        k, w, canonical, mode = _plan(rng)
+        k, w, canonical, mode = _plan(rng, jit=it % 10 == 7)
+        assert (w in _prebuilt(canonical)) == (it % 10 != 7)
         # ---- batch of a few sequences in one buffer
         n_seq = int(rng.integers(1, 7))
         lens = [_length(rng, k, w) for _ in range(n_seq)]
@@ -123,6 +145,7 @@ def test_fuzz_batch_reads_and_ambiguous(sm, oracle, gpu, seed):
             want = oracle.run(data, lens[i], k, w, canonical=canonical, mode=mode, base_offset=int(starts[i]))
             assert np.array_equal(host[offs[i]:offs[i + 1]], want), (case, i)
         tally["batches"] += 1
+        tally["jit"] += it % 10 == 7
         tally["batch_bases"] += sum(lens)
         # ---- reads (minimizer plans) and skip-ambiguous (canonical plans)
         if mode == 0:
@@ -176,4 +199,4 @@ def test_fuzz_batch_reads_and_ambiguous(sm, oracle, gpu, seed):
     print("fuzz tally", seed, tally)
     assert tally["batches"] == 60 and tally["batch_bases"] > 2_000_000
     assert tally["reads_checked"] > 300 and tally["ambiguous"] >= 15 and tally["ambiguous_bases"] > 500_000
-    assert tally.get("long_read_batches", 0) >= 5 and tally.get("lane_table_runs", 0) >= 5
+    assert tally.get("long_read_batches", 0) >= 5 and tally.get("lane_table_runs", 0) >= 5 and tally["jit"] >= 5
