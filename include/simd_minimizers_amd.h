@@ -1401,6 +1401,17 @@ int mm_debug_launch_lds(uint32_t w, int canonical_windows, int mode, uint64_t n_
  * mm_debug_* family: for tests and tools, no part of the drop-in interface.  In the EXPERIMENTS build of the library the
  * answer follows its switches - MM_NO_KC, MM_JIT_FORCE and a non-zero MM_DEBUG all make it 0. */
 int mm_debug_fixed_k_kernel(uint32_t k, uint32_t w, int canonical_windows);
+/* Diagnostics: the strand count of a tied window as the fixed-k canonical walk makes it.  That walk keeps no
+ * running count: where a window's leftmost and rightmost minimum differ it counts the window's T|G bases from the two
+ * byte-aligned sequence buffers it holds in registers, through a compile-time plan of at most three pieces per (kn, jj) - kn the
+ * index of the NEXT block within its load group, jj the step within the block.  This call runs the same plan on the host: it
+ * builds the two buffers as a lane does whose first k-mer begins at base lane_base (-1: the base before the buffer) of the
+ * packed bytes (4 bases per byte, low bits first; bytes past n_bytes read as 0) and counts the window decided at step jj of
+ * block 1 + kn + group * (blocks per load group), i.e. the k + w - 1 bases from lane_base + (kn + group * blocks) * w + jj + 1
+ * on.  Returns a bit mask: 1 - (w, k) walks with one load stream; 2 - ... and counts tied windows by such a plan; 4 - *count
+ * was written (needs bit 2, bytes, count, kn below the blocks per group, jj < w, lane_base >= -1).  No device needed. */
+int mm_debug_kc_count(uint32_t w, uint32_t k, uint32_t kn, uint32_t jj, uint32_t group, const uint8_t *bytes,
+                      uint64_t n_bytes, int64_t lane_base, uint32_t *count);
 /* Diagnostics: what the fused kernel's walk decides at COMPILE time from its window size, for one flavour - window strand,
  * mode (0 minimizers, 1 / 2 closed / open syncmers), super-k-mer indices, reads mode, the skip-ambiguous walk.  Every window
  * size up to 128 is a kernel of its own (prebuilt, or compiled at first use), and the kernel source branches on the window size in

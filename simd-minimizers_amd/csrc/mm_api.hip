@@ -1103,6 +1103,11 @@ int mm_debug_fixed_k_kernel(uint32_t k, uint32_t w, int canonical_windows) {
     return mm::fused_fixed_k(k, w, canonical_windows, canonical_windows) ? 1 : 0;
 }
 
+int mm_debug_kc_count(uint32_t w, uint32_t k, uint32_t kn, uint32_t jj, uint32_t group, const uint8_t *bytes, uint64_t n_bytes,
+                      int64_t lane_base, uint32_t *count) {
+    return mm::fused_kc_count(w, k, kn, jj, group, bytes, n_bytes, lane_base, count);
+}
+
 static_assert(MM_WALK_TRAITS == mm::kWalkTraits, "the header's trait indices and fused_walk_traits list the same fields");
 int mm_debug_walk_traits(uint32_t w, int canonical_windows, int mode, int super_kmers, int reads, int ambiguous, uint32_t *out,
                          int capacity) {

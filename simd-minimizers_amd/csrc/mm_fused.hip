@@ -341,6 +341,69 @@ int fused_walk_traits(uint32_t w, bool canon, uint32_t mode, bool sk, bool reads
     return kWalkTraits;
 }
 
+// mm_debug_kc_count: the strand count of one tied window as the fixed-k canonical walk makes it (kc_count_plan), on the host.
+// The two hash-in buffers are built as lane_walk builds them for a lane whose element 0 begins at base `lane_base` of a tile
+// that starts with the packed bytes (loads of dword-aligned dwords that read 0 past the end, v_alignbyte by the byte part;
+// group 0's earlier buffer as the warm-up fills it, with 0 for the bytes in front of the tile); the window is the one decided at
+// step jj of block b = 1 + kn + MG * group.  Returns 1 (kc_rule) | 2 (kc_count_rule) | 4 (*count written).
+int fused_kc_count(uint32_t w, uint32_t k, uint32_t kn, uint32_t jj, uint32_t group, const uint8_t *bytes, uint64_t n_bytes,
+                   int64_t lane_base, uint32_t *count) {
+    const int W = (int)w, KC = (int)k;
+    if (W < 1 || W > 128 || KC < 1 || KC > 4096) return 0;
+    const int rules = (kc_rule(W, KC) ? 1 : 0) | (kc_count_rule(W, KC) ? 2 : 0);
+    if (!(rules & 2) || !bytes || !count || lane_base < -1 || lane_base > (1ll << 30)) return rules;
+    const KcCountPlan P = kc_count_plan(W, KC, (int)kn, (int)jj);
+    if (!P.ok) return rules;
+    const int MG = wide_group_blocks(W), ND = wide_dwords(W);
+    auto dword = [&](uint64_t i) -> uint32_t {
+        uint32_t v = 0;
+        for (uint64_t j = 0; j < 4; ++j)
+            if (4 * i + j < n_bytes) v |= (uint32_t)bytes[4 * i + j] << (8 * j);
+        return v;
+    };
+    auto alignbyte = [](uint32_t hi, uint32_t lo, uint32_t a) -> uint32_t {
+        return (uint32_t)((((uint64_t)hi << 32) | lo) >> (8u * (a & 3u)));
+    };
+    auto alignbit = [](uint32_t hi, uint32_t lo, uint32_t sh) -> uint32_t {
+        return (uint32_t)((((uint64_t)hi << 32) | lo) >> (sh & 31u));
+    };
+    struct Buf {
+        uint32_t q[5];
+    };
+    const uint32_t pb = (uint32_t)lane_base;                        // (-1: the base before the buffer)
+    const uint32_t gp0 = pb + (uint32_t)KC + 2u * (uint32_t)W;      // first base of load group 0
+    auto group_buf = [&](uint32_t g) -> Buf {                       // wide_load + wide_normalise
+        const uint32_t gpos = gp0 + g * (uint32_t)(MG * W), sh = (gpos << 1) & 30u;
+        uint32_t x[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+        for (int i = 0; i < ND; ++i) x[i] = dword((uint64_t)(gpos >> 4) + (uint64_t)i);
+        Buf b;
+        for (int i = 0; i < 5; ++i) b.q[i] = i < ND ? alignbyte(i + 1 < ND ? x[i + 1] : 0u, x[i], sh >> 3) : 0u;
+        return b;
+    };
+    auto warm_buf = [&]() -> Buf {                                  // block 0's earlier buffer
+        const int32_t A = (int32_t)(gp0 >> 2) - (MG * W) / 4;
+        const bool before = A < 0;
+        const uint64_t d0 = before ? 0u : (uint64_t)(((uint32_t)A & ~3u) >> 2);
+        const uint32_t v[5] = {dword(d0), dword(d0 + 1), dword(d0 + 2), dword(d0 + 3), ND == 5 ? dword(d0 + 4) : 0u};
+        const uint32_t x[6] = {before ? 0u : v[0], before ? v[0] : v[1], before ? v[1] : v[2], before ? v[2] : v[3],
+                               before ? v[3] : v[4], 0u};
+        Buf b;
+        for (int i = 0; i < 5; ++i) b.q[i] = i < ND ? alignbyte(i + 1 < ND ? x[i + 1] : 0u, x[i], (uint32_t)A & 3u) : 0u;
+        return b;
+    };
+    const Buf cur = group_buf(group), prv = group == 0 ? warm_buf() : group_buf(group - 1u);
+    const uint32_t s = (gp0 << 1) & 6u;  // the buffers' common bit part
+    uint32_t c = 0;
+    for (int i = 0; i < P.n; ++i) {
+        const KcCountPiece &pc = P.pc[i];
+        const Buf &src = pc.cur ? cur : prv;
+        const uint32_t v = alignbit(pc.pair + 1 < ND ? src.q[pc.pair + 1] : 0u, src.q[pc.pair], s + (uint32_t)pc.add);
+        c += (uint32_t)__builtin_popcount(v & pc.mask);
+    }
+    *count = c;
+    return rules | 4;
+}
+
 // lower end of the lane lengths tune_whole_rounds may choose from (blocks per lane)
 static uint32_t whole_rounds_lo(uint32_t nblk) { return nblk * 85u / 100u > 6u ? nblk * 85u / 100u : 6u; }
 

@@ -407,10 +407,85 @@ constexpr bool kc_rule(int W, int KC) {
     return true;
 }
 
+// The strand count of a tied window, from the same two buffers (round 11).  The lazy vote needs a window's T|G count only
+// where its two minima differ, one wave-step in a hundred, and a walk with compile-time k holds every base of the window
+// being decided in registers: window i = e - W, decided at step jj of block b, covers the l = KC + W - 1 bases from
+// pb + i + 1 on, and block b + 1's hash-in view (block KN of its load group) begins at base pb + KC + (b + 1) * W, bit
+// s + 2 * W * KN of the current buffer.  So the window begins at bit s + o of the current buffer with
+// o = 2 * W * KN + 2 * (jj + 1 - KC - 2 * W), or - o negative - at s + o + 2 * MG * W of the earlier one.  The plan cuts its
+// 2 * l bits into at most three pieces; a piece is one v_alignbit of a compile-time dword pair of ONE buffer (shift
+// s + add, add <= 24 as for the views), a mask - the T|G bits 2 j + 1 of the piece's own bases, which may begin `skip`
+// bits into the aligned word where the window starts at a bit part above 24 - and a population count.  A piece ends
+// inside the 32 * ND - 24 bits that are valid for every lane.  Such walks keep no running count (no dn, no per-block
+// T|G masks, no strand view).
+struct KcCountPiece {
+    int cur;        // 1: the current hash-in buffer (Wa[0]), 0: the one of the group before (Wr[0])
+    int pair;       // dword pair q[pair], q[pair + 1] of that buffer
+    int add;        // shift of the pair behind the buffer's bit part s
+    uint32_t mask;  // T|G bits of the piece's bases in the aligned word
+};
+struct KcCountPlan {
+    bool ok;
+    int n;
+    KcCountPiece pc[3];
+};
+// (KN: index of block b + 1 within its load group, jj: step within block b)
+constexpr KcCountPlan kc_count_plan(int W, int KC, int KN, int jj) {
+    KcCountPlan P = {false, 0, {{0, 0, 0, 0u}, {0, 0, 0, 0u}, {0, 0, 0, 0u}}};
+    const int MG = wide_group_blocks(W), ND = wide_dwords(W);
+    if (KC <= 0 || MG < 1 || KN < 0 || KN >= MG || jj < 0 || jj >= W) return P;
+    const int span = 2 * MG * W, end = 32 * ND - 24 - 6, bits = 2 * (KC + W - 1);
+    const int o = 2 * W * KN + 2 * (jj + 1 - KC - 2 * W);
+    int t = 0;  // bits of the window the pieces so far cover
+    while (t < bits && P.n < 3) {
+        KcCountPiece best = {0, 0, 0, 0u};
+        int best_take = 0;
+        for (int cur = 1; cur >= 0; --cur) {
+            const int c0 = (cur ? o : o + span) + t;  // where the rest of the window begins in this buffer
+            if (c0 < 0) continue;
+            const int skip = c0 % 32 > 24 ? c0 % 32 - 24 : 0;
+            int take = 32 - skip;
+            if (take > bits - t) take = bits - t;
+            if (take > end - c0) take = end - c0;
+            if (take > best_take) {
+                const uint32_t upto = skip + take >= 32 ? 0xffffffffu : ((1u << (skip + take)) - 1u);
+                best = KcCountPiece{cur, (c0 - skip) / 32, (c0 - skip) % 32, 0xAAAAAAAAu & upto & ~((1u << skip) - 1u)};
+                best_take = take;
+            }
+        }
+        if (best_take <= 0) return P;
+        P.pc[P.n++] = best;
+        t += best_take;
+    }
+    P.ok = t == bits;
+    return P;
+}
+// The walks that count this way: one load stream, the lazy vote, and a plan for every (KN, jj).
+// -DMM_EAGER_COUNT (A/B): none, every lazy walk keeps its per-block count.
+constexpr bool kc_count_rule(int W, int KC) {
+#ifdef MM_EAGER_COUNT
+    return false;
+#endif
+    if (!kc_rule(W, KC) || !lazy_vote_rule(W, true)) return false;
+    for (int KN = 0; KN < wide_group_blocks(W); ++KN)
+        for (int jj = 0; jj < W; ++jj)
+            if (!kc_count_plan(W, KC, KN, jj).ok) return false;
+    return true;
+}
+
 template <int N>
 struct IntTag {
     static constexpr int value = N;
 };
+
+// f(IntTag<i>{}) for the i in [I, N) a run-time value names (a constant after the caller's unrolling, or wave-uniform)
+template <int I, int N, class F>
+__device__ __forceinline__ void static_case(const uint32_t i, F &&f) {
+    if constexpr (I < N) {
+        if (i == (uint32_t)I) f(IntTag<I>{});
+        else static_case<I + 1, N>(i, f);
+    }
+}
 
 template <bool B>
 struct BoolTag {
@@ -539,6 +614,8 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
     const uint32_t rot_l = (32u - p.ht.rot) & 31u;  // alignbit amount for rotl(x, rot)
     const uint32_t rot_r = p.ht.rot & 31u;
     constexpr bool kKC = !AMBI && kc_rule(W, KC);  // (the skip-ambiguous walk keeps its two streams)
+    // ... and, canonical, counts a tied window's strand from that stream's buffers instead of carrying a count (kc_count_rule)
+    constexpr bool kCount = kKC && CANON && kc_count_rule(W, KC);
     const uint32_t k = kKC ? (uint32_t)KC : p.k;
     uint32_t fw = p.ht.fw0, rc = p.ht.rc0;  // (the hasher's constant XOR terms; 0 for NtHasher)
     const uint8_t *tabb = reinterpret_cast<const uint8_t *>(ctx.tab);
@@ -704,7 +781,7 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
         pos_in += W;
         pos_out += W;
         // prefetch block 1 (its strand stream starts at pb + 1: block 0's hash-out view, one base on)
-        if (CANON && !kV2Load) {
+        if (CANON && !kV2Load && !kCount) {
             uint32_t t2[NSUB];
 #pragma unroll
             for (int g = 0; g < NSUB; ++g) t2[g] = next_base_view(vr, g);
@@ -802,7 +879,22 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
     const int thr = (int)(l / 2);
     uint32_t prev;            // key of the predecessor window's k-mer (mode 0)
     uint32_t pos_r2 = pb + 1u;  // window 0 -> 1 drops base pb + 1
-    if (CANON) {
+    if (kCount) {
+        // No count to set up, and window -1's count only decides between two keys that are the same element unless the
+        // window ties: the count - and its loads - only where some walking lane's two minima differ.
+        const uint32_t prev_l = ring_all<W, false>(ring_l), prev_r = ring_all<W, true>(ring_r);
+        prev = prev_l;
+        if (__builtin_expect(__ballot(((prev_l ^ prev_r) & 0xffffu) != 0u) != 0ull, 0)) {
+            uint32_t c = 0;  // window -1 covers bases [pb, pb + l)
+            for (uint32_t g = 0; g * 16u < l; ++g) {
+                uint32_t wd = (g == 0 ? view_first(pb) : view(pb + 16u * g)) & 0xAAAAAAAAu;
+                const uint32_t rem = l - 16u * g;
+                if (rem < 16u) wd &= (1u << (2u * rem)) - 1u;
+                c += __popc(wd);
+            }
+            prev = ((int)c > thr) ? prev_l : prev_r;
+        }
+    } else if (CANON) {
         // window -1 covers bases [pb, pb + l)
         uint32_t c = 0;
 #ifdef MM_EXP_NOWARM
@@ -955,7 +1047,7 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
 #else
                 tgw[g] = (((x ^ y) >> 1) & 0x55555555u) | ((y & ~x) & 0xAAAAAAAAu);
 #endif
-                } else {
+                } else if (!kCount) {
                 // bit 2j+1 of a view word = T|G of base j; only the block's own W bases count
                 const int kCnt = (W - 16 * g) >= 16 ? 16 : (W - 16 * g);  // (constants after unrolling)
                 const uint32_t kBlockMask = 0xAAAAAAAAu & (kCnt >= 16 ? 0xffffffffu : ((1u << (2 * (kCnt > 0 ? kCnt : 0))) - 1u));
@@ -973,7 +1065,7 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
             MM_BUMP(pl_in, W);
             MM_BUMP(pl_out, W);
         }
-        if (CANON && !kV2Load) {  // the next block's strand view, before vr moves on
+        if (CANON && !kV2Load && !kCount) {  // the next block's strand view, before vr moves on
             uint32_t t2[NSUB];
 #pragma unroll
             for (int g = 0; g < NSUB; ++g) t2[g] = next_base_view(vr, g);
@@ -1336,7 +1428,7 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
         // of the block's entering / leaving bases below the step.  The compare's branch is taken ONE STEP LATER, behind
         // the next window's minima (the step's emit waits with it): a branch right behind its compare stalled the wave for
         // the compare's way to the scalar unit, 7 % of the kernel (the kernel without the branch, wrong results: 1.563 ->
-        // 1.451 ms).
+        // 1.451 ms).  kCount walks (round 11) keep no dn, xt, yt: the slow path counts the window itself, see kc_count_plan.
         auto decide = [&](const int jj, const uint32_t sel, const uint32_t selr, unsigned long long differ) -> uint32_t {
             // (Lanes past the end of their range read zeros - poly-A, every hash equal, the two minima different at every
             // step: without this test the last tile of a sequence walked 1.4 x as long as a full one and held up the
@@ -1344,6 +1436,31 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
             if (PARTIAL && !(kTwoBodies<W> && FEK == 1)) {
                 differ &= __ballot((int)(e0 + (uint32_t)jj - (uint32_t)W) < ctx.rem_valid);
                 if (differ == 0ull) return sel;
+            }
+            if constexpr (kCount) {
+                // the window's own count, from the pieces of the two hash-in buffers kc_count_plan names for (kn, jj)
+                uint32_t c = 0;
+                // (block b + 1's index within its group: the tag, or - `kn` has moved on to block b + 2 - the one before `kn`)
+                const uint32_t kn_now = KN >= 0 ? (uint32_t)KN : (kn == 0u ? (uint32_t)(MG ? MG : 1) - 1u : kn - 1u);
+                static_case<0, (MG ? MG : 1)>(kn_now, [&](auto kn_c) {
+                    static_case<0, W>((uint32_t)jj, [&](auto jj_c) {
+                        constexpr int KNc = decltype(kn_c)::value, JJc = decltype(jj_c)::value;
+                        static_assert(kc_count_plan(W, KC, KNc, JJc).ok, "kc_count_rule: a plan for every (kn, jj)");
+                        auto piece = [&](auto i_c) -> uint32_t {
+                            constexpr KcCountPiece pc = kc_count_plan(W, KC, KNc, JJc).pc[decltype(i_c)::value];
+                            // (sh_in is s + 2 * W * kn here and its low five bits count: the shift becomes s + pc.add)
+                            constexpr uint32_t add = (uint32_t)(((pc.add - 2 * W * KNc) % 32 + 32) % 32);
+                            const WideBuf &src = pc.cur ? Wa[0] : Wr[0];
+                            const uint32_t v = __builtin_amdgcn_alignbit(pc.pair + 1 < ND ? src.q[pc.pair + 1 < ND ? pc.pair + 1 : 0] : 0u,
+                                                                         src.q[pc.pair < ND ? pc.pair : 0], sh_in + add);
+                            return (uint32_t)__builtin_popcount(v & pc.mask);
+                        };
+                        c = piece(IntTag<0>{});
+                        if (kc_count_plan(W, KC, KNc, JJc).n > 1) c += piece(IntTag<1>{});
+                        if (kc_count_plan(W, KC, KNc, JJc).n > 2) c += piece(IntTag<2>{});
+                    });
+                });
+                return c <= (uint32_t)thr ? selr : sel;  // rightmost on the reverse strand
             }
             int d = dn;
 #pragma unroll
@@ -1472,7 +1589,7 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
         if (MM_STAGE_GE(3)) {
             ring_turn<W, false>(ring_l);
             if (CANON && MM_STAGE_GE(4)) ring_turn<W, true>(ring_r);
-            if (CANON && kLazyVote && MM_STAGE_GE(4)) {  // the count moves on by the whole block
+            if (CANON && kLazyVote && !kCount && MM_STAGE_GE(4)) {  // the count moves on by the whole block
 #pragma unroll
                 for (int g = 0; g < NSUB; ++g) dn += (int)__builtin_popcount(xt[g]) - (int)__builtin_popcount(yt[g]);
             }

@@ -11,6 +11,10 @@ namespace mm {
 #ifndef MM_NO_KC
 static_assert(kc_rule(11, 21), "k=21 w=11 walks with one load stream");
 static_assert(!kc_rule(51, 31), "k=31 w=51: listed here once the rule admits it");
+#ifndef MM_EAGER_COUNT
+static_assert(kc_count_rule(11, 21), "k=21 w=11 counts a tied window's strand from the hash-in buffers");
+#endif
+static_assert(!kc_count_rule(51, 31) && !kc_count_rule(11, 0), "no count plan without the one load stream");
 #endif
 
 const FusedKcInstance *fused_kc_instances(int *count) {
