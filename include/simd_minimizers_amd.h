@@ -1265,7 +1265,7 @@ int mm_debug_fastx_cut(const uint8_t *text, uint64_t n, int format, int last, ui
  * end inside it ("a record longer than chunk_bytes", as without the flag), for a piece that brings no new base of its record
  * ("cannot advance": a chunk of line ends), for an overlap text longer than chunk_bytes; MM_ERR_LEN_TOO_LARGE for a record
  * that reaches 2^32 bases.  Still out: FASTQ records longer than a chunk, records of 2^32 bases or more, several devices,
- * gzip.  A sequence line that begins with '>' is a header line, as everywhere; a '>' inside a sequence line is a base the
+ * plain (non-BGZF) gzip, CRC32 check.  A sequence line that begins with '>' is a header line, as everywhere; a '>' inside a sequence line is a base the
  * packers map like any other letter, but must not be the first of the l - 1 overlap bytes' line (it would read as a header).
  * Memory: the carry area grows by 16 bytes (2 are used); a packer sees at most 2 * chunk_bytes + 2 bytes. */
 typedef struct mm_fastx_pieces {
@@ -1281,6 +1281,79 @@ int mm_fastx_stream_pieces(const mm_fastx_stream_t *s, mm_fastx_pieces_t *out);
  * first sequence byte, n when there is none), overlap the sequence bytes in text[T, n); open = 0: cut is
  * mm_debug_fastx_cut's and T = overlap = 0. */
 int mm_debug_fastx_split(const uint8_t *text, uint64_t n, uint32_t l, int last, uint64_t out[4]);
+/* ------------------------------------------------------------------ BGZF-compressed input, inflated on the device
+ * BGZF (bgzip, htslib: most .fastq.gz / .fa.gz that pipelines write) is a series of independent gzip members of at most
+ * 64 KiB of text each; every member says its compressed size in its header (extra subfield BC: BSIZE) and its text size in
+ * its trailer (ISIZE).  The host lays out the output from the headers alone, the device inflates the blocks side by side,
+ * one wavefront per block (csrc/mm_bgzf.hip; the decoder, RFC 1951 with stored, fixed and dynamic blocks, is
+ * csrc/mm_inflate.h, the same code on host and device).  The reference reads compressed files through its loader on the
+ * CPU (needletail::parse_fastx_file, bench/src/lib.rs:51-82) and has no other counterpart.
+ * CRC32 IS NOT VERIFIED: a block is accepted when its deflate stream is well formed, ends with its final block's
+ * end-of-block code and gives exactly ISIZE bytes; payload bytes behind the final block are ignored.  Plain gzip (one
+ * serial stream per file) is out of scope and refused by name.
+ *   mm_bgzf_scan_host (no device)  walks the members from data[0]: magic 1f 8b, CM 8, FLG bit 2 (FTEXT may be set, any
+ *     other flag is a bad header), the XLEN subfields for BC with SLEN 2 (not necessarily the first), comp_len = BSIZE + 1
+ *     - XLEN - 20, ISIZE from the trailer (above 65536: MM_ERR_FORMAT).  It stops at the first incomplete block, when
+ *     max_blocks are listed or where *out_bytes would pass max_out_bytes; *consumed = the bytes of the whole blocks taken.
+ *     Blocks with ISIZE 0 (the EOF marker, the seams of concatenated files) are consumed and not listed.  comp_off is the
+ *     payload's offset in data, out_off the running sum of the listed blocks' isize.  A gzip member without a BC subfield
+ *     is MM_ERR_FORMAT with "plain gzip is one serial stream; recompress with bgzip" in mm_last_error(); any other bad
+ *     header is MM_ERR_FORMAT.  MM_ERR_NULL: n_blocks, consumed or out_bytes NULL, data NULL with bytes, blocks NULL with
+ *     max_blocks != 0.
+ *   mm_bgzf_inflate_device_async  queues ONE launch on the workspace's stream: block b's payload d_comp + comp_off
+ *     [comp_len] is inflated to d_out + out_off [isize].  Refused on the host before anything is queued: ws NULL, or with
+ *     n_blocks != 0 d_comp, d_blocks or d_out NULL (MM_ERR_NULL); n_blocks >= 2^31 (MM_ERR_LEN_TOO_LARGE).  The table lives
+ *     in DEVICE memory, so its entries are checked ON THE DEVICE: an entry beyond comp_bytes or out_capacity (or with isize
+ *     above 65536) is not touched, d_status[b] = 100, and mm_workspace_check reports MM_ERR_CAPACITY (kernel error 10).
+ *     A block that does not inflate: d_status[b] = its error (csrc/mm_inflate.h, 1..14), mm_workspace_check reports
+ *     MM_ERR_FORMAT with "BGZF block" in mm_last_error() (kernel error 9); every other block of the launch is inflated
+ *     completely, the failed block's own slot [out_off, out_off + isize) is unspecified and nothing outside it is written.
+ *     A launch with both kinds of failure reports the table's: MM_ERR_CAPACITY (the larger kernel error stays).
+ *     d_status may be NULL.  No byte outside a block's payload is loaded, none outside its slot stored, whatever the bytes
+ *     hold.
+ *   mm_bgzf_inflate_host  scan + upload + kernel + download of a whole BGZF file in host memory: *out_bytes = the text's
+ *     size (also with MM_ERR_CAPACITY, when out_capacity is too small: nothing was inflated); a file that ends inside a
+ *     block is MM_ERR_FORMAT.
+ *   mm_debug_bgzf_inflate (no device)  the decoder on the host: one payload into out[0 .. isize); MM_OK or MM_ERR_FORMAT
+ *     (mm_last_error() names the decoder's error), MM_ERR_NULL.
+ *   mm_fastx_stream_feed_bgzf  serves the unchanged stream handle, DNA and byte text, in place of mm_fastx_stream_feed:
+ *     data is a run of BGZF blocks; whole blocks are gathered into a per-slot page-locked compressed staging buffer
+ *     (chunk_bytes + 64 KiB, with a device twin; allocated by the first call), and a slot launches when the next block's
+ *     ISIZE would pass chunk_bytes, when the staging buffer or the block table (chunk_bytes / 64 + 16 entries, 65536 at
+ *     most) is full - so a chunk carries UP TO chunk_bytes new bytes; the table ends a chunk early only where blocks hold
+ *     fewer than 64 bytes of text on average (bgzip's hold up to 64 KiB), and such a short chunk may then find no cut for a
+ *     record that chunk_bytes would hold: MM_ERR_CAPACITY, "a record longer than chunk_bytes".  The kernel inflates into the slot's text buffer on
+ *     the slot's stream in place of the text upload; everything behind it is unchanged, and so is every flag.
+ *     *consumed stops behind the last whole block taken - before an incomplete block, or when no slot is free (then call
+ *     mm_fastx_stream_next): the caller feeds the rest again, with the bytes that follow it.  mm_fastx_stream_next frees the
+ *     slot of the batch it handed out before even when it answers MM_FASTX_NEED_INPUT, so only a second call in a row that
+ *     takes nothing, with MM_FASTX_NEED_INPUT in between, says that the rest is the front of an incomplete block (the feed
+ *     loops of the Python and C++ mirrors go by this).  mm_fastx_stream_finish after a
+ *     call that ended inside a block is MM_ERR_FORMAT (a truncated file): only a later call that takes a whole block
+ *     clears that, a call without bytes does not.  A block with ISIZE above chunk_bytes is
+ *     MM_ERR_CAPACITY; a bad header or plain gzip MM_ERR_FORMAT as in mm_bgzf_scan_host; a block that does not inflate fails
+ *     the stream with MM_ERR_FORMAT; like every stream error these stay.
+ *     Format and blank bytes in front: while the format is not known (MM_FASTX_AUTO) and while a FASTQ's first '@' has not
+ *     been seen, blocks are inflated on the HOST and their text goes through mm_fastx_stream_feed's own path, so both
+ *     behave exactly as for plain text; later blocks go to the device.  mm_fastx_stream_feed may be called BEFORE the
+ *     first mm_fastx_stream_feed_bgzf (its bytes stand in front); after it, it is refused with MM_ERR_BAD_MODE.
+ *     Offsets (rec_text_pos, text_begin, text_end, first_byte) are offsets in the INFLATED text; BGZF virtual offsets are
+ *     out of scope.  A chunk needs a cut like every chunk: keep chunk_bytes well above 64 KiB + the longest record. */
+typedef struct mm_bgzf_block {
+    uint64_t comp_off;   /* offset of the deflate payload in the compressed bytes */
+    uint32_t comp_len;   /* its size */
+    uint32_t isize;      /* the block's text size, 1 .. 65536 */
+    uint64_t out_off;    /* where the text goes in the output */
+} mm_bgzf_block_t;
+int mm_bgzf_scan_host(const uint8_t *data, uint64_t n_bytes, uint64_t max_blocks, uint64_t max_out_bytes,
+                      mm_bgzf_block_t *blocks, uint64_t *n_blocks, uint64_t *consumed, uint64_t *out_bytes);
+int mm_bgzf_inflate_device_async(mm_workspace_t *ws, const void *d_comp, uint64_t comp_bytes,
+                                 const mm_bgzf_block_t *d_blocks, uint64_t n_blocks, void *d_out, uint64_t out_capacity,
+                                 uint32_t *d_status /* [n_blocks] or NULL */);
+int mm_bgzf_inflate_host(mm_workspace_t *ws, const uint8_t *data, uint64_t n_bytes, uint8_t *out, uint64_t out_capacity,
+                         uint64_t *out_bytes);
+int mm_debug_bgzf_inflate(const uint8_t *payload, uint32_t comp_len, uint8_t *out, uint32_t isize);
+int mm_fastx_stream_feed_bgzf(mm_fastx_stream_t *s, const uint8_t *data, uint64_t n_bytes, uint64_t *consumed);
 /* ------------------------------------------------------------------ several devices from one call
  * The reference's parallel driver is host code: rayon over the contigs, one Builder::run each
  * (bench/src/bin/paper.rs:442-459).  A device group holds one workspace (stream, scratch) per listed device; a

@@ -379,9 +379,12 @@ class Builder {  // src/lib.rs:225-230
     // (const mm_fastx_batch_t &, const uint32_t *one_min) receives the batch's one minimizer per record with it
     // (mm_fastx_stream_one_minimizer: [n_records] words, MM_NO_MINIMIZER for a record without a k-mer - with
     // MM_FASTX_SKIP_AMBIGUOUS without a clean one; nullptr without the flag).
+    // `bgzf`: the source is BGZF-compressed (bgzip, htslib) and goes through mm_fastx_stream_feed_bgzf, inflated on the device:
+    // 1 yes, 0 no, -1 decided by the source's first bytes (1f 8b 08 with FLG bit 2; such input was MM_ERR_FORMAT before).
+    // Plain gzip is refused (MM_ERR_FORMAT).  Offsets in the batches are offsets in the inflated text.
     template <class Reader, class OnBatch>
     void stream_fastx(Reader &&reader, OnBatch &&on_batch, const mm_fastx_stream_config_t &options,
-                      size_t read_bytes = size_t(1) << 22) const {
+                      size_t read_bytes = size_t(1) << 22, int bgzf = -1) const {
         mm_plan_t *plan = nullptr;
         check(mm_plan_create(&plan, k_, w_, CANONICAL, (mm_mode_t)SYNCMER, has_hasher_ ? &hasher_ : nullptr));
         mm_fastx_stream_t *st = nullptr;
@@ -395,7 +398,7 @@ class Builder {  // src/lib.rs:225-230
                 else
                     on_batch(b);
             };
-            r = pump_stream(st, plan, reader, deliver, read_bytes);
+            r = pump_stream(st, plan, reader, deliver, read_bytes, bgzf);
         }
         mm_plan_destroy(plan);
         check(r);
@@ -405,10 +408,10 @@ class Builder {  // src/lib.rs:225-230
     // .text_hasher(..)): `on_batch(const mm_fastx_batch_t &, const mm_fastx_text_extras_t &)` receives every batch with its
     // one minimizer per record (MM_FASTX_TEXT_ONE_MINIMIZER) and the records' bytes (MM_FASTX_TEXT_SEQ); n_bases counts
     // characters, rec_base holds the records' starts.  The reference reads such a file record by record on the CPU
-    // (bench/src/lib.rs:51-82) and runs Builder::run on &[u8] per record (src/lib.rs:378).
+    // (bench/src/lib.rs:51-82) and runs Builder::run on &[u8] per record (src/lib.rs:378).  `bgzf` as stream_fastx takes it.
     template <class Reader, class OnBatch>
     void stream_fasta_text(Reader &&reader, OnBatch &&on_batch, const mm_fastx_text_stream_config_t &options,
-                           size_t read_bytes = size_t(1) << 22) const {
+                           size_t read_bytes = size_t(1) << 22, int bgzf = -1) const {
         mm_plan_t *plan = nullptr;
         check(mm_plan_create_text(&plan, k_, w_, CANONICAL, (mm_mode_t)SYNCMER, has_text_hasher_ ? &text_hasher_ : nullptr));
         mm_fastx_stream_t *st = nullptr;
@@ -419,7 +422,7 @@ class Builder {  // src/lib.rs:225-230
                 check(mm_fastx_text_stream_extras(st, &x));
                 on_batch(b, x);
             };
-            r = pump_stream(st, plan, reader, deliver, read_bytes);
+            r = pump_stream(st, plan, reader, deliver, read_bytes, bgzf);
         }
         mm_plan_destroy(plan);
         check(r);
@@ -553,26 +556,59 @@ class Builder {  // src/lib.rs:225-230
   private:
     // The feed / next loop of both streams; destroys the stream (and, when `deliver` throws, the plan) before it returns.
     template <class Reader, class Deliver>
-    static int pump_stream(mm_fastx_stream_t *st, mm_plan_t *plan, Reader &&reader, Deliver &&deliver, size_t read_bytes) {
+    // `bgzf` (1 / 0 / -1: by the first four bytes): BGZF blocks go through mm_fastx_stream_feed_bgzf, which takes whole blocks;
+    // the front of a block that a read ended in is kept (`held`) and fed again with the bytes that follow.
+    static int pump_stream(mm_fastx_stream_t *st, mm_plan_t *plan, Reader &&reader, Deliver &&deliver, size_t read_bytes, int bgzf = 0) {
         int r = MM_OK;
         std::vector<uint8_t> buf(read_bytes ? read_bytes : 1);
         mm_fastx_batch_t batch;
-        try {
-            for (;;) {
-                const size_t got = reader(buf.data(), buf.size());
-                if (got == 0) break;
-                for (uint64_t done = 0; done < got && r == MM_OK;) {
-                    uint64_t took = 0;
-                    r = mm_fastx_stream_feed(st, buf.data() + done, got - done, &took);
-                    done += took;
-                    if (r == MM_OK && done < got) {
-                        r = mm_fastx_stream_next(st, &batch);
-                        if (r == MM_OK) deliver(batch);
-                        else if (r == MM_FASTX_NEED_INPUT) r = MM_OK;
+        size_t held = 0;
+        // feeds [p, p + n), handing out batches where the stream wants that; returns the bytes taken - all of them, or with
+        // BGZF everything in front of an incomplete block: no byte taken twice in a row although mm_fastx_stream_next, which
+        // frees the slot of the batch handed out before, wanted input in between
+        auto push = [&](const uint8_t *p, size_t n) {
+            size_t done = 0;
+            bool stalled = false;
+            while (done < n && r == MM_OK) {
+                uint64_t took = 0;
+                r = bgzf > 0 ? mm_fastx_stream_feed_bgzf(st, p + done, n - done, &took) : mm_fastx_stream_feed(st, p + done, n - done, &took);
+                done += (size_t)took;
+                if (took) stalled = false;
+                if (r == MM_OK && done < n) {
+                    r = mm_fastx_stream_next(st, &batch);
+                    if (r == MM_OK) {
+                        deliver(batch);
+                    } else if (r == MM_FASTX_NEED_INPUT) {
+                        r = MM_OK;
+                        if (bgzf > 0 && took == 0) {
+                            if (stalled) break;
+                            stalled = true;
+                        }
                     }
                 }
-                if (r != MM_OK) break;
             }
+            return done;
+        };
+        try {
+            for (;;) {
+                if (held == buf.size()) buf.resize(held + (read_bytes > 65536 ? read_bytes : 65536));
+                const size_t got = reader(buf.data() + held, buf.size() - held);
+                if (got == 0) break;
+                const size_t have = held + got;
+                if (bgzf < 0) {
+                    if (have < 4) {
+                        held = have;
+                        continue;
+                    }
+                    bgzf = buf[0] == 0x1f && buf[1] == 0x8b && buf[2] == 8 && (buf[3] & 4) ? 1 : 0;
+                }
+                const size_t done = push(buf.data(), have);
+                if (r != MM_OK) break;
+                held = have - done;
+                if (held) memmove(buf.data(), buf.data() + done, held);
+            }
+            // (a source of fewer than four bytes is text; what is left of a BGZF source is a truncated block, named at finish)
+            if (r == MM_OK && held) push(buf.data(), held);
             if (r == MM_OK) r = mm_fastx_stream_finish(st);
             while (r == MM_OK) {
                 r = mm_fastx_stream_next(st, &batch);

@@ -385,6 +385,12 @@ def _load_lib():
         if hasattr(L, "mm_fastx_stream_pieces"):  # (FASTA records longer than a chunk: MM_FASTX_LONG_RECORDS)
             L.mm_fastx_stream_pieces.argtypes = [vp, vp]
             L.mm_debug_fastx_split.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_int, u64p]
+        if hasattr(L, "mm_bgzf_scan_host"):  # (BGZF-compressed input, inflated on the device)
+            L.mm_bgzf_scan_host.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, vp, u64p, u64p, u64p]
+            L.mm_bgzf_inflate_device_async.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp]
+            L.mm_bgzf_inflate_host.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p]
+            L.mm_debug_bgzf_inflate.argtypes = [vp, C.c_uint32, vp, C.c_uint32]
+            L.mm_fastx_stream_feed_bgzf.argtypes = [vp, vp, C.c_uint64, u64p]
         _lib = L
     return _lib
 
@@ -447,6 +453,8 @@ EXPORTED_SYMBOLS = [
     "mm_one_minimizer_reads_skip_ambiguous_host", "mm_debug_one_minimizer_reads_skip_ambiguous",
     "mm_debug_one_minimizer_reads_skip_ambiguous_counts", "mm_fastx_stream_one_minimizer",
     "mm_debug_walk_traits", "mm_debug_kc_count",
+    "mm_bgzf_scan_host", "mm_bgzf_inflate_device_async", "mm_bgzf_inflate_host", "mm_debug_bgzf_inflate",
+    "mm_fastx_stream_feed_bgzf",
 ]
 
 # the order of mm_debug_walk_traits' values (MM_TRAIT_* of the header)
@@ -2050,6 +2058,17 @@ class FastxStream:
             self._raise(code)
         return int(took.value)
 
+    def feed_bgzf(self, data) -> int:
+        """``feed`` for BGZF-compressed bytes (``mm_fastx_stream_feed_bgzf``): whole blocks are taken, so the return
+        value stops in front of an incomplete block (or where no slot is free: call ``next()``) and the caller feeds the
+        rest again together with the bytes that follow."""
+        buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+        took = C.c_uint64(0)
+        code = lib().mm_fastx_stream_feed_bgzf(self.h, buf.ctypes.data if buf.size else None, buf.size, C.byref(took))
+        if code:
+            self._raise(code)
+        return int(took.value)
+
     def finish(self):
         code = lib().mm_fastx_stream_finish(self.h)
         if code:
@@ -2201,8 +2220,79 @@ def fastx_join(batches):
         yield done(held)
 
 
-def _stream_batches(st, source, read_bytes):
-    """The feed / next loop of ``stream_fastx`` and ``stream_fasta_text`` over an open stream ``st``: numpy COPIES."""
+def is_bgzf(head) -> bool:
+    """Do these first bytes of a file begin a BGZF block (gzip magic ``1f 8b``, deflate, FLG bit 2: an extra field)?"""
+    h = bytes(head[:4])
+    return len(h) == 4 and h[:3] == b"\x1f\x8b\x08" and bool(h[3] & 4)
+
+
+def _check_bgzf(code: int):
+    if code:
+        FastxStream._raise(code)  # (with mm_last_error(): it names the block, or plain gzip)
+
+
+class BgzfBlock(C.Structure):
+    _fields_ = [("comp_off", C.c_uint64), ("comp_len", C.c_uint32), ("isize", C.c_uint32), ("out_off", C.c_uint64)]
+
+
+BGZF_BLOCK_DTYPE = np.dtype([("comp_off", "<u8"), ("comp_len", "<u4"), ("isize", "<u4"), ("out_off", "<u8")])
+
+
+def bgzf_scan(data, max_blocks=None, max_out_bytes=U64_MAX) -> dict:
+    """``mm_bgzf_scan_host`` (no device): the block table of the BGZF bytes ``data`` as a structured array
+    (``BGZF_BLOCK_DTYPE``), ``consumed`` (bytes of whole blocks taken) and ``out_bytes`` (their text's size).
+    ``max_blocks`` None: as many as ``data`` can hold."""
+    buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+    cap = buf.size // 26 + 1 if max_blocks is None else int(max_blocks)
+    blocks = np.zeros(cap, BGZF_BLOCK_DTYPE)
+    n, used, out = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    _check_bgzf(lib().mm_bgzf_scan_host(buf.ctypes.data if buf.size else None, buf.size, cap, int(max_out_bytes),
+                                   blocks.ctypes.data if cap else None, C.byref(n), C.byref(used), C.byref(out)))
+    return {"blocks": blocks[:int(n.value)], "consumed": int(used.value), "out_bytes": int(out.value)}
+
+
+def debug_bgzf_inflate(payload, isize: int) -> bytes:
+    """``mm_debug_bgzf_inflate`` (no device): one BGZF block's deflate payload inflated by the decoder the kernel runs."""
+    buf = np.frombuffer(payload, dtype=np.uint8)
+    out = np.zeros(max(int(isize), 1), np.uint8)
+    _check_bgzf(lib().mm_debug_bgzf_inflate(buf.ctypes.data if buf.size else None, buf.size, out.ctypes.data, int(isize)))
+    return out[:int(isize)].tobytes()
+
+
+def bgzf_inflate_device(d_comp, blocks, d_out, d_status=None, ws=None):
+    """``mm_bgzf_inflate_device_async``: one launch over the table ``blocks`` (a uint8 device tensor holding
+    ``BGZF_BLOCK_DTYPE`` entries, or a host array of them, which is uploaded) - payloads in the uint8 device tensor
+    ``d_comp``, text into the uint8 device tensor ``d_out``, one word per block into the int32 / uint32 tensor
+    ``d_status`` when given.  Queued on the workspace's stream; ``ws.check()`` judges the launch."""
+    import torch
+
+    ws = ws or default_workspace(d_out.device.index or 0)
+    if isinstance(blocks, np.ndarray):
+        host = np.ascontiguousarray(blocks, dtype=BGZF_BLOCK_DTYPE)
+        d_blocks = torch.from_numpy(host.view(np.uint8).copy()).to(d_out.device)
+    else:
+        d_blocks = blocks
+    n = d_blocks.numel() * d_blocks.element_size() // BGZF_BLOCK_DTYPE.itemsize
+    _check_bgzf(lib().mm_bgzf_inflate_device_async(ws.h, _ptr(d_comp), d_comp.numel(), _ptr(d_blocks), n, _ptr(d_out), d_out.numel(),
+                                              _ptr(d_status) if d_status is not None else None))
+    ws._keep_bgzf = (d_comp, d_blocks, d_out, d_status)  # (alive until the queued launch has run)
+    return n
+
+
+def bgzf_inflate_host(data, ws=None, device: int = 0) -> bytes:
+    """``mm_bgzf_inflate_host``: a whole BGZF file in host memory inflated on the device; the text as bytes."""
+    buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+    ws = ws or default_workspace(device)
+    cap = bgzf_scan(buf)["out_bytes"]
+    out = np.zeros(max(cap, 1), np.uint8)
+    n = C.c_uint64(0)
+    _check_bgzf(lib().mm_bgzf_inflate_host(ws.h, buf.ctypes.data if buf.size else None, buf.size, out.ctypes.data, cap, C.byref(n)))
+    return out[:int(n.value)].tobytes()
+
+
+def _stream_batches(st, source, read_bytes, bgzf=None):
+    """The feed / next loop of ``stream_fastx`` and ``stream_fasta_text`` over an open stream ``st``: numpy COPIES.
+    ``bgzf``: the source holds BGZF blocks (None: decided by its first bytes, ``is_bgzf``)."""
     import os
 
     def pieces():
@@ -2222,34 +2312,64 @@ def _stream_batches(st, source, read_bytes):
         else:
             yield from source
 
+    def push(view):
+        """feeds ``view``, yields the batches the stream hands out meanwhile, returns the bytes taken: all of them, or with
+        BGZF everything in front of an incomplete block (no byte taken twice in a row although ``next()``, which frees the
+        slot of the batch handed out before, wanted input in between)"""
+        done, stalled = 0, False
+        while done < len(view):
+            took = st.feed_bgzf(view[done:]) if bgzf else st.feed(view[done:])
+            done += took
+            stalled = stalled and took == 0
+            if done < len(view):
+                b = st.next()
+                if b is not None:
+                    yield b.copy()
+                elif bgzf and took == 0:
+                    if stalled:
+                        break
+                    stalled = True
+        return done
+
     with st:
+        held = b""  # (BGZF: the front of a block whose rest has not been read yet)
         for piece in pieces():
+            if bgzf is None:
+                held += bytes(piece)
+                if len(held) < 4:
+                    continue
+                bgzf = is_bgzf(held)
+                piece, held = held, b""
+            if bgzf:
+                piece = held + bytes(piece)
             view = memoryview(piece)
-            done = 0
-            while done < len(view):
-                done += st.feed(view[done:])
-                if done < len(view):
-                    b = st.next()
-                    if b is not None:
-                        yield b.copy()
+            done = yield from push(view)
+            held = bytes(view[done:])
+        if held:
+            # (a source shorter than 4 bytes is plain text; what is left of a BGZF source is a truncated block, which the
+            # stream names at finish)
+            yield from push(memoryview(held))
         st.finish()
         for b in st:
             yield b.copy()
 
 
 def stream_fastx(builder: "Builder", source, chunk_bytes: int = 64 << 20, max_records: int = 1 << 20, read_bytes: int = 8 << 20,
-                 **options):
+                 bgzf=None, **options):
     """Generator over the batches (``FastxBatch``, numpy COPIES) of a FASTA / FASTQ ``source``: a path, a binary file
     object or an iterable of bytes, of any size.  ``options`` as ``FastxStream`` takes them; ``read_bytes``: how much a
-    path or file object is read at a time."""
-    yield from _stream_batches(FastxStream(builder, chunk_bytes, max_records, **options), source, read_bytes)
+    path or file object is read at a time.  ``bgzf``: the source is BGZF-compressed (bgzip / htslib ``.gz``) and is
+    inflated on the device (``FastxStream.feed_bgzf``); None decides by the source's first bytes (``is_bgzf``), True and
+    False force the choice.  Plain gzip is refused (``MM_ERR_FORMAT``)."""
+    yield from _stream_batches(FastxStream(builder, chunk_bytes, max_records, **options), source, read_bytes, bgzf)
 
 
 def stream_fasta_text(builder: "Builder", source, chunk_bytes: int = 64 << 20, max_records: int = 1 << 20,
-                      read_bytes: int = 8 << 20, **options):
+                      read_bytes: int = 8 << 20, bgzf=None, **options):
     """``stream_fastx`` for a FASTA of byte text (protein): generator over the batches (``FastxBatch`` with ``one_min`` /
-    ``seq``, numpy COPIES) of a ``FastxTextStream`` over ``source``; ``options`` as ``FastxTextStream`` takes them."""
-    yield from _stream_batches(FastxTextStream(builder, chunk_bytes, max_records, **options), source, read_bytes)
+    ``seq``, numpy COPIES) of a ``FastxTextStream`` over ``source``; ``options`` as ``FastxTextStream`` takes them, ``bgzf``
+    as ``stream_fastx`` takes it."""
+    yield from _stream_batches(FastxTextStream(builder, chunk_bytes, max_records, **options), source, read_bytes, bgzf)
 
 
 def run_packed_reads_device(builder: "Builder", records: FastaRecords, out_pos, out_offsets, out_sk=None, max_read_len=None):

@@ -27,6 +27,7 @@
 #include "mm_one_min.h"
 #include "mm_values_reads.h"
 #include "mm_values_text.h"
+#include "mm_bgzf.h"
 
 namespace {
 
@@ -1017,6 +1018,17 @@ int mm_workspace_check(mm_workspace_t *ws) {
     }
     if (code == 8u) {
         g_last_error = kOneMinCountsRefused;
+        return MM_ERR_CAPACITY;
+    }
+    // (kernel errors 9 and 10: mm_bgzf_inflate_device_async, mm_bgzf.h)
+    if (code == mm::kErrBgzfBlock) {
+        g_last_error = "mm_bgzf_inflate_device_async: a BGZF block did not inflate (not deflate, or not ISIZE bytes of it); its "
+                       "output slot is unspecified, every other block of the launch is complete";
+        return MM_ERR_FORMAT;
+    }
+    if (code == mm::kErrBgzfTable) {
+        g_last_error = "mm_bgzf_inflate_device_async: a BGZF block table entry lies beyond comp_bytes or out_capacity (or has "
+                       "isize above 65536); nothing of that block was read or written";
         return MM_ERR_CAPACITY;
     }
     char buf[128];
@@ -5891,4 +5903,8 @@ int api_one_min_reads_plan_counts(const mm_plan_t *plan, mm_workspace_t *ws, con
 }
 hipStream_t api_workspace_stream(mm_workspace_t *ws) { return ws->stream; }
 void api_set_last_error(const char *text) { g_last_error = text; }
+// (mm_bgzf.h)
+uint32_t *api_workspace_error(mm_workspace_t *ws) { return error_word(ws); }
+int api_workspace_device(mm_workspace_t *ws) { return ws->device; }
+void api_workspace_mark_async(mm_workspace_t *ws) { ws->async_unchecked = true; }
 }  // namespace mm

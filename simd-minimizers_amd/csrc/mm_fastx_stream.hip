@@ -31,6 +31,16 @@
 // counts call - with MM_FASTX_SKIP_AMBIGUOUS its skip-ambiguous form over the slot's d_amb - writes one word per record
 // into d_one; the delivered records' words are downloaded with the batch (mm_fastx_stream_one_minimizer).  Still one host
 // wait per chunk.  Refused with MM_FASTX_LONG_RECORDS: a split record's minimizer is not joined across its pieces.
+//
+// BGZF INPUT (mm_fastx_stream_feed_bgzf): only how a slot's new bytes arrive changes.  Whole BGZF blocks are gathered into a
+// page-locked compressed staging buffer of the slot with a block table (payload offset, sizes, where the text goes); at the
+// launch the staging buffer and the table are uploaded in place of the text and the inflate kernel (mm_bgzf.hip, one
+// wavefront per block) writes d_text + A + out_off on the slot's stream, the packer behind it.  A slot's new bytes are
+// host bytes (h_text: what mm_fastx_stream_feed brought, and the stream's first blocks, inflated on the host so that
+// MM_FASTX_AUTO and the blank bytes in front of a text go through the one rule of feed) followed by device-inflated
+// blocks; a chunk carries UP TO chunk_bytes new bytes (the next block would not fit), which launch() and the trim step
+// never took for exactly chunk_bytes.  The workspace's sticky error word comes to the host with the cut, so a block
+// that did not inflate fails the stream with MM_ERR_FORMAT before anything is made of its text.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -39,8 +49,10 @@
 #include <string>
 #include <vector>
 
+#include "mm_bgzf.h"
 #include "mm_fastx_cut.h"
 #include "mm_fastx_stream.h"
+#include "mm_inflate.h"
 
 namespace {
 
@@ -64,6 +76,12 @@ struct Slot {
     uint32_t *h_pos = nullptr, *h_sk = nullptr;
     uint32_t *h_one = nullptr;  // the one-minimizer words ...
     uint8_t *h_seq = nullptr;   // ... and, byte text, the records' bytes (MM_FASTX_TEXT_SEQ)
+    // BGZF input (allocated by the first mm_fastx_stream_feed_bgzf): compressed payloads back to back and their table,
+    // page-locked, and their device twins; n_blk_bytes of the slot's n_new bytes come from the n_blk blocks, behind the
+    // n_new - n_blk_bytes bytes of h_text
+    uint8_t *h_comp = nullptr, *d_comp = nullptr;
+    mm_bgzf_block_t *h_blocks = nullptr, *d_blocks = nullptr;
+    uint64_t n_comp = 0, n_blk = 0, n_blk_bytes = 0;
     hipEvent_t ev_cut = nullptr, ev_run = nullptr, ev_done = nullptr, ev_tail = nullptr;
     bool tail_pending = false;  // the chunk behind this slot's copies its tail out of d_text: ev_tail says when it has
     // the chunk in the slot
@@ -116,6 +134,10 @@ struct mm_fastx_stream {
     std::string line_blanks;  // MM_FASTX_AUTO, before the first non-blank byte: the blank bytes of the line it stands in
     uint64_t skipped = 0;     // blank bytes in front of the text that were not handed to a packer
     bool any_launched = false, finished = false, final_done = false;
+    // BGZF input: feed_bgzf was called (mm_fastx_stream_feed is refused from then on); its last call ended inside a block
+    bool bgzf = false, bgzf_partial = false;
+    uint64_t comp_cap = 0, table_max = 0;
+    std::vector<uint8_t> bgzf_first;  // the text of a block inflated on the host
     int failed = 0;
     std::string fail_text;
 };
@@ -142,6 +164,17 @@ int again(mm_fastx_stream *s) {
         hipError_t e_ = (call);                              \
         if (e_ != hipSuccess) return fail_hip(s, e_, #call); \
     } while (0)
+
+// a slot whose chunk is gone: no new bytes of either kind
+void clear_new(Slot &sl) {
+    sl.n_new = sl.n_comp = sl.n_blk = sl.n_blk_bytes = 0;
+    sl.h_meta[9] = 0;
+}
+// BGZF input: the chunk's inflate raised its error (read behind ev_cut, before anything is made of the chunk's text)
+bool bgzf_failed(const Slot &sl) { return sl.n_blk && (uint32_t)sl.h_meta[9] == mm::kErrBgzfBlock; }
+int fail_bgzf(mm_fastx_stream *s) {
+    return fail(s, MM_ERR_FORMAT, "mm_fastx_stream: a BGZF block did not inflate (not deflate, or not ISIZE bytes of it)");
+}
 
 bool is_blank(uint8_t c) { return c == ' ' || c == '\t' || c == '\r' || c == '\n'; }
 bool can_fill(const Slot &sl) { return sl.state == kFree || sl.state == kFilling; }
@@ -219,11 +252,24 @@ int launch(mm_fastx_stream *s, int last) {
         FX_HIP(hipStreamWaitEvent(sl.stream, sl.ev_tail, 0));
         sl.tail_pending = false;
     }
-    if (sl.n_new) FX_HIP(hipMemcpyAsync(sl.d_text + s->A, sl.h_text, sl.n_new, hipMemcpyHostToDevice, sl.stream));
+    const uint64_t n_host = sl.n_new - sl.n_blk_bytes;
+    if (n_host) FX_HIP(hipMemcpyAsync(sl.d_text + s->A, sl.h_text, n_host, hipMemcpyHostToDevice, sl.stream));
+    if (sl.n_blk) {
+        // BGZF blocks: the compressed bytes and their table in place of the text; the blocks' slots lie behind the host bytes
+        FX_HIP(hipMemcpyAsync(sl.d_comp, sl.h_comp, sl.n_comp, hipMemcpyHostToDevice, sl.stream));
+        FX_HIP(hipMemcpyAsync(sl.d_blocks, sl.h_blocks, sl.n_blk * sizeof(mm_bgzf_block_t), hipMemcpyHostToDevice, sl.stream));
+        uint32_t *const err = mm::api_workspace_error(sl.ws);
+        mm::api_workspace_mark_async(sl.ws);
+        if (mm::launch_bgzf_inflate(sl.d_comp, sl.n_comp, sl.d_blocks, sl.n_blk, sl.d_text + s->A, sl.n_new, nullptr, err, sl.stream))
+            return fail_hip(s, hipGetLastError(), "the BGZF inflate");
+        // (the sticky error word, as the inflate left it: on the host with the cut)
+        FX_HIP(hipMemcpyAsync(sl.h_meta + 9, err + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, sl.stream));
+    }
     uint64_t tail = 0;
     sl.continues = false;
     sl.first_base = sl.first_overlap = sl.rec0_pos = 0;
     if (s->prev >= 0) FX_HIP(hipEventSynchronize(s->slots[s->prev].ev_cut));
+    if (s->prev >= 0 && bgzf_failed(s->slots[s->prev])) return fail_bgzf(s);
     if (s->prev >= 0 && long_fasta(s) && s->slots[s->prev].h_meta[5] && !s->slots[s->prev].h_meta[3]) {
         // the chunk before is a piece of an open record: ">\n", its last l - 1 sequence bytes text[T, n), the new bytes
         Slot &p = s->slots[s->prev];
@@ -280,7 +326,7 @@ int launch(mm_fastx_stream *s, int last) {
     sl.retries = 0;
     if (sl.n_text == 0) {  // (only a last chunk comes here without a byte)
         sl.state = kFree;
-        sl.n_new = 0;
+        clear_new(sl);
         return MM_OK;
     }
     const uint8_t *text = sl.d_text + sl.text_off;
@@ -326,6 +372,7 @@ int collect(mm_fastx_stream *s, Slot &sl, bool block) {
             if (q != hipSuccess) return fail_hip(s, q, "hipEventQuery");
         }
         FX_HIP(hipEventSynchronize(sl.ev_run));
+        if (bgzf_failed(sl)) return fail_bgzf(s);
         const int r = mm_workspace_check(sl.ws);
         if (r == MM_ERR_ORDER && sl.retries < 2) {
             // a look-back timed out: this chunk's run again (the workspace takes its tile ids from a ticket from now on)
@@ -399,10 +446,12 @@ void destroy_slots(mm_fastx_stream *s) {
     }
     for (int i = 0; i < s->n_slots; ++i) {
         Slot &sl = s->slots[i];
-        void *dev[] = {sl.d_text, sl.d_packed, sl.d_amb, sl.d_rec_base, sl.d_rec_pos, sl.d_offsets, sl.d_meta, sl.d_pos, sl.d_sk, sl.d_values, sl.d_one};
+        void *dev[] = {sl.d_text, sl.d_packed, sl.d_amb, sl.d_rec_base, sl.d_rec_pos, sl.d_offsets, sl.d_meta, sl.d_pos, sl.d_sk, sl.d_values, sl.d_one,
+                       sl.d_comp, sl.d_blocks};
         for (void *p : dev)
             if (p) (void)hipFree(p);
-        void *host[] = {sl.h_text, sl.h_meta, sl.h_rec_pos, sl.h_rec_base, sl.h_offsets, sl.h_values, sl.h_pos, sl.h_sk, sl.h_one, sl.h_seq};
+        void *host[] = {sl.h_text, sl.h_meta, sl.h_rec_pos, sl.h_rec_base, sl.h_offsets, sl.h_values, sl.h_pos, sl.h_sk, sl.h_one, sl.h_seq,
+                        sl.h_comp, sl.h_blocks};
         for (void *p : host)
             if (p) (void)hipHostFree(p);
         hipEvent_t ev[] = {sl.ev_cut, sl.ev_run, sl.ev_done, sl.ev_tail};
@@ -496,6 +545,9 @@ int open_stream(mm_fastx_stream_t **out, const mm_plan_t *plan, const mm::ApiPla
     *out = s;
     return MM_OK;
 }
+
+int open_bgzf(mm_fastx_stream *s);
+int feed_text(mm_fastx_stream *s, const uint8_t *text, uint64_t n_bytes, uint64_t *consumed);
 
 }  // namespace
 
@@ -622,8 +674,120 @@ int mm_fastx_stream_feed(mm_fastx_stream_t *s, const uint8_t *text, uint64_t n_b
     if (!s || !consumed || (!text && n_bytes)) return MM_ERR_NULL;
     if (s->failed) return again(s);
     if (s->finished) return fail(s, MM_ERR_BAD_MODE, "mm_fastx_stream_feed: called after mm_fastx_stream_finish");
+    if (s->bgzf) return fail(s, MM_ERR_BAD_MODE, "mm_fastx_stream_feed: called after mm_fastx_stream_feed_bgzf (text behind BGZF blocks)");
     DeviceGuard guard;
     FX_HIP(hipSetDevice(s->cfg.device));
+    return feed_text(s, text, n_bytes, consumed);
+}
+
+int mm_fastx_stream_feed_bgzf(mm_fastx_stream_t *s, const uint8_t *data, uint64_t n_bytes, uint64_t *consumed) {
+    if (consumed) *consumed = 0;
+    if (!s || !consumed || (!data && n_bytes)) return MM_ERR_NULL;
+    if (s->failed) return again(s);
+    if (s->finished) return fail(s, MM_ERR_BAD_MODE, "mm_fastx_stream_feed_bgzf: called after mm_fastx_stream_finish");
+    DeviceGuard guard;
+    FX_HIP(hipSetDevice(s->cfg.device));
+    if (!s->bgzf) {
+        const int r = open_bgzf(s);
+        if (r) return r;
+    }
+    // (bgzf_partial: the bytes fed last end inside a block; only a call that takes a whole block says otherwise, so a call
+    // without bytes in between leaves a truncated file truncated)
+    uint64_t at = 0;
+    while (at < n_bytes) {
+        uint64_t total = 0;
+        uint32_t payload_off = 0, comp_len = 0, isize = 0;
+        const int m = mm::bgzf_member(data + at, n_bytes - at, &total, &payload_off, &comp_len, &isize);
+        if (m > 0) {  // (the rest is the front of a block: the caller feeds it again with what follows)
+            s->bgzf_partial = true;
+            break;
+        }
+        *consumed = at;
+        if (m == -2)
+            return fail(s, MM_ERR_FORMAT, "mm_fastx_stream_feed_bgzf: a gzip member without a BC subfield: plain gzip is one serial stream; "
+                                          "recompress with bgzip");
+        if (m < 0) return fail(s, MM_ERR_FORMAT, "mm_fastx_stream_feed_bgzf: no BGZF block header where one must stand");
+        if (isize > mm::kBgzfMaxIsize) return fail(s, MM_ERR_FORMAT, "mm_fastx_stream_feed_bgzf: ISIZE above 65536");
+        if (isize == 0) {  // (the EOF marker, the seams of concatenated files)
+            at += total;
+            s->bgzf_partial = false;
+            continue;
+        }
+        if (isize > s->C)
+            return fail(s, MM_ERR_CAPACITY, "mm_fastx_stream_feed_bgzf: a BGZF block of " + std::to_string(isize) +
+                                                " bytes of text, more than chunk_bytes = " + std::to_string(s->C));
+        Slot &sl = s->slots[s->fill];
+        if (!can_fill(sl)) break;
+        if (s->format == 0 || (s->format == MM_FASTX_FASTQ && !s->any_launched && sl.n_new == 0)) {
+            // in front of the text (format not known, blank bytes in front of a FASTQ): the block's text through feed's rule.
+            // Nothing has been launched, so every slot is free; held blank bytes of a FASTA header's line can push the end
+            // of the block's text into the slot behind, which is looked at before a byte is taken.
+            if (!can_fill(s->slots[(s->fill + 1) % s->n_slots])) break;
+            if (mm::inflate_payload_host(data + at + payload_off, comp_len, s->bgzf_first.data(), isize)) return fail_bgzf(s);
+            uint64_t took = 0;
+            const int r = feed_text(s, s->bgzf_first.data(), isize, &took);
+            if (r) return r;
+            // (cannot happen: at most chunk_bytes + 64 bytes, and two slots were free)
+            if (took != isize) return fail(s, MM_ERR_BAD_MODE, "mm_fastx_stream_feed_bgzf: the stream's first text did not fit two free slots");
+            at += total;
+            s->bgzf_partial = false;
+            continue;
+        }
+        if (isize > s->C - sl.n_new || comp_len > s->comp_cap - sl.n_comp || sl.n_blk == s->table_max) {
+            // (the slot holds something: a block alone always fits an empty slot)
+            const int r = launch(s, 0);
+            if (r) return r;
+            continue;
+        }
+        memcpy(sl.h_comp + sl.n_comp, data + at + payload_off, comp_len);
+        mm_bgzf_block_t &b = sl.h_blocks[sl.n_blk++];
+        b.comp_off = sl.n_comp, b.comp_len = comp_len, b.isize = isize, b.out_off = sl.n_new;
+        sl.n_comp += comp_len;
+        sl.n_new += isize;
+        sl.n_blk_bytes += isize;
+        sl.state = kFilling;
+        at += total;
+        s->bgzf_partial = false;
+        if (sl.n_new == s->C) {
+            const int r = launch(s, 0);
+            if (r) {
+                *consumed = at;
+                return r;
+            }
+        }
+    }
+    *consumed = at;
+    return s->in_flight ? collect_all(s) : (int)MM_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// BGZF input, first use: the slots' compressed staging buffers (chunk_bytes + 64 KiB: a block's payload is below 64 KiB,
+// so a block alone always fits) and block tables
+int open_bgzf(mm_fastx_stream *s) {
+    s->comp_cap = s->C + 65536;
+    s->table_max = s->C / 64 + 16 < 65536 ? s->C / 64 + 16 : 65536;
+    s->bgzf_first.resize(mm::kBgzfMaxIsize);
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < s->n_slots && e == hipSuccess; ++i) {
+        Slot &sl = s->slots[i];
+        e = host_alloc(sl.h_comp, s->comp_cap);
+        if (e == hipSuccess) e = dev_alloc(sl.d_comp, s->comp_cap);
+        if (e == hipSuccess) e = host_alloc(sl.h_blocks, s->table_max * sizeof(mm_bgzf_block_t));
+        if (e == hipSuccess) e = dev_alloc(sl.d_blocks, s->table_max * sizeof(mm_bgzf_block_t));
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(s, e == hipErrorOutOfMemory ? MM_ERR_ALLOC : MM_ERR_HIP, std::string("mm_fastx_stream_feed_bgzf: ") + hipGetErrorString(e));
+    }
+    s->bgzf = true;
+    return MM_OK;
+}
+
+// what mm_fastx_stream_feed does behind its refusals (mm_fastx_stream_feed_bgzf: the text of the stream's first blocks)
+int feed_text(mm_fastx_stream *s, const uint8_t *text, uint64_t n_bytes, uint64_t *consumed) {
     uint64_t taken = 0;
     // in front of the text: FASTQ has to start with its first '@' (a line's role is the number of newlines in front of it),
     // so blank bytes are passed over and counted; FASTA keeps every byte (what stands in front of a '>' decides about it)
@@ -677,9 +841,15 @@ int mm_fastx_stream_feed(mm_fastx_stream_t *s, const uint8_t *text, uint64_t n_b
     return s->in_flight ? collect_all(s) : (int)MM_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
 int mm_fastx_stream_finish(mm_fastx_stream_t *s) {
     if (!s) return MM_ERR_NULL;
     if (s->failed) return again(s);
+    if (s->bgzf_partial)
+        return fail(s, MM_ERR_FORMAT, "mm_fastx_stream_finish: the last mm_fastx_stream_feed_bgzf ended inside a BGZF block (a truncated file)");
     DeviceGuard guard;
     FX_HIP(hipSetDevice(s->cfg.device));
     s->finished = true;
@@ -695,7 +865,7 @@ int mm_fastx_stream_next(mm_fastx_stream_t *s, mm_fastx_batch_t *out) {
     if (s->delivered >= 0) {  // the batch handed out by the last call: its slot is free again
         Slot &d = s->slots[s->delivered];
         d.state = kFree;
-        d.n_new = 0;
+        clear_new(d);
         s->delivered = -1;
     }
     int r = launch_final(s);
