@@ -1485,6 +1485,13 @@ int mm_debug_fixed_k_kernel(uint32_t k, uint32_t w, int canonical_windows);
  * was written (needs bit 2, bytes, count, kn below the blocks per group, jj < w, lane_base >= -1).  No device needed. */
 int mm_debug_kc_count(uint32_t w, uint32_t k, uint32_t kn, uint32_t jj, uint32_t group, const uint8_t *bytes,
                       uint64_t n_bytes, int64_t lane_base, uint32_t *count);
+/* Diagnostics: the pair table of the fixed-k canonical walk (k=21 w=11), made on the host by the function the
+ * kernel's threads run.  That walk looks its rolling-hash contributions up two bases at a time: entry i = in4 | out4 << 4 -
+ * in4 / out4 the 2-bit codes of two consecutive bases entering / leaving the hash, first base in the low bits - is
+ * out[4 i .. 4 i + 3] = {t1.fw, t1.rc, rotl(t1.fw, rot) ^ t2.fw, rotr(t1.rc, rot) ^ t2.rc} with t1 / t2 the one-base
+ * contributions (in ^ out terms) of the first / second base pair, for the hasher's tables at k = 21.  Two one-base steps
+ * from any state equal the pair step; the CPU test-suite checks that.  MM_ERR_NULL for a null argument.  No device needed. */
+int mm_debug_pair_table(const mm_hasher_t *h, uint32_t out[1024]);
 /* Diagnostics: what the fused kernel's walk decides at COMPILE time from its window size, for one flavour - window strand,
  * mode (0 minimizers, 1 / 2 closed / open syncmers), super-k-mer indices, reads mode, the skip-ambiguous walk.  Every window
  * size up to 128 is a kernel of its own (prebuilt, or compiled at first use), and the kernel source branches on the window size in

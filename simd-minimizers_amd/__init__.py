@@ -193,6 +193,9 @@ def _load_lib():
             L.mm_debug_kc_count.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u8p, C.c_uint64,
                                             C.c_int64, u32p]
             L.mm_debug_kc_count.restype = C.c_int
+        if hasattr(L, "mm_debug_pair_table"):  # (absent from older libraries loaded through MM_LIB_PATH for A/B runs)
+            L.mm_debug_pair_table.argtypes = [C.POINTER(Hasher), u32p]
+            L.mm_debug_pair_table.restype = C.c_int
         if hasattr(L, "mm_debug_walk_traits"):  # (absent from older libraries loaded through MM_LIB_PATH for A/B runs)
             L.mm_debug_walk_traits.argtypes = [C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u32p, C.c_int]
             L.mm_debug_walk_traits.restype = C.c_int
@@ -452,7 +455,7 @@ EXPORTED_SYMBOLS = [
     "mm_one_minimizer_reads_skip_ambiguous_device_async", "mm_one_minimizer_reads_skip_ambiguous_counts_device_async",
     "mm_one_minimizer_reads_skip_ambiguous_host", "mm_debug_one_minimizer_reads_skip_ambiguous",
     "mm_debug_one_minimizer_reads_skip_ambiguous_counts", "mm_fastx_stream_one_minimizer",
-    "mm_debug_walk_traits", "mm_debug_kc_count",
+    "mm_debug_walk_traits", "mm_debug_kc_count", "mm_debug_pair_table",
     "mm_bgzf_scan_host", "mm_bgzf_inflate_device_async", "mm_bgzf_inflate_host", "mm_debug_bgzf_inflate",
     "mm_fastx_stream_feed_bgzf",
 ]

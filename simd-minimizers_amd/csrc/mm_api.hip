@@ -1120,6 +1120,12 @@ int mm_debug_kc_count(uint32_t w, uint32_t k, uint32_t kn, uint32_t jj, uint32_t
     return mm::fused_kc_count(w, k, kn, jj, group, bytes, n_bytes, lane_base, count);
 }
 
+int mm_debug_pair_table(const mm_hasher_t *h, uint32_t out[1024]) {
+    if (!h || !out) return MM_ERR_NULL;
+    mm::fused_pair_table(make_tables(*h, 21), out);  // (k = 21: the k of the instance that walks with the table)
+    return MM_OK;
+}
+
 static_assert(MM_WALK_TRAITS == mm::kWalkTraits, "the header's trait indices and fused_walk_traits list the same fields");
 int mm_debug_walk_traits(uint32_t w, int canonical_windows, int mode, int super_kmers, int reads, int ambiguous, uint32_t *out,
                          int capacity) {

@@ -73,6 +73,22 @@ const FusedKcInstance *find_kc_instance(uint32_t w, uint32_t k, int canonical_wi
     return nullptr;
 }
 
+// Does a launch of this flavour take a fixed-k instance?  resolve_kernel's first choice and geometry()'s question (the
+// instance's static LDS bounds the lanes): one predicate, so that the two cannot disagree.
+const FusedKcInstance *launch_kc_instance(uint32_t w, int canonical_windows, int hasher_canonical, uint32_t mode, bool sk,
+                                          uint32_t k) {
+    if (k == 0 || mode != 0 || sk || force_jit_wanted()) return nullptr;
+    return find_kc_instance(w, k, canonical_windows, hasher_canonical);
+}
+
+// Static LDS a launch's kernel holds on top of the hash tables and counters (which every budget below allows 512 bytes
+// for): the pair table of the instance pair_lookup_rule names, 4 KB; 0 for every other kernel.  The table belongs to the
+// KERNEL, so every launch that resolves to it - plain, window range, batch, with ambiguity bits - pays for it.
+uint32_t extra_static_lds(uint32_t w, int canonical_windows, int hasher_canonical, uint32_t mode, bool sk, uint32_t k) {
+    if (!launch_kc_instance(w, canonical_windows, hasher_canonical, mode, sk, k)) return 0u;
+    return pair_lookup_rule((int)w, canonical_windows != 0, (int)k, (int)mode, sk, false, false) ? kPairTableBytes : 0u;
+}
+
 double emit_density(uint32_t w, uint32_t mode) {
     return mode == 2 ? 1.0 / w : (mode == 1 ? 2.0 / w : 2.0 / (w + 1.0));
 }
@@ -153,6 +169,10 @@ constexpr uint32_t kMaxLdsBytes = 159u * 1024u;  // 160 KB per CU minus the stat
 // S + w <= 255 so that every element index of a lane fits a byte
 bool entry8(const RunArgs &a) { return kEntry8Rule(a.w, a.canonical_windows != 0, a.out.sk != nullptr && a.mode == 0); }
 uint32_t stride_of(const RunArgs &a) { return list_stride(entry8(a)); }
+uint32_t extra_static_lds_of(const RunArgs &a) {
+    return extra_static_lds(a.w, a.canonical_windows, (int)a.ht.canonical, a.mode, a.out.sk != nullptr, a.k);
+}
+constexpr uint32_t kPairWorkgroupLds = 160u * 1024u / 4u;  // a workgroup's share of a CU that holds four (128 registers)
 
 Geometry geometry(const RunArgs &a) {
     Geometry g;
@@ -190,6 +210,15 @@ Geometry geometry(const RunArgs &a) {
         const uint32_t per_cu = a.w <= 37u ? 4u : 3u;  // (the register bounds of the canonical walks, MM_MIN_BLOCKS)
         const uint32_t room = (160u * 1024u / per_cu / 1280u) * 1280u - 512u - ambi_land_bytes((int)a.w);
         while (g.nblk > 6u && list_capacity(a.w, a.mode, a.w * g.nblk) * stride_of(a) > room) --g.nblk;
+    }
+    // A kernel with the pair table (pair_lookup_rule: canonical k=21 w=11) holds 4 KB more static LDS, and four workgroups
+    // share a CU's 160 KB only at 40 960 bytes each: default lanes as long as lists + tables + pair table allow.  w = 11: 26
+    // blocks (69 entries) instead of 28 (74); three workgroups per CU would cost far more than the pair look-ups gain.
+    if (a.nblk == 0) {
+        if (const uint32_t st = extra_static_lds_of(a)) {
+            const uint32_t room = kPairWorkgroupLds - 512u - st - ambi_landing(a.w, a.wamb);
+            while (g.nblk > 6u && list_capacity(a.w, a.mode, a.w * g.nblk) * stride_of(a) > room) --g.nblk;
+        }
     }
     // super-k-mer runs pack (window << shift) + offset-in-window into the 16-bit list entry
     // (kSkShift in mm_fused_impl.h): the lane length is bounded by S << shift <= 65536
@@ -236,11 +265,9 @@ KernelRef resolve_kernel(uint32_t w, int canonical_windows, int hasher_canonical
     if (how) *how = kJitHit;
     if (mode > 2) return kr;
     const bool force_jit = force_jit_wanted();  // tuning experiments (experiments build only)
-    if (k != 0 && mode == 0 && !sk && !force_jit) {
-        if (const FusedKcInstance *kc = find_kc_instance(w, k, canonical_windows, hasher_canonical)) {
-            kr.host = kc->fn;
-            return kr;
-        }
+    if (const FusedKcInstance *kc = launch_kc_instance(w, canonical_windows, hasher_canonical, mode, sk, k)) {
+        kr.host = kc->fn;
+        return kr;
     }
     const Instance *inst = force_jit ? nullptr : find_instance(w, canonical_windows, hasher_canonical);
     if (inst) {
@@ -404,6 +431,17 @@ int fused_kc_count(uint32_t w, uint32_t k, uint32_t kn, uint32_t jj, uint32_t gr
     return rules | 4;
 }
 
+// mm_debug_pair_table: the 256 entries of the pair table (pair_lookup_rule) as the kernel's threads make them, on the host
+void fused_pair_table(const HashTables &ht, uint32_t *out1024) {
+    for (uint32_t i = 0; i < kPairEntries; ++i) {
+        const uint4 e = pair_entry(ht, i);
+        out1024[4 * i + 0] = e.x;
+        out1024[4 * i + 1] = e.y;
+        out1024[4 * i + 2] = e.z;
+        out1024[4 * i + 3] = e.w;
+    }
+}
+
 // lower end of the lane lengths tune_whole_rounds may choose from (blocks per lane)
 static uint32_t whole_rounds_lo(uint32_t nblk) { return nblk * 85u / 100u > 6u ? nblk * 85u / 100u : 6u; }
 
@@ -511,7 +549,8 @@ static uint32_t whole_rounds_nblk(const RunArgs &a, const KernelRef &kr, const G
     const double kOverheadBlocks = 2.4;  // warm-up, look-back and copy-out of a tile, in W-blocks of walking
     if ((double)g.nblocks / slots >= 24.0 || (double)g.nblocks / slots <= 1.0) return g.nblk;
     const uint32_t lds_share = (kMaxLdsBytes - (uint32_t)per_cu * 512u) / (uint32_t)per_cu;
-    const uint32_t lds_limit = lds_share > land ? lds_share - land : 0u;
+    const uint32_t beside = land + extra_static_lds_of(a);  // (what shares the workgroup's LDS with the lists)
+    const uint32_t lds_limit = lds_share > beside ? lds_share - beside : 0u;
     uint32_t sh = 0;
     if (a.out.sk && a.mode == 0)
         for (sh = 1; (1u << sh) <= a.w;) ++sh;

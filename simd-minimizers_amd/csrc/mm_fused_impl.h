@@ -7,7 +7,8 @@
 //            bounds-checked raw buffer loads (two funnel-shifted 16-base views per W-block: base
 //            entering the hash, base leaving the hash; the base leaving the strand window comes
 //            from the previous block's hash-out view), issued two W-blocks ahead.  Rolling ntHash costs ONE LDS table look-up per base
-//            (s_tab[(out<<2)|in], 16 x uint2 = forward / reverse-complement contribution);
+//            (s_tab[(out<<2)|in], 16 x uint2 = forward / reverse-complement contribution; one per TWO bases from a
+//            256-entry table in the fixed-k canonical walk, see pair_lookup_rule);
 //            keys are (hash_hi16 | pos16) for the leftmost minimum and the complemented key for
 //            the rightmost one; the two-stacks sliding minimum runs over blocks of W with the
 //            ring held in W registers (W is a template parameter; suffix minima kept at every second
@@ -473,6 +474,41 @@ constexpr bool kc_count_rule(int W, int KC) {
     return true;
 }
 
+// Pair look-ups (round 12): the hash-table look-up of TWO consecutive steps in one LDS instruction.  The 16-entry table is
+// indexed by one base of each stream, so every step makes an LDS address of its own (a shift and an AND) and issues a read
+// of its own; a table indexed by the bases of two steps - s_pair[in4 | out4 << 4], in4 = in(j) | in(j + 1) << 2 four
+// consecutive bits of the hash-in view, out4 the same of the hash-out view - needs one address and one read per two steps.
+// Its entry holds the first step's contribution t1 and the two steps' folded one:
+//   fw1 = rotl(fw0, rot)     ^ t1.x                      rc1 = rotr(rc0, rot)     ^ t1.y
+//   fw2 = rotl(fw0, 2 * rot) ^ (rotl(t1.x, rot) ^ t2.x)  rc2 = rotr(rc0, 2 * rot) ^ (rotr(t1.y, rot) ^ t2.y)
+// so a step still costs one v_alignbit and one v_xor per strand, and the odd step no longer waits for the even one.
+// 256 entries of 16 bytes: 4 KB of static LDS per workgroup, which the launcher's lane length has to leave room for
+// (geometry() in mm_fused.hip).  The fixed-k canonical positions-only walk of sequence mode only; odd W only: a block of odd
+// W is (W - 1) / 2 pairs and one single base, which reads the first 8 bytes (t1) of the entry its base starts - t1 depends
+// on the pair's first base alone, and the view's next base is valid data of the next block.  An even W would need nothing
+// else inside a block (W / 2 pairs, no single base) but has no fixed-k instance to measure it on, so it keeps the one-base
+// look-ups.  -DMM_NO_PAIR (A/B): no walk takes this form.
+constexpr bool pair_lookup_rule(int W, bool CANON, int KC, int MODE, bool SK, bool READS, bool AMBI) {
+#ifdef MM_NO_PAIR
+    return false;
+#endif
+    return CANON && MODE == 0 && !SK && !READS && !AMBI && (W & 1) == 1 && kc_rule(W, KC);
+}
+constexpr uint32_t kPairEntries = 256u;
+constexpr uint32_t kPairTableBytes = kPairEntries * 16u;
+// entry `idx` of the pair table (the kernel's 256 threads make one each; the host runs it behind mm_debug_pair_table)
+__host__ __device__ inline uint4 pair_entry(const HashTables &ht, const uint32_t idx) {
+    const uint32_t in4 = idx & 15u, out4 = (idx >> 4) & 15u;
+    const uint2 t1 = ht.t_in_out[((out4 & 3u) << 2) | (in4 & 3u)], t2 = ht.t_in_out[(out4 & 12u) | (in4 >> 2)];
+    const uint32_t r = ht.rot & 31u;
+    uint4 e;
+    e.x = t1.x;
+    e.y = t1.y;
+    e.z = (r ? (t1.x << r) | (t1.x >> (32u - r)) : t1.x) ^ t2.x;
+    e.w = (r ? (t1.y >> r) | (t1.y << (32u - r)) : t1.y) ^ t2.y;
+    return e;
+}
+
 template <int N>
 struct IntTag {
     static constexpr int value = N;
@@ -510,6 +546,7 @@ struct LaneCtx {
     const uint32_t *seq_d;   // the sequence the tile reads (p.seq, or the batch entry)
     uint32_t seq_dwords;
     uint32_t land;           // LDS byte address of this WAVE's landing area (kAmbiLand walks), 0 = none (wave-uniform)
+    const uint4 *pair;       // LDS pair table (walks under pair_lookup_rule; not set otherwise)
 };
 
 // Skip-ambiguous walks over large windows (round 5).  The walk that knows skipped windows carries its
@@ -657,6 +694,11 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
     uint32_t m33, m55;
     asm volatile("v_mov_b32 %0, 0x33333333" : "=v"(m33));
     asm volatile("v_mov_b32 %0, 0x55555555" : "=v"(m55));
+    // pair look-ups (pair_lookup_rule): the blocks' table look-ups two steps at a time; lane_walk is never a reads walk
+    // with KC > 0 (fused_kernel passes KC to the walks of sequence mode only)
+    constexpr bool kPair = pair_lookup_rule(W, CANON, KC, MODE, SK, false, AMBI);
+    uint32_t m0f = 0;  // mask of the byte-pitch merges below
+    if constexpr (kPair) asm volatile("v_mov_b32 %0, 0x0f0f0f0f" : "=v"(m0f));
 
     uint32_t va[NSUB], vr[NSUB], v2[NSUB];  // views of the block being processed
     // The base leaving the strand window lags the base leaving the hash by exactly one W-block minus
@@ -1029,6 +1071,12 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
         uint32_t xt[NSUB], yt[NSUB];  // lazy strand vote (below): T|G bits of the block's entering / leaving bases
 #pragma unroll
         for (int g = 0; g < NSUB; ++g) {
+            if constexpr (kPair) {
+                // byte-pitch merges: byte i of me holds the pair table's index (in4 | out4 << 4) of bases 4 i, 4 i + 1 of the
+                // view - pairs (0,1), (4,5), (8,9), (12,13) - and byte i of mo that of bases 4 i + 2, 4 i + 3
+                me[g] = select3(m0f, va[g], vr[g] << 4);
+                mo[g] = select3(m0f, va[g] >> 4, vr[g]);
+            } else {
 #if !defined(MM_VGPR_MASKS) || MM_VGPR_MASKS
             me[g] = select3(m33, va[g], vr[g] << 2);
             mo[g] = select3(m33, va[g] >> 2, vr[g]);
@@ -1036,6 +1084,7 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
             me[g] = (va[g] & 0x33333333u) | ((vr[g] << 2) & 0xccccccccu);
             mo[g] = ((va[g] >> 2) & 0x33333333u) | (vr[g] & 0xccccccccu);
 #endif
+            }
             if (CANON) {
                 const uint32_t x = va[g], y = v2[g];
                 if (!kLazyVote) {
@@ -1229,8 +1278,27 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
             if (!MM_STAGE_GE(2)) return uint2{a8, a8};
             return *reinterpret_cast<const uint2 *>(tabb + a8);
         };
+        // kPair: the look-up of steps 2 q and 2 q + 1 of the block, entry (byte of the merge word) << 4 of the pair table; the
+        // single last base of an odd W takes the entry's first 8 bytes (t1).  Still PF steps ahead, counted in steps: pair q
+        // is asked for at step 2 q - PF.
+        static_assert(!kPair || (PF % 2 == 0 && PF >= 2 && PF <= W), "pair look-ups are issued at even steps");
+        uint4 tqp[(W + 1) / 2];
+        auto lookup_pair = [&](int q) -> uint4 {
+            const int g = q >> 3, qq = q & 7, byte = qq >> 1;
+            const uint32_t mw = (qq & 1) ? mo[g] : me[g];
+            const uint32_t a16 = ((mw >> (8 * byte)) & 0xffu) << 4;
+            const uint8_t *pairb = reinterpret_cast<const uint8_t *>(ctx.pair);
+            if (2 * q + 1 < W) return *reinterpret_cast<const uint4 *>(pairb + a16);
+            const uint2 t1 = *reinterpret_cast<const uint2 *>(pairb + a16);
+            return uint4{t1.x, t1.y, 0u, 0u};
+        };
+        if constexpr (kPair) {
+#pragma unroll
+            for (int q = 0; 2 * q < PF; ++q) tqp[q] = lookup_pair(q);
+        } else {
 #pragma unroll
         for (int j = 0; j < PF; ++j) tq[j] = lookup(j);
+        }
         // The W steps of the block.  FE (fast emit): the exec-masked append in inline assembly, legal
         // when every window of the block is inside the range and none is skipped.
         auto steps = [&](auto fe_tag) {
@@ -1473,10 +1541,15 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
         };
         uint32_t p_sel = 0, p_selr = 0;      // the step whose branch and emit are pending
         unsigned long long p_differ = 0ull, p_valid = ~0ull;
+        uint32_t fwk = fw, rck = rc;  // kPair: the state an even step started from (its odd step is made from it)
 #pragma unroll
         for (int j = 0; j < W; ++j) {
             const uint32_t e = e0 + (uint32_t)j;  // uniform
+            if constexpr (kPair) {
+                if (((j + PF) & 1) == 0 && j + PF < W) tqp[(j + PF) >> 1] = lookup_pair((j + PF) >> 1);
+            } else {
             if (j + PF < W) tq[j + PF] = lookup(j + PF);
+            }
             const uint32_t h = HASH_RC ? fw + rc : fw;
 #ifdef MM_STAGE
             if (!MM_STAGE_GE(3)) {  // timing build: stages 1 / 2 end here
@@ -1543,9 +1616,22 @@ __device__ __forceinline__ uint32_t lane_walk(const FusedParams &p, const LaneCt
 #endif
             if (!deferred) emit_step(j, sel, valid);
 
+            if constexpr (kPair) {
+                const uint4 t = tqp[j >> 1];
+                if ((j & 1) == 0) {
+                    fwk = fw;
+                    rck = rc;
+                    fw = __builtin_amdgcn_alignbit(fwk, fwk, rot_l) ^ t.x;
+                    if (HASH_RC) rc = __builtin_amdgcn_alignbit(rck, rck, rot_r) ^ t.y;
+                } else {
+                    fw = __builtin_amdgcn_alignbit(fwk, fwk, rot2_l) ^ t.z;
+                    if (HASH_RC) rc = __builtin_amdgcn_alignbit(rck, rck, rot2_r) ^ t.w;
+                }
+            } else {
             const uint2 t = tq[j];
             fw = __builtin_amdgcn_alignbit(fw, fw, rot_l) ^ t.x;
             if (HASH_RC) rc = __builtin_amdgcn_alignbit(rc, rc, rot_r) ^ t.y;
+            }
             if (CANON && !kLazyVote) dn += __builtin_amdgcn_sbfe((int)tgw[j >> 4], 2 * (j & 15), 2);
         }
         if (CANON && kLazyVote && MM_STAGE_GE(5) && !(MM_VOTE_NO_DEFER)) {  // the block's last step
@@ -2055,6 +2141,16 @@ __global__ __launch_bounds__(kFusedThreads, MM_MIN_BLOCKS) void fused_kernel(con
     constexpr bool kE8 = kEntry8<W, CANON, SK, READS>;       // 8-bit list entries (see kEntry8)
     constexpr uint32_t kStride = list_stride(kE8), kEB = kE8 ? 1u : 2u;
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    // the pair table of the walks under pair_lookup_rule: 4 KB of static LDS in this instance only
+    constexpr bool kPair = pair_lookup_rule(W, CANON, KC, MODE, SK, READS, false);
+    uint4 *pair_tab = nullptr;
+    uint32_t pair_end = 0;
+    if constexpr (kPair) {
+        static_assert(kFusedThreads == kPairEntries, "one pair-table entry per thread");
+        __shared__ uint4 s_pair[kPairEntries];
+        pair_tab = s_pair;
+        pair_end = (uint32_t)reinterpret_cast<uintptr_t>(s_pair) + (uint32_t)sizeof(s_pair);
+    }
     // Layout contract of the list overflow (see "redo" in the header comment): the lists are the dynamic
     // LDS and must lie behind every static variable, so that entries past a list's capacity fall beyond
     // the lists (into padding or out of the workgroup's allocation, where the hardware drops them) and
@@ -2070,6 +2166,7 @@ __global__ __launch_bounds__(kFusedThreads, MM_MIN_BLOCKS) void fused_kernel(con
         st_end = max(st_end, lds_end(&s_done, sizeof(s_done)));
         st_end = max(st_end, lds_end(s_wave_tot, sizeof(s_wave_tot)));
         st_end = max(st_end, lds_end(&s_excl, sizeof(s_excl)));
+        if constexpr (kPair) st_end = max(st_end, pair_end);
         if ((uint32_t)reinterpret_cast<uintptr_t>(smem) < st_end) {
             if (tid == 0) flag_error(p.out.error, 2u);
             return;
@@ -2091,6 +2188,9 @@ __global__ __launch_bounds__(kFusedThreads, MM_MIN_BLOCKS) void fused_kernel(con
     if (tid < 16) s_tab[tid] = p.ht.t_in_out[tid];
     else if (tid < 20) s_tab[tid] = p.ht.t_in[tid - 16];
     else if (tid < 36) s_tab[tid] = p.ht.t_in2[tid - 20];
+    // (one entry per thread, straight from the kernel argument like the tables above: its dynamic index is a load from the
+    // argument segment, no scratch)
+    if constexpr (kPair) pair_tab[tid] = pair_entry(p.ht, (uint32_t)tid);
     __syncthreads();
     const uint32_t bid = __builtin_amdgcn_readfirstlane(s_bid);  // keep tile scalars in SGPRs
     const unsigned long long etag = (unsigned long long)p.epoch << kEpochShift;
@@ -2181,6 +2281,7 @@ __global__ __launch_bounds__(kFusedThreads, MM_MIN_BLOCKS) void fused_kernel(con
     uint8_t *const lists = smem + p.land_bytes;
     LaneCtx ctx;
     ctx.tab = s_tab;
+    if constexpr (kPair) ctx.pair = pair_tab;
     ctx.list = lists + kEB * (uint32_t)tid;
     ctx.list_bytes = p.list_cap * kStride;
     ctx.dst = 0;

@@ -80,6 +80,8 @@ int fused_walk_traits(uint32_t w, bool canonical_windows, uint32_t mode, bool sk
 // the strand count of one tied window through the fixed-k canonical walk's plan (kc_count_plan), on the host; see mm_fused.hip
 int fused_kc_count(uint32_t w, uint32_t k, uint32_t kn, uint32_t jj, uint32_t group, const uint8_t *bytes, uint64_t n_bytes,
                    int64_t lane_base, uint32_t *count);
+// the 256 x 4 words of the pair table (pair_lookup_rule, mm_fused_impl.h) made from these hash tables, on the host
+void fused_pair_table(const HashTables &ht, uint32_t *out1024);
 // *nblk_out receives the longest lane of the table (RunArgs::nblk of the launch: it sizes the lists).
 bool fused_batch_tiles(const RunArgs &a, const uint64_t *n_windows, uint64_t n_seqs, std::vector<BatchTile> &tiles,
                        uint32_t *nblk_out);

@@ -63,8 +63,12 @@ for i, s in enumerate(insts):
     writes = ops["ds_write_b16"] + ops["ds_write_b8"]
     if writes == 0 or writes % W or writes // W > 8 or emit_cmp != writes:
         continue
-    if sum(v for o, v in ops.items() if o.startswith("ds_read")) != writes or not any(o.startswith("buffer_load") for o in ops):
-        continue  # (the block loop proper: one table look-up and one list append per window, the sequence loads of a later group)
+    # (the block loop proper: one table look-up and one list append per window - or, under pair_lookup_rule, one look-up per
+    # TWO windows and one for the single last base of an odd block: (W + 1) / 2 reads per W appends, 6 per 11 - and the
+    # sequence loads of a later group)
+    reads = sum(v for o, v in ops.items() if o.startswith("ds_read"))
+    if reads not in (writes, writes // W * ((W + 1) // 2)) or not any(o.startswith("buffer_load") for o in ops):
+        continue
     if any(o.startswith(("v_cmp_lt_i32", "buffer_store", "global_store")) for o in ops):
         continue  # range-checked or direct-store walks
     # the hot loop is the one that walks the most windows per iteration (the group-unrolled one), then the shortest
