@@ -1265,7 +1265,7 @@ int mm_debug_fastx_cut(const uint8_t *text, uint64_t n, int format, int last, ui
  * end inside it ("a record longer than chunk_bytes", as without the flag), for a piece that brings no new base of its record
  * ("cannot advance": a chunk of line ends), for an overlap text longer than chunk_bytes; MM_ERR_LEN_TOO_LARGE for a record
  * that reaches 2^32 bases.  Still out: FASTQ records longer than a chunk, records of 2^32 bases or more, several devices,
- * plain (non-BGZF) gzip, CRC32 check.  A sequence line that begins with '>' is a header line, as everywhere; a '>' inside a sequence line is a base the
+ * plain (non-BGZF) gzip.  A sequence line that begins with '>' is a header line, as everywhere; a '>' inside a sequence line is a base the
  * packers map like any other letter, but must not be the first of the l - 1 overlap bytes' line (it would read as a header).
  * Memory: the carry area grows by 16 bytes (2 are used); a packer sees at most 2 * chunk_bytes + 2 bytes. */
 typedef struct mm_fastx_pieces {
@@ -1288,9 +1288,14 @@ int mm_debug_fastx_split(const uint8_t *text, uint64_t n, uint32_t l, int last, 
  * one wavefront per block (csrc/mm_bgzf.hip; the decoder, RFC 1951 with stored, fixed and dynamic blocks, is
  * csrc/mm_inflate.h, the same code on host and device).  The reference reads compressed files through its loader on the
  * CPU (needletail::parse_fastx_file, bench/src/lib.rs:51-82) and has no other counterpart.
- * CRC32 IS NOT VERIFIED: a block is accepted when its deflate stream is well formed, ends with its final block's
- * end-of-block code and gives exactly ISIZE bytes; payload bytes behind the final block are ignored.  Plain gzip (one
- * serial stream per file) is out of scope and refused by name.
+ * The inflate accepts a block when its deflate stream is well formed, ends with its final block's end-of-block code and
+ * gives exactly ISIZE bytes; payload bytes behind the final block are ignored.  CRC32 IS VERIFIED ON REQUEST, as zlib,
+ * htslib and the reference's loader verify it: a kernel of its own (csrc/mm_crc32.hip, one workgroup of 256 threads per
+ * block; the arithmetic is csrc/mm_crc32.h, the same code on host and device) computes the CRC32 of every block's text
+ * where the inflate has written it and compares it with the block's gzip trailer - mm_bgzf_crc32_device_async,
+ * mm_bgzf_inflate_verify_host and, for the stream, the flag MM_FASTX_BGZF_CRC below.  Without a request nothing changes: a
+ * flipped byte in a stored block, or a changed literal that keeps the Huffman stream valid, passes as text.  Plain gzip
+ * (one serial stream per file) is out of scope and refused by name.
  *   mm_bgzf_scan_host (no device)  walks the members from data[0]: magic 1f 8b, CM 8, FLG bit 2 (FTEXT may be set, any
  *     other flag is a bad header), the XLEN subfields for BC with SLEN 2 (not necessarily the first), comp_len = BSIZE + 1
  *     - XLEN - 20, ISIZE from the trailer (above 65536: MM_ERR_FORMAT).  It stops at the first incomplete block, when
@@ -1300,6 +1305,11 @@ int mm_debug_fastx_split(const uint8_t *text, uint64_t n, uint32_t l, int last, 
  *     is MM_ERR_FORMAT with "plain gzip is one serial stream; recompress with bgzip" in mm_last_error(); any other bad
  *     header is MM_ERR_FORMAT.  MM_ERR_NULL: n_blocks, consumed or out_bytes NULL, data NULL with bytes, blocks NULL with
  *     max_blocks != 0.
+ *   mm_bgzf_scan_crc_host (no device)  mm_bgzf_scan_host in every respect (one walk serves both), and crcs[i] = the CRC32
+ *     of listed block i's trailer (little-endian, the four bytes in front of ISIZE); crcs NULL with max_blocks != 0 is
+ *     MM_ERR_NULL.  Blocks with ISIZE 0 are not listed, so THEIR TRAILERS ARE NOT CHECKED by anything that follows.
+ *   mm_debug_crc32 (no device)  the gzip CRC32 (zlib's crc32(0, data, n)) of data[0 .. n) by the header's host function;
+ *     MM_ERR_NULL for crc NULL, or data NULL with bytes.
  *   mm_bgzf_inflate_device_async  queues ONE launch on the workspace's stream: block b's payload d_comp + comp_off
  *     [comp_len] is inflated to d_out + out_off [isize].  Refused on the host before anything is queued: ws NULL, or with
  *     n_blocks != 0 d_comp, d_blocks or d_out NULL (MM_ERR_NULL); n_blocks >= 2^31 (MM_ERR_LEN_TOO_LARGE).  The table lives
@@ -1311,9 +1321,23 @@ int mm_debug_fastx_split(const uint8_t *text, uint64_t n, uint32_t l, int last, 
  *     A launch with both kinds of failure reports the table's: MM_ERR_CAPACITY (the larger kernel error stays).
  *     d_status may be NULL.  No byte outside a block's payload is loaded, none outside its slot stored, whatever the bytes
  *     hold.
+ *   mm_bgzf_crc32_device_async  queues ONE launch on the workspace's stream over the same table (only out_off and isize are
+ *     read) and the text d_text [text_capacity]: d_crc (may be NULL) receives every block's CRC32; with d_expect (may be
+ *     NULL; the trailers' values, from mm_bgzf_scan_crc_host) a block whose CRC32 differs gets d_status[b] = 15, and
+ *     mm_workspace_check reports MM_ERR_FORMAT with "CRC32" in mm_last_error() (kernel error 11).  With d_expect, d_status
+ *     is also READ: a block whose word is not 0 is skipped - queued behind mm_bgzf_inflate_device_async with the same
+ *     array, a block that did not inflate keeps its code and kernel error 9 and is not re-labelled (without an inflate in
+ *     front the caller clears the array).  Table entries are checked on the device as above (nothing is read, d_status[b] =
+ *     100, d_crc[b] is not written, kernel error 10).  The sticky error word keeps the LARGEST code: a queue with a mismatch
+ *     and a bad table entry, or a block that did not inflate, reports the mismatch; d_status tells the blocks apart.
+ *     No byte outside [out_off, out_off + isize) is loaded, whatever the alignment.  Refused on the host: ws NULL, d_expect
+ *     and d_crc both NULL, or with n_blocks != 0 d_text or d_blocks NULL (MM_ERR_NULL); n_blocks >= 2^31
+ *     (MM_ERR_LEN_TOO_LARGE).  d_status may be NULL.
  *   mm_bgzf_inflate_host  scan + upload + kernel + download of a whole BGZF file in host memory: *out_bytes = the text's
  *     size (also with MM_ERR_CAPACITY, when out_capacity is too small: nothing was inflated); a file that ends inside a
  *     block is MM_ERR_FORMAT.
+ *   mm_bgzf_inflate_verify_host  the same with every listed block's CRC32 verified: scan with CRCs, upload, inflate with a
+ *     status array, the verify launch, download; a mismatch is MM_ERR_FORMAT with "CRC32" in mm_last_error().
  *   mm_debug_bgzf_inflate (no device)  the decoder on the host: one payload into out[0 .. isize); MM_OK or MM_ERR_FORMAT
  *     (mm_last_error() names the decoder's error), MM_ERR_NULL.
  *   mm_fastx_stream_feed_bgzf  serves the unchanged stream handle, DNA and byte text, in place of mm_fastx_stream_feed:
@@ -1338,7 +1362,16 @@ int mm_debug_fastx_split(const uint8_t *text, uint64_t n, uint32_t l, int last, 
  *     behave exactly as for plain text; later blocks go to the device.  mm_fastx_stream_feed may be called BEFORE the
  *     first mm_fastx_stream_feed_bgzf (its bytes stand in front); after it, it is refused with MM_ERR_BAD_MODE.
  *     Offsets (rec_text_pos, text_begin, text_end, first_byte) are offsets in the INFLATED text; BGZF virtual offsets are
- *     out of scope.  A chunk needs a cut like every chunk: keep chunk_bytes well above 64 KiB + the longest record. */
+ *     out of scope.  A chunk needs a cut like every chunk: keep chunk_bytes well above 64 KiB + the longest record.
+ *   MM_FASTX_BGZF_CRC  a flag of mm_fastx_stream_create and mm_fastx_text_stream_create: every block fed through
+ *     mm_fastx_stream_feed_bgzf is verified.  A slot keeps the trailers' CRC32s beside its table and uploads them with it,
+ *     the inflate gets a status array and the verify launch runs behind it on the slot's stream; a mismatch fails the stream
+ *     with MM_ERR_FORMAT, "CRC32" in mm_last_error(), before anything is made of the chunk's text, and like every stream
+ *     error it stays.  Blocks inflated on the HOST (above) are checked on the host by the same arithmetic.  Without
+ *     mm_fastx_stream_feed_bgzf the flag does nothing.  Which block failed is not reported (the status array stays on the
+ *     device).  Per slot: 8 bytes per table entry on the device, 4 page-locked.  The value is 1024: 512 stays an unknown
+ *     bit that both creates refuse (MM_ERR_BAD_MODE), as it always was. */
+enum { MM_FASTX_BGZF_CRC = 1024 };
 typedef struct mm_bgzf_block {
     uint64_t comp_off;   /* offset of the deflate payload in the compressed bytes */
     uint32_t comp_len;   /* its size */
@@ -1347,11 +1380,20 @@ typedef struct mm_bgzf_block {
 } mm_bgzf_block_t;
 int mm_bgzf_scan_host(const uint8_t *data, uint64_t n_bytes, uint64_t max_blocks, uint64_t max_out_bytes,
                       mm_bgzf_block_t *blocks, uint64_t *n_blocks, uint64_t *consumed, uint64_t *out_bytes);
+int mm_bgzf_scan_crc_host(const uint8_t *data, uint64_t n_bytes, uint64_t max_blocks, uint64_t max_out_bytes,
+                          mm_bgzf_block_t *blocks, uint64_t *n_blocks, uint64_t *consumed, uint64_t *out_bytes,
+                          uint32_t *crcs /* [max_blocks] */);
+int mm_debug_crc32(const uint8_t *data, uint64_t n, uint32_t *crc);
 int mm_bgzf_inflate_device_async(mm_workspace_t *ws, const void *d_comp, uint64_t comp_bytes,
                                  const mm_bgzf_block_t *d_blocks, uint64_t n_blocks, void *d_out, uint64_t out_capacity,
                                  uint32_t *d_status /* [n_blocks] or NULL */);
 int mm_bgzf_inflate_host(mm_workspace_t *ws, const uint8_t *data, uint64_t n_bytes, uint8_t *out, uint64_t out_capacity,
                          uint64_t *out_bytes);
+int mm_bgzf_crc32_device_async(mm_workspace_t *ws, const void *d_text, uint64_t text_capacity,
+                               const mm_bgzf_block_t *d_blocks, uint64_t n_blocks, const uint32_t *d_expect /* or NULL */,
+                               uint32_t *d_crc /* [n_blocks] or NULL */, uint32_t *d_status /* [n_blocks] or NULL */);
+int mm_bgzf_inflate_verify_host(mm_workspace_t *ws, const uint8_t *data, uint64_t n_bytes, uint8_t *out,
+                                uint64_t out_capacity, uint64_t *out_bytes);
 int mm_debug_bgzf_inflate(const uint8_t *payload, uint32_t comp_len, uint8_t *out, uint32_t isize);
 int mm_fastx_stream_feed_bgzf(mm_fastx_stream_t *s, const uint8_t *data, uint64_t n_bytes, uint64_t *consumed);
 /* ------------------------------------------------------------------ several devices from one call

@@ -382,6 +382,7 @@ class Builder {  // src/lib.rs:225-230
     // `bgzf`: the source is BGZF-compressed (bgzip, htslib) and goes through mm_fastx_stream_feed_bgzf, inflated on the device:
     // 1 yes, 0 no, -1 decided by the source's first bytes (1f 8b 08 with FLG bit 2; such input was MM_ERR_FORMAT before).
     // Plain gzip is refused (MM_ERR_FORMAT).  Offsets in the batches are offsets in the inflated text.
+    // MM_FASTX_BGZF_CRC in options.flags: every block's CRC32 is verified on the device; a mismatch throws MM_ERR_FORMAT ("CRC32").
     template <class Reader, class OnBatch>
     void stream_fastx(Reader &&reader, OnBatch &&on_batch, const mm_fastx_stream_config_t &options,
                       size_t read_bytes = size_t(1) << 22, int bgzf = -1) const {

@@ -394,6 +394,11 @@ def _load_lib():
             L.mm_bgzf_inflate_host.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p]
             L.mm_debug_bgzf_inflate.argtypes = [vp, C.c_uint32, vp, C.c_uint32]
             L.mm_fastx_stream_feed_bgzf.argtypes = [vp, vp, C.c_uint64, u64p]
+        if hasattr(L, "mm_bgzf_crc32_device_async"):  # (the blocks' CRC32, verified on the device on request)
+            L.mm_debug_crc32.argtypes = [vp, C.c_uint64, vp]
+            L.mm_bgzf_scan_crc_host.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, vp, u64p, u64p, u64p, vp]
+            L.mm_bgzf_crc32_device_async.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp]
+            L.mm_bgzf_inflate_verify_host.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p]
         _lib = L
     return _lib
 
@@ -458,6 +463,7 @@ EXPORTED_SYMBOLS = [
     "mm_debug_walk_traits", "mm_debug_kc_count", "mm_debug_pair_table",
     "mm_bgzf_scan_host", "mm_bgzf_inflate_device_async", "mm_bgzf_inflate_host", "mm_debug_bgzf_inflate",
     "mm_fastx_stream_feed_bgzf",
+    "mm_debug_crc32", "mm_bgzf_scan_crc_host", "mm_bgzf_crc32_device_async", "mm_bgzf_inflate_verify_host",
 ]
 
 # the order of mm_debug_walk_traits' values (MM_TRAIT_* of the header)
@@ -1918,6 +1924,7 @@ def fastx_pipeline_device(builder: "Builder", text, max_records: int, fmt: str, 
 FASTX_AUTO, FASTX_FASTA, FASTX_FASTQ = 0, 1, 2
 FASTX_SK, FASTX_SKIP_AMBIGUOUS, FASTX_VALUES_U64, FASTX_VALUES_U128, FASTX_LONG_RECORDS = 1, 2, 4, 8, 16
 FASTX_ONE_MINIMIZER = 256  # (mm_fastx_stream_create only; the byte-text stream has FASTX_TEXT_ONE_MINIMIZER)
+FASTX_BGZF_CRC = 1024  # (both streams: every block fed through feed_bgzf has its CRC32 verified)
 FASTX_NEED_INPUT, FASTX_END = 1, 2
 _FASTX_FORMATS = {"auto": FASTX_AUTO, "fasta": FASTX_FASTA, "fastq": FASTX_FASTQ}
 
@@ -2001,12 +2008,14 @@ class FastxStream:
     first byte fed, ``slots`` chunks in flight (0: the default of 3), ``long_records`` FASTA records longer than a chunk
     come in pieces (``MM_FASTX_LONG_RECORDS``; see ``FastxBatch`` and ``fastx_join``), ``one_minimizer`` one minimizer
     per read in ``FastxBatch.one_min`` (``MM_FASTX_ONE_MINIMIZER``: the builder's k and hasher, with ``skip_ambiguous``
-    over clean k-mers only, ``NO_MINIMIZER`` for a read without one; refused with ``long_records``).  Iterating yields the remaining batches (after
+    over clean k-mers only, ``NO_MINIMIZER`` for a read without one; refused with ``long_records``), ``bgzf_crc`` the
+    CRC32 of every block fed through ``feed_bgzf`` is verified on the device (``MM_FASTX_BGZF_CRC``: a mismatch fails the
+    stream with ``MM_ERR_FORMAT``, "CRC32" in its text; nothing changes for plain text).  Iterating yields the remaining batches (after
     ``finish()``).  A failing stream raises ``MinimizerError`` from every later call."""
 
     def __init__(self, builder: "Builder", chunk_bytes: int, max_records: int, fmt="auto", values=None, super_kmers=False,
                  skip_ambiguous=False, max_positions=0, first_byte=0, slots=0, device=None, long_records=False,
-                 one_minimizer=False):
+                 one_minimizer=False, bgzf_crc=False):
         if fmt not in _FASTX_FORMATS:
             raise ValueError('fmt is "auto", "fasta" or "fastq"')
         if values not in (None, "u64", "u128"):
@@ -2015,6 +2024,7 @@ class FastxStream:
         flags |= {None: 0, "u64": FASTX_VALUES_U64, "u128": FASTX_VALUES_U128}[values]
         flags |= FASTX_LONG_RECORDS if long_records else 0
         flags |= FASTX_ONE_MINIMIZER if one_minimizer else 0
+        flags |= FASTX_BGZF_CRC if bgzf_crc else 0
         self.h = None
         self.long_records = bool(long_records)
         self.one_minimizer = bool(one_minimizer)
@@ -2127,16 +2137,17 @@ class FastxTextStream(FastxStream):
     ``one_minimizer`` (``FastxBatch.one_min``: per record the leftmost position of the minimal ``hash & 0xffff0000`` with
     the builder's k and hasher, ``NO_MINIMIZER`` for a record shorter than k), ``seq`` (``FastxBatch.seq``: the records'
     bytes, record r = ``seq[rec_base[r]:rec_base[r + 1]]``).  ``fmt`` "auto" / "fasta": FASTQ raises ``MM_ERR_FORMAT``.
-    ``n_bases`` counts characters."""
+    ``n_bases`` counts characters.  ``bgzf_crc`` as ``FastxStream`` takes it."""
 
     def __init__(self, builder: "Builder", chunk_bytes: int, max_records: int, values=None, encoding=None, super_kmers=False,
-                 one_minimizer=False, seq=False, fmt="auto", max_positions=0, first_byte=0, slots=0, device=None):
+                 one_minimizer=False, seq=False, fmt="auto", max_positions=0, first_byte=0, slots=0, device=None, bgzf_crc=False):
         if fmt not in _FASTX_FORMATS:
             raise ValueError('fmt is "auto" or "fasta"')
         if values not in (None, "u64", "u128"):
             raise ValueError('values is None, "u64" or "u128"')
         flags = (FASTX_SK if super_kmers else 0) | {None: 0, "u64": FASTX_VALUES_U64, "u128": FASTX_VALUES_U128}[values]
         flags |= (FASTX_TEXT_ONE_MINIMIZER if one_minimizer else 0) | (FASTX_TEXT_SEQ if seq else 0)
+        flags |= FASTX_BGZF_CRC if bgzf_crc else 0
         self.h = None
         self.long_records = False
         self.one_minimizer = False  # (the text stream's words come with its extras)
@@ -2241,14 +2252,29 @@ class BgzfBlock(C.Structure):
 BGZF_BLOCK_DTYPE = np.dtype([("comp_off", "<u8"), ("comp_len", "<u4"), ("isize", "<u4"), ("out_off", "<u8")])
 
 
-def bgzf_scan(data, max_blocks=None, max_out_bytes=U64_MAX) -> dict:
+def crc32(data) -> int:
+    """``mm_debug_crc32`` (no device): the gzip CRC32 of ``data`` (``zlib.crc32``) by the arithmetic the verify kernel runs."""
+    buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+    out = C.c_uint32(0)
+    _check_bgzf(lib().mm_debug_crc32(buf.ctypes.data if buf.size else None, buf.size, C.byref(out)))
+    return int(out.value)
+
+
+def bgzf_scan(data, max_blocks=None, max_out_bytes=U64_MAX, crc=False) -> dict:
     """``mm_bgzf_scan_host`` (no device): the block table of the BGZF bytes ``data`` as a structured array
     (``BGZF_BLOCK_DTYPE``), ``consumed`` (bytes of whole blocks taken) and ``out_bytes`` (their text's size).
-    ``max_blocks`` None: as many as ``data`` can hold."""
+    ``max_blocks`` None: as many as ``data`` can hold.  ``crc``: also ``"crc"``, the CRC32 of every listed block's gzip
+    trailer as a uint32 array (``mm_bgzf_scan_crc_host``)."""
     buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
     cap = buf.size // 26 + 1 if max_blocks is None else int(max_blocks)
     blocks = np.zeros(cap, BGZF_BLOCK_DTYPE)
     n, used, out = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    if crc:
+        crcs = np.zeros(cap, np.uint32)
+        _check_bgzf(lib().mm_bgzf_scan_crc_host(buf.ctypes.data if buf.size else None, buf.size, cap, int(max_out_bytes),
+                                           blocks.ctypes.data if cap else None, C.byref(n), C.byref(used), C.byref(out),
+                                           crcs.ctypes.data if cap else None))
+        return {"blocks": blocks[:int(n.value)], "consumed": int(used.value), "out_bytes": int(out.value), "crc": crcs[:int(n.value)]}
     _check_bgzf(lib().mm_bgzf_scan_host(buf.ctypes.data if buf.size else None, buf.size, cap, int(max_out_bytes),
                                    blocks.ctypes.data if cap else None, C.byref(n), C.byref(used), C.byref(out)))
     return {"blocks": blocks[:int(n.value)], "consumed": int(used.value), "out_bytes": int(out.value)}
@@ -2282,14 +2308,47 @@ def bgzf_inflate_device(d_comp, blocks, d_out, d_status=None, ws=None):
     return n
 
 
-def bgzf_inflate_host(data, ws=None, device: int = 0) -> bytes:
-    """``mm_bgzf_inflate_host``: a whole BGZF file in host memory inflated on the device; the text as bytes."""
+def bgzf_crc32_device(d_text, blocks, expect=None, d_status=None, ws=None):
+    """``mm_bgzf_crc32_device_async``: one launch over the table ``blocks`` (as ``bgzf_inflate_device`` takes it) and the
+    text in the uint8 device tensor ``d_text``; returns the int32 device tensor of the blocks' CRC32s (their bits are the
+    uint32 values).  ``expect`` (the trailers' CRC32s: a host array, which is uploaded, or an int32 device tensor): a block
+    that differs gets 15 in ``d_status`` and ``ws.check()`` raises ``MM_ERR_FORMAT`` ("CRC32"); a block whose ``d_status``
+    word is already non-zero is skipped.  ``d_status`` None with ``expect``: a zeroed array of the call's own (kept as
+    ``ws._keep_bgzf_crc[-1]``).  Queued on the workspace's stream."""
+    import torch
+
+    ws = ws or default_workspace(d_text.device.index or 0)
+    if isinstance(blocks, np.ndarray):
+        host = np.ascontiguousarray(blocks, dtype=BGZF_BLOCK_DTYPE)
+        d_blocks = torch.from_numpy(host.view(np.uint8).copy()).to(d_text.device)
+    else:
+        d_blocks = blocks
+    n = d_blocks.numel() * d_blocks.element_size() // BGZF_BLOCK_DTYPE.itemsize
+    d_expect = None
+    if expect is not None:
+        if isinstance(expect, torch.Tensor):
+            d_expect = expect
+        else:
+            d_expect = torch.from_numpy(np.ascontiguousarray(expect, dtype=np.uint32).view(np.int32).copy()).to(d_text.device)
+        if d_status is None:
+            d_status = torch.zeros(max(n, 1), dtype=torch.int32, device=d_text.device)
+    d_crc = torch.zeros(max(n, 1), dtype=torch.int32, device=d_text.device)
+    _check_bgzf(lib().mm_bgzf_crc32_device_async(ws.h, _ptr(d_text), d_text.numel(), _ptr(d_blocks), n,
+                                            _ptr(d_expect) if d_expect is not None else None, _ptr(d_crc),
+                                            _ptr(d_status) if d_status is not None else None))
+    ws._keep_bgzf_crc = (d_text, d_blocks, d_expect, d_crc, d_status)  # (alive until the queued launch has run)
+    return d_crc[:n]
+
+
+def bgzf_inflate_host(data, ws=None, device: int = 0, verify=False) -> bytes:
+    """``mm_bgzf_inflate_host``: a whole BGZF file in host memory inflated on the device; the text as bytes.  ``verify``:
+    ``mm_bgzf_inflate_verify_host``, every block's CRC32 checked on the device (``MM_ERR_FORMAT``, "CRC32", on a mismatch)."""
     buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
     ws = ws or default_workspace(device)
     cap = bgzf_scan(buf)["out_bytes"]
     out = np.zeros(max(cap, 1), np.uint8)
     n = C.c_uint64(0)
-    _check_bgzf(lib().mm_bgzf_inflate_host(ws.h, buf.ctypes.data if buf.size else None, buf.size, out.ctypes.data, cap, C.byref(n)))
+    _check_bgzf((lib().mm_bgzf_inflate_verify_host if verify else lib().mm_bgzf_inflate_host)(ws.h, buf.ctypes.data if buf.size else None, buf.size, out.ctypes.data, cap, C.byref(n)))
     return out[:int(n.value)].tobytes()
 
 
@@ -2363,7 +2422,8 @@ def stream_fastx(builder: "Builder", source, chunk_bytes: int = 64 << 20, max_re
     object or an iterable of bytes, of any size.  ``options`` as ``FastxStream`` takes them; ``read_bytes``: how much a
     path or file object is read at a time.  ``bgzf``: the source is BGZF-compressed (bgzip / htslib ``.gz``) and is
     inflated on the device (``FastxStream.feed_bgzf``); None decides by the source's first bytes (``is_bgzf``), True and
-    False force the choice.  Plain gzip is refused (``MM_ERR_FORMAT``)."""
+    False force the choice.  Plain gzip is refused (``MM_ERR_FORMAT``).  ``bgzf_crc=True`` (an option of ``FastxStream``)
+    verifies every BGZF block's CRC32 on the device."""
     yield from _stream_batches(FastxStream(builder, chunk_bytes, max_records, **options), source, read_bytes, bgzf)
 
 

@@ -1031,6 +1031,12 @@ int mm_workspace_check(mm_workspace_t *ws) {
                        "isize above 65536); nothing of that block was read or written";
         return MM_ERR_CAPACITY;
     }
+    // (kernel error 11: mm_bgzf_crc32_device_async; the largest of the three, so it is what a queue with several reports)
+    if (code == mm::kErrBgzfCrc) {
+        g_last_error = "mm_bgzf_crc32_device_async: CRC32 mismatch: a BGZF block's text does not have the CRC32 of its gzip "
+                       "trailer (d_status 15 names the block); the file is corrupt";
+        return MM_ERR_FORMAT;
+    }
     char buf[128];
     snprintf(buf, sizeof(buf), code == 2u   ? "kernel error 2: dynamic LDS does not lie behind the static LDS"
                                : code == 4u ? "kernel error 4: a skip-ambiguous launch without its LDS landing area"

@@ -18,13 +18,15 @@
 //   tables   in LDS (2 592 bytes); the first-level tables' entries are filled lane-parallel
 // A wave's loads see its own earlier stores of other lanes: vector memory operations of one wavefront execute in order,
 // and the wavefront-scope fences keep the compiler from reordering them.  Every global store is a per-lane store.
-// CRC32 is not verified (mm_inflate.h).
+// CRC32 is verified on request, by a kernel of its own behind this one (mm_crc32.hip): mm_bgzf_crc32_device_async,
+// mm_bgzf_inflate_verify_host, the stream's MM_FASTX_BGZF_CRC.  This kernel accepts a block by its structure and ISIZE alone.
 #include <hip/hip_runtime.h>
 
 #include <string>
 #include <vector>
 
 #include "mm_bgzf.h"
+#include "mm_crc32.h"
 #include "mm_fastx_stream.h"
 #include "mm_inflate.h"
 
@@ -126,16 +128,16 @@ int launch_bgzf_inflate(const uint8_t *d_comp, uint64_t comp_bytes, const mm_bgz
     return hipPeekAtLastError() == hipSuccess ? 0 : -1;
 }
 
-}  // namespace mm
+namespace {
 
-extern "C" {
-
-int mm_bgzf_scan_host(const uint8_t *data, uint64_t n_bytes, uint64_t max_blocks, uint64_t max_out_bytes, mm_bgzf_block_t *blocks,
-                      uint64_t *n_blocks, uint64_t *consumed, uint64_t *out_bytes) {
+// the walk of mm_bgzf_scan_host and mm_bgzf_scan_crc_host (with_crcs: crcs[i] = the CRC32 of listed block i's trailer)
+int scan_host(const uint8_t *data, uint64_t n_bytes, uint64_t max_blocks, uint64_t max_out_bytes, mm_bgzf_block_t *blocks,
+              uint64_t *n_blocks, uint64_t *consumed, uint64_t *out_bytes, bool with_crcs, uint32_t *crcs) {
     if (n_blocks) *n_blocks = 0;
     if (consumed) *consumed = 0;
     if (out_bytes) *out_bytes = 0;
-    if (!n_blocks || !consumed || !out_bytes || (!data && n_bytes) || (!blocks && max_blocks)) return MM_ERR_NULL;
+    if (!n_blocks || !consumed || !out_bytes || (!data && n_bytes) || (!blocks && max_blocks) || (with_crcs && !crcs && max_blocks))
+        return MM_ERR_NULL;
     uint64_t at = 0, nb = 0, ob = 0;
     while (at < n_bytes) {
         uint64_t total = 0;
@@ -155,6 +157,7 @@ int mm_bgzf_scan_host(const uint8_t *data, uint64_t n_bytes, uint64_t max_blocks
             blocks[nb].comp_len = comp_len;
             blocks[nb].isize = isize;
             blocks[nb].out_off = ob;
+            if (with_crcs) crcs[nb] = mm::bgzf_trailer_crc(data + at, total);
             ++nb;
             ob += isize;
         }
@@ -163,6 +166,27 @@ int mm_bgzf_scan_host(const uint8_t *data, uint64_t n_bytes, uint64_t max_blocks
     *n_blocks = nb;
     *consumed = at;
     *out_bytes = ob;
+    return MM_OK;
+}
+
+}  // namespace
+}  // namespace mm
+
+extern "C" {
+
+int mm_bgzf_scan_host(const uint8_t *data, uint64_t n_bytes, uint64_t max_blocks, uint64_t max_out_bytes, mm_bgzf_block_t *blocks,
+                      uint64_t *n_blocks, uint64_t *consumed, uint64_t *out_bytes) {
+    return mm::scan_host(data, n_bytes, max_blocks, max_out_bytes, blocks, n_blocks, consumed, out_bytes, false, nullptr);
+}
+
+int mm_bgzf_scan_crc_host(const uint8_t *data, uint64_t n_bytes, uint64_t max_blocks, uint64_t max_out_bytes, mm_bgzf_block_t *blocks,
+                          uint64_t *n_blocks, uint64_t *consumed, uint64_t *out_bytes, uint32_t *crcs) {
+    return mm::scan_host(data, n_bytes, max_blocks, max_out_bytes, blocks, n_blocks, consumed, out_bytes, true, crcs);
+}
+
+int mm_debug_crc32(const uint8_t *data, uint64_t n, uint32_t *crc) {
+    if (!crc || (!data && n)) return MM_ERR_NULL;
+    *crc = mm::crc32_bytes(0, data, n);
     return MM_OK;
 }
 
@@ -189,16 +213,40 @@ int mm_bgzf_inflate_device_async(mm_workspace_t *ws, const void *d_comp, uint64_
     return MM_OK;
 }
 
-int mm_bgzf_inflate_host(mm_workspace_t *ws, const uint8_t *data, uint64_t n_bytes, uint8_t *out, uint64_t out_capacity,
-                         uint64_t *out_bytes) {
+int mm_bgzf_crc32_device_async(mm_workspace_t *ws, const void *d_text, uint64_t text_capacity, const mm_bgzf_block_t *d_blocks,
+                               uint64_t n_blocks, const uint32_t *d_expect, uint32_t *d_crc, uint32_t *d_status) {
+    if (!ws || (!d_expect && !d_crc) || (n_blocks && (!d_text || !d_blocks))) return MM_ERR_NULL;
+    if (n_blocks >= (1ull << 31)) return MM_ERR_LEN_TOO_LARGE;
+    if (n_blocks == 0) return MM_OK;
+    mm::DeviceGuard guard;
+    if (hipSetDevice(mm::api_workspace_device(ws)) != hipSuccess)
+        return mm::refuse(MM_ERR_HIP, std::string("mm_bgzf_crc32_device_async: hipSetDevice: ") + hipGetErrorString(hipGetLastError()));
+    mm::api_workspace_mark_async(ws);
+    if (mm::launch_bgzf_crc32(static_cast<const uint8_t *>(d_text), text_capacity, d_blocks, n_blocks, d_expect, d_crc, d_status,
+                              mm::api_workspace_error(ws), mm::api_workspace_stream(ws)))
+        return mm::refuse(MM_ERR_HIP, std::string("mm_bgzf_crc32_device_async: ") + hipGetErrorString(hipGetLastError()));
+    return MM_OK;
+}
+
+}  // extern "C"
+
+namespace mm {
+namespace {
+
+// mm_bgzf_inflate_host, and with `verify` mm_bgzf_inflate_verify_host: the trailers' CRC32s go up with the table, the inflate
+// gets a status array and the verify kernel runs behind it
+int inflate_host(mm_workspace_t *ws, const uint8_t *data, uint64_t n_bytes, uint8_t *out, uint64_t out_capacity, uint64_t *out_bytes,
+                 bool verify) {
     if (out_bytes) *out_bytes = 0;
     if (!ws || !out_bytes || (!data && n_bytes) || (!out && out_capacity)) return MM_ERR_NULL;
     std::vector<mm_bgzf_block_t> blocks;
+    std::vector<uint32_t> crcs;
     uint64_t at = 0, total_out = 0;
     while (at < n_bytes) {
         mm_bgzf_block_t part[256];
+        uint32_t part_crc[256];
         uint64_t nb = 0, used = 0, ob = 0;
-        const int r = mm_bgzf_scan_host(data + at, n_bytes - at, 256, ~0ull, part, &nb, &used, &ob);
+        const int r = scan_host(data + at, n_bytes - at, 256, ~0ull, part, &nb, &used, &ob, verify, part_crc);
         if (r) return r;
         if (used == 0)
             return mm::refuse(MM_ERR_FORMAT, "mm_bgzf_inflate_host: the last BGZF block is incomplete (a truncated file), at byte " +
@@ -207,6 +255,7 @@ int mm_bgzf_inflate_host(mm_workspace_t *ws, const uint8_t *data, uint64_t n_byt
             part[i].comp_off += at;
             part[i].out_off += total_out;
             blocks.push_back(part[i]);
+            if (verify) crcs.push_back(part_crc[i]);
         }
         at += used;
         total_out += ob;
@@ -218,17 +267,25 @@ int mm_bgzf_inflate_host(mm_workspace_t *ws, const uint8_t *data, uint64_t n_byt
     hipStream_t stream = mm::api_workspace_stream(ws);
     uint8_t *d_comp = nullptr, *d_out = nullptr;
     mm_bgzf_block_t *d_blocks = nullptr;
-    const uint64_t table_bytes = blocks.size() * sizeof(mm_bgzf_block_t);
+    uint32_t *d_expect = nullptr, *d_status = nullptr;
+    const uint64_t table_bytes = blocks.size() * sizeof(mm_bgzf_block_t), words_bytes = blocks.size() * sizeof(uint32_t);
     hipError_t e = hipSetDevice(mm::api_workspace_device(ws));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_comp), n_bytes);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_out), total_out);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_blocks), table_bytes);
     if (e == hipSuccess) e = hipMemcpyAsync(d_comp, data, n_bytes, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_blocks, blocks.data(), table_bytes, hipMemcpyHostToDevice, stream);
+    if (verify) {
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_expect), words_bytes);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_status), words_bytes);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_expect, crcs.data(), words_bytes, hipMemcpyHostToDevice, stream);
+    }
     int rc = MM_OK;
     if (e == hipSuccess) {
         // (the copies read pageable memory: they are done when the calls return, and the stream is waited for below)
-        rc = mm_bgzf_inflate_device_async(ws, d_comp, n_bytes, d_blocks, blocks.size(), d_out, total_out, nullptr);
+        // (the inflate writes every block's status word, so the array needs no clearing)
+        rc = mm_bgzf_inflate_device_async(ws, d_comp, n_bytes, d_blocks, blocks.size(), d_out, total_out, d_status);
+        if (rc == MM_OK && verify) rc = mm_bgzf_crc32_device_async(ws, d_out, total_out, d_blocks, blocks.size(), d_expect, nullptr, d_status);
         if (rc == MM_OK) e = hipMemcpyAsync(out, d_out, total_out, hipMemcpyDeviceToHost, stream);
     }
     const hipError_t es = hipStreamSynchronize(stream);
@@ -236,12 +293,29 @@ int mm_bgzf_inflate_host(mm_workspace_t *ws, const uint8_t *data, uint64_t n_byt
     if (d_comp) (void)hipFree(d_comp);
     if (d_out) (void)hipFree(d_out);
     if (d_blocks) (void)hipFree(d_blocks);
+    if (d_expect) (void)hipFree(d_expect);
+    if (d_status) (void)hipFree(d_status);
     if (rc) return rc;
     if (e != hipSuccess) {
         (void)hipGetLastError();
         return mm::refuse(e == hipErrorOutOfMemory ? MM_ERR_ALLOC : MM_ERR_HIP, std::string("mm_bgzf_inflate_host: ") + hipGetErrorString(e));
     }
     return mm_workspace_check(ws);
+}
+
+}  // namespace
+}  // namespace mm
+
+extern "C" {
+
+int mm_bgzf_inflate_host(mm_workspace_t *ws, const uint8_t *data, uint64_t n_bytes, uint8_t *out, uint64_t out_capacity,
+                         uint64_t *out_bytes) {
+    return mm::inflate_host(ws, data, n_bytes, out, out_capacity, out_bytes, false);
+}
+
+int mm_bgzf_inflate_verify_host(mm_workspace_t *ws, const uint8_t *data, uint64_t n_bytes, uint8_t *out, uint64_t out_capacity,
+                                uint64_t *out_bytes) {
+    return mm::inflate_host(ws, data, n_bytes, out, out_capacity, out_bytes, true);
 }
 
 }  // extern "C"

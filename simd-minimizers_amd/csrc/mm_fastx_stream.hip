@@ -40,7 +40,10 @@
 // MM_FASTX_AUTO and the blank bytes in front of a text go through the one rule of feed) followed by device-inflated
 // blocks; a chunk carries UP TO chunk_bytes new bytes (the next block would not fit), which launch() and the trim step
 // never took for exactly chunk_bytes.  The workspace's sticky error word comes to the host with the cut, so a block
-// that did not inflate fails the stream with MM_ERR_FORMAT before anything is made of its text.
+// that did not inflate fails the stream with MM_ERR_FORMAT before anything is made of its text.  With MM_FASTX_BGZF_CRC the
+// trailers' CRC32s go up with the table, the inflate writes a status array and the verify kernel (mm_crc32.hip, one workgroup
+// per block) runs behind it, in front of the copy of the sticky word: a mismatch fails the stream the same way, "CRC32" in
+// its text.  The host-inflated blocks are checked on the host.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -50,6 +53,7 @@
 #include <vector>
 
 #include "mm_bgzf.h"
+#include "mm_crc32.h"
 #include "mm_fastx_cut.h"
 #include "mm_fastx_stream.h"
 #include "mm_inflate.h"
@@ -82,6 +86,9 @@ struct Slot {
     uint8_t *h_comp = nullptr, *d_comp = nullptr;
     mm_bgzf_block_t *h_blocks = nullptr, *d_blocks = nullptr;
     uint64_t n_comp = 0, n_blk = 0, n_blk_bytes = 0;
+    // MM_FASTX_BGZF_CRC: the blocks' trailer CRC32s beside the table (table_max words each), and the status array that the
+    // inflate writes and the verify kernel reads
+    uint32_t *h_crc = nullptr, *d_crc = nullptr, *d_status = nullptr;
     hipEvent_t ev_cut = nullptr, ev_run = nullptr, ev_done = nullptr, ev_tail = nullptr;
     bool tail_pending = false;  // the chunk behind this slot's copies its tail out of d_text: ev_tail says when it has
     // the chunk in the slot
@@ -170,11 +177,20 @@ void clear_new(Slot &sl) {
     sl.n_new = sl.n_comp = sl.n_blk = sl.n_blk_bytes = 0;
     sl.h_meta[9] = 0;
 }
-// BGZF input: the chunk's inflate raised its error (read behind ev_cut, before anything is made of the chunk's text)
-bool bgzf_failed(const Slot &sl) { return sl.n_blk && (uint32_t)sl.h_meta[9] == mm::kErrBgzfBlock; }
+// BGZF input: the chunk's inflate - or, with MM_FASTX_BGZF_CRC, the verify kernel behind it - raised its error (read behind
+// ev_cut, before anything is made of the chunk's text)
+bool bgzf_failed(const Slot &sl) {
+    return sl.n_blk && ((uint32_t)sl.h_meta[9] == mm::kErrBgzfBlock || (uint32_t)sl.h_meta[9] == mm::kErrBgzfCrc);
+}
 int fail_bgzf(mm_fastx_stream *s) {
     return fail(s, MM_ERR_FORMAT, "mm_fastx_stream: a BGZF block did not inflate (not deflate, or not ISIZE bytes of it)");
 }
+int fail_crc(mm_fastx_stream *s) {
+    return fail(s, MM_ERR_FORMAT, "mm_fastx_stream: CRC32 mismatch: a BGZF block's text does not have the CRC32 of its gzip trailer "
+                                  "(the file is corrupt)");
+}
+// (the sticky word keeps the larger code: a chunk with both kinds of failure reports the mismatch)
+int fail_bgzf(mm_fastx_stream *s, const Slot &sl) { return (uint32_t)sl.h_meta[9] == mm::kErrBgzfCrc ? fail_crc(s) : fail_bgzf(s); }
 
 bool is_blank(uint8_t c) { return c == ' ' || c == '\t' || c == '\r' || c == '\n'; }
 bool can_fill(const Slot &sl) { return sl.state == kFree || sl.state == kFilling; }
@@ -260,16 +276,22 @@ int launch(mm_fastx_stream *s, int last) {
         FX_HIP(hipMemcpyAsync(sl.d_blocks, sl.h_blocks, sl.n_blk * sizeof(mm_bgzf_block_t), hipMemcpyHostToDevice, sl.stream));
         uint32_t *const err = mm::api_workspace_error(sl.ws);
         mm::api_workspace_mark_async(sl.ws);
-        if (mm::launch_bgzf_inflate(sl.d_comp, sl.n_comp, sl.d_blocks, sl.n_blk, sl.d_text + s->A, sl.n_new, nullptr, err, sl.stream))
+        const bool verify = (s->cfg.flags & MM_FASTX_BGZF_CRC) != 0;
+        if (verify) FX_HIP(hipMemcpyAsync(sl.d_crc, sl.h_crc, sl.n_blk * sizeof(uint32_t), hipMemcpyHostToDevice, sl.stream));
+        // (the inflate writes every block's status word; the verify kernel skips the blocks it has failed)
+        if (mm::launch_bgzf_inflate(sl.d_comp, sl.n_comp, sl.d_blocks, sl.n_blk, sl.d_text + s->A, sl.n_new, verify ? sl.d_status : nullptr,
+                                    err, sl.stream))
             return fail_hip(s, hipGetLastError(), "the BGZF inflate");
-        // (the sticky error word, as the inflate left it: on the host with the cut)
+        if (verify && mm::launch_bgzf_crc32(sl.d_text + s->A, sl.n_new, sl.d_blocks, sl.n_blk, sl.d_crc, nullptr, sl.d_status, err, sl.stream))
+            return fail_hip(s, hipGetLastError(), "the BGZF CRC32");
+        // (the sticky error word, as the inflate and the verify left it: on the host with the cut)
         FX_HIP(hipMemcpyAsync(sl.h_meta + 9, err + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, sl.stream));
     }
     uint64_t tail = 0;
     sl.continues = false;
     sl.first_base = sl.first_overlap = sl.rec0_pos = 0;
     if (s->prev >= 0) FX_HIP(hipEventSynchronize(s->slots[s->prev].ev_cut));
-    if (s->prev >= 0 && bgzf_failed(s->slots[s->prev])) return fail_bgzf(s);
+    if (s->prev >= 0 && bgzf_failed(s->slots[s->prev])) return fail_bgzf(s, s->slots[s->prev]);
     if (s->prev >= 0 && long_fasta(s) && s->slots[s->prev].h_meta[5] && !s->slots[s->prev].h_meta[3]) {
         // the chunk before is a piece of an open record: ">\n", its last l - 1 sequence bytes text[T, n), the new bytes
         Slot &p = s->slots[s->prev];
@@ -372,7 +394,7 @@ int collect(mm_fastx_stream *s, Slot &sl, bool block) {
             if (q != hipSuccess) return fail_hip(s, q, "hipEventQuery");
         }
         FX_HIP(hipEventSynchronize(sl.ev_run));
-        if (bgzf_failed(sl)) return fail_bgzf(s);
+        if (bgzf_failed(sl)) return fail_bgzf(s, sl);
         const int r = mm_workspace_check(sl.ws);
         if (r == MM_ERR_ORDER && sl.retries < 2) {
             // a look-back timed out: this chunk's run again (the workspace takes its tile ids from a ticket from now on)
@@ -447,11 +469,11 @@ void destroy_slots(mm_fastx_stream *s) {
     for (int i = 0; i < s->n_slots; ++i) {
         Slot &sl = s->slots[i];
         void *dev[] = {sl.d_text, sl.d_packed, sl.d_amb, sl.d_rec_base, sl.d_rec_pos, sl.d_offsets, sl.d_meta, sl.d_pos, sl.d_sk, sl.d_values, sl.d_one,
-                       sl.d_comp, sl.d_blocks};
+                       sl.d_comp, sl.d_blocks, sl.d_crc, sl.d_status};
         for (void *p : dev)
             if (p) (void)hipFree(p);
         void *host[] = {sl.h_text, sl.h_meta, sl.h_rec_pos, sl.h_rec_base, sl.h_offsets, sl.h_values, sl.h_pos, sl.h_sk, sl.h_one, sl.h_seq,
-                        sl.h_comp, sl.h_blocks};
+                        sl.h_comp, sl.h_blocks, sl.h_crc};
         for (void *p : host)
             if (p) (void)hipHostFree(p);
         hipEvent_t ev[] = {sl.ev_cut, sl.ev_run, sl.ev_done, sl.ev_tail};
@@ -597,7 +619,7 @@ int mm_fastx_text_stream_create(mm_fastx_stream_t **out, const mm_plan_t *text_p
     if (refusal) return refusal;
     if (cfg->format == MM_FASTX_FASTQ) return refuse(MM_ERR_FORMAT, "FASTQ to byte records is not provided");
     if (cfg->format < MM_FASTX_AUTO || cfg->format > MM_FASTX_FASTQ || (cfg->slots != 0 && (cfg->slots < 2 || cfg->slots > 8)) ||
-        (flags & ~127u))
+        (flags & ~(127u | MM_FASTX_BGZF_CRC)))
         return refuse(MM_ERR_BAD_MODE, "format is MM_FASTX_AUTO / _FASTA, slots 0 or 2..8, flags MM_FASTX_*");
     mm_fastx_stream_config_t base{};
     base.device = cfg->device, base.format = cfg->format, base.flags = flags, base.slots = cfg->slots;
@@ -642,7 +664,7 @@ int mm_fastx_stream_create(mm_fastx_stream_t **out, const mm_plan_t *plan, const
                                                      (flags & MM_FASTX_SKIP_AMBIGUOUS) != 0);
     if (refusal) return refusal;
     if (cfg->format < MM_FASTX_AUTO || cfg->format > MM_FASTX_FASTQ || (cfg->slots != 0 && (cfg->slots < 2 || cfg->slots > 8)) ||
-        (flags & ~(31u | MM_FASTX_ONE_MINIMIZER))) {
+        (flags & ~(31u | MM_FASTX_ONE_MINIMIZER | MM_FASTX_BGZF_CRC))) {
         mm::api_set_last_error("mm_fastx_stream_create: format is MM_FASTX_AUTO / _FASTA / _FASTQ, slots 0 or 2..8, flags MM_FASTX_*");
         return MM_ERR_BAD_MODE;
     }
@@ -724,6 +746,10 @@ int mm_fastx_stream_feed_bgzf(mm_fastx_stream_t *s, const uint8_t *data, uint64_
             // of the block's text into the slot behind, which is looked at before a byte is taken.
             if (!can_fill(s->slots[(s->fill + 1) % s->n_slots])) break;
             if (mm::inflate_payload_host(data + at + payload_off, comp_len, s->bgzf_first.data(), isize)) return fail_bgzf(s);
+            // (MM_FASTX_BGZF_CRC: a block inflated on the host is checked on the host, by the arithmetic the kernel runs)
+            if ((s->cfg.flags & MM_FASTX_BGZF_CRC) &&
+                mm::crc32_bytes(0, s->bgzf_first.data(), isize) != mm::bgzf_trailer_crc(data + at, total))
+                return fail_crc(s);
             uint64_t took = 0;
             const int r = feed_text(s, s->bgzf_first.data(), isize, &took);
             if (r) return r;
@@ -740,6 +766,7 @@ int mm_fastx_stream_feed_bgzf(mm_fastx_stream_t *s, const uint8_t *data, uint64_
             continue;
         }
         memcpy(sl.h_comp + sl.n_comp, data + at + payload_off, comp_len);
+        if (sl.h_crc) sl.h_crc[sl.n_blk] = mm::bgzf_trailer_crc(data + at, total);
         mm_bgzf_block_t &b = sl.h_blocks[sl.n_blk++];
         b.comp_off = sl.n_comp, b.comp_len = comp_len, b.isize = isize, b.out_off = sl.n_new;
         sl.n_comp += comp_len;
@@ -777,6 +804,11 @@ int open_bgzf(mm_fastx_stream *s) {
         if (e == hipSuccess) e = dev_alloc(sl.d_comp, s->comp_cap);
         if (e == hipSuccess) e = host_alloc(sl.h_blocks, s->table_max * sizeof(mm_bgzf_block_t));
         if (e == hipSuccess) e = dev_alloc(sl.d_blocks, s->table_max * sizeof(mm_bgzf_block_t));
+        if (e == hipSuccess && (s->cfg.flags & MM_FASTX_BGZF_CRC)) {
+            e = host_alloc(sl.h_crc, s->table_max * sizeof(uint32_t));
+            if (e == hipSuccess) e = dev_alloc(sl.d_crc, s->table_max * sizeof(uint32_t));
+            if (e == hipSuccess) e = dev_alloc(sl.d_status, s->table_max * sizeof(uint32_t));
+        }
     }
     if (e != hipSuccess) {
         (void)hipGetLastError();

@@ -17,7 +17,9 @@
 //   zlib allows (a literal/length or distance set with at most one code, of length 1); bits that are no code of such a set.
 //   Work is bounded: every step of the symbol loop consumes at least one input bit or ends, a match copies at most isize
 //   bytes, a stored block at most comp_len.
-//   CRC32 IS NOT VERIFIED: ISIZE and the deflate structure are.  (A wave-parallel CRC32 is a later change.)
+//   The decoder verifies ISIZE and the deflate structure.  The CRC32 of the gzip trailer is verified ON REQUEST by code of
+//   its own over the text written here: mm_crc32.h, the kernel mm_crc32.hip (mm_bgzf_crc32_device_async,
+//   mm_bgzf_inflate_verify_host, the stream's MM_FASTX_BGZF_CRC).
 //
 // The decode state (bit buffer, offsets, tables) is the same in every lane of a wavefront: MM_INFLATE_UNIFORM makes that
 // provable for what comes back from LDS, so the symbol loop is wave-uniform.  The Io object does the byte traffic:
@@ -374,6 +376,10 @@ inline int bgzf_member(const uint8_t *d, uint64_t n, uint64_t *total, uint32_t *
     *comp_len = (uint32_t)(size - xlen - 20);
     *isize = d[size - 4] | (uint32_t)d[size - 3] << 8 | (uint32_t)d[size - 2] << 16 | (uint32_t)d[size - 1] << 24;
     return 0;
+}
+// the CRC32 of a whole member's trailer (d and total as bgzf_member found them): the four bytes in front of ISIZE
+inline uint32_t bgzf_trailer_crc(const uint8_t *d, uint64_t total) {
+    return d[total - 8] | (uint32_t)d[total - 7] << 8 | (uint32_t)d[total - 6] << 16 | (uint32_t)d[total - 5] << 24;
 }
 
 }  // namespace mm
